@@ -13,6 +13,10 @@ shard across ranks (no data-path collective) and each step ends with one RCCL al
 
   roofline        dominant KERNEL of the timed steps: algorithmic GB/s vs the 8 TB/s HBM peak (+ PMC traffic from profiles/)
   kernels         every kernel: avg ms per launch, algorithmic bytes, fraction of peak;  scatter_read_frac (north star)
+
+and, with --full only (a plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line):
+
+  roofline.traffic   measured by two rocprofv3 --pmc child runs of the headline instead of read from profiles/
   parity_checked_in_run   the TIMED batch's own outputs (labels, returned-cloud order, counts, ground, groundpatch of sampled
                   slots after the last timed step) against the oracle, bit-exact
   warm_map        the steady state (clouds keep rotating over warm maps), sampled slots replayed on the oracle
@@ -24,6 +28,8 @@ shard across ranks (no data-path collective) and each step ends with one RCCL al
                   reference's default 8 + 4 thread shape (timing only)
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]        (N > 1: re-launches itself under torch.distributed.run)
+  python bench.py --full                              every leg above
+  python bench.py --dump-outputs DIR                  + DIR/<name>.npy: what the last timed step computed (dump_outputs)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
   python bench.py --kitti-dir <.../sequences/00>     BASELINE configs[0] / configs[4]: replay a SemanticKITTI sequence
@@ -46,6 +52,7 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
 ROT = 37               # slots a cloud advances per step (see the module docstring)
 N_SCENES = 32          # distinct ray-cast scenes per GPU; the other clouds of a batch are yaw rotations of them
+DUMP_CLOUDS = 16       # --dump-outputs: clouds of the last timed step whose outputs are written (a seeded sample of the batch)
 
 
 def make_clouds(batch: int, rank: int, n_scenes: int = N_SCENES, seed0: int = 20240113):
@@ -248,6 +255,35 @@ def ordered_line(result, world):
     return out
 
 
+def dump_outputs(directory, pipe, n_points):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy.  counts [B, 4] of every cloud (float64);
+    for DUMP_CLOUDS clouds drawn with a fixed seed (cloud_ids, and map_slots: the slots they met) their labels and out_index
+    ([k, longest of them], -1 past a cloud's end) and the ground and groundpatch layers of their maps ([k, rows, cols]), float32 --
+    exact, as labels and indices are integers below 2^24 and the layers are float32 themselves.  About 34 MB for the headline."""
+    os.makedirs(directory, exist_ok=True)
+    out, last = pipe.out, pipe.shifts[-1]
+    ids = np.sort(np.random.default_rng(0).choice(pipe.nb, size=min(DUMP_CLOUDS, pipe.nb), replace=False))
+    slots = [pipe.slot_of(int(b), last) for b in ids]
+    width = max(1, max(int(n_points[b]) for b in ids))
+    labels = np.full((len(ids), width), -1.0, dtype=np.float32)
+    index = np.full((len(ids), width), -1.0, dtype=np.float32)
+    for i, b in enumerate(ids):
+        n = int(n_points[b])
+        labels[i, :n] = out.labels[b, :n].cpu().numpy()
+        index[i, :n] = out.out_index[b, :n].cpu().numpy()
+    arrays = {
+        "counts": out.counts.cpu().numpy().astype(np.float64),
+        "cloud_ids": ids.astype(np.float64),
+        "map_slots": np.asarray(slots, dtype=np.float64),
+        "labels": labels,
+        "out_index": index,
+        "ground": np.stack([pipe.seg.map(s)["ground"] for s in slots]).astype(np.float32),
+        "groundpatch": np.stack([pipe.seg.map(s)["groundpatch"] for s in slots]).astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -275,6 +311,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1024, help="independent (cloud, map) pairs per GPU per step")
+    ap.add_argument("--full", action="store_true", help="every leg: the live PMC passes, the oracle checks of the timed outputs, warm / "
+                    "halves / layers / config3 / config4 / host_api / CPU legs and the synthetic drive (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed as "
+                    "DIR/<name>.npy (float32 / float64): counts of every cloud; labels, out_index, ground and groundpatch of a seeded sample")
     ap.add_argument("--eager-layers", action="store_true", help="GG_FLAG_EAGER_LAYERS: maintain all nine per-call layers for every cloud (the library's default for "
                     "gg_filter_batch leaves the three that nothing on the path reads to their first reader)")
     ap.add_argument("--minimal-layers", action="store_true", help="(the default since round 6; kept for old command lines)")
@@ -555,7 +595,7 @@ def main():
         alg = algorithmic_bytes(n_mean, n_in, n_kept, C, T, (stride + pw - 1) // pw, full_layers=args.eager_layers)
         table = kernel_table(ktimes, alg, B)
         traffic_source = "profiles/pmc_summary.json (the committed profile round, rescaled to this batch)"
-        if world == 1 and dist is None and not args.no_extras and not args.no_live_pmc and not args.only_config4:
+        if world == 1 and dist is None and args.full and not args.no_extras and not args.no_live_pmc and not args.only_config4:
             live = live_pmc_passes(B)
             if "kernels" in live:
                 LIVE_PMC.update(live["kernels"])
@@ -590,7 +630,10 @@ def main():
         result["step_real_frac_hbm"] = step_real
         result["kernels"] = table
 
-    extras = not args.no_extras and not args.only_config4
+    if rank == 0 and args.dump_outputs:  # (before any leg below touches the maps or the output buffers)
+        dump_outputs(args.dump_outputs, pipe, n_points)
+
+    extras = args.full and not args.no_extras and not args.only_config4
     do_checks = rank == 0 and extras and args.cpu_seconds > 0
     # ---------------------------------------------------------------- the timed batch's own outputs against the oracle
     if do_checks:

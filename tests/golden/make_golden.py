@@ -9,6 +9,7 @@ the GPU box, where the HIP path is compared with them bit for bit.
 """
 import os
 import sys
+import zipfile
 
 import numpy as np
 
@@ -30,7 +31,11 @@ def save(name, cloud, length, resolution, pos, origin, base_z, frames):
         d[f"cls_{f}"] = r["cls"].copy()
         for layer in ("ground", "groundpatch", "variance"):
             d[f"{layer}_{f}"] = m.layer(layer).copy()
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **d)
+    # np.savez_compressed's members at zlib's strongest level: random_364_moved stays under the 1 MiB limit of a committed file
+    with zipfile.ZipFile(os.path.join(HERE, name + ".npz"), "w", compression=zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for key, val in d.items():
+            with zf.open(key + ".npy", "w", force_zip64=True) as fp:
+                np.lib.format.write_array(fp, np.asanyarray(val), allow_pickle=False)
     print(name, len(cloud), "points;", {int(k): int(v) for k, v in zip(*np.unique(r["cls"], return_counts=True))})
 
 

@@ -191,7 +191,7 @@ def test_bench_scales_to_two_gpus_over_rccl():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "64", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--batch", "64", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -244,7 +244,7 @@ def test_bench_multi_gpu_code_path_with_one_rank(abi):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--batch", "48", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--force-dist", "--batch", "48", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1",
            "--config4-batch", "2"] + (["--abi-collective"] if abi else [])
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

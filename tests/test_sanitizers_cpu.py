@@ -8,6 +8,7 @@ src/GroundSegmentation.cpp:101-106).
   returned cloud in parallel parts) built WITHOUT HIP under ThreadSanitizer, and under ASan + UBSan with the fork() case.
 """
 import os
+import platform
 import shutil
 import subprocess
 import sys
@@ -22,6 +23,18 @@ GXX = shutil.which("g++")
 def _runtime(name):
     p = subprocess.run([GCC, f"-print-file-name={name}"], capture_output=True, text=True).stdout.strip()
     return p if os.path.isabs(p) and os.path.exists(p) else None
+
+
+def _without_aslr():
+    """Command prefix that runs a program with address-space randomisation off, where setarch may do that ([] elsewhere).
+    A ThreadSanitizer runtime older than the kernel's ASLR entropy (vm.mmap_rnd_bits above 28) stops at start-up with
+    "unexpected memory mapping" before the program runs; without randomisation the same program runs unchanged."""
+    setarch = shutil.which("setarch")
+    if setarch:
+        cmd = [setarch, platform.machine(), "-R"]
+        if subprocess.run(cmd + ["true"], capture_output=True).returncode == 0:
+            return cmd
+    return []
 
 
 ORACLE_DRIVER = r'''
@@ -104,7 +117,8 @@ def test_host_helper_threads_under_sanitizers(sanitizer, tmp_path):
     subprocess.check_call([GXX, "-std=c++17", "-O1", "-g", f"-fsanitize={sanitizer}", "-fno-omit-frame-pointer", "-ffp-contract=off",
                            "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "groundgrid_amd", "csrc"),
                            os.path.join(ROOT, "tests", "cpp", "test_host_helper.cpp"), "-o", exe, "-lpthread"])
-    p = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1", ASAN_OPTIONS="detect_leaks=0"))
+    prefix = _without_aslr() if sanitizer == "thread" else []
+    p = subprocess.run(prefix + [exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1", ASAN_OPTIONS="detect_leaks=0"))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     assert "ThreadSanitizer" not in p.stderr and "AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-4000:]
     assert "host helper OK" in p.stdout

@@ -48,8 +48,8 @@ rm -rf "$OUT/kt1"
 cd "$REPO"
 timeout 600 python bench.py --force-dist --no-extras --no-live-pmc --steps 10 --warmup 3 > "$OUT/bench_force_dist.json" 2> "$OUT/bench_force_dist.err"
 timeout 600 python bench.py --force-dist --gather config3-only --no-extras --no-live-pmc --steps 10 --warmup 3 > "$OUT/bench_force_dist_no_gather.json" 2>> "$OUT/bench_force_dist.err"
-# the bench line proper (with the fresh pmc_summary in place so that roofline.traffic is filled in)
-cd "$REPO" && timeout 900 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+# the bench line proper, every leg (--full; with the fresh pmc_summary in place so that roofline.traffic is filled in)
+cd "$REPO" && timeout 900 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 rm -rf "$OUT/kt" "$OUT/fetch" "$OUT/write" "$OUT/profiles"
 ls -la "$OUT"
 tail -c 1500 "$OUT/bench_default.json"
