@@ -276,6 +276,42 @@ class GroundSegmentation:
         for s in range(first_slot, first_slot + n):
             self._maps[s]._pos = (float(pos[0]), float(pos[1]))
 
+    def move_maps(self, odoms, base_to_maps, *, slots=None, first_slot: int = 0, rotation: str = "kdl", on_torch_stream: bool = False,
+                  stream=None) -> np.ndarray:
+        """GroundGrid::update (src/GroundGrid.cpp:83-147) for many map states in one set of launches: map k (slots[k], or first_slot + k)
+        moves to odoms[k] = (x, y) with base_to_maps[k] = (tx, ty, tz, qx, qy, qz, qw), exactly as map(slot).move(...) would.
+        on_torch_stream: enqueue on the current torch stream (where filter_batch runs); `stream`: a stream handle of the caller's; by
+        default the context's own stream.  Returns the [n, 2] index shifts."""
+        od = np.ascontiguousarray(np.asarray(odoms, dtype=np.float64).reshape(-1, 2))
+        n = od.shape[0]
+        poses = np.asarray(base_to_maps, dtype=np.float64).reshape(n, 7)
+        planes = np.empty((n, 4), dtype=np.float64)
+        for k in range(n):
+            M = transform_from_pose(poses[k], rotation)
+            planes[k] = (M[2, 0], M[2, 1], M[2, 2], M[2, 3])
+        sl = None
+        if slots is not None:
+            sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(n))
+        h = None  # the context's own stream
+        if stream is None and on_torch_stream:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        if stream is not None:
+            h = stream if stream else _lib.GG_STREAM_DEFAULT  # (0 = torch's default stream = GG_STREAM_DEFAULT)
+        shifts = np.zeros((n, 2), dtype=np.int32)
+        P = C.POINTER
+        rc = self._L.gg_move_maps(self._ctx, n, sl.ctypes.data_as(P(C.c_int32)) if sl is not None else None, first_slot,
+                                  od.ctypes.data_as(P(C.c_double)), planes.ctypes.data_as(P(C.c_double)),
+                                  shifts.ctypes.data_as(P(C.c_int32)), C.c_void_p(h) if h is not None else None)
+        _check(self._L, self._ctx, rc, "gg_move_maps")
+        for k in range(n):
+            slot = int(sl[k]) if sl is not None else first_slot + k
+            x, y = C.c_double(), C.c_double()
+            self._L.gg_get_map_position(self._ctx, slot, C.byref(x), C.byref(y))
+            self._maps[slot]._pos = (x.value, y.value)
+        return shifts
+
     # -- GroundSegmentation::setConfig (src/GroundSegmentation.cpp:468-471)
     def setConfig(self, config: GGConfig):
         _check(self._L, self._ctx, self._L.gg_set_config(self._ctx, C.byref(config)), "gg_set_config")

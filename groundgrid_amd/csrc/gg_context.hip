@@ -26,6 +26,7 @@
 
 #include "gg_internal.h"
 #include "host_helper.h"
+#include "scroll_core.h"
 #include "sweep_core.h"
 
 using namespace gg;
@@ -152,6 +153,17 @@ struct gg_context {
     uint8_t *d_stage_class = nullptr;
     int32_t *d_stage_cell = nullptr;
     float *d_scroll_scratch = nullptr; // 2 layers
+    // gg_move_maps (allocated at its first call; contexts that never call it do not pay): one device block holding the cell table (element,
+    // row | col << 16 of every cell in element order), the parameter ring [PARAM_RING][n_slots] and move_cap scratch rows of C cells
+    void *d_move_block = nullptr;
+    const int2 *d_move_cells = nullptr;
+    MoveParams *d_move_params = nullptr, *h_move_params = nullptr; // (h_: pinned)
+    float2 *d_move_scratch = nullptr;
+    int move_cap = 0;        // scratch rows: maps per chunk (half of them per stream when the call runs as two halves)
+    int move_chunk_tune = 0; // tuning "move_chunk": at most this many maps per chunk (tests: several chunks in a small call)
+    hipEvent_t move_done[PARAM_RING]{}, move_done2[PARAM_RING]{};
+    bool move_used[PARAM_RING]{}, move_used2[PARAM_RING]{};
+    int move_next = 0;
     float *d_image = nullptr;          // 3 * C floats (wire-format images)
     float *d_planes = nullptr;         // GG_NUM_LAYERS * Cpad floats: dense planes of gg_get_layers (allocated on first use)
     float *h_planes = nullptr;         // ... and their pinned landing zone on the host (one download for all requested layers)
@@ -791,6 +803,20 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
 
 bool slot_ok(const gg_context *ctx, int slot) { return ctx && slot >= 0 && slot < ctx->n_slots; }
 
+// GroundGrid::update's host arithmetic (gg_move_map, gg_move_maps): grid_map_core getIndexShiftFromPositionShift -- round half away from
+// zero, map frame -> buffer order (sign flip) -- and getPositionShiftFromIndexShift: the position advances by whole cells, not to the
+// odometry position
+void map_shift(double res, double pos_x, double pos_y, double odom_x, double odom_y, int s[2], double moved[2])
+{
+    const double odom[2] = {odom_x, odom_y};
+    const double pos[2] = {pos_x, pos_y};
+    for (int i = 0; i < 2; ++i) {
+        const double tmp = (odom[i] - pos[i]) / res;
+        s[i] = -(int)(tmp + 0.5 * (tmp > 0 ? 1 : -1));
+        moved[i] = pos[i] + (double)(-s[i]) * res;
+    }
+}
+
 // Before anything reads (or densifies) one of the three layers GG_FLAG_MINIMAL_LAYERS leaves out: compute them for this slot, once,
 // on the context's stream (the callers have ordered it behind the batches).  SURVEY Appendix E: the published-only layers are
 // materialised when somebody asks, from the retained tile-sorted records; gg_get_layer returns at all times what the reference holds.
@@ -1283,6 +1309,12 @@ void gg_destroy(gg_context *ctx)
     if (ctx->h_stage_index) hipHostFree(ctx->h_stage_index);
     if (ctx->h_stage_counts) hipHostFree(ctx->h_stage_counts);
     if (ctx->d_planes) hipFree(ctx->d_planes);
+    if (ctx->d_move_block) hipFree(ctx->d_move_block);
+    if (ctx->h_move_params) hipHostFree(ctx->h_move_params);
+    for (int i = 0; i < PARAM_RING; ++i) {
+        if (ctx->move_done[i]) hipEventDestroy(ctx->move_done[i]);
+        if (ctx->move_done2[i]) hipEventDestroy(ctx->move_done2[i]);
+    }
     if (ctx->d_pc2) hipFree(ctx->d_pc2);
     if (ctx->h_pc2) hipHostFree(ctx->h_pc2);
     if (ctx->h_planes) hipHostFree(ctx->h_planes);
@@ -1522,27 +1554,198 @@ int gg_move_map(gg_context *ctx, int slot, double odom_x, double odom_y, const d
     if (!slot_ok(ctx, slot)) return GG_ERR_CAPACITY;
     if (!base_plane) return GG_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const double res = ctx->arena.g.resolution;
-    // grid_map_core getIndexShiftFromPositionShift: round half away from zero, map frame -> buffer order (sign flip)
-    const double odom[2] = {odom_x, odom_y};
-    const double pos[2] = {ctx->pos_x[slot], ctx->pos_y[slot]};
     int s[2];
-    for (int i = 0; i < 2; ++i) {
-        const double tmp = (odom[i] - pos[i]) / res;
-        s[i] = -(int)(tmp + 0.5 * (tmp > 0 ? 1 : -1));
-    }
+    double moved[2];
+    map_shift(ctx->arena.g.resolution, ctx->pos_x[slot], ctx->pos_y[slot], odom_x, odom_y, s, moved);
     if (shift_out) {
         shift_out[0] = s[0];
         shift_out[1] = s[1];
     }
     if (s[0] == 0 && s[1] == 0) return GG_OK; // src/GroundGrid.cpp:135-137
     if (const int rc = own_stream_waits_for_batches(ctx)) return rc;
-    // getPositionShiftFromIndexShift: the position advances by whole cells, not to the odometry position
-    ctx->pos_x[slot] += (double)(-s[0]) * res;
-    ctx->pos_y[slot] += (double)(-s[1]) * res;
+    ctx->pos_x[slot] = moved[0];
+    ctx->pos_y[slot] = moved[1];
     launch_scroll(ctx->arena, slot, reinterpret_cast<float2 *>(ctx->d_scroll_scratch), s[0], s[1], ctx->pos_x[slot], ctx->pos_y[slot], base_plane, ctx->stream);
     HIPCHK(ctx, hipGetLastError());
     return own_stream_mutated_map(ctx);
+}
+
+// gg_move_maps' device block and pinned parameter ring, at its first call (not while `st` is being captured into a graph: an allocation
+// cannot be captured).  Nothing of the context changes when this fails.
+static int ensure_move_scratch(gg_context *ctx, hipStream_t st)
+{
+    if (ctx->d_move_block) return GG_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(ctx, GG_ERR_INVALID, "gg_move_maps: the first call allocates its scratch and cannot be captured into a graph");
+    (void)hipGetLastError();
+    const Arena &a = ctx->arena;
+    const size_t row = (size_t)a.g.C * sizeof(float2);
+    // scratch rows: one per slot, at most 256 MB (at least 2: the two halves of a divided call each need one)
+    const int cap = (int)std::max<size_t>(2, std::min<size_t>((size_t)ctx->n_slots, ((size_t)256 << 20) / row));
+    const size_t o_cells = 0;
+    const size_t o_params = align_up(o_cells + (size_t)a.g.C * sizeof(int2), 256);
+    const size_t o_scratch = align_up(o_params + (size_t)PARAM_RING * ctx->n_slots * sizeof(MoveParams), 256);
+    const size_t bytes = o_scratch + (size_t)cap * row;
+    std::vector<int2> cells;
+    cells.reserve((size_t)a.g.C);
+    for (int e = 0; e < a.gpl.elems; ++e) {
+        int r, c;
+        if (gp_cell_of(a.gpl, e, r, c)) cells.push_back(make_int2(e, r | (c << 16)));
+    }
+    if ((int)cells.size() != a.g.C) return fail(ctx, GG_ERR_GEOMETRY, "gg_move_maps: the layer's cell elements do not cover the map");
+    void *block = nullptr;
+    MoveParams *h = nullptr;
+    hipEvent_t ev[2 * PARAM_RING]{};
+    hipError_t e = hipMalloc(&block, bytes);
+    int code = GG_ERR_NOMEM;
+    const char *what = "gg_move_maps: device scratch";
+    if (e != hipSuccess) block = nullptr;
+    if (e == hipSuccess) {
+        what = "gg_move_maps: pinned parameter ring";
+        e = hipHostMalloc((void **)&h, (size_t)PARAM_RING * ctx->n_slots * sizeof(MoveParams), hipHostMallocDefault);
+        if (e != hipSuccess) h = nullptr;
+    }
+    for (int i = 0; i < 2 * PARAM_RING && e == hipSuccess; ++i) {
+        code = GG_ERR_HIP;
+        what = "gg_move_maps: events";
+        e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+        if (e != hipSuccess) ev[i] = nullptr;
+    }
+    if (e == hipSuccess) { // (synchronous: the table is on the device before any stream can launch a scroll)
+        what = "gg_move_maps: cell table";
+        e = hipMemcpy(block, cells.data(), cells.size() * sizeof(int2), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        for (hipEvent_t x : ev)
+            if (x) hipEventDestroy(x);
+        if (h) hipHostFree(h);
+        if (block) hipFree(block);
+        (void)hipGetLastError();
+        return fail(ctx, code, what, e);
+    }
+    ctx->d_move_block = block;
+    ctx->d_move_cells = (const int2 *)((char *)block + o_cells);
+    ctx->d_move_params = (MoveParams *)((char *)block + o_params);
+    ctx->d_move_scratch = (float2 *)((char *)block + o_scratch);
+    ctx->h_move_params = h;
+    ctx->move_cap = cap;
+    for (int i = 0; i < PARAM_RING; ++i) {
+        ctx->move_done[i] = ev[i];
+        ctx->move_done2[i] = ev[PARAM_RING + i];
+    }
+    return GG_OK;
+}
+
+int gg_move_maps(gg_context *ctx, int n, const int32_t *slots, int first_slot, const double *odom_xy, const double *base_planes, int32_t *shifts,
+                 void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    if (n < 0) return fail(ctx, GG_ERR_INVALID, "gg_move_maps: n < 0");
+    if (n == 0) return GG_OK;
+    if (!odom_xy || !base_planes) return fail(ctx, GG_ERR_INVALID, "gg_move_maps: odom_xy and base_planes are required");
+    if (n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, "gg_move_maps: more maps than the context has");
+    if (!slots && (first_slot < 0 || first_slot > ctx->n_slots - n)) return fail(ctx, GG_ERR_CAPACITY, "gg_move_maps: slot range");
+    if (slots) { // distinct and in range: two scrolls of one map in one launch would race
+        std::vector<char> &seen = ctx->slot_seen;
+        seen.assign((size_t)ctx->n_slots, 0);
+        for (int i = 0; i < n; ++i) {
+            const int s = slots[i];
+            if (s < 0 || s >= ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, "gg_move_maps: slot outside the context");
+            if (seen[(size_t)s]) return fail(ctx, GG_ERR_INVALID, "gg_move_maps: slots must be distinct");
+            seen[(size_t)s] = 1;
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = pick_stream(ctx, stream);
+    const Arena &a = ctx->arena;
+    // the shift and the position after the move of every map, as gg_move_map computes them; maps with a zero shift are not touched (:135-137)
+    std::vector<int> sh((size_t)2 * n);
+    std::vector<double> moved((size_t)2 * n);
+    std::vector<int> order; // the maps that move: those of the lower half of the slots first when the call runs as two halves
+    order.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int slot = slots ? slots[i] : first_slot + i;
+        map_shift(a.g.resolution, ctx->pos_x[slot], ctx->pos_y[slot], odom_xy[2 * i], odom_xy[2 * i + 1], &sh[(size_t)2 * i], &moved[(size_t)2 * i]);
+        if (sh[(size_t)2 * i] != 0 || sh[(size_t)2 * i + 1] != 0) order.push_back(i);
+    }
+    auto slot_of = [&](int i) { return slots ? slots[i] : first_slot + i; };
+    if (!order.empty()) {
+        if (const int rc = ensure_move_scratch(ctx, st)) return rc;
+        // GG_FLAG_CONCURRENT_HALVES: on a caller stream the maps of the upper half of the slots scroll on the side stream, where their
+        // batches run (as gg_reset_maps divides its fills): a loop of moves and batches on one stream keeps both halves concurrent
+        std::stable_partition(order.begin(), order.end(), [&](int i) { return !second_half_slot(ctx, slot_of(i)); });
+        int n_lo = 0;
+        while (n_lo < (int)order.size() && !second_half_slot(ctx, slot_of(order[(size_t)n_lo]))) ++n_lo;
+        const int nm = (int)order.size();
+        const bool split = halves_enabled(ctx) && st != ctx->stream && st != ctx->half_stream && st != nullptr && n_lo > 0 && n_lo < nm;
+        // parameter ring slot (the pinned entries are rewritten only when the copy that read them last has run)
+        const int g = ctx->move_next;
+        ctx->move_next = (g + 1) % PARAM_RING;
+        if (ctx->move_used[g]) HIPCHK(ctx, hipEventSynchronize(ctx->move_done[g]));
+        if (ctx->move_used2[g]) HIPCHK(ctx, hipEventSynchronize(ctx->move_done2[g]));
+        ctx->move_used[g] = ctx->move_used2[g] = false;
+        MoveParams *hp = ctx->h_move_params + (size_t)g * ctx->n_slots;
+        MoveParams *dp = ctx->d_move_params + (size_t)g * ctx->n_slots;
+        for (int k = 0; k < nm; ++k) {
+            const int i = order[(size_t)k], slot = slot_of(i);
+            MoveParams &p = hp[k];
+            p.sp = make_scroll_params(a, sh[(size_t)2 * i], sh[(size_t)2 * i + 1], moved[(size_t)2 * i], moved[(size_t)2 * i + 1], base_planes + (size_t)4 * i);
+            p.slot = slot;
+            p.fresh = ctx->fresh[slot] ? 1 : 0;
+            p.fresh_z = ctx->fresh_z[slot];
+        }
+        // ordered like gg_reset_maps on `st`
+        if (st == ctx->stream) {
+            if (const int rc = own_stream_waits_for_batches(ctx, false)) return rc;
+        } else {
+            if (ctx->map_event_pending) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->map_event, 0));
+            if (ctx->have_batch_event && ctx->last_batch_stream != st && !ctx->probe_unordered_streams) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->batch_event, 0));
+            if (!(split && ctx->last_batch_stream == st))
+                if (const int rc = stream_waits_for_second_half(ctx, st)) return rc;
+        }
+        HIPCHK(ctx, hipMemcpyAsync(dp, hp, sizeof(MoveParams) * nm, hipMemcpyHostToDevice, st));
+        // chunks of at most `per` maps through the scratch rows [row0, row0 + per): consecutive chunks on one stream reuse them in order
+        auto run = [&](int lo, int hi, int row0, int per, hipStream_t on) {
+            if (ctx->move_chunk_tune > 0) per = std::min(per, ctx->move_chunk_tune);
+            for (int k = lo; k < hi; k += per)
+                launch_scroll_batch(a, ctx->d_move_cells, dp + k, std::min(per, hi - k), ctx->d_move_scratch + (size_t)row0 * a.g.C, on);
+        };
+        if (split) { // (the two halves scroll through disjoint scratch rows: they run side by side)
+            HIPCHK(ctx, hipEventRecord(ctx->half_fork, st)); // (behind the parameter upload, which the side stream reads too)
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->half_stream, ctx->half_fork, 0));
+            const int half = ctx->move_cap / 2;
+            run(0, n_lo, 0, half, st);
+            run(n_lo, nm, half, half, ctx->half_stream);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipEventRecord(ctx->move_done2[g], ctx->half_stream));
+            HIPCHK(ctx, hipEventRecord(ctx->half_done, ctx->half_stream));
+            ctx->move_used2[g] = true;
+            ctx->have_half_event = true;
+        } else {
+            run(0, nm, 0, ctx->move_cap, st);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        HIPCHK(ctx, hipEventRecord(ctx->move_done[g], st));
+        ctx->move_used[g] = true;
+        if (st == ctx->stream) {
+            if (const int rc = own_stream_mutated_map(ctx)) return rc;
+        } else {
+            HIPCHK(ctx, hipEventRecord(ctx->batch_event, st));
+            ctx->have_batch_event = true;
+            ctx->last_batch_stream = st;
+        }
+        // every enqueue succeeded: the moved maps are at their new positions, and real (the scroll wrote every cell); no_confidence stays
+        for (int i : order) {
+            const int slot = slot_of(i);
+            ctx->pos_x[slot] = moved[(size_t)2 * i];
+            ctx->pos_y[slot] = moved[(size_t)2 * i + 1];
+            ctx->fresh[slot] = 0;
+        }
+    }
+    if (shifts)
+        for (int k = 0; k < 2 * n; ++k) shifts[k] = sh[(size_t)k];
+    return GG_OK;
 }
 
 int gg_get_map_position(const gg_context *ctx, int slot, double *pos_x, double *pos_y)
@@ -2446,6 +2649,7 @@ extern "C" int gg_debug_set_tuning(gg_context *ctx, const char *key, int value)
     else if (!strcmp(key, "upload_pieces")) ctx->upload_pieces = value;
     else if (!strcmp(key, "results_direct")) ctx->results_direct = value; // (A/B: 0 = results into HBM and a copy behind k_label, as before round 5)
     else if (!strcmp(key, "halves_min_clouds")) ctx->halves_min_clouds = std::max(2, value); // (tests: GG_FLAG_CONCURRENT_HALVES on small batches)
+    else if (!strcmp(key, "move_chunk")) ctx->move_chunk_tune = value;
     else if (!strcmp(key, "halves_no_fork")) ctx->probe_no_fork = value != 0; // (measurement only: the side stream does not wait for the caller's)
     else if (!strcmp(key, "scan_fault")) ctx->arena.tune_scan_fault = value;
     else if (!strcmp(key, "sweep_fault")) ctx->arena.tune_sweep_fault = value;

@@ -327,6 +327,8 @@ void launch_materialise_layers(const Arena &a, int slot, hipStream_t s);        
 void launch_layer_to_u8(const float *layer, int rows, int cols, float *d_bounds, uint8_t *d_img, hipStream_t s);
 void launch_terrain_image(const Arena &a, int slot, float *d_img, hipStream_t s);
 void launch_scroll(const Arena &a, int slot, float2 *scratch, int s0, int s1, double pos_x, double pos_y, const double plane[4], hipStream_t s);
+struct MoveParams; // scroll_core.h
+void launch_scroll_batch(const Arena &a, const int2 *cells, const MoveParams *d_params, int n_maps, float2 *scratch, hipStream_t s); // k0b_scroll_batch.hip (gg_move_maps)
 void launch_pack16(const gg_point32 *src, gg_point16 *dst, size_t n, hipStream_t s);
 void launch_decode_classes(const Arena &a, int slot, size_t n, uint8_t *d_class, int32_t *d_cell, hipStream_t s);
 

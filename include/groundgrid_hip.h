@@ -219,6 +219,19 @@ int gg_set_map_position(gg_context *ctx, int slot, double pos_x, double pos_y);
  * is the binding's decision (gg_rotation_from_quaternion offers both).  shift (nullable) receives the index shift
  * (rows, cols). */
 int gg_move_map(gg_context *ctx, int slot, double odom_x, double odom_y, const double base_plane[4], int shift[2]);
+/* GroundGrid::update (src/GroundGrid.cpp:83-147) for n maps in one set of launches: map i = slots ? slots[i] : first_slot + i (distinct)
+ * moves to (odom_xy[2i], odom_xy[2i+1]) with base_planes[4i..4i+3] exactly as gg_move_map(ctx, map i, ...) would -- the same shift,
+ * position and cells, bit for bit.  A map whose shift is (0, 0) is not touched (it stays fresh, if it was).  A FRESH map (gg_reset_maps)
+ * is scrolled as it is, without the fill gg_move_map puts first; the other fresh maps of the context stay fresh.  shifts (nullable)
+ * receives [n][2] index shifts.  Enqueued on `stream` (NULL = the context's stream, GG_STREAM_DEFAULT or a caller stream: ordered like
+ * gg_reset_maps there, and under GG_FLAG_CONCURRENT_HALVES the maps of the upper half of the slots scroll on the library's side stream);
+ * returns without waiting, and the host arrays may be freed when it returns.  Errors change nothing: GG_ERR_INVALID (null ctx, null
+ * odom_xy / base_planes with n > 0, repeated slots, n < 0), GG_ERR_CAPACITY (a slot outside the context), GG_ERR_NOMEM (the scratch
+ * this entry point allocates at its first call -- at most 256 MB, one map layer per slot below that -- did not fit).  The first call
+ * must not be captured into a graph.  n == 0 is GG_OK. */
+int gg_move_maps(gg_context *ctx, int n, const int32_t *slots, int first_slot, const double *odom_xy, const double *base_planes, int32_t *shifts,
+                 void *stream);
+#define GG_HAS_MOVE_MAPS 1
 int gg_get_map_position(const gg_context *ctx, int slot, double *pos_x, double *pos_y);
 /* any of the 11 layers, column-major rows x cols float32 (Eigen::MatrixXf), host memory */
 int gg_set_layer(gg_context *ctx, int slot, int layer, const float *src);
