@@ -36,7 +36,7 @@ LAYERS = [
 # every symbol include/groundgrid_hip.h declares
 SYMBOLS = [
     "gg_abi_version", "gg_kernel_name", "gg_default_config", "gg_default_geometry", "gg_create", "gg_destroy",
-    "gg_set_config", "gg_get_config", "gg_set_flags", "gg_get_size", "gg_get_geometry", "gg_last_error",
+    "gg_set_config", "gg_get_config", "gg_set_slot_configs", "gg_get_slot_config", "gg_set_flags", "gg_get_size", "gg_get_geometry", "gg_last_error",
     "gg_reset_map", "gg_reset_maps", "gg_set_map_position", "gg_move_map", "gg_move_maps", "gg_get_map_position", "gg_set_layer", "gg_get_layer", "gg_get_layers", "gg_get_expected_points",
     "gg_filter_cloud", "gg_filter_cloud_tf", "gg_filter_cloud_pc2", "gg_get_layer_image_u8", "gg_get_terrain_image", "gg_filter_batch", "gg_synchronize", "gg_get_point_classes", "gg_get_kernel_times",
     "gg_set_conventions", "gg_get_conventions", "gg_rotation_from_quaternion", "gg_transform_from_pose",
@@ -154,6 +154,8 @@ def load():
     L.gg_destroy.restype = None
     L.gg_set_config.argtypes = [vp, P(GGConfig)]
     L.gg_get_config.argtypes = [vp, P(GGConfig)]
+    L.gg_set_slot_configs.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, P(GGConfig)]
+    L.gg_get_slot_config.argtypes = [vp, C.c_int, P(GGConfig), P(C.c_int)]
     L.gg_set_flags.argtypes = [vp, C.c_uint]
     L.gg_get_size.argtypes = [vp, P(C.c_int), P(C.c_int)]
     L.gg_get_geometry.argtypes = [vp, P(C.c_double), P(C.c_double), P(C.c_double)]

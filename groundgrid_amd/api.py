@@ -89,6 +89,14 @@ class GridMap:
     def getPosition(self):
         return self._pos
 
+    def setConfig(self, config: Optional[GGConfig]):
+        """This map's own configuration (GroundSegmentation::setConfig of the reference's object for this map); None: follow the
+        context's configuration again."""
+        self._seg.set_slot_configs(None if config is None else [config], slots=[self.slot])
+
+    def getConfig(self) -> GGConfig:
+        return self._seg.slot_config(self.slot)[0]
+
     def setPosition(self, x: float, y: float):
         """Map position after grid_map::move (src/GroundGrid.cpp:97)."""
         L, ctx = self._seg._L, self._seg._ctx
@@ -320,6 +328,35 @@ class GroundSegmentation:
         c = GGConfig()
         _check(self._L, self._ctx, self._L.gg_get_config(self._ctx, C.byref(c)), "gg_get_config")
         return c
+
+    # -- per-map configuration: every GroundSegmentation object of the reference has its own setConfig; here every map slot may
+    def set_slot_configs(self, configs, slots=None, first_slot: int = 0):
+        """Give map k (slots[k], or first_slot + k) its own configuration configs[k].  configs=None: those maps follow the context's
+        configuration (setConfig) again -- then `slots` (or first_slot and a count given as configs=None, slots=range) names them.
+        Blocks like setConfig; on any error no map's configuration changes."""
+        if configs is None:
+            if slots is None:
+                raise ValueError("set_slot_configs(None) needs the slots to clear")
+            arr = None
+            n = len(slots)
+        else:
+            configs = list(configs)
+            n = len(configs)
+            arr = (GGConfig * max(n, 1))(*configs)
+        sl = None
+        if slots is not None:
+            sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+            if sl.shape[0] != n:
+                raise ValueError("slots and configs differ in length")
+        rc = self._L.gg_set_slot_configs(self._ctx, n, sl.ctypes.data_as(C.POINTER(C.c_int32)) if sl is not None else None, int(first_slot),
+                                         arr)
+        _check(self._L, self._ctx, rc, "gg_set_slot_configs")
+
+    def slot_config(self, slot: int):
+        """(the configuration map `slot` runs with, True if it is its own / False if it follows the context's)"""
+        c, own = GGConfig(), C.c_int(0)
+        _check(self._L, self._ctx, self._L.gg_get_slot_config(self._ctx, int(slot), C.byref(c), C.byref(own)), "gg_get_slot_config")
+        return c, bool(own.value)
 
     def set_flags(self, minimal_layers: bool = False, profile: bool = False, concurrent_halves: bool = False, eager_layers: bool = False):
         """gg_set_flags.  minimal_layers: maxGroundHeight / groundCandidates / planeDist -- written by insert_cloud

@@ -74,6 +74,12 @@ struct gg_context {
     bool probe_unordered_streams = false; // measurement only: batches and resets on different caller streams are NOT ordered by the library
     std::vector<char> lazy_pending;
     std::vector<gg::CloudParams> lazy_params;
+    // gg_set_slot_configs: per slot, does it have a configuration of its own (else it follows `cfg`), which, and its DevConfig; the device
+    // copy (Arena::slot_cfg, entry s = slot s) is allocated at the first call and uploaded whenever the slot configurations change
+    std::vector<char> slot_own;
+    std::vector<gg_config> slot_cfg;
+    std::vector<DevConfig> slot_dev;
+    DevConfig *d_slot_cfg = nullptr;
 
     gg_conventions conv{};
     gg::sweep::Params sweep_params{};
@@ -288,6 +294,8 @@ void make_dev_config(const gg_config &c, DevConfig &d)
     d.min_dist_fac = c.minimum_distance_factor * 5; // :154
     d.min_point_height_thres = c.miminum_point_height_threshold;
     d.min_point_height_obs_thres = c.minimum_point_height_obstacle_threshold;
+    d.inv_decrease = 1.0 / c.occupied_cells_decrease_factor;                                        // (launch_sequence's sweep::Params)
+    d.decay_fast = c.occupied_cells_decrease_factor >= 1.25 && c.occupied_cells_decrease_factor < 1e300 ? 1 : 0;
 }
 
 hipStream_t pick_stream(gg_context *ctx, void *stream)
@@ -671,6 +679,7 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
         for (int k = 0; k < 12; ++k) p.tf[k] = b->transforms ? b->transforms[(size_t)i * 12 + k] : 0.0;
         p.label_shift = nb == 1 ? ctx->next_label_shift : 0;
         p.io_index = i;
+        p.cfg_index = ctx->slot_own[slot] ? slot : -1;
         max_n[half] = std::max(max_n[half], p.n_points);
         ctx->lazy_pending[slot] = lazy ? 1 : 0;
         if (lazy) ctx->lazy_params[slot] = p;
@@ -762,6 +771,10 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
     a.flags = eff_flags;
     a.eigen_reduction = ctx->conv.eigen_reduction;
     a.fresh_launch = 0;
+    // a (half) launch with a cloud of its own configuration takes the kernels' SLOT_CFG variants; any other runs the kernels it always ran
+    bool own_half[2] = {false, false};
+    for (int i = 0; i < nb; ++i) own_half[i < n_first ? 0 : 1] |= hp[i].cfg_index >= 0;
+    a.slot_cfg_launch = own_half[0] ? 1 : 0;
     if (split) {
         // the side stream sees what the caller's stream holds up to here (its inputs, a re-initialisation of the maps on that stream)
         if (!ctx->probe_no_fork) {
@@ -773,6 +786,7 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
         a2.sweep_sync = a.sweep_sync2;
         a2.sweep_rec_clouds = 0; // (one scratch region: the side stream's half keeps k_sweep)
         a2.scan_sync = a.scan_sync2; // (its own region: the halves of consecutive divided batches need not be the same size)
+        a2.slot_cfg_launch = own_half[1] ? 1 : 0;
         a.fresh_launch = fresh_half[0] ? 1 : 0;
         a2.fresh_launch = fresh_half[1] ? 1 : 0;
         if (const int rc = fill_fresh(0, n_first, s)) return rc;
@@ -915,6 +929,9 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
     ctx->fresh_enabled = !(getenv("GG_FRESH_MAPS") && atoi(getenv("GG_FRESH_MAPS")) == 0);
     ctx->lazy_pending.assign(n_slots, 0);
     ctx->lazy_params.assign(n_slots, CloudParams{});
+    ctx->slot_own.assign(n_slots, 0);
+    ctx->slot_cfg.assign(n_slots, gg_config{});
+    ctx->slot_dev.assign(n_slots, DevConfig{});
     ctx->pos_y.assign(n_slots, 0.0);
 
 #define CREATE_CHK(call)                                             \
@@ -1319,6 +1336,7 @@ void gg_destroy(gg_context *ctx)
     if (ctx->h_pc2) hipHostFree(ctx->h_pc2);
     if (ctx->h_planes) hipHostFree(ctx->h_planes);
     if (ctx->d_arena) hipFree(ctx->d_arena);
+    if (ctx->d_slot_cfg) hipFree(ctx->d_slot_cfg);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1328,6 +1346,16 @@ void gg_destroy(gg_context *ctx)
 // k_patch's instructions -- although they depend on the cell and the configuration only.
 // `cfg`: the configuration the table is for -- the caller commits it to the context only when the table is in place, so that k_patch's
 // thresholds and the rest of the path never come from two configurations.
+// every batch enqueued so far has finished (what gg_set_config and gg_set_slot_configs wait for before they change what batches read)
+static int wait_for_batches_in_flight(gg_context *ctx)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->have_batch_event) HIPCHK(ctx, hipEventSynchronize(ctx->batch_event));
+    if (ctx->have_half_event) HIPCHK(ctx, hipEventSynchronize(ctx->half_done));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return GG_OK;
+}
+
 static int rebuild_patch_table(gg_context *ctx, const DevConfig &cfg)
 {
     const Geometry &g = ctx->arena.g;
@@ -1353,11 +1381,8 @@ static int rebuild_patch_table(gg_context *ctx, const DevConfig &cfg)
             const int gidx = gp_index(ctx->arena.gpl, i, j);
             memcpy(&e[3], &gidx, 4);
         }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     // (batches may be reading the old table: wait for them; gg_set_config is a rare, synchronous call)
-    if (ctx->have_batch_event) HIPCHK(ctx, hipEventSynchronize(ctx->batch_event));
-    if (ctx->have_half_event) HIPCHK(ctx, hipEventSynchronize(ctx->half_done));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = wait_for_batches_in_flight(ctx)) return rc;
     HIPCHK(ctx, hipMemcpy(const_cast<float4 *>(ctx->arena.patch_table), t.data(), t.size() * 4, hipMemcpyHostToDevice));
     return GG_OK;
 }
@@ -1380,6 +1405,59 @@ int gg_get_config(const gg_context *ctx, gg_config *cfg)
 {
     if (!ctx || !cfg) return GG_ERR_INVALID;
     *cfg = ctx->cfg;
+    return GG_OK;
+}
+
+// Per-slot configurations.  The context's configuration stays where it was (Arena::cfg and the per-cell table, gg_set_config); a slot
+// with its own has its DevConfig in a device table (Arena::slot_cfg, entry = slot) that every launch names and only this call writes, and
+// its clouds carry the entry's index (CloudParams::cfg_index).  Launches with such a cloud take the kernels' SLOT_CFG variants.
+int gg_set_slot_configs(gg_context *ctx, int n, const int32_t *slots, int first_slot, const gg_config *cfgs)
+{
+    if (!ctx || n < 0) return fail(ctx, GG_ERR_INVALID, "gg_set_slot_configs: null context or n < 0");
+    if (n == 0) return GG_OK;
+    std::vector<char> seen((size_t)ctx->n_slots, 0);
+    for (int k = 0; k < n; ++k) {
+        const long long slot = slots ? (long long)slots[k] : (long long)first_slot + k;
+        if (slot < 0 || slot >= ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, "gg_set_slot_configs: slot outside the context");
+        if (seen[(size_t)slot]++) return fail(ctx, GG_ERR_INVALID, "gg_set_slot_configs: a slot is named twice");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_slot_cfg) {
+        void *p = nullptr;
+        if (hipMalloc(&p, sizeof(DevConfig) * (size_t)ctx->n_slots) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, GG_ERR_NOMEM, "gg_set_slot_configs: device table");
+        }
+        ctx->d_slot_cfg = static_cast<DevConfig *>(p);
+    }
+    std::vector<char> own = ctx->slot_own;
+    std::vector<gg_config> cfg = ctx->slot_cfg;
+    std::vector<DevConfig> dev = ctx->slot_dev;
+    for (int k = 0; k < n; ++k) {
+        const int slot = slots ? slots[k] : first_slot + k;
+        own[slot] = cfgs ? 1 : 0;
+        cfg[slot] = cfgs ? cfgs[k] : gg_config{};
+        dev[slot] = DevConfig{};
+        if (cfgs) make_dev_config(cfgs[k], dev[slot]);
+    }
+    // (batches in flight read the old table and carry the old indices: they finish first, like gg_set_config's)
+    if (const int rc = wait_for_batches_in_flight(ctx)) return rc;
+    HIPCHK(ctx, hipMemcpy(ctx->d_slot_cfg, dev.data(), sizeof(DevConfig) * dev.size(), hipMemcpyHostToDevice));
+    ctx->slot_own.swap(own);
+    ctx->slot_cfg.swap(cfg);
+    ctx->slot_dev.swap(dev);
+    ctx->arena.slot_cfg = ctx->d_slot_cfg;
+    drop_graphs(ctx); // (a captured launch names the kernels and the context configuration it was captured with)
+    return GG_OK;
+}
+
+int gg_get_slot_config(const gg_context *ctx, int slot, gg_config *cfg, int *own)
+{
+    if (!ctx || !cfg) return GG_ERR_INVALID;
+    if (!slot_ok(ctx, slot)) return GG_ERR_CAPACITY;
+    const bool o = ctx->slot_own[slot] != 0;
+    *cfg = o ? ctx->slot_cfg[slot] : ctx->cfg;
+    if (own) *own = o ? 1 : 0;
     return GG_OK;
 }
 
@@ -2526,6 +2604,8 @@ int gg_run_stage(gg_context *ctx, int slot, int stage, const gg_stage_args *args
     Arena a = ctx->arena;
     a.flags = ctx->flags;
     a.eigen_reduction = ctx->conv.eigen_reduction;
+    const bool own = ctx->slot_own[slot] != 0;
+    if (own) a.cfg = ctx->slot_dev[slot]; // (the single-cell stages read it by value; k_patch takes its SLOT_CFG variant below)
     if (stage == GG_STAGE_DETECT_GROUND_PATCHES || stage == GG_STAGE_SPIRAL_GROUND_INTERPOLATION) {
         // the many-cell stages are the path's own kernels: they take their slot and base_z from a parameter record like a batch of one
         const int r = ctx->ring_next;
@@ -2537,12 +2617,14 @@ int gg_run_stage(gg_context *ctx, int slot, int stage, const gg_stage_args *args
         hp[0].base_z = (float)args->base_z;
         hp[0].pos_x = ctx->pos_x[slot];
         hp[0].pos_y = ctx->pos_y[slot];
+        hp[0].cfg_index = own ? slot : -1;
         HIPCHK(ctx, hipMemcpyAsync(dp, hp, sizeof(CloudParams), hipMemcpyHostToDevice, s));
         if (stage == GG_STAGE_DETECT_GROUND_PATCHES) {
+            a.slot_cfg_launch = own ? 1 : 0;
             launch_patch_stage(a, dp, slot, args->section, s);
         } else {
             sweep::Params sp = ctx->sweep_params;
-            sp.decrease = ctx->cfg.occupied_cells_decrease_factor;
+            sp.decrease = own ? ctx->slot_cfg[slot].occupied_cells_decrease_factor : ctx->cfg.occupied_cells_decrease_factor;
             sp.inv_decrease = 1.0 / sp.decrease;
             sp.decay_fast = sp.decrease >= 1.25 && sp.decrease < 1e300;
             sp.keep_points = 1;
@@ -2578,6 +2660,7 @@ int gg_insert_cloud(gg_context *ctx, int slot, const gg_point32 *cloud, size_t s
     Arena a = ctx->arena;
     a.flags = ctx->flags & ~(unsigned)GG_FLAG_MINIMAL_LAYERS;
     a.eigen_reduction = ctx->conv.eigen_reduction;
+    if (ctx->slot_own[slot]) a.cfg = ctx->slot_dev[slot]; // (k_classify is the only kernel here that reads the configuration: by value)
     launch_materialise_layers(a, slot, s);
     HIPCHK(ctx, hipGetLastError());
     for (size_t i = 0; i < n; ++i) {

@@ -23,6 +23,24 @@ namespace gg {
 
 #define GG_DEV __device__ __forceinline__
 
+// The configuration of the cloud a work-group works on, in the SLOT_CFG kernel variants (gg_internal.h Arena::slot_cfg): its slot's own
+// entry, or the context's when cfg_index < 0.  A cloud's configuration is uniform over its wavefronts: the index and every word go
+// through readfirstlane (scalar registers), whatever the compiler can prove about the address.
+GG_DEV void load_cloud_config(const Arena &a, int cfg_index, DevConfig &out)
+{
+    const int k = __builtin_amdgcn_readfirstlane(cfg_index);
+    if (k < 0) {
+        out = a.cfg;
+        return;
+    }
+    static_assert(sizeof(DevConfig) % 4 == 0, "DevConfig is read as 32-bit words");
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(a.slot_cfg + k);
+    uint32_t w[sizeof(DevConfig) / 4];
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(DevConfig) / 4); ++i) w[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)src[i]);
+    __builtin_memcpy(&out, w, sizeof(DevConfig));
+}
+
 // libstdc++ std::min / std::max (NaN: return the first argument when the comparison is false)
 GG_DEV double std_min(double a, double b) { return (b < a) ? b : a; }
 GG_DEV double std_max(double a, double b) { return (a < b) ? b : a; }

@@ -57,6 +57,9 @@ struct DevConfig {
     double min_dist_fac;                    // minimum_distance_factor * 5   (:154)
     double min_point_height_thres;          // :155
     double min_point_height_obs_thres;      // :156
+    // the sweep's decay (:464, sweep_core.h decayed_confidence): 1 / occupied_cells_decrease_factor and "the product form is safe" (>= 1.25)
+    double inv_decrease;
+    int decay_fast;
 };
 
 struct Geometry {
@@ -89,6 +92,7 @@ struct CloudParams {
                      // download for both -- and a captured launch must not bake that n in: it travels here)
     int io_index;    // the cloud's row of the batch's I/O buffers (d_points, d_labels, ...): its position in gg_batch, which is not its position
                      // in the parameter array when a batch runs as two halves (GG_FLAG_CONCURRENT_HALVES)
+    int cfg_index = -1; // the slot has a configuration of its own (gg_set_slot_configs): its entry of Arena::slot_cfg; -1 = the context's (Arena::cfg)
 };
 
 // everything a kernel needs to find its data
@@ -185,6 +189,12 @@ struct Arena {
                          // 4 = no `points` atomics
     int k3_debug;        // env GG_K3_DEBUG (measurement only): 1 = k_patch stops after the tile check, 2 = after staging, 3 = after the first test (:364)
     int eigen_reduction; // gg_conventions::eigen_reduction (GG_EIGEN_33 / GG_EIGEN_34_SSE): order of the 5x5 block sums in K3
+    // per-slot configurations (gg_set_slot_configs): entry s = slot s's own DevConfig, read through CloudParams::cfg_index.  Uploaded when
+    // the slot configurations change, never per launch.  slot_cfg_launch: some cloud of THIS launch has one -- the launchers then pick the
+    // SLOT_CFG variants of k_classify, k_patch, the sweeps and k_label, which read the configuration per cloud; a launch without one runs
+    // the kernels it always ran, with Arena::cfg and Arena::patch_table
+    const DevConfig *slot_cfg;
+    int slot_cfg_launch;
 };
 
 // The nine per-call layers (everything but ground / groundpatch) are stored tile by tile: the 16x16 tile of Morton rank r owns the

@@ -61,12 +61,12 @@ GG_DEV bool locate_point(const Arena &a, const CloudParams &cp, const PointIn &p
 }
 
 // :237-244 -- ignore test and the entry condition of the line-of-sight test.  `oldgroundheight` = ground(gi) before this cloud.
-GG_DEV int classify_point(const Arena &a, const CloudParams &cp, const PointIn &pt, float oldgroundheight, bool &walk)
+GG_DEV int classify_point(const Arena &a, const DevConfig &cfg, const CloudParams &cp, const PointIn &pt, float oldgroundheight, bool &walk)
 {
     const float dx = pt.x - cp.ox, dy = pt.y - cp.oy;
     const float sqdist = (float)((double)dx * (double)dx + (double)dy * (double)dy); // :223
     walk = false;
-    if (pt.ring > a.cfg.max_ring || sqdist < a.g.min_dist_squared) return GG_CLASS_IGNORED; // :237
+    if (pt.ring > cfg.max_ring || sqdist < a.g.min_dist_squared) return GG_CLASS_IGNORED; // :237
     // :243-244 Outlier detection test.  (A map that holds no confidence above 0.01 anywhere -- the first cloud after
     // gg_reset_map -- cannot produce an outlier, :269: the walk is skipped instead of marching every ground return's ray
     // to its end.)
@@ -85,7 +85,7 @@ GG_DEV int classify_point(const Arena &a, const CloudParams &cp, const PointIn &
 // (v_readlane); a candidate that has hit gives up the rest of its steps.  Round 4 walked one candidate per pass (64 steps, mostly
 // beyond the end of a 20-step ray) or, above a dozen candidates, every lane its own ray serially.  Returns the lanes whose ray hits.
 GG_DEV float lane_value(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
-GG_DEV unsigned long long walk_packed(const Arena &a, const CloudParams &cp, const float2 *__restrict__ gp2, float px, float py, float pz, bool walk, int lane)
+GG_DEV unsigned long long walk_packed(const Arena &a, const DevConfig &cfg, const CloudParams &cp, const float2 *__restrict__ gp2, float px, float py, float pz, bool walk, int lane)
 {
     const Geometry &g = a.g;
     const int rows = g.rows, cols = g.cols;
@@ -138,7 +138,7 @@ GG_DEV unsigned long long walk_packed(const Arena &a, const CloudParams &cp, con
                 // ray the stored ground lies BELOW the ray, so they rule the step out -- and the 3 x 3 confidence sum (nine gathers in the
                 // sheared layer, the walk's traffic) only for the steps they let through
                 const float2 gI = gp2[gp_idx(a, I0, I1)];
-                hit = gI.y > 0.01f && (double)gI.x >= (double)(sz + cp.oz) + a.cfg.outlier_tolerance;
+                hit = gI.y > 0.01f && (double)gI.x >= (double)(sz + cp.oz) + cfg.outlier_tolerance;
                 r0 = max(I0 - 1, 2), c0 = max(I1 - 1, 2); // :268
             }
         }
@@ -148,7 +148,7 @@ GG_DEV unsigned long long walk_packed(const Arena &a, const CloudParams &cp, con
                 float e[9];
 #pragma unroll
                 for (int s = 0; s < 9; ++s) e[s] = gp2[gp_idx(a, r0 + s % 3, c0 + s / 3)].y;
-                hit = (double)tree9(e) > a.cfg.min_outlier_detection_ground_confidence;
+                hit = (double)tree9(e) > cfg.min_outlier_detection_ground_confidence;
             }
             for (hm = __ballot(hit); hm != 0ull; hm &= hm - 1ull) hits |= 1ull << __builtin_amdgcn_readlane(owner, __builtin_ctzll(hm));
             if ((hits >> cur) & 1ull) cur_left = 0; // the ray in hand has its answer: its remaining steps are not needed
@@ -161,7 +161,7 @@ GG_DEV unsigned long long walk_packed(const Arena &a, const CloudParams &cp, con
 // a map that meets an unrelated scene: the near rings' returns all lie under the stored terrain, 64 candidates with rays of five to
 // thirty steps -- where 64 lanes walking their own rays side by side, each leaving at its first hit, beat any dealing of items
 // (measured on that stress case: 3.2 ms per 1024 clouds against 6.4 for walk_packed, profiles/r05a/walk_ab.log).
-GG_DEV bool ray_walk_hits_lane(const Arena &a, const CloudParams &cp, const float2 *__restrict__ gp2, float px, float py, float pz)
+GG_DEV bool ray_walk_hits_lane(const Arena &a, const DevConfig &cfg, const CloudParams &cp, const float2 *__restrict__ gp2, float px, float py, float pz)
 {
     const Geometry &g = a.g;
     const int rows = g.rows, cols = g.cols;
@@ -196,12 +196,12 @@ GG_DEV bool ray_walk_hits_lane(const Arena &a, const CloudParams &cp, const floa
 #pragma unroll
         for (int k = 0; k < WALK_UNROLL; ++k) {
             // :269, the cell's own two conditions first (most steps of a ray run above the stored ground: they end here)
-            if (!(inside[k] && gI[k].y > 0.01f && (double)gI[k].x >= (double)rz[k] + a.cfg.outlier_tolerance)) continue;
+            if (!(inside[k] && gI[k].y > 0.01f && (double)gI[k].x >= (double)rz[k] + cfg.outlier_tolerance)) continue;
             const int r0 = max(I0[k] - 1, 2), c0 = max(I1[k] - 1, 2); // :268
             float e[9];
 #pragma unroll
             for (int s = 0; s < 9; ++s) e[s] = gp2[gp_idx(a, r0 + s % 3, c0 + s / 3)].y;
-            if ((double)tree9(e) > a.cfg.min_outlier_detection_ground_confidence) return true;
+            if ((double)tree9(e) > cfg.min_outlier_detection_ground_confidence) return true;
         }
         if (!on[WALK_UNROLL - 1]) return false;
     }
@@ -234,7 +234,9 @@ GG_DEV uint32_t make_key(const Arena &a, const uint16_t *tile_rank, int gi0, int
 // a memset node in front of every launch.
 constexpr uint32_t FRONT_WAIT_POLLS = 1u << 22; // x ~0.3 us: gives up after about a second
 
-template <int FMT, int SHAPE>
+// SC (SLOT_CFG): some cloud of the launch has its slot's own configuration (gg_internal.h Arena::slot_cfg): every work-group reads the
+// configuration of the cloud whose chunks it holds -- one cloud per work-group, whatever shape hands the work out
+template <int FMT, int SHAPE, bool SC = false>
 __global__ __launch_bounds__(256, 5) void k_classify(const Arena a, const CloudParams *__restrict__ params, const BatchIO io, int n_counters)
 {
     // dynamic LDS only (a static variable would shift its base off 16 bytes): [4][words] histograms, the tile ranks, 16 scratch words
@@ -275,6 +277,9 @@ __global__ __launch_bounds__(256, 5) void k_classify(const Arena a, const CloudP
     }
     const int cloud = (int)(item / gridDim.x), bx = (int)(item % gridDim.x);
     const CloudParams &cp = params[cloud]; // (a reference: the 12 transform doubles stay in memory unless has_tf)
+    DevConfig own_cfg;
+    if (SC) load_cloud_config(a, cp.cfg_index, own_cfg);
+    const DevConfig &cfg = SC ? own_cfg : a.cfg;
     const int chunk = bx * 4 + wave;
     const int n = cp.n_points;
     const int nch = (n + a.PW - 1) / a.PW;
@@ -334,12 +339,12 @@ __global__ __launch_bounds__(256, 5) void k_classify(const Arena a, const CloudP
                 const int p = p0 + j * 64 + lane;
                 int cls = GG_CLASS_KEPT;
                 bool walk = false;
-                if (inmap_[j]) cls = classify_point(a, cp, pt[j], og[j], walk);
+                if (inmap_[j]) cls = classify_point(a, cfg, cp, pt[j], og[j], walk);
                 const int n_walk = __popcll(__ballot(walk));
                 if (n_walk > WALK_PACKED_MAX) { // (uniform) most lanes are candidates: every lane walks its own ray
-                    if (walk && ray_walk_hits_lane(a, cp, gp2, pt[j].x, pt[j].y, pt[j].z)) cls = GG_CLASS_OUTLIER;
+                    if (walk && ray_walk_hits_lane(a, cfg, cp, gp2, pt[j].x, pt[j].y, pt[j].z)) cls = GG_CLASS_OUTLIER;
                 } else if (n_walk > 0) { // (uniform) a few candidates: their steps dealt to the 64 lanes
-                    const unsigned long long hits = walk_packed(a, cp, gp2, pt[j].x, pt[j].y, pt[j].z, walk, lane);
+                    const unsigned long long hits = walk_packed(a, cfg, cp, gp2, pt[j].x, pt[j].y, pt[j].z, walk, lane);
                     if ((hits >> lane) & 1ull) cls = GG_CLASS_OUTLIER;
                 }
                 uint32_t key = KEY_OUTSIDE;
@@ -436,16 +441,17 @@ size_t classify_lds_bytes(const Arena &a)
 template <int FMT, int SHAPE>
 static void launch_classify_as(const Arena &a, const CloudParams *d_params, const BatchIO &io, dim3 grid, size_t lds, int n_counters, hipStream_t s)
 {
-    hipLaunchKernelGGL((k_classify<FMT, SHAPE>), grid, dim3(256), lds, s, a, d_params, io, n_counters);
+    if (a.slot_cfg_launch) hipLaunchKernelGGL((k_classify<FMT, SHAPE, true>), grid, dim3(256), lds, s, a, d_params, io, n_counters);
+    else hipLaunchKernelGGL((k_classify<FMT, SHAPE>), grid, dim3(256), lds, s, a, d_params, io, n_counters);
 }
 
 // work-groups of k_classify<.., FRONT_ONE_LAUNCH> the current device holds at a time (0: unknown)
-static int front_resident_groups(size_t lds)
+static int front_resident_groups(size_t lds, bool sc)
 {
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k_classify<GG_POINT16, FRONT_ONE_LAUNCH>), 256, lds) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sc ? reinterpret_cast<const void *>(k_classify<GG_POINT16, FRONT_ONE_LAUNCH, true>) : reinterpret_cast<const void *>(k_classify<GG_POINT16, FRONT_ONE_LAUNCH>), 256, lds) != hipSuccess) return 0;
     // (the API can overstate what the hardware admits by one work-group per CU, MI355X_MICROARCH.md "Residency": count one less)
     return std::max(0, per_cu - 1) * cus;
 }
@@ -467,13 +473,19 @@ int launch_classify(const Arena &a, const CloudParams *d_params, const BatchIO &
             hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify<GG_POINT32, FRONT_SCAN_IN_CLASSIFY>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify<GG_POINT16, FRONT_ONE_LAUNCH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify<GG_POINT32, FRONT_ONE_LAUNCH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify<GG_POINT16, FRONT_THREE_LAUNCHES, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify<GG_POINT32, FRONT_THREE_LAUNCHES, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify<GG_POINT16, FRONT_SCAN_IN_CLASSIFY, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify<GG_POINT32, FRONT_SCAN_IN_CLASSIFY, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify<GG_POINT16, FRONT_ONE_LAUNCH, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_classify<GG_POINT32, FRONT_ONE_LAUNCH, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         });
     int shape = a.tune_front != FRONT_AUTO ? a.tune_front : FRONT_DEFAULT_SHAPE;
     int n_counters = 8;
     if (shape == FRONT_ONE_LAUNCH) {
         // a waiting work-group needs the rest of its cloud to start: with one ticket counter per XCD at most 8 clouds are partly
         // started, with a single counter one -- the device must hold more work-groups than those can have waiting
-        const int resident = front_resident_groups(lds);
+        const int resident = front_resident_groups(lds, a.slot_cfg_launch != 0);
         if (resident >= 8 * groups + 8) n_counters = 8;
         else if (resident >= groups + 1) n_counters = 1;
         else shape = FRONT_SCAN_IN_CLASSIFY;

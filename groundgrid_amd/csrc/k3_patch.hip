@@ -85,10 +85,9 @@ template <class F> GG_DEV float stream_tree25_eigen34(F get)
 // first half: the two weighted sums (:372-375) of a cell that passed the point-count test of :364-365 (k_patch computes the
 // count itself, as a box filter).  Everything that needs the LDS window.
 template <int S>
-GG_DEV void patch_sums(const Arena &a, const float (*pts)[LR], const float (*var)[LR], const float (*mnl)[LR], int lr, int lc, PatchCarry &pc)
+GG_DEV void patch_sums(const Arena &a, const DevConfig &cfg, const float (*pts)[LR], const float (*var)[LR], const float (*mnl)[LR], int lr, int lc, PatchCarry &pc)
 {
     constexpr int ci = S / 2;
-    const DevConfig &cfg = a.cfg;
     const bool e34 = a.eigen_reduction == GG_EIGEN_34_SSE;
     auto block_sum = [&](auto get) { return (S == 3) ? stream_tree9(get) : e34 ? stream_tree25_eigen34(get) : stream_tree25(get); };
     auto P = [&](int s) { return pts[lc - ci + s / S][lr - ci + s % S]; };
@@ -112,10 +111,9 @@ GG_DEV void patch_sums(const Arena &a, const float (*pts)[LR], const float (*var
 
 // second half (:360-393): the decision against the old cell, one block later
 // bits: the fresh map's written-cell bits (Arena::gp_bits of the slot), or null
-GG_DEV void detect_ground_patch_b(const Arena &a, const PatchCarry &pc, float2 *gp2, unsigned long long *bits)
+GG_DEV void detect_ground_patch_b(const DevConfig &cfg, const PatchCarry &pc, float2 *gp2, unsigned long long *bits)
 {
     if (!pc.live) return;
-    const DevConfig &cfg = a.cfg;
     const float oldConfidence = pc.old.y;   // :360
     const float oldGroundheight = pc.old.x; // :361
     const float pointsblockSum = pc.pointsblockSum, groundlevel = pc.groundlevel, maxVar = pc.maxVar;
@@ -155,7 +153,10 @@ constexpr int RING = 32, SLOTS = RING + 4, MAXTC = 256;
 // the layers are whatever the slot holds -- not what k_reduce left a moment ago -- so no block is skipped on the strength of the last
 // cloud's record counts, the S x S point count of :359 is summed in Eigen's order like the two weighted sums (a host-written `points`
 // layer need not hold integers), and only the cells of the quadrant `bounds` = {i_lo, i_hi, j_lo, j_hi} (:325-328) are visited.
-template <bool STAGE>
+// SC (SLOT_CFG): some cloud of the launch has its slot's own configuration.  The per-cell table holds the CONTEXT'S thresholds (.y, .z):
+// such a cloud takes only the geometry from it (.x expectedPoints, .w the layer element) and computes the threshold of :364-365 and
+// varThresholdsq of :369 per cell, with the binary64 operations of rebuild_patch_table (gg_context.hip) in their order
+template <bool STAGE, bool SC = false>
 __global__ __launch_bounds__(256) void k_patch(const Arena a, const CloudParams *__restrict__ params, int n_bands, int blocks_per_segment, const int4 bounds)
 {
     __shared__ __attribute__((aligned(16))) float pts[SLOTS][LR], var[SLOTS][LR], mnl[SLOTS][LR]; // (LR * 4 bytes = 9 x 16: every row quad is 16-byte aligned)
@@ -173,6 +174,11 @@ __global__ __launch_bounds__(256) void k_patch(const Arena a, const CloudParams 
     const uint32_t item = xcd_contiguous_item(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
     const int cloud = (int)(item / gridDim.x), band = (int)(item % gridDim.x) % n_bands, segment = (int)(item % gridDim.x) / n_bands;
     const CloudParams cp = params[cloud];
+    DevConfig own_cfg;
+    if (SC) load_cloud_config(a, cp.cfg_index, own_cfg);
+    const DevConfig &cfg = SC ? own_cfg : a.cfg;
+    const bool own_thresholds = SC && __builtin_amdgcn_readfirstlane(cp.cfg_index) >= 0;
+    const double res2 = (double)a.g.resolution_f * (double)a.g.resolution_f;
     const int rows = a.g.rows, cols = a.g.cols;
     const int r0 = HALO + band * PR; // first output row of the band
     const int b_first = segment * blocks_per_segment;
@@ -240,7 +246,19 @@ __global__ __launch_bounds__(256) void k_patch(const Arena a, const CloudParams 
             const int jj = HALO + PC * b + tcl;
             const bool v = i < rows && jj < cols && (!STAGE || (i >= bounds.x && i < bounds.y && jj >= bounds.z && jj < bounds.w));
             const float4 e = a.patch_table[v ? (size_t)i + (size_t)jj * rows : (size_t)0]; // :358, :334, :364, :369 and the layer element
-            cell_next = make_float4(e.x, v ? e.y : __builtin_inff(), e.z, e.w); // (no such cell: never visited)
+            float thr_y = e.y, var_z = e.z;
+            if (SC && own_thresholds) { // (uniform) rebuild_patch_table for this cloud's configuration
+                const bool visited = i >= 2 && jj >= 2 && !(i >= 2 * (cols / 2) - 2 || jj >= rows - 2);
+                const double di = (double)i - (double)rows / 2.0, dj = (double)jj - (double)cols / 2.0;
+                const float sqdist = (float)((di * di + dj * dj) * res2);                  // :332
+                const bool near = (double)sqdist <= cfg.patch_size_change_distance_sq;     // :334
+                const double S = near ? 3.0 : 5.0;
+                const double thr = std_max(floor(cfg.gpd_min_point_count_threshold * S * (double)e.x), 3.0); // :364
+                const float thr_f = (float)thr;
+                thr_y = !visited || !(thr < 16777216.0) ? __builtin_inff() : (near ? -thr_f : thr_f);
+                var_z = (float)std_min(std_max((double)sqdist * cfg.distance_factor_sq, cfg.minimum_distance_factor_sq), cfg.minimum_distance_factor_x10_sq); // :369
+            }
+            cell_next = make_float4(e.x, v ? thr_y : __builtin_inff(), var_z, e.w); // (no such cell: never visited)
         }
         const int gr = r0 - HALO + q_lr, gcol = first_col + q_lc;
         const bool ok = q_lc < n_cols && gr < rows && gcol < cols;
@@ -292,7 +310,7 @@ __global__ __launch_bounds__(256) void k_patch(const Arena a, const CloudParams 
         req_cols = nb == b + 1 ? PC : LC;
         request(nb, req_first, req_cols);
         __syncthreads();
-        detect_ground_patch_b(a, consume, gp2, bits); // the previous block's cell: its old (ground, confidence) has arrived meanwhile
+        detect_ground_patch_b(cfg, consume, gp2, bits); // the previous block's cell: its old (ground, confidence) has arrived meanwhile
         consume.live = false;
 
         const int base = (PC * b) & (RING - 1); // 0, 8, 16 or 24: the window is slots base .. base + LC - 1
@@ -337,9 +355,9 @@ __global__ __launch_bounds__(256) void k_patch(const Arena a, const CloudParams 
         group_fence();
         if (pass) {
             if (near)
-                patch_sums<3>(a, pts + base, var + base, mnl + base, lr, lc, produce);
+                patch_sums<3>(a, cfg, pts + base, var + base, mnl + base, lr, lc, produce);
             else
-                patch_sums<5>(a, pts + base, var + base, mnl + base, lr, lc, produce);
+                patch_sums<5>(a, cfg, pts + base, var + base, mnl + base, lr, lc, produce);
         }
         // The next block's deposit overwrites column slots.  When it is the neighbour, its 8 new columns go to the slots BEHIND this
         // window (the ring holds 32: 12 of this window + 8 new ones never meet), so wavefronts without cells in the weighted sums go
@@ -356,8 +374,8 @@ __global__ __launch_bounds__(256) void k_patch(const Arena a, const CloudParams 
         if (b >= n_blocks) break;
         block_step(c1, c0);
     }
-    detect_ground_patch_b(a, c0, gp2, bits);
-    detect_ground_patch_b(a, c1, gp2, bits);
+    detect_ground_patch_b(cfg, c0, gp2, bits);
+    detect_ground_patch_b(cfg, c1, gp2, bits);
 }
 
 void launch_patch(const Arena &a, const CloudParams *d_params, int n_clouds, hipStream_t s)
@@ -370,7 +388,8 @@ void launch_patch(const Arena &a, const CloudParams *d_params, int n_clouds, hip
     const int segments = std::max(1, std::min(n_blocks, 8192 / std::max(1, n_clouds * n_bands)));
     const int per_segment = (n_blocks + segments - 1) / segments;
     dim3 grid(n_bands * ((n_blocks + per_segment - 1) / per_segment), n_clouds);
-    hipLaunchKernelGGL(k_patch<false>, grid, dim3(256), 0, s, a, d_params, n_bands, per_segment, make_int4(0, 0, 0, 0));
+    if (a.slot_cfg_launch) hipLaunchKernelGGL((k_patch<false, true>), grid, dim3(256), 0, s, a, d_params, n_bands, per_segment, make_int4(0, 0, 0, 0));
+    else hipLaunchKernelGGL(k_patch<false>, grid, dim3(256), 0, s, a, d_params, n_bands, per_segment, make_int4(0, 0, 0, 0));
 }
 
 // :323 on its own: variance := m2 ./ (points + FLT_MIN) over the slot's live half columns (a dead one logically holds
@@ -405,7 +424,8 @@ void launch_patch_stage(const Arena &a, const CloudParams *d_params, int slot, i
     const int segments = std::max(1, std::min(n_blocks, 8192 / std::max(1, n_bands)));
     const int per_segment = (n_blocks + segments - 1) / segments;
     dim3 grid(n_bands * ((n_blocks + per_segment - 1) / per_segment), 1);
-    hipLaunchKernelGGL(k_patch<true>, grid, dim3(256), 0, s, a, d_params, n_bands, per_segment, b);
+    if (a.slot_cfg_launch) hipLaunchKernelGGL((k_patch<true, true>), grid, dim3(256), 0, s, a, d_params, n_bands, per_segment, b);
+    else hipLaunchKernelGGL(k_patch<true>, grid, dim3(256), 0, s, a, d_params, n_bands, per_segment, b);
 }
 
 } // namespace gg

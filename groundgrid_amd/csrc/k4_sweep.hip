@@ -634,8 +634,10 @@ template <bool DBG> GG_DEV void run_export(const Params &P, const LdsMap &L, Dev
 // throughput launches -- one work-group per cloud -- are compiled without any of that.
 // FRESH: every map of the launch is fresh (gg_internal.h Arena::gp_bits; no split steps): a variant of its own --
 // the work-groups of a throughput launch share the instruction cache, a kernel that carried both step codes was the slower one for both
-template <bool DBG, bool PARTS, bool FRESH = false>
-__global__ __launch_bounds__(1024, 5) void k_sweep(const Arena a, const Params P, const CloudParams *__restrict__ params, int n_clouds, int n_parts_rt,
+// SC (SLOT_CFG): some cloud of the launch has its slot's own configuration: the decay of :463-464 (decrease, its inverse and the fast /
+// exact split) is the cloud's -- three values per work-group, uniform, in scalar registers
+template <bool DBG, bool PARTS, bool FRESH = false, bool SC = false>
+__global__ __launch_bounds__(1024, 5) void k_sweep(const Arena a, const Params P_arg, const CloudParams *__restrict__ params, int n_clouds, int n_parts_rt,
                                                    unsigned long long *dbg)
 {
     const int n_parts = PARTS ? n_parts_rt : 1;
@@ -660,7 +662,7 @@ __global__ __launch_bounds__(1024, 5) void k_sweep(const Arena a, const Params P
         __syncthreads();
         id = s_sync[0];
         epoch = s_sync[1];
-        if (P.debug_fault == 1) id = gridDim.x - 1u - id;
+        if (P_arg.debug_fault == 1) id = gridDim.x - 1u - id;
     }
     int cloud, part;
     {
@@ -675,9 +677,19 @@ __global__ __launch_bounds__(1024, 5) void k_sweep(const Arena a, const Params P
             cloud = full + rem % tail;
         }
     }
-    const int g0 = part * P.gpw, g1 = min(g0 + P.gpw, P.groups);
-    const LdsMap L = lds_layout(P.c, P.groups, g0, g1, P.split_steps != 0);
+    const int g0 = part * P_arg.gpw, g1 = min(g0 + P_arg.gpw, P_arg.groups);
+    const LdsMap L = lds_layout(P_arg.c, P_arg.groups, g0, g1, P_arg.split_steps != 0);
     const CloudParams &cp = params[cloud];
+    Params P_own;
+    if (SC) {
+        P_own = P_arg;
+        DevConfig c;
+        load_cloud_config(a, cp.cfg_index, c);
+        P_own.decrease = c.occupied_cells_decrease_factor;
+        P_own.inv_decrease = c.inv_decrease;
+        P_own.decay_fast = c.decay_fast;
+    }
+    const Params &P = SC ? P_own : P_arg;
     float2 *gp2 = gp2_ptr(a, cp.slot);
     float *percall = percall_ptr(a, cp.slot);
     const int nthreads = blockDim.x;
@@ -834,7 +846,8 @@ void launch_sweep(const Arena &a, const Params &P_in, const CloudParams *d_param
     // (the pair sweep on the layer in place, sweep_pairb.h / k4b_sweep_pair_batch.hip, takes a launch only when asked to -- tuning
     // sweep_pair = 4: correct on every geometry, but at 1024 clouds per launch 1.12 ms where k_sweep takes 0.89 ms)
     if (!dbg && a.tune_sweep_pair != 2 && !k_sweep_forced) {
-        if (a.tune_sweep_pair == 4 && launch_sweep_pair_batch(a, P_in, d_params, n_clouds, s)) return;
+        // (k4b takes the decay by value: never a launch with clouds of their own configuration -- those keep k_sweep)
+        if (a.tune_sweep_pair == 4 && !a.slot_cfg_launch && launch_sweep_pair_batch(a, P_in, d_params, n_clouds, s)) return;
         if (a.tune_sweep_pair != 4 && launch_sweep_pair(a, P_in, d_params, n_clouds, s)) return;
     }
     Params P = P_in;
@@ -874,6 +887,10 @@ void launch_sweep(const Arena &a, const Params &P_in, const CloudParams *d_param
             hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
             hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
             hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
         });
     P.fresh_cell = a.gp_fresh_cell;
     P.poll_cap = a.tune_sweep_poll_cap > 0 ? a.tune_sweep_poll_cap : 1 << 22; // (x ~0.2 us: about a second)
@@ -881,7 +898,16 @@ void launch_sweep(const Arena &a, const Params &P_in, const CloudParams *d_param
     const int threads = P.split_steps ? 12 * 64 : (4 * P.waves_per_side + 2 + (n_parts > 1 ? 2 : 0)) * 64; // (+ importer and exporter)
     if (dbg) // (GG_SWEEP_TIMING: the instrumented twin)
         hipLaunchKernelGGL((k_sweep<true, true>), dim3(n_clouds * n_parts), dim3(threads), lds, s, a, P, d_params, n_clouds, n_parts, dbg);
-    else if (a.fresh_launch && !P.split_steps && n_parts == 1)
+    else if (a.slot_cfg_launch) { // (the same shapes, each with the decay of every cloud's own configuration)
+        if (a.fresh_launch && !P.split_steps && n_parts == 1)
+            hipLaunchKernelGGL((k_sweep<false, false, true, true>), dim3(n_clouds), dim3(threads), lds, s, a, P, d_params, n_clouds, n_parts, dbg);
+        else if (a.fresh_launch && !P.split_steps)
+            hipLaunchKernelGGL((k_sweep<false, true, true, true>), dim3(n_clouds * n_parts), dim3(threads), lds, s, a, P, d_params, n_clouds, n_parts, dbg);
+        else if (n_parts > 1)
+            hipLaunchKernelGGL((k_sweep<false, true, false, true>), dim3(n_clouds * n_parts), dim3(threads), lds, s, a, P, d_params, n_clouds, n_parts, dbg);
+        else
+            hipLaunchKernelGGL((k_sweep<false, false, false, true>), dim3(n_clouds * n_parts), dim3(threads), lds, s, a, P, d_params, n_clouds, n_parts, dbg);
+    } else if (a.fresh_launch && !P.split_steps && n_parts == 1)
         hipLaunchKernelGGL((k_sweep<false, false, true>), dim3(n_clouds), dim3(threads), lds, s, a, P, d_params, n_clouds, n_parts, dbg);
     else if (a.fresh_launch && !P.split_steps)
         hipLaunchKernelGGL((k_sweep<false, true, true>), dim3(n_clouds * n_parts), dim3(threads), lds, s, a, P, d_params, n_clouds, n_parts, dbg);

@@ -57,9 +57,28 @@ size_t sweep_pair_rec_floats(const Params &P)
 // ---------------------------------------------------------------------------------------------------------------------
 // the preparation
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_sweep_records(const Arena a, const Params P, const sp::Plan pl, const CloudParams *__restrict__ params)
+// SC (SLOT_CFG): some cloud of the launch has its slot's own configuration -- the decay of :463-464 is the cloud's (k_sweep_records and
+// k_sweep_finish decay confidences; k_sweep_pair only streams what the records hold)
+template <bool SC>
+GG_DEV const Params &cloud_params(const Arena &a, const Params &P_arg, const CloudParams &cp, Params &P_own)
+{
+    if (SC) {
+        P_own = P_arg;
+        DevConfig c;
+        load_cloud_config(a, cp.cfg_index, c);
+        P_own.decrease = c.occupied_cells_decrease_factor;
+        P_own.inv_decrease = c.inv_decrease;
+        P_own.decay_fast = c.decay_fast;
+    }
+    return SC ? P_own : P_arg;
+}
+
+template <bool SC>
+GG_DEV void sweep_records(const Arena &a, const Params &P_arg, const sp::Plan &pl, const CloudParams *__restrict__ params)
 {
     const CloudParams &cp = params[blockIdx.y];
+    Params P_own;
+    const Params &P = cloud_params<SC>(a, P_arg, cp, P_own);
     const float2 *gp2 = gp2_ptr(a, cp.slot);
     float *rec = a.sweep_rec + (size_t)blockIdx.y * a.sweep_rec_stride;
     const RecLayout RL = rec_layout(pl, P.rings);
@@ -550,9 +569,12 @@ __global__ __launch_bounds__(THREADS) void k_sweep_pair(const Arena a, const Par
 }
 
 // the streamed heights into the layer: one thread per layer element (coalesced; padding elements hold no cell), plus :147 and the centre
-__global__ __launch_bounds__(256) void k_sweep_finish(const Arena a, const Params P, const sp::Plan pl, const CloudParams *__restrict__ params)
+template <bool SC>
+GG_DEV void sweep_finish(const Arena &a, const Params &P_arg, const sp::Plan &pl, const CloudParams *__restrict__ params)
 {
     const CloudParams &cp = params[blockIdx.y];
+    Params P_own;
+    const Params &P = cloud_params<SC>(a, P_arg, cp, P_own);
     float2 *gp2 = gp2_ptr(a, cp.slot);
     const float *rec = a.sweep_rec + (size_t)blockIdx.y * a.sweep_rec_stride;
     const RecLayout RL = rec_layout(pl, P.rings);
@@ -584,6 +606,11 @@ __global__ __launch_bounds__(256) void k_sweep_finish(const Arena a, const Param
     }
 }
 
+__global__ __launch_bounds__(256) void k_sweep_records(const Arena a, const Params P, const sp::Plan pl, const CloudParams *__restrict__ params) { sweep_records<false>(a, P, pl, params); }
+__global__ __launch_bounds__(256) void k_sweep_records_sc(const Arena a, const Params P, const sp::Plan pl, const CloudParams *__restrict__ params) { sweep_records<true>(a, P, pl, params); }
+__global__ __launch_bounds__(256) void k_sweep_finish(const Arena a, const Params P, const sp::Plan pl, const CloudParams *__restrict__ params) { sweep_finish<false>(a, P, pl, params); }
+__global__ __launch_bounds__(256) void k_sweep_finish_sc(const Arena a, const Params P, const sp::Plan pl, const CloudParams *__restrict__ params) { sweep_finish<true>(a, P, pl, params); }
+
 // returns false when the launch cannot take the pair sweep (the caller falls back to k_sweep)
 bool launch_sweep_pair(const Arena &a, const Params &P, const CloudParams *d_params, int n_clouds, hipStream_t s)
 {
@@ -611,11 +638,13 @@ bool launch_sweep_pair(const Arena &a, const Params &P, const CloudParams *d_par
     const void *fn = both ? (const void *)k_sweep_pair<true, 12, 512> : (const void *)k_sweep_pair<false, 12, 512>;
     if (lds > 64 * 1024) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); // (idempotent; big maps only)
     const size_t n_rec = (size_t)pl.total_steps / 4 * 64 + 2 * (size_t)P.rings;
-    hipLaunchKernelGGL(k_sweep_records, dim3((unsigned)((n_rec + 255) / 256), (unsigned)n_clouds), dim3(256), 0, s, a, P, pl, d_params);
+    if (a.slot_cfg_launch) hipLaunchKernelGGL(k_sweep_records_sc, dim3((unsigned)((n_rec + 255) / 256), (unsigned)n_clouds), dim3(256), 0, s, a, P, pl, d_params);
+    else hipLaunchKernelGGL(k_sweep_records, dim3((unsigned)((n_rec + 255) / 256), (unsigned)n_clouds), dim3(256), 0, s, a, P, pl, d_params);
     const dim3 grid(both ? n_clouds : 2 * n_clouds), block(waves * 64);
     if (both) hipLaunchKernelGGL((k_sweep_pair<true, 12, 512>), grid, block, lds, s, a, P, pl, d_params, W);
     else hipLaunchKernelGGL((k_sweep_pair<false, 12, 512>), grid, block, lds, s, a, P, pl, d_params, W);
-    hipLaunchKernelGGL(k_sweep_finish, dim3((unsigned)((P.gl.elems + 255) / 256), (unsigned)n_clouds), dim3(256), 0, s, a, P, pl, d_params);
+    if (a.slot_cfg_launch) hipLaunchKernelGGL(k_sweep_finish_sc, dim3((unsigned)((P.gl.elems + 255) / 256), (unsigned)n_clouds), dim3(256), 0, s, a, P, pl, d_params);
+    else hipLaunchKernelGGL(k_sweep_finish, dim3((unsigned)((P.gl.elems + 255) / 256), (unsigned)n_clouds), dim3(256), 0, s, a, P, pl, d_params);
     return true;
 }
 

@@ -53,7 +53,8 @@ GG_DEV void store_pc2_record(uint8_t *out, int32_t idx, uint32_t x, uint32_t y, 
 
 // PC2: the instantiation that also emits the returned cloud as 18-byte PointCloud2 records (gg_batch.d_out_pc2) -- a twin, so that the
 // throughput kernel keeps its registers
-template <int FMT, bool PC2>
+// SC (SLOT_CFG): some cloud of the launch has its slot's own configuration: the three thresholds of :155-171 are the cloud's
+template <int FMT, bool PC2, bool SC = false>
 __global__ __launch_bounds__(256) void k_label(const Arena a, const CloudParams *__restrict__ params, const BatchIO io)
 {
     // XCD-aware (gg_device.h): the chunks of one cloud run on one XCD, so its layers / records are cached in ONE L2
@@ -98,7 +99,9 @@ __global__ __launch_bounds__(256) void k_label(const Arena a, const CloudParams 
     uint32_t ign_base = totals[0] + ce[1];
     uint32_t outl_base = totals[0] + totals[1] + ce[2];
 
-    const DevConfig &cfg = a.cfg;
+    DevConfig own_cfg;
+    if (SC) load_cloud_config(a, cp.cfg_index, own_cfg);
+    const DevConfig &cfg = SC ? own_cfg : a.cfg;
     const int base = chunk * a.PW;
     const int end = min(base + a.PW, n);
     // :171 tolerance = max(min(t, thres), obs), t = (5 mdf * dist) / variance * thres.  On real data t is far above
@@ -269,7 +272,15 @@ void launch_label(const Arena &a, const CloudParams *d_params, const BatchIO &io
     if (nch == 0) nch = 1; // still publish the (all-zero) counts
     dim3 grid((nch + 3) / 4, n_clouds);
     const size_t lds = (size_t)a.g.T * sizeof(uint32_t);
-    if (io.point_format == GG_POINT16) {
+    if (a.slot_cfg_launch) {
+        if (io.point_format == GG_POINT16) {
+            if (io.d_out_pc2) hipLaunchKernelGGL((k_label<GG_POINT16, true, true>), grid, dim3(256), lds, s, a, d_params, io);
+            else hipLaunchKernelGGL((k_label<GG_POINT16, false, true>), grid, dim3(256), lds, s, a, d_params, io);
+        } else {
+            if (io.d_out_pc2) hipLaunchKernelGGL((k_label<GG_POINT32, true, true>), grid, dim3(256), lds, s, a, d_params, io);
+            else hipLaunchKernelGGL((k_label<GG_POINT32, false, true>), grid, dim3(256), lds, s, a, d_params, io);
+        }
+    } else if (io.point_format == GG_POINT16) {
         if (io.d_out_pc2)
             hipLaunchKernelGGL((k_label<GG_POINT16, true>), grid, dim3(256), lds, s, a, d_params, io);
         else

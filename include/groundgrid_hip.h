@@ -155,6 +155,19 @@ void gg_destroy(gg_context *ctx);
  * the context keeps its previous configuration entirely. */
 int gg_set_config(gg_context *ctx, const gg_config *cfg);
 int gg_get_config(const gg_context *ctx, gg_config *cfg);
+/* Per-map configuration: every GroundSegmentation object of the reference has its own setConfig, so one context (one launch) may
+ * mix them -- a 32-beam and a 64-beam vehicle in one fleet, or K candidate configurations of a parameter sweep as K slots.
+ * slots[k] (or first_slot + k when slots == NULL) get their own configuration cfgs[k]; cfgs == NULL: those slots follow the
+ * context's configuration (gg_set_config) again.  Blocks like gg_set_config: batches in flight finish with the old settings,
+ * everything enqueued after the call returns uses the new ones.  GG_ERR_CAPACITY for a slot outside the context,
+ * GG_ERR_INVALID for duplicates / n < 0 / null ctx; on any error no slot's configuration changes.  n == 0 is GG_OK.
+ * A slot without its own configuration follows gg_set_config, later calls included; one with its own keeps it through
+ * gg_set_config, gg_reset_map(s) and gg_move_map(s).  Every entry point that runs the path (or a stage of it) on a slot uses the
+ * slot's configuration; gg_get_config still returns the context's.  thread_count is accepted and ignored. */
+int gg_set_slot_configs(gg_context *ctx, int n, const int32_t *slots, int first_slot, const gg_config *cfgs);
+/* the configuration slot `slot` runs with; *own = 1 if it has its own, 0 if it follows the context (own may be NULL) */
+int gg_get_slot_config(const gg_context *ctx, int slot, gg_config *cfg, int *own);
+#define GG_HAS_SLOT_CONFIG 1
 int gg_set_flags(gg_context *ctx, unsigned flags);
 
 /* Third-party conventions the reference inherits from the libraries it is built against (versions unpinned by the
