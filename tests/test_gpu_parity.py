@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 from groundgrid_amd import api, synth  # noqa: E402
 from oracle import oracle  # noqa: E402
+from tests import edge_scenes  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 ORIGIN0 = (0.0, 0.0, 0.0)
@@ -89,15 +90,11 @@ def test_hdl64_full_size_three_frames():
 def test_line_of_sight_walk_many_candidates():
     """k_classify runs the ray walk of :246-275 cooperatively (64 steps of one point per wavefront pass); it must
     decide exactly like the serial loop for short and long rays, rays leaving the map, and candidates in every lane."""
-    base = synth.hdl64_cloud(seed=12, n_az=900)
-    rng = np.random.default_rng(12)
-    low = synth.clone_cloud(base)
-    sel = rng.random(len(low)) < 0.2            # one point in five dives 0.3 .. 2.5 m under the surface
-    low["z"][sel] -= rng.uniform(0.3, 2.5, sel.sum()).astype(np.float32)
+    base, low = edge_scenes.line_of_sight_clouds()
     seg = api.GroundSegmentation().init(120.0, 0.33, n_slots=1, max_points=len(base))
     ref = oracle.OracleMap(120.0, 0.33)
     n_out = 0
-    for f, (cloud, origin) in enumerate([(base, ORIGIN0), (low, ORIGIN0), (low, (7.5, -3.0, 0.4)), (low, (-80.0, 20.0, 1.0))]):
+    for f, (cloud, origin) in enumerate(zip([base, low, low, low], edge_scenes.LINE_OF_SIGHT_ORIGINS)):
         _, labels, index = seg.filter_cloud(cloud, origin, -1.73, return_details=True)
         r = ref.filter_cloud(cloud, origin, -1.73)
         cls, _ = seg.point_classes(len(cloud))
@@ -131,11 +128,7 @@ def test_unstructured_cloud_moved_map_and_origin():
 
 def test_dense_single_cells_and_ties():
     # thousands of points in a handful of cells: long ordered Welford chains, LDS staging over several chunks
-    rng = np.random.default_rng(4)
-    n = 30000
-    xy = rng.choice(np.array([5.0, 5.2, 5.4, 7.7]), size=(n, 2)) + rng.uniform(0, 0.05, size=(n, 2))
-    z = rng.normal(-1.7, 0.05, size=n)
-    run_pair(synth.make_cloud(np.column_stack([xy, z]), ring=rng.integers(0, 64, n)), frames=2)
+    run_pair(edge_scenes.dense_single_cells_and_ties().cloud, frames=2)
 
 
 def test_config_variations():
@@ -160,21 +153,14 @@ def test_confidence_decay_factor_fast_and_exact_branches(factor):
 
 
 def test_edge_cases():
-    pts = np.array([[5, 5, -1], [1, 1, -1], [5, 5, -1], [500, 0, -1], [np.nan, 0, -1], [5, 5, np.nan], [-59.9, -59.9, -1],
-                    [np.inf, 1, 0], [59.99, 59.99, 0.5], [0, 0, 3], [3, -59.5, -1.6], [5, 5, -np.inf], [-1e30, 2, 0]],
-                   dtype=np.float32)
-    cloud = synth.make_cloud(pts, ring=[0, 0, 2000, 0, 0, 0, 0, 0, 1, 2, 3, 4, 5])
-    run_pair(cloud, frames=2)
+    run_pair(edge_scenes.edge_cases().cloud, frames=2)
     # a SIGNALLING NaN height between two ordinary returns of one cell (np.nan is a quiet one): std::max(mx, z) of :307 must leave the
     # cell's maximum alone (k2_reduce.hip quiet)
-    snan = synth.make_cloud(np.array([[5, 5, -1.2], [5.01, 5.01, 0.0], [5.02, 5.0, -1.1], [7, 7, 0.0], [7.01, 7.0, -1.0]], dtype=np.float32))
-    z = snan["z"].view(np.uint32)
-    z[1] = 0x7FA00000
-    z[3] = 0xFF800001
+    snan = edge_scenes.signalling_nan_heights().cloud
     assert np.isnan(snan["z"][1]) and np.isnan(snan["z"][3])
     run_pair(snan, frames=2)
-    run_pair(synth.empty_cloud(0), frames=2)
-    run_pair(synth.make_cloud(np.array([[900.0, 900.0, 0.0]], dtype=np.float32)), frames=1)  # everything outside
+    run_pair(edge_scenes.empty().cloud, frames=2)
+    run_pair(edge_scenes.all_outside().cloud, frames=1)  # everything outside
 
 
 def test_initial_ground_height_nonzero():
@@ -830,42 +816,21 @@ def test_config4_full_2M_points_one_frame():
 def test_index_fast_path_boundaries():
     """K1 replaces the f64 divide of getIndex by a multiply + exactness check (gg_device.h index_of); points that sit
     exactly on / next to cell boundaries (where the exact division must decide) have to match the oracle too."""
-    m = oracle.OracleMap(120.0, 0.33)
-    half, res = 0.5 * m.length[0], m.resolution
-    xs = []
-    for k in (0, 1, 2, 17, 181, 182, 183, 300, 362, 363):
-        edge = half - k * res  # x of the boundary between rows k-1 and k (exact in double)
-        f = np.float32(edge)
-        xs += [f, np.nextafter(f, np.float32(np.inf)), np.nextafter(f, np.float32(-np.inf))]
-    xs = np.array(xs, dtype=np.float32)
-    X, Y = np.meshgrid(xs, xs)
-    pts = np.column_stack([X.ravel(), Y.ravel(), np.full(X.size, -1.7, dtype=np.float32)])
-    run_pair(synth.make_cloud(pts), frames=1)
+    run_pair(edge_scenes.index_fast_path_boundaries().cloud, frames=1)
     # a == 0 exactly: map position chosen so that (x - L/2) - pos == 0 for x = 5 -> the exact-division path
-    pos = (float(np.float64(np.float32(5.0)) - half), float(np.float64(np.float32(-7.25)) - half))
-    pts = np.array([[5.0, -7.25, -1.0], [5.0, -7.0, -1.0], [4.9, -7.25, -1.2], [3.0, -9.0, -1.1]], dtype=np.float32)
-    run_pair(synth.make_cloud(pts), pos=pos, origin=(pos[0], pos[1], 0.0), frames=1)
+    sc = edge_scenes.index_exact_division()
+    pos = sc.pos
+    run_pair(sc.cloud, pos=pos, origin=(pos[0], pos[1], 0.0), frames=1)
 
 
-@pytest.mark.parametrize("pos", [(0.0, 0.0), (500000.3, 5800000.7), (-1.0e7, 3.3e6), (9.0e8, -9.9e8), (3.0e9, -2.0e10), (1.0e15, 1.0e15)])
+@pytest.mark.parametrize("pos", edge_scenes.MAP_BORDER_POSITIONS)
 def test_map_border_points_near_and_far_from_the_frame_origin(pos):
     """isInside (grid_map GridMapMath.cpp checkIfPositionWithinMap, called from src/GroundSegmentation.cpp:230) and getIndex at
     the map's four borders: points on, next to and beyond them, at UTM-sized map positions and at positions so far out that an
     ulp of the coordinates is larger than a cell, have to match the oracle.  (Written for an experiment that took the isInside
     test only for points whose index is not strictly interior -- tools/experiments/k1_interior_index_shortcut.patch: exact, no
     faster -- and kept for the cases.)"""
-    m = oracle.OracleMap(120.0, 0.33, pos=pos)
-    half, res = 0.5 * m.length[0], m.resolution
-    offs = []
-    for k in (-2, -1, 0, 1, 2, 3, 180, 361, 362, 363, 364, 365):
-        for d in (0.0, 1e-7, -1e-7, 0.5 * res):
-            offs.append(half - k * res + d)
-    offs = np.array(offs + [1e30, -1e30, np.inf, np.nan])
-    xs = (np.float64(pos[0]) + offs).astype(np.float32)
-    ys = (np.float64(pos[1]) + offs).astype(np.float32)
-    X, Y = np.meshgrid(xs, ys)
-    pts = np.column_stack([X.ravel(), Y.ravel(), np.full(X.size, -1.7, dtype=np.float32)])
-    run_pair(synth.make_cloud(pts), pos=pos, origin=(np.float32(pos[0]), np.float32(pos[1]), 0.0), frames=2)
+    run_pair(edge_scenes.map_border(pos).cloud, pos=pos, origin=(np.float32(pos[0]), np.float32(pos[1]), 0.0), frames=2)
 
 
 # ---------------------------------------------------------------- N1: map follows the vehicle (GroundGrid::update)
@@ -1109,11 +1074,7 @@ def test_corrupt_z_does_not_hang_the_device():
     deviation shared with the oracle); the call returns promptly and still matches."""
     import time
 
-    good = synth.hdl64_cloud(seed=2, n_az=300)
-    bad = synth.make_cloud(np.array([[4.0, 4.0, -1e9], [10.0, -3.0, -3e38], [0.2, 25.0, -1e7], [7.0, 7.0, -70000.0]], dtype=np.float32))
-    cloud = synth.empty_cloud(len(good) + len(bad))
-    cloud[: len(good)] = good
-    cloud[len(good):] = bad
+    cloud = edge_scenes.corrupt_z_cloud()
     seg = api.GroundSegmentation().init(120.0, 0.33, n_slots=1, max_points=len(cloud))
     ref = oracle.OracleMap(120.0, 0.33)
     for f in range(3):
@@ -1175,28 +1136,8 @@ def test_reduce_tile_classes_long_cells_and_quotient_fallbacks():
     """k_reduce's corner cases: tiles with exactly 512 / 513 records (wavefront path / work-group path), a cell with more points
     than the reciprocal table holds (IEEE tail), constant heights (every delta is 0: all quotients take the exact path),
     heights so small that quotients fall below 2^-100, huge heights, and a second frame on the live tiles."""
-    rng = np.random.default_rng(77)
-    res = 0.33
-    parts = []
-
-    def cell_points(cx, cy, n, z):
-        xy = np.column_stack([np.full(n, cx), np.full(n, cy)]) + rng.uniform(0.01, res - 0.01, size=(n, 2))
-        return np.column_stack([xy, z])
-
-    # one cell with 5000 points (> RCAP = 4080), noisy heights
-    parts.append(cell_points(6 * res, 6 * res, 5000, rng.normal(-1.7, 0.03, 5000)))
-    # one cell, constant height: mean == planeDist from the second point on
-    parts.append(cell_points(-9 * res, 4 * res, 700, np.full(700, -1.5, np.float32)))
-    # tiny and huge heights
-    parts.append(cell_points(12 * res, -7 * res, 300, rng.normal(0, 1, 300) * 1e-36))
-    parts.append(cell_points(-14 * res, -11 * res, 300, rng.normal(0, 1, 300) * 1e30))
-    # a tile of 16x16 cells holding exactly 512 records and one holding 513 (spread over its cells)
-    for tile_x, count in ((40, 512), (60, 513)):
-        xy = np.column_stack([rng.uniform(tile_x * res + 0.02, (tile_x + 15) * res, count), rng.uniform(-90 * res, -76 * res, count)])
-        parts.append(np.column_stack([xy, rng.normal(-1.7, 0.05, count)]))
-    pts = np.concatenate(parts).astype(np.float32)
-    rng.shuffle(pts)
-    run_pair(synth.make_cloud(pts, ring=rng.integers(0, 64, len(pts))), frames=2)
+    run_pair(edge_scenes.reduce_tile_classes_long_cells_and_quotient_fallbacks().cloud, frames=2)
+    run_pair(edge_scenes.exact_tile_records().cloud, frames=2)  # (the 512 / 513 regions above straddle tile borders)
 
 
 def test_reduce_recurrence_rare_cases_off_the_fast_path():
@@ -1204,54 +1145,16 @@ def test_reduce_recurrence_rare_cases_off_the_fast_path():
     that break either are redone with the reference's expressions.  Cells whose running mean is or returns to exactly zero,
     NaN / +-inf heights at every position of a four-point block, -0.0, in a light tile (one wavefront), in a dense tile
     (work-group, count-sorted lanes) and in a tile whose fullest cells run one chain per wavefront."""
-    rng = np.random.default_rng(123)
-    res = 0.33
-    seqs = [
-        [0.0, 0.0, 0.5, -0.5, 0.25, 0.0, 1.0],
-        [1.0, -1.0, 3.0, 0.125, -0.125],          # the mean returns to exactly 0 after the second point
-        [-0.0, 2.0, -2.0, -0.0, 0.0, 7.0],
-        [2.0, 2.0, -4.0, 1.0, 1.0, 1.0, 1.0, -4.0],
-        [-1.7, np.inf, -1.6, -np.inf, -1.5, -1.4],
-    ]
-    for k in range(9):                               # a NaN at position k
-        z = list(rng.normal(-1.7, 0.02, 12))
-        z[k] = np.nan
-        seqs.append(z)
-    long_cell = list(rng.normal(-1.7, 0.02, 40))    # >= 24 points: the tile's fullest cells run one chain per wavefront
-    long_cell[17] = 0.0
-    long_cell[23] = np.nan
-    long_cell[24] = 0.0
-    long_cell[25] = 0.0
-    seqs.append(long_cell)
-
-    def region(x0, y0, fillers):
-        """the sequences in cells (x0 + k, y0) ... of one 16x16 tile, `fillers` more points spread over the tile's other rows"""
-        parts = []
-        for k, z in enumerate(seqs):
-            cx, cy = (x0 + k % 16) * res, (y0 + k // 16) * res
-            xy = np.column_stack([np.full(len(z), cx), np.full(len(z), cy)]) + rng.uniform(0.02, res - 0.02, size=(len(z), 2))
-            parts.append(np.column_stack([xy, np.asarray(z, np.float64)]))
-        if fillers:
-            xy = np.column_stack([rng.uniform(x0 * res + 0.02, (x0 + 15) * res, fillers), rng.uniform((y0 + 3) * res, (y0 + 12) * res, fillers)])
-            parts.append(np.column_stack([xy, rng.normal(-1.7, 0.05, fillers)]))
-        return np.concatenate(parts)
-
-    # (a region straddles up to four tiles: enough fillers that its tiles leave the single-wavefront path / split their chains)
-    pts = np.concatenate([region(30, 30, 0), region(-70, 30, 3000), region(30, -70, 12000)]).astype(np.float32)
-    run_pair(synth.make_cloud(pts, ring=rng.integers(0, 64, len(pts))), frames=2)
+    run_pair(edge_scenes.reduce_recurrence_rare_cases().cloud, frames=2)
 
 
-@pytest.mark.parametrize("mdf,thres,obs", [(0.0005, 0.3, 0.1), (2e-5, 0.3, 0.1), (2e-6, 0.3, 0.1), (1e-7, 0.3, 0.1), (0.0005, 0.1, 0.3),
-                                           (0.0005, 0.0, 0.1), (-0.0005, 0.3, 0.1), (0.02, 0.3, 0.299)])
+@pytest.mark.parametrize("mdf,thres,obs", edge_scenes.LABEL_TOLERANCE_CONFIGS)
 def test_label_tolerance_branches(mdf, thres, obs):
     """k_label decides the clamp of the tolerance (:170-171) from the point's CELL (its distance from the origin to within
     0.75 cell) and reads x, y only when the two ends of that bound disagree.  Factors that put most points above the clamp,
     inside the band, below it; thresholds in the unusual order, zero, a negative factor; origin off the map centre."""
-    def edit(c):
-        c.minimum_distance_factor = mdf
-        c.miminum_point_height_threshold = thres
-        c.minimum_point_height_obstacle_threshold = obs
-    r = run_pair(synth.hdl64_cloud(seed=33, n_az=500), origin=(3.7, -2.2, 0.1), frames=2, cfg_edit=edit)
+    sc = edge_scenes.label_tolerance(mdf, thres, obs)
+    r = run_pair(sc.cloud, origin=sc.origin, frames=2, cfg_edit=sc.cfg_edit)
     assert len(np.unique(r["label"])) >= 2
 
 
@@ -1318,26 +1221,9 @@ def test_reset_maps_on_the_callers_stream_is_ordered_with_batches():
 def test_random_scenes_fuzz(seed):
     """Random geometry, random clusters (one of them packing tens of thousands of points into a single 16x16 tile), random map
     position / origin / base height, three frames: everything compared with the oracle."""
-    rng = np.random.default_rng(1000 + seed)
-    # (GroundSegmentation::init takes the dimension as size_t: whole metres)
-    length, resolution = [(20.0, 0.2), (30.0, 0.25), (40.0, 0.33), (50.0, 0.5), (64.0, 0.33), (80.0, 0.33), (45.0, 0.2), (33.0, 0.25)][
-        int(rng.integers(0, 8))]
-    n_clusters = int(rng.integers(3, 9))
-    parts = []
-    for k in range(n_clusters):
-        centre = rng.uniform(-0.55 * length, 0.55 * length, size=2)  # some clusters straddle or miss the map
-        spread = float(rng.choice([0.05, 0.3, 1.5, 6.0, 20.0]))
-        m = int(rng.integers(50, 40000 if k == 0 else 6000))
-        xy = centre + rng.normal(0, spread, size=(m, 2))
-        z = rng.normal(rng.uniform(-2.5, 0.5), rng.choice([0.0, 0.02, 0.4]), size=m)
-        parts.append(np.column_stack([xy, z]))
-    pts = np.concatenate(parts).astype(np.float32)
-    rng.shuffle(pts)
-    pos = tuple(np.round(rng.uniform(-3, 3, size=2), 2))
-    origin = (float(pos[0]) + float(rng.uniform(-1, 1)), float(pos[1]) + float(rng.uniform(-1, 1)), float(rng.uniform(-0.2, 0.2)))
-    cloud = synth.make_cloud(pts + np.array([pos[0], pos[1], 0.0], np.float32), ring=rng.integers(0, 64, len(pts)))
-    run_pair(cloud, length=length, resolution=resolution, pos=pos, origin=origin, base_z=float(rng.uniform(-2.0, -1.4)), frames=3,
-             odom_z=float(rng.uniform(-0.5, 0.5)))
+    sc = edge_scenes.random_scene(seed)
+    run_pair(sc.cloud, length=sc.length, resolution=sc.resolution, pos=sc.pos, origin=sc.origin, base_z=sc.base_z, frames=3,
+             odom_z=sc.odom_z)
 
 
 @pytest.mark.parametrize("wgs,waves", [(2, 0), (1, 0), (2, 1), (2, 3), (1, 2)])
