@@ -1,7 +1,8 @@
 /*
  * gg_oracle.c -- CPU restatement of GroundGrid's per-cloud hot path.  TEST INFRASTRUCTURE ONLY
- * (see gg_oracle.h).  PARITY UNPINNED: no reference test vectors exist and the reference cannot
- * be built in this image; every function below cites the reference lines it restates.
+ * (see gg_oracle.h).  Held bit for bit to the reference's own translation unit compiled against stand-ins
+ * (oracle/ref_build.py); PARITY UNPINNED for the third-party conventions, which no build in this image can
+ * settle; every function below cites the reference lines it restates.
  *
  * Build: gcc -O2 -std=c11 -ffp-contract=off -fno-fast-math -fexcess-precision=standard
  * (x86-64 SSE2 scalar math, FLT_EVAL_METHOD == 0, no FMA contraction: what `catkin build

@@ -5,9 +5,14 @@
  * bench.py's cpu_baseline leg may link or load it.  The product (libgroundgrid_hip.so)
  * never calls into it and has no CPU fallback.
  *
- * PARITY UNPINNED: the reference (dcmlr/groundgrid) ships no tests, golden vectors or
- * fixtures for this path, and it cannot be built in this image (it needs ROS Noetic,
- * grid_map_core, PCL, Eigen, tf2 -- none present, no network).  This restatement follows
+ * PINNED: the reference's own program text.  src/GroundSegmentation.cpp is compiled unmodified
+ * against functional stand-in headers (oracle/ref_shim/, oracle/ref_build.py) and this
+ * restatement is held to that build bit for bit on 67 scenes (tests/test_reference_build_cpu.py,
+ * tests/golden/ref_build_digests.json): the casts below are what a C++ compiler decides.
+ * PARITY UNPINNED: the third-party arithmetic.  The reference (dcmlr/groundgrid) ships no tests,
+ * golden vectors or fixtures for this path, and its package cannot be built in this image (it
+ * needs ROS Noetic, grid_map_core, PCL, Eigen, tf2 -- none present, no network); the stand-ins
+ * carry the same restated conventions as this file (tools/pin/ pins those).  This restatement follows
  * the reference source text line by line (citations below are into /root/reference) and
  * restates the two third-party pieces of arithmetic it relies on from their published
  * sources: grid_map_core 1.6.x (GridMapMath.cpp getIndexFromPosition /

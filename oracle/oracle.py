@@ -1,7 +1,8 @@
 """ctypes binding of the CPU oracle (oracle/libgg_oracle.so).  TEST INFRASTRUCTURE ONLY.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
-The product package (groundgrid_amd) never does.  PARITY UNPINNED -- see gg_oracle.h.
+The product package (groundgrid_amd) never does.  Held to the reference's own translation unit (oracle/ref_build.py);
+PARITY UNPINNED for the third-party conventions -- see gg_oracle.h.
 """
 from __future__ import annotations
 

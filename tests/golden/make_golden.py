@@ -1,8 +1,11 @@
 """Regenerates tests/golden/*.npz from the CPU oracle (oracle/gg_oracle.c).
 
-These are REGRESSION vectors of this repository's own oracle on seeded synthetic inputs, not outputs of the
-reference: the reference ships no tests or vectors and cannot be built or run in this image
-(parity unpinned).  They (a) pin the oracle against accidental change and (b) travel to
+These vectors are written by this repository's own oracle on seeded synthetic inputs.  The reference ships no tests or
+vectors, but its own translation unit (src/GroundSegmentation.cpp, compiled unmodified against the functional stand-ins of
+oracle/ref_shim/, oracle/ref_build.py) reproduces every array in them bit for bit
+(tests/test_reference_build_cpu.py::test_reference_build_reproduces_the_golden_vectors): they are vectors of that build under
+the project's restated third-party conventions -- not of a real ROS build, whose Eigen / grid_map / tf2 arithmetic stays
+parity unpinned (tools/pin/).  They (a) pin the oracle against accidental change and (b) travel to
 the GPU box, where the HIP path is compared with them bit for bit.
 
     python tests/golden/make_golden.py
