@@ -43,6 +43,7 @@ SYMBOLS = [
     "gg_filter_cloud_async", "gg_filter_cloud_wait", "gg_debug_emulate_ring_sweep", "gg_debug_sweep_sync_selftest",
     "gg_batch_fence", "gg_device_error", "gg_filter_cloud_layers", "gg_host_register", "gg_host_unregister", "gg_run_stage", "gg_insert_cloud", "gg_filter_cloud_pc2_out", "gg_get_gridmap_message",
     "gg_collective_available", "gg_comm_unique_id", "gg_comm_init_rank", "gg_comm_init_rank_for", "gg_comm_destroy", "gg_allgather_label_masks",
+    "gg_set_score_labels", "gg_set_slot_scoring", "gg_get_slot_scores", "gg_reset_slot_scores", "gg_get_score_kernel_time",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -108,6 +109,15 @@ class GGBatch(C.Structure):
 
 
 GG_PC2_POINT_STEP = 18
+GG_SCORE_MAX_LABELS = 64
+
+
+class GGSlotScores(C.Structure):
+    """gg_slot_scores: counts[bin][0] = predicted non-ground, [bin][1] = predicted ground; bin n_ids = every id that is not listed"""
+
+    _fields_ = [("clouds", C.c_uint64), ("counts", (C.c_uint64 * 2) * (GG_SCORE_MAX_LABELS + 1))]
+
+
 GG_STAGE_DETECT_GROUND_PATCHES, GG_STAGE_SPIRAL_GROUND_INTERPOLATION = 1, 2
 GG_STAGE_DETECT_GROUND_PATCH_3, GG_STAGE_DETECT_GROUND_PATCH_5, GG_STAGE_INTERPOLATE_CELL = 3, 4, 5
 
@@ -201,5 +211,10 @@ def load():
     L.gg_comm_init_rank_for.argtypes = [vp, vp, C.c_int, C.c_int, P(vp)]
     L.gg_comm_destroy.argtypes = [vp]
     L.gg_allgather_label_masks.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
+    L.gg_set_score_labels.argtypes = [vp, C.c_int, P(C.c_int32)]
+    L.gg_set_slot_scoring.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_int]
+    L.gg_get_slot_scores.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, P(GGSlotScores)]
+    L.gg_reset_slot_scores.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int]
+    L.gg_get_score_kernel_time.argtypes = [vp, P(C.c_double), P(C.c_int64), C.c_int]
     _lib = L
     return L

@@ -202,6 +202,10 @@ class GridMap:
         _check(L, ctx, L.gg_insert_cloud(ctx, self.slot, cloud.ctypes.data, start, end, org, cls.ctypes.data, cell.ctypes.data), "gg_insert_cloud")
         return cls, cell
 
+    def scores(self, allow_unknown: bool = False):
+        """This map's evaluator (GroundSegmentation.scores for one slot)."""
+        return self._seg.scores(slots=[self.slot], allow_unknown=allow_unknown)[0]
+
     def terrain_image(self) -> np.ndarray:
         """The 32FC3 terrain image of Nodelet.cpp:247-268: rows x cols x (ground, visited flag, pointsRaw)."""
         L, ctx = self._seg._L, self._seg._ctx
@@ -251,6 +255,7 @@ class GroundSegmentation:
         self._L.gg_get_geometry(ctx, C.byref(res), C.byref(lx), C.byref(ly))
         self.resolution, self.length = res.value, (lx.value, ly.value)
         self._maps = [GridMap(self, s) for s in range(n_slots)]
+        self._score_ids = None
         return self
 
     def close(self):
@@ -357,6 +362,60 @@ class GroundSegmentation:
         c, own = GGConfig(), C.c_int(0)
         _check(self._L, self._ctx, self._L.gg_get_slot_config(self._ctx, int(slot), C.byref(c), C.byref(own)), "gg_get_slot_config")
         return c, bool(own.value)
+
+    # -- the score of a labelled cloud: per-map evaluator counters on the device (scripts/eval_groundpoint_classifier.py:95-132)
+    def _slot_args(self, slots, first_slot, n):
+        if slots is not None:
+            sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+            return sl.shape[0], sl.ctypes.data_as(C.POINTER(C.c_int32)), sl, 0
+        count = self.n_slots - first_slot if n is None else int(n)
+        return count, None, None, int(first_slot)
+
+    def set_score_labels(self, ids=None):
+        """The label ids that get a bin of their own (default: the keys of evaluate.LABELS, the reference's yaml); every other id is
+        counted in one more bin.  Zeroes all counters."""
+        from .evaluate import LABELS
+
+        ids = list(LABELS.keys()) if ids is None else [int(i) for i in ids]
+        arr = (C.c_int32 * max(len(ids), 1))(*ids)
+        _check(self._L, self._ctx, self._L.gg_set_score_labels(self._ctx, len(ids), arr), "gg_set_score_labels")
+        self._score_ids = ids
+
+    def set_scoring(self, slots=None, first_slot: int = 0, n: Optional[int] = None, enable: bool = True):
+        """Scoring on / off for the named maps (default: all): every later filter call on such a map adds its returned cloud to the
+        map's counters, on the device."""
+        if getattr(self, "_score_ids", None) is None and enable:
+            self.set_score_labels()
+        cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
+        _check(self._L, self._ctx, self._L.gg_set_slot_scoring(self._ctx, cnt, ptr, first, 1 if enable else 0), "gg_set_slot_scoring")
+
+    def scores_raw(self, slots=None, first_slot: int = 0, n: Optional[int] = None):
+        """(clouds [n], counts [n, 65, 2] uint64) of the named maps: the counters as the library keeps them."""
+        cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
+        out = (_lib.GGSlotScores * max(cnt, 1))()
+        _check(self._L, self._ctx, self._L.gg_get_slot_scores(self._ctx, cnt, ptr, first, out), "gg_get_slot_scores")
+        words = np.frombuffer(out, dtype=np.uint64).reshape(max(cnt, 1), 1 + 2 * (_lib.GG_SCORE_MAX_LABELS + 1))[:cnt]
+        return words[:, 0].copy(), words[:, 1:].reshape(cnt, _lib.GG_SCORE_MAX_LABELS + 1, 2).copy()
+
+    def scores(self, slots=None, first_slot: int = 0, n: Optional[int] = None, allow_unknown: bool = False):
+        """One evaluate.GroundEvaluator per named map, from its device counters.  A returned point whose label id is not in the list
+        raises KeyError, like the reference's evaluator, unless allow_unknown."""
+        from .evaluate import GroundEvaluator
+
+        clouds, counts = self.scores_raw(slots, first_slot, n)
+        ids = self._score_ids
+        return [GroundEvaluator.from_device_counts(ids, counts[k, : len(ids) + 1], int(clouds[k]), allow_unknown) for k in range(len(clouds))]
+
+    def reset_scores(self, slots=None, first_slot: int = 0, n: Optional[int] = None):
+        """Zero the counters of the named maps (default: all); scoring stays on or off as it was."""
+        cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
+        _check(self._L, self._ctx, self._L.gg_reset_slot_scores(self._ctx, cnt, ptr, first), "gg_reset_slot_scores")
+
+    def score_kernel_time(self, reset: bool = True):
+        """(ms, launches) of k_score accumulated under set_flags(profile=True), next to kernel_times()."""
+        ms, ln = C.c_double(0.0), C.c_int64(0)
+        _check(self._L, self._ctx, self._L.gg_get_score_kernel_time(self._ctx, C.byref(ms), C.byref(ln), 1 if reset else 0), "gg_get_score_kernel_time")
+        return ms.value, ln.value
 
     def set_flags(self, minimal_layers: bool = False, profile: bool = False, concurrent_halves: bool = False, eager_layers: bool = False):
         """gg_set_flags.  minimal_layers: maxGroundHeight / groundCandidates / planeDist -- written by insert_cloud

@@ -34,6 +34,7 @@ using namespace gg;
 namespace {
 
 constexpr int PARAM_RING = 4;
+constexpr int K_SCORE = GG_NUM_KERNELS; // k_score's entry of the profiler's sums, behind the seven kernels of the path
 
 // one timed kernel of a profiled launch sequence (GG_FLAG_PROFILE).  Consecutive kernels of a sequence SHARE the event between them -- the
 // stop of one is the start of the next (owns_start = false): eight events per batch instead of fourteen (the markers cost the 1024-cloud
@@ -80,6 +81,15 @@ struct gg_context {
     std::vector<gg_config> slot_cfg;
     std::vector<DevConfig> slot_dev;
     DevConfig *d_slot_cfg = nullptr;
+    // the evaluator counters (gg_set_score_labels / gg_set_slot_scoring): one device block, allocated by the first label list -- the ring ->
+    // bin table, the slots' on / off bytes, the counters and the 2-bit label masks k_label leaves for k_score when the caller passed none
+    // (row = position in the batch, like gg_batch.d_label_masks)
+    void *d_score_block = nullptr;
+    gg::ScoreArgs score{};
+    uint8_t *d_score_masks = nullptr;
+    size_t score_masks_bytes = 0;
+    int score_n_ids = 0; // 0: no label list yet
+    std::vector<char> score_on;
 
     gg_conventions conv{};
     gg::sweep::Params sweep_params{};
@@ -103,7 +113,7 @@ struct gg_context {
     // stream) may write the same row of the same buffer from different streams.  The last few divided batches' output ranges and
     // row-to-half maps are remembered; a batch that shares a range with one of them under another map joins first (enqueue_batch).
     struct HalvesRecord {
-        const uint8_t *lo[6] = {}, *hi[6] = {};
+        const uint8_t *lo[7] = {}, *hi[7] = {}; // (the seventh: the context's own label masks, when k_score reads them)
         uint64_t map_hash = 0;
     };
     HalvesRecord halves_hist[4];
@@ -214,8 +224,8 @@ struct gg_context {
     // profiling
     std::vector<EventPair> pending;
     std::vector<hipEvent_t> free_single_events;
-    double k_ms[GG_NUM_KERNELS]{};
-    int64_t k_launches[GG_NUM_KERNELS]{};
+    double k_ms[GG_NUM_KERNELS + 1]{}; // (+ k_score, which gg_get_kernel_times' arrays have no room for: gg_get_score_kernel_time)
+    int64_t k_launches[GG_NUM_KERNELS + 1]{};
 };
 
 namespace {
@@ -479,8 +489,9 @@ void enqueue_layer_downloads(gg_context *ctx, const Arena &a, int slot, unsigned
 }
 
 // the kernels of one batched filter_cloud call (and the layer branch of the fused call), on stream s
+// score: some cloud's slot keeps evaluator counters (io.d_label_masks is set then): k_score follows the label loop
 void launch_sequence(gg_context *ctx, const Arena &a, const CloudParams *dp, const BatchIO &io, int nb, int max_n, hipStream_t s, const LayerPlan *plan, int slot0,
-                     bool profile)
+                     bool profile, bool score)
 {
     Profiler prof{ctx, s, profile};
     {
@@ -531,6 +542,11 @@ void launch_sequence(gg_context *ctx, const Arena &a, const CloudParams *dp, con
         prof.begin(GG_K_LABEL);
         launch_label(a, dp, io, nb, max_n, s);
         prof.end();
+        if (score) { // scripts/eval_groundpoint_classifier.py:95-132
+            prof.begin(K_SCORE);
+            launch_score(a, dp, io, ctx->score, nb, max_n, s);
+            prof.end();
+        }
     }
     if (side) hipStreamWaitEvent(s, ctx->join_event, 0); // join (the late layers -- ground, groundpatch, points -- follow the results: enqueue_ticket)
 }
@@ -545,7 +561,8 @@ void drop_graphs(gg_context *ctx)
 }
 
 // One cloud per call replays a captured graph (gg_context::GraphKey); everything else, and the first call of a kind, launches eagerly.
-int launch_or_replay(gg_context *ctx, const Arena &a, const CloudParams *hp, CloudParams *dp, const BatchIO &io, int nb, int max_n, hipStream_t s, const LayerPlan *plan)
+int launch_or_replay(gg_context *ctx, const Arena &a, const CloudParams *hp, CloudParams *dp, const BatchIO &io, int nb, int max_n, hipStream_t s, const LayerPlan *plan,
+                     bool score)
 {
     const bool profile = (ctx->flags & GG_FLAG_PROFILE) != 0;
     // (the fused filter + layers call stays eager: its side branch runs on a second stream beside the sweep, and a captured graph
@@ -553,7 +570,7 @@ int launch_or_replay(gg_context *ctx, const Arena &a, const CloudParams *hp, Clo
     const bool eligible = nb == 1 && !plan && ctx->graphs_enabled && !profile && !ctx->d_sweep_dbg && s != nullptr && !a.k2_debug && !a.k3_debug && !a.k5_debug && !a.k2_skip;
     if (!eligible) {
         HIPCHK(ctx, hipMemcpyAsync(dp, hp, sizeof(CloudParams) * nb, hipMemcpyHostToDevice, s));
-        launch_sequence(ctx, a, dp, io, nb, max_n, s, plan, hp[0].slot, profile);
+        launch_sequence(ctx, a, dp, io, nb, max_n, s, plan, hp[0].slot, profile, score);
         return GG_OK;
     }
     gg_context::GraphKey key;
@@ -595,17 +612,17 @@ int launch_or_replay(gg_context *ctx, const Arena &a, const CloudParams *hp, Clo
         return GG_OK;
     }
     if (entry->uses++ == 0) { // first call of a kind: eager (per-device one-time settings of the launchers happen here, outside any capture)
-        launch_sequence(ctx, a, ctx->d_gparams, io, 1, key.max_n, s, plan, key.slot, false);
+        launch_sequence(ctx, a, ctx->d_gparams, io, 1, key.max_n, s, plan, key.slot, false, score);
         return GG_OK;
     }
     HIPCHK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    launch_sequence(ctx, a, ctx->d_gparams, io, 1, key.max_n, s, plan, key.slot, false);
+    launch_sequence(ctx, a, ctx->d_gparams, io, 1, key.max_n, s, plan, key.slot, false, score);
     hipGraph_t graph = nullptr;
     const hipError_t e_end = hipStreamEndCapture(s, &graph);
     if (e_end != hipSuccess || !graph) {
         (void)hipGetLastError();
         ctx->graphs_enabled = false; // (a runtime that cannot capture this sequence: stay eager)
-        launch_sequence(ctx, a, ctx->d_gparams, io, 1, key.max_n, s, plan, key.slot, false);
+        launch_sequence(ctx, a, ctx->d_gparams, io, 1, key.max_n, s, plan, key.slot, false, score);
         return GG_OK;
     }
     hipGraphExec_t exec = nullptr;
@@ -613,7 +630,7 @@ int launch_or_replay(gg_context *ctx, const Arena &a, const CloudParams *hp, Clo
         (void)hipGetLastError();
         hipGraphDestroy(graph);
         ctx->graphs_enabled = false;
-        launch_sequence(ctx, a, ctx->d_gparams, io, 1, key.max_n, s, plan, key.slot, false);
+        launch_sequence(ctx, a, ctx->d_gparams, io, 1, key.max_n, s, plan, key.slot, false, score);
         return GG_OK;
     }
     entry->graph = graph;
@@ -684,6 +701,12 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
         ctx->lazy_pending[slot] = lazy ? 1 : 0;
         if (lazy) ctx->lazy_params[slot] = p;
     }
+    // a (half) launch with a scoring slot is followed by k_score, which reads the labels as the 2-bit masks k_label writes: into the
+    // caller's d_label_masks, or into the context's own when there are none; any other launch runs what it always ran
+    bool score_half[2] = {false, false};
+    if (ctx->score_n_ids)
+        for (int i = 0; i < nb; ++i) score_half[i < n_first ? 0 : 1] |= ctx->score_on[hp[i].slot] != 0;
+    const bool own_masks = (score_half[0] || score_half[1]) && !b->d_label_masks;
     // FRESH maps (gg_context::fresh): a (half) launch whose maps are all fresh, and large enough for the plain k_sweep, takes them as they
     // are -- k_patch marks what it writes, the sweep reads nothing else of the layer --; in any other launch they are filled first
     bool fresh_half[2] = {false, false};
@@ -720,10 +743,11 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
         // position, halves the slot): join the two streams once, in both directions, before such a batch
         gg_context::HalvesRecord now;
         const size_t per = b->cloud_stride;
-        const uint8_t *p6[6] = {(const uint8_t *)b->d_labels, (const uint8_t *)b->d_out_index, (const uint8_t *)b->d_out_clouds, (const uint8_t *)b->d_out_counts,
-                                (const uint8_t *)b->d_label_masks, (const uint8_t *)b->d_out_pc2};
-        const size_t bytes6[6] = {(size_t)nb * per, (size_t)nb * per * 4, (size_t)nb * per * sizeof(gg_point32), (size_t)nb * 64, (size_t)nb * ((per + 3) / 4), (size_t)nb * per * 18};
-        for (int k = 0; k < 6; ++k) now.lo[k] = p6[k], now.hi[k] = p6[k] ? p6[k] + bytes6[k] : nullptr;
+        const uint8_t *p6[7] = {(const uint8_t *)b->d_labels, (const uint8_t *)b->d_out_index, (const uint8_t *)b->d_out_clouds, (const uint8_t *)b->d_out_counts,
+                                (const uint8_t *)b->d_label_masks, (const uint8_t *)b->d_out_pc2, own_masks ? ctx->d_score_masks : nullptr};
+        const size_t bytes6[7] = {(size_t)nb * per, (size_t)nb * per * 4, (size_t)nb * per * sizeof(gg_point32), (size_t)nb * 64, (size_t)nb * ((per + 3) / 4), (size_t)nb * per * 18,
+                                  (size_t)nb * ((per + 3) / 4)};
+        for (int k = 0; k < 7; ++k) now.lo[k] = p6[k], now.hi[k] = p6[k] ? p6[k] + bytes6[k] : nullptr;
         uint64_t h = 1469598103934665603ull;
         for (int i = 0; i < nb; ++i) h = (h ^ (uint64_t)(second_half_slot(ctx, b->slots ? b->slots[i] : b->first_slot + i) ? 2 * i + 1 : 2 * i)) * 1099511628211ull;
         now.map_hash = h ^ (uint64_t)nb;
@@ -731,8 +755,8 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
         for (int r = 0; r < ctx->halves_hist_n && !joined && !clash; ++r) {
             const gg_context::HalvesRecord &o = ctx->halves_hist[r];
             if (o.map_hash == now.map_hash) continue; // every row on the stream it was on: ordered by the streams themselves
-            for (int x = 0; x < 6 && !clash; ++x)
-                for (int y = 0; y < 6 && !clash; ++y) clash = now.lo[x] && o.lo[y] && now.lo[x] < o.hi[y] && o.lo[y] < now.hi[x];
+            for (int x = 0; x < 7 && !clash; ++x)
+                for (int y = 0; y < 7 && !clash; ++y) clash = now.lo[x] && o.lo[y] && now.lo[x] < o.hi[y] && o.lo[y] < now.hi[x];
         }
         if (clash) {
             if (const int rc = stream_waits_for_second_half(ctx, s)) return rc;
@@ -766,6 +790,8 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
     io.d_out_counts = b->d_out_counts;
     io.d_label_masks = b->d_label_masks;
     io.d_out_pc2 = b->d_out_pc2;
+    BatchIO io_score = io;
+    if (own_masks) io_score.d_label_masks = ctx->d_score_masks;
 
     Arena a = ctx->arena;
     a.flags = eff_flags;
@@ -793,8 +819,8 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
         if (const int rc = fill_fresh(n_first, nb, ctx->half_stream)) return rc;
         HIPCHK(ctx, hipMemcpyAsync(dp, hp, sizeof(CloudParams) * n_first, hipMemcpyHostToDevice, s));
         HIPCHK(ctx, hipMemcpyAsync(dp + n_first, hp + n_first, sizeof(CloudParams) * (nb - n_first), hipMemcpyHostToDevice, ctx->half_stream));
-        launch_sequence(ctx, a, dp, io, n_first, max_n[0], s, nullptr, hp[0].slot, false);
-        launch_sequence(ctx, a2, dp + n_first, io, nb - n_first, max_n[1], ctx->half_stream, nullptr, hp[n_first].slot, false);
+        launch_sequence(ctx, a, dp, score_half[0] ? io_score : io, n_first, max_n[0], s, nullptr, hp[0].slot, false, score_half[0]);
+        launch_sequence(ctx, a2, dp + n_first, score_half[1] ? io_score : io, nb - n_first, max_n[1], ctx->half_stream, nullptr, hp[n_first].slot, false, score_half[1]);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipEventRecord(ctx->ring_done2[g], ctx->half_stream));
         ctx->ring_used2[g] = true;
@@ -803,7 +829,7 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
     } else {
         a.fresh_launch = fresh_half[0] ? 1 : 0;
         if (const int rc = fill_fresh(0, nb, s)) return rc;
-        if (const int rc = launch_or_replay(ctx, a, hp, dp, io, nb, max_n[0], s, plan)) return rc;
+        if (const int rc = launch_or_replay(ctx, a, hp, dp, score_half[0] ? io_score : io, nb, max_n[0], s, plan, score_half[0])) return rc;
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipEventRecord(ctx->ring_done[g], s));
@@ -930,6 +956,7 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
     ctx->lazy_pending.assign(n_slots, 0);
     ctx->lazy_params.assign(n_slots, CloudParams{});
     ctx->slot_own.assign(n_slots, 0);
+    ctx->score_on.assign(n_slots, 0);
     ctx->slot_cfg.assign(n_slots, gg_config{});
     ctx->slot_dev.assign(n_slots, DevConfig{});
     ctx->pos_y.assign(n_slots, 0.0);
@@ -1337,6 +1364,7 @@ void gg_destroy(gg_context *ctx)
     if (ctx->h_planes) hipHostFree(ctx->h_planes);
     if (ctx->d_arena) hipFree(ctx->d_arena);
     if (ctx->d_slot_cfg) hipFree(ctx->d_slot_cfg);
+    if (ctx->d_score_block) hipFree(ctx->d_score_block);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1458,6 +1486,128 @@ int gg_get_slot_config(const gg_context *ctx, int slot, gg_config *cfg, int *own
     const bool o = ctx->slot_own[slot] != 0;
     *cfg = o ? ctx->slot_cfg[slot] : ctx->cfg;
     if (own) *own = o ? 1 : 0;
+    return GG_OK;
+}
+
+// ---- evaluator counters (include/groundgrid_hip.h "the score of a labelled cloud", k8_score.hip) ----
+
+// the slots a call names, checked like gg_set_slot_configs': GG_ERR_CAPACITY outside the context, GG_ERR_INVALID for duplicates
+static int check_slot_list(gg_context *ctx, const char *who, int n, const int32_t *slots, int first_slot)
+{
+    std::vector<char> seen((size_t)ctx->n_slots, 0);
+    for (int k = 0; k < n; ++k) {
+        const long long slot = slots ? (long long)slots[k] : (long long)first_slot + k;
+        if (slot < 0 || slot >= ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, (std::string(who) + ": slot outside the context").c_str());
+        if (seen[(size_t)slot]++) return fail(ctx, GG_ERR_INVALID, (std::string(who) + ": a slot is named twice").c_str());
+    }
+    return GG_OK;
+}
+
+int gg_set_score_labels(gg_context *ctx, int n_ids, const int32_t *ids)
+{
+    if (!ctx || !ids || n_ids < 1 || n_ids > GG_SCORE_MAX_LABELS) return fail(ctx, GG_ERR_INVALID, "gg_set_score_labels: null argument or n_ids outside 1..GG_SCORE_MAX_LABELS");
+    std::vector<uint8_t> table(65536, (uint8_t)n_ids); // every id that is not listed: the last bin
+    for (int k = 0; k < n_ids; ++k) {
+        if (ids[k] < 0 || ids[k] > 65535) return fail(ctx, GG_ERR_INVALID, "gg_set_score_labels: id outside 0..65535");
+        if (table[(size_t)ids[k]] != (uint8_t)n_ids) return fail(ctx, GG_ERR_INVALID, "gg_set_score_labels: an id is listed twice");
+        table[(size_t)ids[k]] = (uint8_t)k;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t on_off = 65536, scores_off = align_up(on_off + (size_t)ctx->n_slots, 256), scores_bytes = (size_t)ctx->n_slots * SCORE_WORDS * 8;
+    const size_t masks_off = align_up(scores_off + scores_bytes, 256);
+    if (!ctx->d_score_block) {
+        const size_t masks_bytes = (size_t)ctx->n_slots * ((ctx->max_points + 3) / 4) + 64;
+        void *p = nullptr;
+        if (hipMalloc(&p, masks_off + masks_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, GG_ERR_NOMEM, "gg_set_score_labels: device block");
+        }
+        if (hipMemset(p, 0, masks_off) != hipSuccess) { // (every slot off, every counter 0)
+            hipFree(p);
+            return fail(ctx, GG_ERR_HIP, "gg_set_score_labels: hipMemset");
+        }
+        ctx->d_score_block = p;
+        uint8_t *base = static_cast<uint8_t *>(p);
+        ctx->score.ring_bin = base;
+        ctx->score.slot_on = base + on_off;
+        ctx->score.scores = reinterpret_cast<unsigned long long *>(base + scores_off);
+        ctx->d_score_masks = base + masks_off;
+        ctx->score_masks_bytes = masks_bytes;
+    }
+    // (batches in flight count into the old bins: they finish first)
+    if (const int rc = wait_for_batches_in_flight(ctx)) return rc;
+    HIPCHK(ctx, hipMemcpy(const_cast<uint8_t *>(ctx->score.ring_bin), table.data(), table.size(), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemset(ctx->score.scores, 0, scores_bytes));
+    ctx->score_n_ids = n_ids;
+    return GG_OK;
+}
+
+int gg_set_slot_scoring(gg_context *ctx, int n, const int32_t *slots, int first_slot, int enable)
+{
+    if (!ctx || n < 0) return fail(ctx, GG_ERR_INVALID, "gg_set_slot_scoring: null context or n < 0");
+    if (!ctx->score_n_ids) return fail(ctx, GG_ERR_INVALID, "gg_set_slot_scoring: no label list (gg_set_score_labels)");
+    if (n == 0) return GG_OK;
+    if (const int rc = check_slot_list(ctx, "gg_set_slot_scoring", n, slots, first_slot)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<char> on = ctx->score_on;
+    for (int k = 0; k < n; ++k) on[slots ? slots[k] : first_slot + k] = enable ? 1 : 0;
+    if (const int rc = wait_for_batches_in_flight(ctx)) return rc;
+    HIPCHK(ctx, hipMemcpy(const_cast<uint8_t *>(ctx->score.slot_on), on.data(), on.size(), hipMemcpyHostToDevice));
+    ctx->score_on.swap(on);
+    drop_graphs(ctx); // (a captured launch sequence ends with k_score, or does not)
+    return GG_OK;
+}
+
+int gg_get_slot_scores(gg_context *ctx, int n, const int32_t *slots, int first_slot, gg_slot_scores *out)
+{
+    static_assert(sizeof(gg_slot_scores) == (size_t)SCORE_WORDS * 8, "the device keeps a slot's counters in the layout of gg_slot_scores");
+    if (!ctx || n < 0 || (!out && n > 0)) return fail(ctx, GG_ERR_INVALID, "gg_get_slot_scores: null argument or n < 0");
+    if (!ctx->score_n_ids) return fail(ctx, GG_ERR_INVALID, "gg_get_slot_scores: no label list (gg_set_score_labels)");
+    if (n == 0) return GG_OK;
+    if (const int rc = check_slot_list(ctx, "gg_get_slot_scores", n, slots, first_slot)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // behind every batch (and second half) enqueued so far -- but no map is read: fresh maps stay as they are
+    if (const int rc = own_stream_waits_for_batches(ctx, false)) return rc;
+    int lo = ctx->n_slots, hi = 0;
+    for (int k = 0; k < n; ++k) {
+        const int slot = slots ? slots[k] : first_slot + k;
+        lo = std::min(lo, slot), hi = std::max(hi, slot + 1);
+    }
+    if (!slots) { // a run of slots: straight into the caller's array
+        HIPCHK(ctx, hipMemcpyAsync(out, ctx->score.scores + (size_t)lo * SCORE_WORDS, (size_t)n * sizeof(gg_slot_scores), hipMemcpyDeviceToHost, ctx->stream));
+        SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return GG_OK;
+    }
+    std::vector<gg_slot_scores> all((size_t)(hi - lo));
+    HIPCHK(ctx, hipMemcpyAsync(all.data(), ctx->score.scores + (size_t)lo * SCORE_WORDS, all.size() * sizeof(gg_slot_scores), hipMemcpyDeviceToHost, ctx->stream));
+    SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; ++k) out[k] = all[(size_t)(slots[k] - lo)];
+    return GG_OK;
+}
+
+int gg_reset_slot_scores(gg_context *ctx, int n, const int32_t *slots, int first_slot)
+{
+    if (!ctx || n < 0) return fail(ctx, GG_ERR_INVALID, "gg_reset_slot_scores: null context or n < 0");
+    if (!ctx->score_n_ids) return fail(ctx, GG_ERR_INVALID, "gg_reset_slot_scores: no label list (gg_set_score_labels)");
+    if (n == 0) return GG_OK;
+    if (const int rc = check_slot_list(ctx, "gg_reset_slot_scores", n, slots, first_slot)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = wait_for_batches_in_flight(ctx)) return rc;
+    if (!slots)
+        HIPCHK(ctx, hipMemset(ctx->score.scores + (size_t)first_slot * SCORE_WORDS, 0, (size_t)n * SCORE_WORDS * 8));
+    else
+        for (int k = 0; k < n; ++k) HIPCHK(ctx, hipMemset(ctx->score.scores + (size_t)slots[k] * SCORE_WORDS, 0, (size_t)SCORE_WORDS * 8));
+    return GG_OK;
+}
+
+int gg_get_score_kernel_time(gg_context *ctx, double *ms, int64_t *launches, int reset)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = drain_profile(ctx)) return rc;
+    if (ms) *ms = ctx->k_ms[K_SCORE];
+    if (launches) *launches = ctx->k_launches[K_SCORE];
+    if (reset) ctx->k_ms[K_SCORE] = 0.0, ctx->k_launches[K_SCORE] = 0;
     return GG_OK;
 }
 
@@ -2712,6 +2862,11 @@ extern "C" int gg_debug_set_tuning(gg_context *ctx, const char *key, int value)
     if (!ctx || !key || value < 0) return GG_ERR_INVALID;
     if (!strcmp(key, "pw")) return ctx->arena.PW;
     if (!strcmp(key, "graph_replays")) return (int)std::min<long>(ctx->graph_replays, 1 << 30); // (read-only: how many calls replayed a captured graph)
+    if (!strcmp(key, "fresh_count")) { // (read-only: how many maps are fresh -- gg_reset_maps left their layer unwritten and nothing has filled it since)
+        int c = 0;
+        for (int k = 0; k < ctx->n_slots; ++k) c += ctx->fresh[k] ? 1 : 0;
+        return c;
+    }
     if (!strcmp(key, "graphs")) { // 0 = every call launches eagerly, 1 = one cloud per call replays a captured graph (the default)
         ctx->graphs_enabled = value != 0;
         drop_graphs(ctx);

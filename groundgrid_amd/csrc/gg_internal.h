@@ -268,6 +268,16 @@ struct BatchIO {
     uint8_t *d_out_pc2;
 };
 
+// The evaluator counters (gg_set_slot_scoring, k8_score.hip).  Kept out of Arena and CloudParams: the kernels of a launch that does not
+// score take the arguments they always took.  A slot's counters have the layout of gg_slot_scores: clouds, then [bin][non-ground, ground]
+constexpr int SCORE_BINS = GG_SCORE_MAX_LABELS + 1;  // the listed ids, then "every other id"
+constexpr int SCORE_WORDS = 1 + SCORE_BINS * 2;      // 64-bit words per slot
+struct ScoreArgs {
+    const uint8_t *ring_bin;      // [65536] ring -> bin (gg_set_score_labels)
+    const uint8_t *slot_on;       // [n_slots] does the slot score
+    unsigned long long *scores;   // [n_slots][SCORE_WORDS]
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -321,6 +331,7 @@ constexpr int SWEEP_PAIR_MAX_CLOUDS = 16;              // launches of more cloud
 size_t sweep_lds_bytes(const sweep::Params &P);
 size_t sweep_xchg_entries(const sweep::Params &P);
 void launch_label(const Arena &a, const CloudParams *d_params, const BatchIO &io, int n_clouds, int max_n, hipStream_t s);
+void launch_score(const Arena &a, const CloudParams *d_params, const BatchIO &io, const ScoreArgs &sc, int n_clouds, int max_n, hipStream_t s); // k8_score.hip; io.d_label_masks is set
 void launch_fill(float *dst, size_t n, float v, hipStream_t s);
 void launch_fill_bytes(uint8_t *dst, size_t n, uint8_t v, hipStream_t s);
 void launch_fill_strided(float *dst, size_t n, size_t stride, int count, float v, hipStream_t s);   // count regions of n floats, `stride` apart

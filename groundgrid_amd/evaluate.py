@@ -39,14 +39,32 @@ class GroundEvaluator:
         self.true_positive = {n: 0 for n in names}    # truePositiveCloudLabelCount
         self.false_positive = {n: 0 for n in names}   # falsePositiveCloudLabelCount
         self.cloud_count = 0
+        self.unknown_non_ground = 0   # points whose label id is outside the yaml: only ever counted on request (allow_unknown),
+        self.unknown_total = 0        # the reference raises KeyError there (:106)
 
-    def add_cloud(self, predicted: np.ndarray, semantic: np.ndarray):
-        """predicted: 49 / 99 per point of the RETURNED cloud; semantic: SemanticKITTI label id (the `ring` field)."""
+    def add_cloud(self, predicted: np.ndarray, semantic: np.ndarray, points: np.ndarray = None, allow_unknown: bool = False):
+        """predicted: 49 / 99 per point of the RETURNED cloud; semantic: SemanticKITTI label id (the `ring` field).
+        points (optional): the returned cloud's points, a structured array with x, y, z or an [n, 3] array -- a point any of whose
+        coordinates is NaN is left out, as pc2.read_points(..., skip_nans=True) does (eval_groundpoint_classifier.py:99).  This is
+        the definition the device counters (api.GroundSegmentation.scores) are held to.  allow_unknown: ids outside LABELS are counted
+        in unknown_non_ground / unknown_total instead of raising KeyError."""
         predicted = np.asarray(predicted)
         semantic = np.asarray(semantic).astype(np.int64)
+        if points is not None:
+            points = np.asarray(points)
+            if points.dtype.names:
+                xyz = np.stack([points["x"], points["y"], points["z"]], axis=1)
+            else:
+                xyz = points.reshape(-1, 3)
+            keep = ~np.isnan(xyz).any(axis=1)
+            predicted, semantic = predicted[keep], semantic[keep]
         for lid in np.unique(semantic):
-            name = LABELS[int(lid)]  # KeyError for ids outside the yaml, like the reference
             sel = semantic == lid
+            if allow_unknown and int(lid) not in LABELS:
+                self.unknown_non_ground += int(np.count_nonzero(predicted[sel] == NONGROUND))
+                self.unknown_total += int(np.count_nonzero(sel))
+                continue
+            name = LABELS[int(lid)]  # KeyError for ids outside the yaml, like the reference
             ng = int(np.count_nonzero(predicted[sel] == NONGROUND))
             gr = int(np.count_nonzero(predicted[sel] == GROUND))
             self.non_ground[name] += ng                      # :108-109
@@ -69,6 +87,37 @@ class GroundEvaluator:
             else:
                 ev.false_positive[name] = tot - ng
         return ev
+
+    @classmethod
+    def from_device_counts(cls, ids, counts, clouds: int = 0, allow_unknown: bool = False) -> "GroundEvaluator":
+        """The evaluator a map slot's device counters stand for (gg_get_slot_scores): ids = the label ids given to
+        gg_set_score_labels (keys of LABELS), counts[k] = (predicted non-ground, predicted ground) of ids[k], and one more row for
+        every id that is not listed.  The reference raises KeyError for such a point (:106); so does this unless allow_unknown."""
+        ids = [int(i) for i in ids]
+        rows = [(int(r[0]), int(r[1])) for r in counts]
+        if len(rows) < len(ids) + 1:
+            raise ValueError("counts needs one row per id and one for the unlisted ids")
+        unknown = sum(rows[len(ids)])
+        if unknown and not allow_unknown:
+            raise KeyError(f"{unknown} returned points carry a label id outside the list")
+        ev = cls()
+        ev.unknown_non_ground, ev.unknown_total = rows[len(ids)][0], unknown
+        for lid, (ng, gr) in zip(ids, rows):
+            name = LABELS[lid]
+            ev.non_ground[name] += ng
+            ev.total[name] += ng + gr
+            if name in GROUND_LABELS or name in ADDITIONAL_GROUND_LABELS:
+                ev.true_positive[name] += gr
+            else:
+                ev.false_positive[name] += gr
+        ev.cloud_count = int(clouds)
+        return ev
+
+    def counters(self) -> dict:
+        """Everything the evaluator holds, as one comparable value."""
+        return {"clouds": self.cloud_count, "non_ground": dict(self.non_ground), "total": dict(self.total),
+                "true_positive": dict(self.true_positive), "false_positive": dict(self.false_positive),
+                "unknown_non_ground": self.unknown_non_ground, "unknown_total": self.unknown_total}
 
     def summary(self) -> dict:
         """eval_groundpoint_classifier.py:153-195."""

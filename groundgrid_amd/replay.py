@@ -55,6 +55,49 @@ def replay(frames, backend, evaluator: GroundEvaluator = None, on_frame=None):
     return ev, spent
 
 
+def score_configs(frames, configs, *, max_points: int, dimension: float = 120.0, resolution: float = 0.33, device: int = 0,
+                  allow_unknown: bool = False, seg=None):
+    """The parameter sweep: K candidate configurations as K map slots of one context (set_slot_configs), every frame's cloud uploaded
+    once and filtered against all K maps in one batch (frame 0: reset_maps, later frames: one move_maps), the evaluator of every map
+    kept on the device (set_scoring).  Nothing is downloaded per frame; returns the K GroundEvaluators of replay(frames, ...) run once
+    per configuration.  frames: iterable of groundgrid_amd.kitti.Frame whose clouds carry the semantic label in `ring`."""
+    import torch
+
+    from . import api, kitti
+
+    configs = list(configs)
+    K = len(configs)
+    stride = (int(max_points) + 63) // 64 * 64
+    own = seg is None
+    if own:
+        seg = api.GroundSegmentation().init(dimension, resolution, n_slots=K, max_points=stride, device=device)
+    try:
+        seg.set_slot_configs(configs)
+        seg.set_score_labels()
+        seg.set_scoring(first_slot=0, n=K)
+        dev = torch.device("cuda", device)
+        one = torch.zeros((1, stride, 16), dtype=torch.uint8, device=dev)
+        out = None
+        first = True
+        for fr in frames:
+            n = len(fr.cloud_map)
+            if n > stride:
+                raise ValueError(f"frame {fr.index} has {n} points, max_points is {max_points}")
+            packed = torch.from_numpy(api.pack16(fr.cloud_map).view(np.uint8).reshape(n, 16))
+            one[0, :n].copy_(packed, non_blocking=False)
+            pts = one.expand(K, stride, 16).contiguous() if K > 1 else one  # (gg_batch has one row per cloud)
+            if first:
+                seg.reset_maps(0, K, odom_z=float(np.float32(fr.odom[2])), pos=(fr.odom[0], fr.odom[1]), on_torch_stream=True)
+                first = False
+            else:
+                seg.move_maps([(fr.odom[0], fr.odom[1])] * K, [fr.base_to_map] * K, rotation=kitti.ROTATION_CONVENTION, on_torch_stream=True)
+            out = seg.filter_batch(pts, [n] * K, [fr.origin] * K, [fr.map_to_base_z] * K, out=out)
+        return seg.scores(first_slot=0, n=K, allow_unknown=allow_unknown)
+    finally:
+        if own:
+            seg.close()
+
+
 def replay_side_by_side(frames, device, cpu, cpu_frames: int = 0):
     """One pass over `frames` through two backends (`cpu`: the checker -- tests and bench.py pass the oracle's; None: device only), frame by frame: (evaluator of the device path, its seconds, the CPU path's
     seconds and frames, labels_equal_in_every_frame, first frame that differed or -1).  cpu_frames > 0 stops the CPU path (and the

@@ -367,6 +367,45 @@ int gg_synchronize(gg_context *ctx);
  * (0 = none, > 0 = a wait ran out) without synchronising; clear != 0 also clears it. */
 int gg_device_error(gg_context *ctx, int clear);
 
+/* ---- the score of a labelled cloud: per-map evaluator counters ------------------------------------------------------
+ * The reference's evaluation node (scripts/eval_groundpoint_classifier.py:95-132) receives the RETURNED cloud, in which `ring`
+ * carries the point's SemanticKITTI label (scripts/kitti_data_publisher.py:124-130) and `intensity` the prediction (49 ground /
+ * 99 non-ground), and counts both predictions per label.  Here every map slot has such an evaluator on the device, fed by the
+ * launches that filter the slot: K candidate configurations as K slots (gg_set_slot_configs) are scored without one label
+ * leaving HBM.
+ * What is counted: every input point that is in the returned cloud (label 49 or 99; dropped points never), in the bin of its
+ * `ring` and under its label -- except a returned point whose map-frame z is NaN: pc2.read_points(..., skip_nans=True) (:99)
+ * leaves out a point any of whose x, y, z is NaN, and a point inside the map has finite x and y, so z decides.  `total` of a
+ * label (:118) is ground + non-ground; true / false positives and the summary figures (:153-195) are host arithmetic.
+ * Every entry point that runs the label loop on a scoring slot accumulates: gg_filter_batch and gg_filter_cloud, _tf, _async /
+ * _wait, _layers, _pc2, _pc2_out (`ring` from off_ring).  gg_insert_cloud and gg_run_stage do not label and do not score.  A
+ * launch in which no slot scores runs the kernels it always ran.  Counters survive gg_reset_map(s), gg_move_map(s),
+ * gg_set_config, gg_set_slot_configs and switching scoring off and on: an evaluator spans a whole sequence. */
+#define GG_HAS_SCORES 1
+#define GG_SCORE_MAX_LABELS 64
+typedef struct gg_slot_scores {
+    uint64_t clouds;                                /* filter calls scored (the evaluator's "Received N point clouds", :137) */
+    uint64_t counts[GG_SCORE_MAX_LABELS + 1][2];    /* [bin][0] predicted non-ground, [bin][1] predicted ground */
+} gg_slot_scores;
+/* The label ids that get a bin of their own, in the caller's order: bin k counts ring == ids[k], bin n_ids every other id (the
+ * reference raises KeyError for an id outside its yaml, :106: a documented deviation -- a caller that wants the reference's
+ * behaviour treats a non-zero last bin as that error).  1 <= n_ids <= GG_SCORE_MAX_LABELS, each id in 0..65535, all distinct;
+ * otherwise GG_ERR_INVALID and nothing changes.  The library holds no label table of its own.  Per context; blocks like
+ * gg_set_config; zeroes the counters of every slot (the on / off state of the slots stays). */
+int gg_set_score_labels(gg_context *ctx, int n_ids, const int32_t *ids);
+/* Scoring on (enable != 0) or off for slots[k] (or first_slot + k when slots == NULL); off for every slot by default.  Slot
+ * addressing and errors as gg_set_slot_configs: GG_ERR_CAPACITY for a slot outside the context, GG_ERR_INVALID for duplicates /
+ * n < 0 / null ctx, and GG_ERR_INVALID while no label list is set; on any error nothing changes; n == 0 is GG_OK.  Blocks:
+ * batches in flight finish under the old setting. */
+int gg_set_slot_scoring(gg_context *ctx, int n, const int32_t *slots, int first_slot, int enable);
+/* out[k] = the counters of slots[k] (or first_slot + k).  Orders itself after every batch enqueued so far (both halves under
+ * GG_FLAG_CONCURRENT_HALVES) and synchronises, like the other getters -- but touches no map: fresh maps stay fresh.  Bins at and
+ * above n_ids + 1 read 0, and so does every bin of a slot that never scored.  Same slot errors; GG_ERR_INVALID while no label
+ * list is set or out == NULL with n > 0. */
+int gg_get_slot_scores(gg_context *ctx, int n, const int32_t *slots, int first_slot, gg_slot_scores *out);
+/* zero the counters of the named slots; their on / off state stays.  Blocks like gg_set_slot_scoring. */
+int gg_reset_slot_scores(gg_context *ctx, int n, const int32_t *slots, int first_slot);
+
 /* ---- the one collective of the path: the all-gather of the per-cloud label masks (BASELINE configs[2]) ----
  * The reference has no distributed code; clouds shard as independent (cloud, map) pairs and the only exchange is that every
  * rank ends up with every cloud's labels.  These entry points let a C / C++ host run that configuration without Python:
@@ -495,6 +534,9 @@ enum {
 /* With GG_FLAG_PROFILE: accumulated milliseconds and launch counts per kernel since the last reset. */
 int gg_get_kernel_times(gg_context *ctx, double ms[GG_NUM_KERNELS], int64_t launches[GG_NUM_KERNELS], int reset);
 const char *gg_kernel_name(int k);
+/* ... and the same for k_score, the evaluator's count behind the label loop of a launch with a scoring slot (GG_NUM_KERNELS and the
+ * arrays above keep their size) */
+int gg_get_score_kernel_time(gg_context *ctx, double *ms, int64_t *launches, int reset);
 int gg_abi_version(void);
 
 /* Testing hook, runs on the host (no GPU): the terrain sweep the device runs (ring-per-lane dataflow, csrc/sweep_core.h) --
