@@ -44,9 +44,11 @@ SYMBOLS = [
     "gg_batch_fence", "gg_device_error", "gg_filter_cloud_layers", "gg_host_register", "gg_host_unregister", "gg_run_stage", "gg_insert_cloud", "gg_filter_cloud_pc2_out", "gg_get_gridmap_message",
     "gg_collective_available", "gg_comm_unique_id", "gg_comm_init_rank", "gg_comm_init_rank_for", "gg_comm_destroy", "gg_allgather_label_masks",
     "gg_set_score_labels", "gg_set_slot_scoring", "gg_get_slot_scores", "gg_reset_slot_scores", "gg_get_score_kernel_time",
+    "gg_export_layers",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
+GG_PLANES_COLMAJOR, GG_PLANES_ROWMAJOR = 0, 1
 GG_ROT_TF2, GG_ROT_KDL = 0, 1
 ROTATION = {"tf2": GG_ROT_TF2, "kdl": GG_ROT_KDL}
 GG_ASYNC_DEPTH = 2
@@ -176,6 +178,7 @@ def load():
     L.gg_set_map_position.argtypes = [vp, C.c_int, C.c_double, C.c_double]
     L.gg_move_map.argtypes = [vp, C.c_int, C.c_double, C.c_double, P(C.c_double), P(C.c_int)]
     L.gg_move_maps.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, P(C.c_double), P(C.c_double), P(C.c_int32), vp]
+    L.gg_export_layers.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

@@ -325,6 +325,34 @@ class GroundSegmentation:
             self._maps[slot]._pos = (x.value, y.value)
         return shifts
 
+    def export_layers(self, names=None, *, slots=None, first_slot: int = 0, n: Optional[int] = None, out=None, row_major: bool = False,
+                      stream=None):
+        """The named layers (default: all eleven, in gg_layer order) of many maps as one CUDA torch.float32 tensor [n, K, cols, rows]
+        (Eigen's column-major planes: element [i, k, c, r] is cell (r, c)), or [n, K, rows, cols] with row_major -- what
+        map(slot).layers() returns for each map, bit for bit, without leaving the device (gg_export_layers).  Map i = slots[i], or
+        first_slot + i for n maps (default: up to the last slot).  `out` (same shape, contiguous) is reused when given.  Enqueued on the
+        current torch stream like filter_batch (or on `stream`), without synchronising: torch ops enqueued there afterwards see the
+        planes.  Fresh maps stay fresh; the three lazily kept layers are computed first where the mask names them."""
+        import torch
+
+        self._torch_used = True
+        names = list(LAYERS) if names is None else list(names)
+        mask = 0
+        for k in names:
+            mask |= 1 << LAYERS.index(k)
+        if bin(mask).count("1") != len(names) or [k for k in LAYERS if k in names] != names:
+            raise ValueError("export_layers: names must be distinct and in gg_layer order")
+        cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
+        shape = (cnt, len(names), self.rows, self.cols) if row_major else (cnt, len(names), self.cols, self.rows)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", self.device))
+        assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._L.gg_export_layers(self._ctx, cnt, ptr, first, mask, _lib.GG_PLANES_ROWMAJOR if row_major else _lib.GG_PLANES_COLMAJOR,
+                                      C.c_void_p(out.data_ptr()), self.rows * self.cols, C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
+        _check(self._L, self._ctx, rc, "gg_export_layers")
+        return out
+
     # -- GroundSegmentation::setConfig (src/GroundSegmentation.cpp:468-471)
     def setConfig(self, config: GGConfig):
         _check(self._L, self._ctx, self._L.gg_set_config(self._ctx, C.byref(config)), "gg_set_config")

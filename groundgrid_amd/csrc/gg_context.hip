@@ -34,6 +34,7 @@ using namespace gg;
 namespace {
 
 constexpr int PARAM_RING = 4;
+constexpr int EXPORT_VARIANT_DEFAULT = 0; // gg_export_layers: 0 = k_export_tiled, 1 = k_export_gather; the measured winner
 constexpr int K_SCORE = GG_NUM_KERNELS; // k_score's entry of the profiler's sums, behind the seven kernels of the path
 
 // one timed kernel of a profiled launch sequence (GG_FLAG_PROFILE).  Consecutive kernels of a sequence SHARE the event between them -- the
@@ -180,6 +181,17 @@ struct gg_context {
     hipEvent_t move_done[PARAM_RING]{}, move_done2[PARAM_RING]{};
     bool move_used[PARAM_RING]{}, move_used2[PARAM_RING]{};
     int move_next = 0;
+    // gg_export_layers (allocated at its first call): one device block holding the export table (gg_internal.h ExportArgs), a ring of map
+    // tables [PARAM_RING][n_slots] and a ring of parameter records for the batched launch of the lazily kept layers; their pinned host copies
+    void *d_export_block = nullptr, *h_export_block = nullptr;
+    const uint32_t *d_export_off = nullptr, *d_export_elem = nullptr;
+    const uint16_t *d_export_cell = nullptr;
+    ExportMap *d_export_maps = nullptr, *h_export_maps = nullptr;
+    CloudParams *d_export_lazy = nullptr, *h_export_lazy = nullptr;
+    hipEvent_t export_done[PARAM_RING]{};
+    bool export_used[PARAM_RING]{};
+    int export_next = 0;
+    int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
     float *d_image = nullptr;          // 3 * C floats (wire-format images)
     float *d_planes = nullptr;         // GG_NUM_LAYERS * Cpad floats: dense planes of gg_get_layers (allocated on first use)
     float *h_planes = nullptr;         // ... and their pinned landing zone on the host (one download for all requested layers)
@@ -1359,6 +1371,10 @@ void gg_destroy(gg_context *ctx)
         if (ctx->move_done[i]) hipEventDestroy(ctx->move_done[i]);
         if (ctx->move_done2[i]) hipEventDestroy(ctx->move_done2[i]);
     }
+    if (ctx->d_export_block) hipFree(ctx->d_export_block);
+    if (ctx->h_export_block) hipHostFree(ctx->h_export_block);
+    for (int i = 0; i < PARAM_RING; ++i)
+        if (ctx->export_done[i]) hipEventDestroy(ctx->export_done[i]);
     if (ctx->d_pc2) hipFree(ctx->d_pc2);
     if (ctx->h_pc2) hipHostFree(ctx->h_pc2);
     if (ctx->h_planes) hipHostFree(ctx->h_planes);
@@ -1973,6 +1989,163 @@ int gg_move_maps(gg_context *ctx, int n, const int32_t *slots, int first_slot, c
     }
     if (shifts)
         for (int k = 0; k < 2 * n; ++k) shifts[k] = sh[(size_t)k];
+    return GG_OK;
+}
+
+// gg_export_layers' device block, pinned rings and events, at its first call (not while `st` is being captured into a graph: an allocation
+// cannot be captured).  Nothing of the context changes when this fails.
+static int ensure_export_scratch(gg_context *ctx, hipStream_t st)
+{
+    if (ctx->d_export_block) return GG_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(ctx, GG_ERR_INVALID, "gg_export_layers: the first call allocates its scratch and cannot be captured into a graph");
+    (void)hipGetLastError();
+    const Arena &a = ctx->arena;
+    const int C = a.g.C;
+    const int br = (a.g.rows + EXPORT_TILE - 1) / EXPORT_TILE, bc = (a.g.cols + EXPORT_TILE - 1) / EXPORT_TILE;
+    // the export table: every block's cells in the order of their elements in the sheared layer
+    std::vector<uint32_t> off((size_t)br * bc + 1, 0u), elem;
+    std::vector<uint16_t> cell;
+    elem.reserve((size_t)C);
+    cell.reserve((size_t)C);
+    std::vector<std::pair<uint32_t, uint16_t>> blk;
+    for (int b = 0; b < br * bc; ++b) {
+        const int r0 = (b % br) * EXPORT_TILE, c0 = (b / br) * EXPORT_TILE;
+        blk.clear();
+        for (int ci = 0; ci < EXPORT_TILE && c0 + ci < a.g.cols; ++ci)
+            for (int ri = 0; ri < EXPORT_TILE && r0 + ri < a.g.rows; ++ri) blk.emplace_back((uint32_t)gp_idx(a, r0 + ri, c0 + ci), (uint16_t)(ri | (ci << 6)));
+        std::sort(blk.begin(), blk.end());
+        for (const auto &e : blk) {
+            if (e.first >= (uint32_t)a.gpl.elems) return fail(ctx, GG_ERR_GEOMETRY, "gg_export_layers: a cell's element lies outside the layer");
+            elem.push_back(e.first);
+            cell.push_back(e.second);
+        }
+        off[(size_t)b + 1] = (uint32_t)elem.size();
+    }
+    const size_t ring = (size_t)PARAM_RING * ctx->n_slots;
+    const size_t o_off = 0;
+    const size_t o_elem = align_up(o_off + off.size() * sizeof(uint32_t), 256);
+    const size_t o_cell = align_up(o_elem + elem.size() * sizeof(uint32_t), 256);
+    const size_t o_maps = align_up(o_cell + cell.size() * sizeof(uint16_t), 256);
+    const size_t o_lazy = align_up(o_maps + ring * sizeof(ExportMap), 256);
+    const size_t bytes = o_lazy + ring * sizeof(CloudParams);
+    const size_t h_lazy = align_up(ring * sizeof(ExportMap), 256), h_bytes = h_lazy + ring * sizeof(CloudParams);
+    void *block = nullptr, *h = nullptr;
+    hipEvent_t ev[PARAM_RING]{};
+    hipError_t e = hipMalloc(&block, bytes);
+    int code = GG_ERR_NOMEM;
+    const char *what = "gg_export_layers: device scratch";
+    if (e != hipSuccess) block = nullptr;
+    if (e == hipSuccess) {
+        what = "gg_export_layers: pinned parameter ring";
+        e = hipHostMalloc(&h, h_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) h = nullptr;
+    }
+    for (int i = 0; i < PARAM_RING && e == hipSuccess; ++i) {
+        code = GG_ERR_HIP;
+        what = "gg_export_layers: events";
+        e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+        if (e != hipSuccess) ev[i] = nullptr;
+    }
+    // (synchronous copies: the table is on the device before any stream can launch an export)
+    what = e == hipSuccess ? "gg_export_layers: export table" : what;
+    if (e == hipSuccess) e = hipMemcpy((char *)block + o_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy((char *)block + o_elem, elem.data(), elem.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy((char *)block + o_cell, cell.data(), cell.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        for (hipEvent_t x : ev)
+            if (x) hipEventDestroy(x);
+        if (h) hipHostFree(h);
+        if (block) hipFree(block);
+        (void)hipGetLastError();
+        return fail(ctx, code, what, e);
+    }
+    ctx->d_export_block = block;
+    ctx->h_export_block = h;
+    ctx->d_export_off = (const uint32_t *)((char *)block + o_off);
+    ctx->d_export_elem = (const uint32_t *)((char *)block + o_elem);
+    ctx->d_export_cell = (const uint16_t *)((char *)block + o_cell);
+    ctx->d_export_maps = (ExportMap *)((char *)block + o_maps);
+    ctx->d_export_lazy = (CloudParams *)((char *)block + o_lazy);
+    ctx->h_export_maps = (ExportMap *)h;
+    ctx->h_export_lazy = (CloudParams *)((char *)h + h_lazy);
+    for (int i = 0; i < PARAM_RING; ++i) ctx->export_done[i] = ev[i];
+    return GG_OK;
+}
+
+int gg_export_layers(gg_context *ctx, int n, const int32_t *slots, int first_slot, unsigned layer_mask, int order, float *d_dst, size_t plane_stride,
+                     void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    if (n < 0) return fail(ctx, GG_ERR_INVALID, "gg_export_layers: n < 0");
+    if (n == 0) return GG_OK;
+    if (layer_mask == 0u || (layer_mask >> GG_NUM_LAYERS) != 0u) return fail(ctx, GG_ERR_INVALID, "gg_export_layers: layer_mask");
+    if (order != GG_PLANES_COLMAJOR && order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, "gg_export_layers: order");
+    if (!d_dst) return fail(ctx, GG_ERR_INVALID, "gg_export_layers: d_dst is null");
+    if (plane_stride < (size_t)ctx->arena.g.C) return fail(ctx, GG_ERR_INVALID, "gg_export_layers: plane_stride is smaller than rows * cols");
+    if (const int rc = check_slot_list(ctx, "gg_export_layers", n, slots, first_slot)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = pick_stream(ctx, stream);
+    if (const int rc = ensure_export_scratch(ctx, st)) return rc;
+    const Arena &a = ctx->arena;
+    auto slot_of = [&](int i) { return slots ? slots[i] : first_slot + i; };
+    // ring entry (the pinned tables are rewritten only when the copies that read them last have run)
+    const int g = ctx->export_next;
+    ctx->export_next = (g + 1) % PARAM_RING;
+    if (ctx->export_used[g]) HIPCHK(ctx, hipEventSynchronize(ctx->export_done[g]));
+    ctx->export_used[g] = false;
+    ExportMap *hm = ctx->h_export_maps + (size_t)g * ctx->n_slots, *dm = ctx->d_export_maps + (size_t)g * ctx->n_slots;
+    CloudParams *hl = ctx->h_export_lazy + (size_t)g * ctx->n_slots, *dl = ctx->d_export_lazy + (size_t)g * ctx->n_slots;
+    const unsigned lazy_mask = (1u << GG_LAYER_MAXGROUNDHEIGHT) | (1u << GG_LAYER_GROUNDCANDIDATES) | (1u << GG_LAYER_PLANEDIST);
+    int n_lazy = 0;
+    for (int i = 0; i < n; ++i) {
+        const int slot = slot_of(i);
+        hm[i].slot = slot;
+        hm[i].fresh = ctx->fresh[slot] ? 1 : 0; // (a fresh map stays fresh: its planes are the reset's constants)
+        hm[i].fresh_z = ctx->fresh_z[slot];
+        hm[i].reserved = 0;
+        if ((layer_mask & lazy_mask) && ctx->lazy_pending[slot]) hl[n_lazy++] = ctx->lazy_params[slot];
+    }
+    // `st` follows every earlier map mutation and batch of the context, and both halves of a divided batch: the export reads maps of either
+    if (st == ctx->stream) {
+        if (const int rc = own_stream_waits_for_batches(ctx, false)) return rc;
+    } else {
+        if (ctx->map_event_pending) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->map_event, 0));
+        if (ctx->have_batch_event && ctx->last_batch_stream != st && !ctx->probe_unordered_streams) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->batch_event, 0));
+        if (const int rc = stream_waits_for_second_half(ctx, st)) return rc;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(dm, hm, sizeof(ExportMap) * n, hipMemcpyHostToDevice, st));
+    if (n_lazy) { // the three layers GG_FLAG_MINIMAL_LAYERS left out, for exactly the exported slots that still miss them: one launch
+        HIPCHK(ctx, hipMemcpyAsync(dl, hl, sizeof(CloudParams) * n_lazy, hipMemcpyHostToDevice, st));
+        launch_reduce_lazy_batch(a, dl, n_lazy, st);
+    }
+    ExportArgs x;
+    x.maps = dm;
+    x.block_off = ctx->d_export_off;
+    x.elem = ctx->d_export_elem;
+    x.cell = ctx->d_export_cell;
+    x.blocks_r = (a.g.rows + EXPORT_TILE - 1) / EXPORT_TILE;
+    x.blocks_c = (a.g.cols + EXPORT_TILE - 1) / EXPORT_TILE;
+    x.mask = layer_mask;
+    x.n_planes = __builtin_popcount(layer_mask);
+    x.order = order;
+    x.dst = d_dst;
+    x.plane_stride = plane_stride;
+    launch_export(a, x, n, ctx->export_variant, st);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->export_done[g], st));
+    ctx->export_used[g] = true;
+    // whatever writes one of these maps next on another stream waits for the export (and for the lazily kept layers it computed)
+    if (st == ctx->stream) {
+        if (const int rc = own_stream_mutated_map(ctx)) return rc;
+    } else {
+        HIPCHK(ctx, hipEventRecord(ctx->batch_event, st));
+        ctx->have_batch_event = true;
+        ctx->last_batch_stream = st;
+        ctx->map_event_pending = false; // (this stream has waited; later batches anywhere follow batch_event)
+    }
+    for (int i = 0; i < n_lazy; ++i) ctx->lazy_pending[hl[i].slot] = 0;
     return GG_OK;
 }
 
@@ -2867,6 +3040,7 @@ extern "C" int gg_debug_set_tuning(gg_context *ctx, const char *key, int value)
         for (int k = 0; k < ctx->n_slots; ++k) c += ctx->fresh[k] ? 1 : 0;
         return c;
     }
+    if (!strcmp(key, "export_variant_default")) return EXPORT_VARIANT_DEFAULT; // (read-only: the kernel gg_export_layers ships with)
     if (!strcmp(key, "graphs")) { // 0 = every call launches eagerly, 1 = one cloud per call replays a captured graph (the default)
         ctx->graphs_enabled = value != 0;
         drop_graphs(ctx);
@@ -2888,6 +3062,7 @@ extern "C" int gg_debug_set_tuning(gg_context *ctx, const char *key, int value)
     else if (!strcmp(key, "results_direct")) ctx->results_direct = value; // (A/B: 0 = results into HBM and a copy behind k_label, as before round 5)
     else if (!strcmp(key, "halves_min_clouds")) ctx->halves_min_clouds = std::max(2, value); // (tests: GG_FLAG_CONCURRENT_HALVES on small batches)
     else if (!strcmp(key, "move_chunk")) ctx->move_chunk_tune = value;
+    else if (!strcmp(key, "export_variant")) ctx->export_variant = value ? 1 : 0; // (A/B: 1 = gg_export_layers gathers in destination order, k_export_gather)
     else if (!strcmp(key, "halves_no_fork")) ctx->probe_no_fork = value != 0; // (measurement only: the side stream does not wait for the caller's)
     else if (!strcmp(key, "scan_fault")) ctx->arena.tune_scan_fault = value;
     else if (!strcmp(key, "sweep_fault")) ctx->arena.tune_sweep_fault = value;

@@ -278,6 +278,29 @@ struct ScoreArgs {
     unsigned long long *scores;   // [n_slots][SCORE_WORDS]
 };
 
+// gg_export_layers (k9_export.hip): one entry per exported map, and what the kernels of a call share.  The export table cuts the map into
+// blocks of EXPORT_TILE x EXPORT_TILE cells (block = block row + block column * blocks_r) and lists every block's cells sorted by their
+// element in the sheared (ground, confidence) layer: block b owns entries [block_off[b], block_off[b + 1]) of `elem` (the element) and
+// `cell` (row in block | column in block << 6)
+constexpr int EXPORT_TILE = 64;
+struct ExportMap {
+    int slot;
+    int fresh;     // the map is fresh (gg_context::fresh): ground = fresh_z, groundpatch = 1e-7 everywhere, its layer is not read
+    float fresh_z;
+    int reserved;
+};
+struct ExportArgs {
+    const ExportMap *maps;
+    const uint32_t *block_off, *elem;
+    const uint16_t *cell;
+    int blocks_r, blocks_c;
+    unsigned mask; // bit per gg_layer
+    int n_planes;  // its popcount
+    int order;     // GG_PLANES_*
+    float *dst;
+    size_t plane_stride;
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -314,6 +337,8 @@ void launch_scatter(const Arena &a, const CloudParams *d_params, int n_clouds, i
 void launch_reduce(const Arena &a, const CloudParams *d_params, int n_clouds, hipStream_t s);
 void launch_stage_insert(const Arena &a, const CloudParams *d_params, hipStream_t s); // gg_insert_cloud: :282-309 continued from the layers as they stand (one slot, dense layers)
 void launch_reduce_lazy(const Arena &a, const CloudParams &cp, hipStream_t s); // (GG_FLAG_MINIMAL_LAYERS: the other three layers, one slot)
+void launch_reduce_lazy_batch(const Arena &a, const CloudParams *d_params, int n_clouds, hipStream_t s); // (... of n slots in one launch: gg_export_layers)
+void launch_export(const Arena &a, const ExportArgs &x, int n_maps, int variant, hipStream_t s); // k9_export.hip; variant 0 = k_export_tiled, 1 = k_export_gather
 void launch_patch(const Arena &a, const CloudParams *d_params, int n_clouds, hipStream_t s);
 void launch_patch_stage(const Arena &a, const CloudParams *d_params, int slot, int section, hipStream_t s); // gg_run_stage: :323 + one quadrant (-1: all) on the slot's layers as they stand
 void launch_stage_cell(const Arena &a, int slot, int stage, int i, int j, hipStream_t s);                    // gg_run_stage: detect_ground_patch<S> / interpolate_cell of one cell

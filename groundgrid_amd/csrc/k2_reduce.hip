@@ -839,6 +839,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
     reduce_share<K2_LAZY3>(a, &cp, lds, 0, (int)blockIdx.x, (int)gridDim.x, n_dense_groups);
 }
 
+// ... and for MANY slots in one launch (gg_export_layers): the same walk with blockIdx.y as the map, params[blockIdx.y] = the parameters
+// of that slot's last call.  A tile is reduced by one work-group whatever the grid: the values do not depend on the launch shape.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_reduce_lazy_batch(const Arena a, const CloudParams *__restrict__ params, int n_dense_groups)
+{
+    __shared__ ReduceLds lds;
+    reduce_share<K2_LAZY3>(a, params, lds, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, n_dense_groups);
+}
+
 // GroundSegmentation::insert_cloud as a member of its own (gg_insert_cloud; include/groundgrid/GroundSegmentation.h:55,
 // src/GroundSegmentation.cpp:282-309 and the count of :234): the recurrences CONTINUE from what the layers hold -- no reset (:61-75 is
 // filter_cloud's), a cell's count starts wherever an earlier range left it -- so none of k_reduce's shortcuts apply (a wave-uniform
@@ -911,6 +919,16 @@ void launch_reduce_lazy(const Arena &a, const CloudParams &cp, hipStream_t s)
     const int per_cloud = std::min(4096, 2 * a.g.T);
     const int gd = std::max(1, per_cloud * 12 / 16), gl = std::max(1, per_cloud - gd);
     hipLaunchKernelGGL(k_reduce_lazy, dim3(gd + gl), dim3(256), 0, s, a, cp, gd);
+}
+
+void launch_reduce_lazy_batch(const Arena &a, const CloudParams *d_params, int n_clouds, hipStream_t s)
+{
+    for (int first = 0; first < n_clouds; first += 32768) { // (gridDim.y)
+        const int count = std::min(32768, n_clouds - first);
+        const int per_cloud = std::min(std::max(4096 / count, K2_MIN_GROUPS_PER_CLOUD), 2 * a.g.T); // (launch_reduce's shape)
+        const int gd = std::max(1, per_cloud * 12 / 16), gl = std::max(1, per_cloud - gd);
+        hipLaunchKernelGGL(k_reduce_lazy_batch, dim3(gd + gl, count), dim3(256), 0, s, a, d_params + first, gd);
+    }
 }
 
 } // namespace gg

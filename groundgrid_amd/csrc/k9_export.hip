@@ -1,0 +1,172 @@
+// K9 -- gg_export_layers: the layers of MANY maps as dense planes in device memory, one launch (include/groundgrid_hip.h).
+//
+// The sources are not planes.  `ground` / `groundpatch` are interleaved float2 pairs in the sheared ring order of gp_layout.h: cells
+// that are neighbours in a plane lie 512 bytes or more apart there, and 64 consecutive elements belong to 64 different rings.  The
+// nine per-call layers are 16 x 16 tile blocks behind per-tile liveness words (gg_internal.h tile_live).  k_layers_extract (k6_wire.hip)
+// walks the DESTINATION cell by cell and gathers: every lane of a wavefront then reads its pair from another 128-byte line.
+//
+// k_export_tiled gives every work-group one 64 x 64 block of cells of one map and
+//   * reads the pairs of that block in ELEMENT order: the export table (built once per context, shared by all maps) lists each block's
+//     cells sorted by their element in the sheared layer, so consecutive lanes read consecutive elements wherever the layout has them
+//     (inside one 64-ring group a block holds runs of 32 consecutive elements: 256 bytes),
+//   * reads a per-call layer tile by tile, 1 KiB contiguous per wavefront and tile, and only the half columns that are live and only
+//     the layers the mask names,
+//   * stages the block in LDS (row + 65 * column: both walks of it are free of bank conflicts) and writes each destination plane in
+//     runs of 64 consecutive floats -- 256 bytes per wavefront store -- for either order: the row-major planes are the transposed
+//     read of the same LDS block, not a second pass over the source.
+// A fresh map (gg_reset_maps left its layer unwritten) gets the reset's constants; its layer is not read.
+//
+// k_export_gather is the straightforward form (destination order, blockIdx.y = map), kept for the A/B of tools/bench_export.py
+// (gg_debug_set_tuning "export_variant" = 1).
+#include "gg_device.h"
+
+#include <algorithm>
+
+namespace gg {
+
+constexpr int EXP_LD = EXPORT_TILE + 1; // LDS pitch of a block: element (row, col) at row + EXP_LD * col
+
+__device__ __forceinline__ int export_plane_index(unsigned mask, int layer) { return __popc(mask & ((1u << layer) - 1u)); }
+
+__global__ __launch_bounds__(256) void k_export_tiled(const Arena a, const ExportArgs x)
+{
+    __shared__ float lds[2][EXPORT_TILE * EXP_LD];
+    const int tid = threadIdx.x;
+    const ExportMap m = x.maps[blockIdx.y];
+    const int mt = (int)blockIdx.x, mtr = mt % x.blocks_r, mtc = mt / x.blocks_r;
+    const int r0 = mtr * EXPORT_TILE, c0 = mtc * EXPORT_TILE;
+    const int rows = a.g.rows, cols = a.g.cols;
+    const int nr = min(EXPORT_TILE, rows - r0), nc = min(EXPORT_TILE, cols - c0);
+    float *out = x.dst + (size_t)blockIdx.y * (size_t)x.n_planes * x.plane_stride;
+    const bool row_major = x.order == GG_PLANES_ROWMAJOR;
+
+    // the block -> one destination plane: a wavefront covers 64 consecutive floats of the plane in either order
+    auto store = [&](float *plane, auto value) {
+#pragma unroll 4
+        for (int idx = tid; idx < EXPORT_TILE * EXPORT_TILE; idx += 256) {
+            const int fast = idx & (EXPORT_TILE - 1), slow = idx >> 6;
+            const int ri = row_major ? slow : fast, ci = row_major ? fast : slow;
+            if (ri >= nr || ci >= nc) continue;
+            const size_t at = row_major ? (size_t)(r0 + ri) * cols + (size_t)(c0 + ci) : (size_t)(r0 + ri) + (size_t)(c0 + ci) * rows;
+            plane[at] = value(ri + ci * EXP_LD);
+        }
+    };
+
+    const unsigned gp_mask = x.mask & ((1u << GG_LAYER_GROUND) | (1u << GG_LAYER_GROUNDPATCH));
+    if (gp_mask) {
+        float *p_ground = out + (size_t)export_plane_index(x.mask, GG_LAYER_GROUND) * x.plane_stride;
+        float *p_conf = out + (size_t)export_plane_index(x.mask, GG_LAYER_GROUNDPATCH) * x.plane_stride;
+        if (m.fresh) { // the reset's values by definition (gg_context::fresh): nothing of the layer is read
+            const float z = m.fresh_z, w = (float)0.0000001;
+            if (gp_mask & (1u << GG_LAYER_GROUND)) store(p_ground, [&](int) { return z; });
+            if (gp_mask & (1u << GG_LAYER_GROUNDPATCH)) store(p_conf, [&](int) { return w; });
+        } else {
+            const float2 *gp2 = gp2_ptr(a, m.slot);
+            const uint32_t first = x.block_off[mt], end = x.block_off[mt + 1];
+            for (uint32_t i = first + tid; i < end; i += 256) {
+                const float2 v = gp2[x.elem[i]];
+                const uint32_t c = x.cell[i]; // row in block | column in block << 6
+                const int at = (int)(c & 63u) + (int)(c >> 6) * EXP_LD;
+                lds[0][at] = v.x;
+                lds[1][at] = v.y;
+            }
+            __syncthreads();
+            if (gp_mask & (1u << GG_LAYER_GROUND)) store(p_ground, [&](int at) { return lds[0][at]; });
+            if (gp_mask & (1u << GG_LAYER_GROUNDPATCH)) store(p_conf, [&](int at) { return lds[1][at]; });
+        }
+    }
+    if (!(x.mask & ~gp_mask)) return; // (uniform)
+
+    // the per-call layers: wavefront w stages tiles 4 w .. 4 w + 3 of the block's 4 x 4 tiles; a lane owns four consecutive rows of one
+    // column of a tile (16 bytes, half of one liveness bit's half column)
+    const int wave = tid >> 6, lane = tid & 63;
+    const float *percall = percall_ptr(a, m.slot);
+    const uint32_t *tile_live = a.tile_live + (size_t)m.slot * a.tile_live_stride;
+    int rank[4];
+    bool live[4];
+    int lds_at[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = wave * 4 + j, ltr = t & 3, ltc = t >> 2;
+        const int tr = mtr * (EXPORT_TILE / TILE) + ltr, tc = mtc * (EXPORT_TILE / TILE) + ltc;
+        rank[j] = -1;
+        live[j] = false;
+        lds_at[j] = (ltr * TILE + (lane & 3) * 4) + (ltc * TILE + (lane >> 2)) * EXP_LD;
+        if (tr < a.g.tiles_r && tc < a.g.tiles_c) {
+            rank[j] = (int)a.tile_rank[tr + tc * a.g.tiles_r];
+            live[j] = ((tile_live[rank[j]] >> live_bit(lane * 4)) & 1u) != 0u;
+        }
+    }
+    __syncthreads(); // (the stores of the pairs above have read both LDS blocks)
+    int buf = 0;     // the two blocks alternate: a layer's staging never meets the stores of the layer before it, one barrier per layer
+    for (int l = 0; l < GG_NUM_LAYERS; ++l) {
+        if (!((x.mask >> l) & 1u) || percall_position(l) < 0) continue; // (uniform)
+        const float dead = layer_reset_value(l);
+        const int position = percall_position(l);
+        float *blk = lds[buf];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (rank[j] < 0) continue;
+            float4 v = make_float4(dead, dead, dead, dead);
+            if (live[j]) v = *reinterpret_cast<const float4 *>(percall + percall_index(rank[j], position, lane * 4));
+            blk[lds_at[j] + 0] = v.x;
+            blk[lds_at[j] + 1] = v.y;
+            blk[lds_at[j] + 2] = v.z;
+            blk[lds_at[j] + 3] = v.w;
+        }
+        __syncthreads();
+        store(out + (size_t)export_plane_index(x.mask, l) * x.plane_stride, [&](int at) { return blk[at]; });
+        buf ^= 1;
+    }
+}
+
+// destination order, cell by cell (k_layers_extract with the map in blockIdx.y, both orders and the fresh maps)
+__global__ __launch_bounds__(256) void k_export_gather(const Arena a, const ExportArgs x)
+{
+    const ExportMap m = x.maps[blockIdx.y];
+    const float *src = percall_ptr(a, m.slot);
+    const float2 *gp2 = gp2_ptr(a, m.slot);
+    const int rows = a.g.rows, cols = a.g.cols;
+    float *out = x.dst + (size_t)blockIdx.y * (size_t)x.n_planes * x.plane_stride;
+    const bool row_major = x.order == GG_PLANES_ROWMAJOR;
+    const bool any_percall = (x.mask & ~((1u << GG_LAYER_GROUND) | (1u << GG_LAYER_GROUNDPATCH))) != 0u;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.g.C; i += gridDim.x * blockDim.x) {
+        const int r = row_major ? i / cols : i % rows, c = row_major ? i % cols : i / rows;
+        bool live = false;
+        size_t at = 0;
+        if (any_percall) {
+            live = cell_is_live(a, m.slot, r, c);
+            at = percall_index_of(a, 0, r, c);
+        }
+        float2 g = make_float2(m.fresh_z, (float)0.0000001);
+        if (!m.fresh && (x.mask & ((1u << GG_LAYER_GROUND) | (1u << GG_LAYER_GROUNDPATCH)))) g = gp2[gp_idx(a, r, c)];
+        int k = 0;
+#pragma unroll
+        for (int l = 0; l < GG_NUM_LAYERS; ++l) {
+            if (!((x.mask >> l) & 1u)) continue; // (uniform)
+            float v;
+            if (l == GG_LAYER_GROUND) v = g.x;
+            else if (l == GG_LAYER_GROUNDPATCH) v = g.y;
+            else v = live ? src[at + (size_t)percall_position(l) * (TILE * TILE)] : layer_reset_value(l);
+            out[(size_t)k * x.plane_stride + i] = v;
+            ++k;
+        }
+    }
+}
+
+void launch_export(const Arena &a, const ExportArgs &x, int n_maps, int variant, hipStream_t s)
+{
+    for (int first = 0; first < n_maps; first += 32768) { // (gridDim.y: one launch for every context of up to 32768 maps)
+        const int count = std::min(32768, n_maps - first);
+        ExportArgs part = x;
+        part.maps = x.maps + first;
+        part.dst = x.dst + (size_t)first * (size_t)x.n_planes * x.plane_stride;
+        if (variant == 1) {
+            const int blocks = std::min((a.g.C + 255) / 256, count >= 64 ? 64 : 2048);
+            hipLaunchKernelGGL(k_export_gather, dim3(blocks, count), dim3(256), 0, s, a, part);
+        } else
+            hipLaunchKernelGGL(k_export_tiled, dim3(x.blocks_r * x.blocks_c, count), dim3(256), 0, s, a, part);
+    }
+}
+
+} // namespace gg

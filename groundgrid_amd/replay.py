@@ -56,11 +56,13 @@ def replay(frames, backend, evaluator: GroundEvaluator = None, on_frame=None):
 
 
 def score_configs(frames, configs, *, max_points: int, dimension: float = 120.0, resolution: float = 0.33, device: int = 0,
-                  allow_unknown: bool = False, seg=None):
+                  allow_unknown: bool = False, seg=None, return_ground: bool = False):
     """The parameter sweep: K candidate configurations as K map slots of one context (set_slot_configs), every frame's cloud uploaded
     once and filtered against all K maps in one batch (frame 0: reset_maps, later frames: one move_maps), the evaluator of every map
     kept on the device (set_scoring).  Nothing is downloaded per frame; returns the K GroundEvaluators of replay(frames, ...) run once
-    per configuration.  frames: iterable of groundgrid_amd.kitti.Frame whose clouds carry the semantic label in `ring`."""
+    per configuration.  frames: iterable of groundgrid_amd.kitti.Frame whose clouds carry the semantic label in `ring`.
+    return_ground: also return every configuration's final `ground` layer, a CUDA float32 tensor [K, cols, rows] (Eigen's column-major
+    planes, export_layers) -- (evaluators, ground) -- so that a sweep can compare terrains without a host round trip per map."""
     import torch
 
     from . import api, kitti
@@ -92,7 +94,12 @@ def score_configs(frames, configs, *, max_points: int, dimension: float = 120.0,
             else:
                 seg.move_maps([(fr.odom[0], fr.odom[1])] * K, [fr.base_to_map] * K, rotation=kitti.ROTATION_CONVENTION, on_torch_stream=True)
             out = seg.filter_batch(pts, [n] * K, [fr.origin] * K, [fr.map_to_base_z] * K, out=out)
-        return seg.scores(first_slot=0, n=K, allow_unknown=allow_unknown)
+        scores = seg.scores(first_slot=0, n=K, allow_unknown=allow_unknown)
+        if not return_ground:
+            return scores
+        ground = seg.export_layers(["ground"], first_slot=0, n=K)[:, 0].clone()
+        torch.cuda.current_stream(dev).synchronize()  # (the planes are complete before a context of our own is destroyed)
+        return scores, ground
     finally:
         if own:
             seg.close()

@@ -253,6 +253,32 @@ int gg_get_layer(gg_context *ctx, int slot, int layer, float *dst);
  * (src/GroundGridNodelet.cpp:211-224 publishes every layer that has a subscriber): the extraction kernels and the downloads of
  * all requested layers are enqueued back to back and waited for once, instead of one synchronisation per layer. */
 int gg_get_layers(gg_context *ctx, int slot, float *const dst[GG_NUM_LAYERS]);
+/* The layers of n maps as dense planes in DEVICE memory, one launch, no synchronisation: what gg_get_layers returns for each of the
+ * maps, bit for bit, where a consumer on the GPU (a planner, a model, a server that forwards terrain) can read it.
+ * Map i = slots ? slots[i] : first_slot + i (distinct).  layer_mask has one bit per gg_layer, K = its popcount; the k-th requested
+ * layer (in gg_layer order) of map i lands at d_dst + (i * K + k) * plane_stride.  plane_stride is in floats (>= rows * cols); the
+ * elements between rows * cols and plane_stride are not written.  order: where cell (row, col) lies inside a plane. */
+enum { GG_PLANES_COLMAJOR = 0,   /* cell (row, col) at row + col * rows: Eigen's order, what gg_get_layers returns */
+       GG_PLANES_ROWMAJOR = 1 }; /* cell (row, col) at row * cols + col: image order, what the image getters use */
+/* `stream` follows the gg_filter_batch convention (NULL = the context's stream, GG_STREAM_DEFAULT, or a caller stream).  The call
+ * enqueues and returns: the host `slots` array may be freed on return, and work the caller enqueues on `stream` afterwards sees
+ * the planes.  Ordering is the library's job, as for a batch: the export waits for every earlier map mutation and batch of the
+ * context on other streams (both halves under GG_FLAG_CONCURRENT_HALVES), and every later entry point that writes one of the maps on
+ * another stream waits for the export.
+ * A FRESH map (gg_reset_maps, nothing since) exports ground = odom_z and groundpatch = 1e-7f without its layer being read or filled:
+ * it, and every other fresh map of the context, stays fresh.  When layer_mask names maxGroundHeight, groundCandidates or planeDist,
+ * the exported maps whose last cloud left them out (GG_FLAG_MINIMAL_LAYERS, the default of gg_filter_batch) get them computed first, in
+ * one launch over exactly those maps on `stream`; a mask without the three launches nothing extra.
+ * Argument errors write nothing and change nothing: GG_ERR_CAPACITY (a slot outside the context), GG_ERR_INVALID (null ctx, n < 0,
+ * repeated slots, layer_mask == 0 or with a bit at or above GG_NUM_LAYERS, unknown order, null d_dst, plane_stride < rows * cols -- the
+ * last five only with n > 0).  n == 0 is GG_OK.  (A GG_ERR_HIP from the runtime in the middle of the call is not covered by that.)
+ * The FIRST call of a context is slower and blocks: it builds the export table (6 bytes per cell) on the host, allocates it with the
+ * call's parameter rings (GG_ERR_NOMEM when that does not fit) and uploads it with synchronous copies; later calls allocate nothing
+ * and only enqueue.  Capturing the call into a caller's graph is neither supported nor tested: it waits on events that were recorded
+ * outside the capture, and the first call allocates. */
+int gg_export_layers(gg_context *ctx, int n, const int32_t *slots, int first_slot, unsigned layer_mask, int order, float *d_dst,
+                     size_t plane_stride, void *stream);
+#define GG_HAS_EXPORT_LAYERS 1
 /* GroundSegmentation::expectedPoints (src/GroundSegmentation.cpp:40-46), host copy */
 int gg_get_expected_points(const gg_context *ctx, float *dst);
 
