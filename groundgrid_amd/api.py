@@ -326,13 +326,16 @@ class GroundSegmentation:
         return shifts
 
     def export_layers(self, names=None, *, slots=None, first_slot: int = 0, n: Optional[int] = None, out=None, row_major: bool = False,
-                      stream=None):
+                      stream=None, own_stream: bool = False, plane_stride: Optional[int] = None):
         """The named layers (default: all eleven, in gg_layer order) of many maps as one CUDA torch.float32 tensor [n, K, cols, rows]
         (Eigen's column-major planes: element [i, k, c, r] is cell (r, c)), or [n, K, rows, cols] with row_major -- what
         map(slot).layers() returns for each map, bit for bit, without leaving the device (gg_export_layers).  Map i = slots[i], or
         first_slot + i for n maps (default: up to the last slot).  `out` (same shape, contiguous) is reused when given.  Enqueued on the
         current torch stream like filter_batch (or on `stream`), without synchronising: torch ops enqueued there afterwards see the
-        planes.  Fresh maps stay fresh; the three lazily kept layers are computed first where the mask names them."""
+        planes.  Fresh maps stay fresh; the three lazily kept layers are computed first where the mask names them.
+        own_stream: enqueue on the context's own stream instead (the caller orders its own streams around the call).  plane_stride
+        (in floats, >= rows * cols): the planes lie that far apart in a flat [n * K * plane_stride] tensor, which is returned (or `out`
+        of that size reused); the elements between a plane's end and the next plane are not written."""
         import torch
 
         self._torch_used = True
@@ -344,12 +347,15 @@ class GroundSegmentation:
             raise ValueError("export_layers: names must be distinct and in gg_layer order")
         cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
         shape = (cnt, len(names), self.rows, self.cols) if row_major else (cnt, len(names), self.cols, self.rows)
+        if plane_stride is not None:
+            shape = (cnt * len(names) * int(plane_stride),)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", self.device))
         assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()
         s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
         rc = self._L.gg_export_layers(self._ctx, cnt, ptr, first, mask, _lib.GG_PLANES_ROWMAJOR if row_major else _lib.GG_PLANES_COLMAJOR,
-                                      C.c_void_p(out.data_ptr()), self.rows * self.cols, C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
+                                      C.c_void_p(out.data_ptr()), self.rows * self.cols if plane_stride is None else int(plane_stride),
+                                      None if own_stream else C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
         _check(self._L, self._ctx, rc, "gg_export_layers")
         return out
 
@@ -593,9 +599,10 @@ class GroundSegmentation:
     # -- batched device-resident form
     def filter_batch(self, points, n_points: Sequence[int], origins, base_z, *, first_slot: int = 0,
                      out: Optional[BatchOutputs] = None, want_clouds: bool = False, want_masks: bool = False, stream=None,
-                     transforms=None, slots=None, want_pc2: bool = False) -> BatchOutputs:
+                     transforms=None, slots=None, want_pc2: bool = False, own_stream: bool = False) -> BatchOutputs:
         """points: CUDA torch tensor [B, stride, 16] (packed gg_point16) or [B, stride, 32] (PointXYZIR), uint8.
-        Enqueues on the current torch stream and returns without synchronising."""
+        Enqueues on the current torch stream and returns without synchronising.  own_stream: on the context's own stream instead (NULL in
+        the C ABI): the caller makes sure that `points` is complete before the call."""
         import torch
 
         self._torch_used = True
@@ -636,7 +643,7 @@ class GroundSegmentation:
         s = stream if stream is not None else torch.cuda.current_stream(points.device).cuda_stream
         # torch hands out 0 for its default stream = the legacy null stream; NULL would mean "the context's own stream" to
         # the library, which is not ordered with torch ops / RCCL -- so name the default stream explicitly
-        rc = self._L.gg_filter_batch(self._ctx, C.byref(b), C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
+        rc = self._L.gg_filter_batch(self._ctx, C.byref(b), None if own_stream else C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
         _check(self._L, self._ctx, rc, "gg_filter_batch")
         return out
 

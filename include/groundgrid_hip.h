@@ -209,7 +209,8 @@ const char *gg_last_error(const gg_context *ctx);
 int gg_reset_map(gg_context *ctx, int slot, double pos_x, double pos_y, float odom_z);
 /* The same for n_slots consecutive map states in one launch (position (pos_x, pos_y) and height odom_z for all).  With
  * persistent_only != 0 only the state that outlives a cloud is re-initialised -- ground := odom_z, groundpatch := 1e-7 -- which
- * is all a "cold" start needs: the nine per-call layers are rewritten by the next filter call anyway (:61-75).
+ * is all a "cold" start needs: the nine per-call layers are rewritten by the next filter call anyway (:61-75).  Until then they read
+ * as they stood (the three lazily kept ones as the map's last cloud left them), and the map position becomes (pos_x, pos_y) either way.
  * `stream`: NULL = the context's stream (like every other map mutation); a caller stream (or GG_STREAM_DEFAULT) enqueues the
  * fills there, ordered like a batch on that stream -- a server that re-initialises maps between batches on its own stream
  * then has no cross-stream hand-over in its loop.
@@ -224,7 +225,9 @@ int gg_set_map_position(gg_context *ctx, int slot, double pos_x, double pos_y);
 /* GroundGrid::update for an initialised map (src/GroundGrid.cpp:83-147): grid_map::GridMap::move to the odometry
  * position (whole cells; the map position is snapped), newly exposed cells get ground = -(z of the cell centre in
  * base_link) and groundpatch = 0 (:121-131), then convertToDefaultStartIndex (:143) -- on the device, so that the two
- * persistent layers never leave HBM between clouds.
+ * persistent layers never leave HBM between clouds.  ONLY those two scroll: the nine per-call layers are rewritten by the next filter call
+ * (:61-75) and are left where they are -- a reader between the move and that call gets them as they stood before the move, where the
+ * reference's grid_map::move would show them shifted, with NaN in the newly exposed cells (documented deviation; gg_move_maps alike).
  * base_plane = {r20, r21, r22, tz}: third row of the rotation and z of the translation of
  * lookupTransform("base_link", "map") (:103), i.e. z_base(p) = ((r20 * p.x + r21 * p.y) + r22 * p.z) + tz, evaluated in
  * this order in double (:129).  ABI v2: the caller hands over matrix entries, NOT a quaternion -- which rotation matrix
