@@ -12,6 +12,7 @@ PyTorch is used only for device buffers / streams in the batched path.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -239,6 +240,9 @@ class GroundSegmentation:
              min_dist_squared: float = 0.0):
         if self._ctx:
             self.close()
+        for name, v in (("vertical_point_ang_dist", vertical_point_ang_dist), ("min_dist_squared", min_dist_squared)):
+            if not (float(v) >= 0.0) or math.isinf(float(v)):   # (what gg_create answers with GG_ERR_GEOMETRY; zero = the reference's value)
+                raise GroundGridError(f"gg_create: {name} = {v!r} must be finite and not negative")
         geom = GGGeometry(float(dimension), float(resolution), float(vertical_point_ang_dist), float(min_dist_squared))
         ctx = C.c_void_p()
         rc = self._L.gg_create(C.byref(geom), int(n_slots), int(max_points), int(device), C.byref(ctx))

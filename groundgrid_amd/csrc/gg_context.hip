@@ -935,6 +935,11 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
     if (geom_in) {
         if (geom_in->length > 0.f) geom.length = geom_in->length;
         if (geom_in->resolution > 0.f) geom.resolution = geom_in->resolution;
+        // the two sensor constants: zero (either sign) selects the reference's value; a negative, infinite or NaN one is an error, not
+        // silently the default (a NaN compares false with everything: `> 0` alone would let it through as "zero")
+        const float sensor[2] = {geom_in->vertical_point_ang_dist, geom_in->min_dist_squared};
+        for (const float v : sensor)
+            if (!(v >= 0.f) || isinf(v)) return GG_ERR_GEOMETRY;
         if (geom_in->vertical_point_ang_dist > 0.f) geom.vertical_point_ang_dist = geom_in->vertical_point_ang_dist;
         if (geom_in->min_dist_squared > 0.f) geom.min_dist_squared = geom_in->min_dist_squared;
     }

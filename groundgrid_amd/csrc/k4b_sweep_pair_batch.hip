@@ -174,6 +174,9 @@ template <int PAIR> GG_DEV void run_pairb(const Params &P, const sp::Plan &pl, c
                 } else if (res4 == y_join) {
                     j = WP{partner_for_y(st.h1.w), partner_for_y(st.h1.p)};
                 }
+                // (uniform, once per cloud) the visit of B_1(1) rewrites a cell the CD corner wavefront reads as OLD: after its loads
+                if (PAIR == sp::PAIR_BC && u == 2 && !has_prev && t == 0)
+                    while (__builtin_amdgcn_readfirstlane(mem.lds_i(sp::cd_loaded_word(L))) == 0) __builtin_amdgcn_s_sleep(1);
                 const int slot = u % (int)sp::PFB;
                 WP res;
                 if (u == 0) res = st.template step<0>(t, slot, x, j, first, c0, c1, P, mem);
@@ -198,6 +201,10 @@ template <int CD> GG_DEV void run_pairb_corner(const Params &P, const sp::LdsB &
     for (int r0 = 1; r0 <= P.rings; r0 += 64) {
         const int nl = min(P.rings - (r0 - 1), 64);
         st.init(r0 + lane, P, mem); // the batch's old cells, all at once ...
+        if (CD && r0 == 1) {        // ... the first batch's have arrived: the B chain may rewrite B_1(1) (sweep_pairb.h cd_loaded_word)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            mem.lds_set(sp::cd_loaded_word(L), 1);
+        }
         held.flush(mem);            // ... and only then the cells of the batch before (sweep_pairb.h CornerHeld)
         for (int l = 0; l < nl; ++l) {
             if (CD && r0 + l == 1) { // B_1 of ring 1, from the B/C pair's first wavefront

@@ -1017,6 +1017,8 @@ template <int PAIR> struct PairWaveB : WaveBase {
     {
         if (done()) return false;
         WP imp[64], jl[64];
+        // the visit of B_1(1) rewrites a cell the CD corner wavefront's first batch reads as OLD: not before those loads (sweep_pairb.h cd_loaded)
+        if (PAIR == gp::PAIR_BC && group == 0 && t == 0 && mem.lds_i(gp::cd_loaded_word(L)) == 0) return false;
         for (int k = 0; k < 64; ++k) { // everything the step takes from other wavefronts must be there
             const gp::PairLaneB<PAIR> &c = lane[k];
             if (c.first_at(t) && mem.lds_i(L.cnt_corner + c.cd) < c.r) return false;
@@ -1062,23 +1064,29 @@ template <int CD> struct PairCornerWaveB : WaveBase {
     gp::CornerLaneB<CD> lane[64];
     gp::CornerHeld held[64]; // the batch before: stored after this batch's loads
     bool have_held = false;
+    int loaded_batch = 0; // first ring of the batch whose records are loaded
     float in_corner, in_x1 = 0.f;
     PairCornerWaveB(const Params &p, const gp::LdsB &l, PairBHostMem &m, float centre_p) : P(p), L(l), mem(m), in_corner(centre_p) {}
     bool done() const override { return r > P.rings; }
     bool try_step() override
     {
         if (done()) return false;
-        if (CD && r == 1) {
-            WP b1;
-            if (!mem.entry_read(L.b1, b1)) return false;
-            in_x1 = b1.p;
-        }
+        // (as run_pairb_corner: a batch's old cells are loaded BEFORE the wait for B_1(1) -- the cell that visit rewrites is one of them, and
+        // the record applies the decay to its OLD confidence itself; loaded afterwards it would be decayed twice wherever ring 1 decays --
+        // and the B chain's first visit waits for cd_loaded)
         const int k = (r - 1) % 64;
-        if (k == 0) {
+        if (k == 0 && loaded_batch != r) {
             for (int j = 0; j < 64; ++j) lane[j].init(r + j, P, mem);
             if (have_held)
                 for (int j = 0; j < 64; ++j) held[j].flush(mem);
             have_held = false;
+            loaded_batch = r;
+            if (CD && r == 1) mem.lds_set(gp::cd_loaded_word(L), 1);
+        }
+        if (CD && r == 1) {
+            WP b1;
+            if (!mem.entry_read(L.b1, b1)) return false;
+            in_x1 = b1.p;
         }
         float x1g, x1, y0g, y0;
         lane[k].c.visits(in_corner, in_x1, x1g, x1, y0g, y0);

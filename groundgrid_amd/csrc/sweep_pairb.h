@@ -31,7 +31,7 @@ enum { PFB = GG_PAIRB_PF }; // wave-steps a layer cell is requested ahead (the q
 // LDS image of one work-group (4-byte words): entries are (w, tag, p, tag) = 16 bytes -- each half one 8-byte unit that is written and read
 // whole, so a reader that finds both tags set has both values however the 16 bytes travel --, the corner table holds plain pairs
 struct LdsB {
-    int cnt_corner; // [2]
+    int cnt_corner; // [2], then cd_loaded_word, then one word of padding
     int b1;         // [4] B_1 of ring 1, an entry
     int corner;     // WP [2][c + 1][2]: AB (A_1, B_0), CD (C_1, D_0); ring 0 second entry = the centre cell
     int scratch;    // [64][4]
@@ -60,6 +60,11 @@ SW_HD LdsB ldsb_of(int c, const Plan &pl, bool both_pairs)
     L.words = o;
     return L;
 }
+// The one cell of the layer that a CHAIN visit rewrites while a corner wavefront may still want its OLD value: B_1(1) = (c, c - 1), visited at
+// wave-step 0 of pair B/C and an element of the CD corner's first record (make_corner_rec applies the decay to the confidence it loads:
+// loaded after the visit it would be decayed twice -- visible only where ring 1 decays, r2min == 1).  The CD corner wavefront sets this word
+// once its first batch is loaded; that visit waits for it.  (Word 2 of the counter block: words 2 and 3 were padding.)
+SW_HD int cd_loaded_word(const LdsB &L) { return L.cnt_corner + 2; }
 SW_HD int cornerb_word(const LdsB &L, int c, int cd, int ring, int k) { return L.corner + 2 * ((cd * (c + 1) + ring) * 2 + k); }
 
 // :457-460 on a window given by roles (sweep_pair.h Slots): the pair's common positions, I0, the OP / I1 swap, the FLEX ends

@@ -32,7 +32,7 @@ extern "C" {
 typedef enum gg_status {
     GG_OK = 0,
     GG_ERR_INVALID = -1,   /* null pointer / bad argument                        */
-    GG_ERR_GEOMETRY = -2,  /* grid_map size and GroundSegmentation::init cell count disagree */
+    GG_ERR_GEOMETRY = -2,  /* grid_map size and GroundSegmentation::init cell count disagree, or a sensor constant of gg_geometry is negative or not finite */
     GG_ERR_NOMEM = -3,     /* device or host allocation failed                   */
     GG_ERR_HIP = -4,       /* a HIP runtime call or kernel failed (see gg_last_error) */
     GG_ERR_CAPACITY = -5,  /* cloud larger than max_points / slot out of range   */
@@ -79,7 +79,9 @@ typedef struct gg_config {
 /* Compile-time constants of the reference made run-time parameters:
  * GroundGrid::mDimension / mResolution (include/groundgrid/GroundGrid.h:70-71) and
  * GroundSegmentation::verticalPointAngDist / minDistSquared (include/groundgrid/GroundSegmentation.h:69-70).
- * Zero selects the reference value. */
+ * Zero selects the reference value.  vertical_point_ang_dist (radians between two neighbouring beams: 32- and 128-beam sensors change
+ * it) and min_dist_squared (m^2) must be finite and not negative: gg_create returns GG_ERR_GEOMETRY for a negative, infinite or NaN
+ * value of either and creates no context. */
 typedef struct gg_geometry {
     float length;                  /* 120.0f */
     float resolution;              /* .33f   */

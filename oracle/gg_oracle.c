@@ -202,7 +202,8 @@ void ggo_map_reset_state(ggo_map *m, double pos_x, double pos_y, float odom_z)
     fill(m->layer[GGO_VARIANCE], C, 0.0f);
 }
 
-ggo_map *ggo_map_create(float length_f, float resolution_f, double pos_x, double pos_y, float odom_z)
+ggo_map *ggo_map_create_geom(float length_f, float resolution_f, double pos_x, double pos_y, float odom_z,
+                             float vertical_point_ang_dist, float min_dist_squared)
 {
     /* grid_map::GridMap::setGeometry(Length(l,l), resolution, position) as called at
      * src/GroundGrid.cpp:58: size = round(length / resolution) in double; length_ = size * res */
@@ -222,8 +223,9 @@ ggo_map *ggo_map_create(float length_f, float resolution_f, double pos_x, double
     m->resolution = res;
     m->length[0] = (double)n * res;
     m->length[1] = (double)n * res;
-    m->verticalPointAngDist = (float)(0.00174532925 * 2); /* GroundSegmentation.h:69 */
-    m->minDistSquared = 12.0f;                            /* GroundSegmentation.h:70 */
+    /* GroundSegmentation.h:69-70: compile-time constants of the reference, parameters here; 0 = the reference's value */
+    m->verticalPointAngDist = vertical_point_ang_dist != 0.0f ? vertical_point_ang_dist : (float)(0.00174532925 * 2);
+    m->minDistSquared = min_dist_squared != 0.0f ? min_dist_squared : 12.0f;
     const size_t C = (size_t)n * (size_t)n;
     for (int l = 0; l < GGO_NUM_LAYERS; ++l) m->layer[l] = (float *)malloc(C * sizeof(float));
     m->expectedPoints = (float *)malloc(C * sizeof(float));
@@ -238,6 +240,11 @@ ggo_map *ggo_map_create(float length_f, float resolution_f, double pos_x, double
     }
     ggo_map_reset_state(m, pos_x, pos_y, odom_z);
     return m;
+}
+
+ggo_map *ggo_map_create(float length_f, float resolution_f, double pos_x, double pos_y, float odom_z)
+{
+    return ggo_map_create_geom(length_f, resolution_f, pos_x, pos_y, odom_z, 0.0f, 0.0f);
 }
 
 void ggo_map_destroy(ggo_map *m)

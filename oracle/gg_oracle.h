@@ -114,6 +114,11 @@ void ggo_default_config(ggo_config *c);
  * length_f/resolution_f are the reference's float constants (GroundGrid.h:70-71). Returns NULL
  * if the two cell counts (grid_map's and init()'s) disagree. */
 ggo_map *ggo_map_create(float length_f, float resolution_f, double pos_x, double pos_y, float odom_z);
+/* the same with the two constants of GroundSegmentation.h:69-70 as parameters (the sensor's vertical angular resolution in radians,
+ * the squared radius in m^2 inside which points are ignored and confidences do not decay); 0 = the reference's value.
+ * ggo_map_create is this with two zeros. */
+ggo_map *ggo_map_create_geom(float length_f, float resolution_f, double pos_x, double pos_y, float odom_z,
+                             float vertical_point_ang_dist, float min_dist_squared);
 void ggo_map_destroy(ggo_map *m);
 /* re-apply GroundGrid.cpp:71-75 initial layer values */
 void ggo_map_reset_state(ggo_map *m, double pos_x, double pos_y, float odom_z);

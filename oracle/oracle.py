@@ -103,6 +103,8 @@ def lib():
         L.ggo_default_config.argtypes = [C.POINTER(Config)]
         L.ggo_map_create.restype = C.POINTER(_Map)
         L.ggo_map_create.argtypes = [C.c_float, C.c_float, C.c_double, C.c_double, C.c_float]
+        L.ggo_map_create_geom.restype = C.POINTER(_Map)
+        L.ggo_map_create_geom.argtypes = [C.c_float, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_float]
         L.ggo_map_destroy.argtypes = [C.POINTER(_Map)]
         L.ggo_map_reset_state.argtypes = [C.POINTER(_Map), C.c_double, C.c_double, C.c_float]
         L.ggo_filter_cloud.restype = C.c_size_t
@@ -193,9 +195,12 @@ def make_cloud(xyz: np.ndarray, ring=None, intensity=None) -> np.ndarray:
 class OracleMap:
     """One grid map + the reference algorithm state (ground / groundpatch persist across clouds)."""
 
-    def __init__(self, length=120.0, resolution=0.33, pos=(0.0, 0.0), odom_z=0.0):
+    def __init__(self, length=120.0, resolution=0.33, pos=(0.0, 0.0), odom_z=0.0, vertical_point_ang_dist=0.0, min_dist_squared=0.0):
+        """vertical_point_ang_dist, min_dist_squared: the two constants of include/groundgrid/GroundSegmentation.h:69-70 (0 = the
+        reference's value), as gg_geometry carries them"""
         self._L = lib()
-        self._m = self._L.ggo_map_create(C.c_float(length), C.c_float(resolution), pos[0], pos[1], C.c_float(odom_z))
+        self._m = self._L.ggo_map_create_geom(C.c_float(length), C.c_float(resolution), pos[0], pos[1], C.c_float(odom_z),
+                                              C.c_float(vertical_point_ang_dist), C.c_float(min_dist_squared))
         if not self._m:
             raise ValueError("inconsistent geometry (grid_map size != GroundSegmentation::init cell count)")
         self.rows = self._m.contents.rows
@@ -213,6 +218,18 @@ class OracleMap:
     @property
     def resolution(self) -> float:
         return self._m.contents.resolution
+
+    @property
+    def vertical_point_ang_dist(self) -> float:
+        return float(self._m.contents.verticalPointAngDist)
+
+    @property
+    def min_dist_squared(self) -> float:
+        return float(self._m.contents.minDistSquared)
+
+    def set_min_dist_squared(self, v: float):
+        """tests only: another value from now on (a sensitivity run moves the constant for ONE stage of a frame)"""
+        self._m.contents.minDistSquared = float(v)
 
     @property
     def length(self):
@@ -252,8 +269,9 @@ class OracleMap:
         return flat.reshape((self.rows, self.cols), order="F")
 
     def expected_points(self) -> np.ndarray:
+        """The table as (rows, cols) Fortran-ordered float32: a copy (it is fixed at creation), so it may outlive the map."""
         flat = np.ctypeslib.as_array(self._m.contents.expectedPoints, shape=(self.rows * self.cols,))
-        return flat.reshape((self.rows, self.cols), order="F")
+        return flat.reshape((self.rows, self.cols), order="F").copy(order="F")
 
     def layers_copy(self) -> dict:
         return {n: self.layer(n).copy() for n in LAYERS}

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from oracle import ref, ref_build  # noqa: E402
+from oracle import ref_build  # noqa: E402
 
 
 def record() -> dict:
@@ -29,14 +29,9 @@ def record() -> dict:
     scenes = {}
     for name in rs.names():
         scene = rs.scene(name)
-        # (the configuration goes to the scenario as plain numbers: ref.Scenario's defaults edited, no oracle involved)
-        cfg = ref.default_config()
-        if scene.cfg_edit:
-            scene.cfg_edit(cfg)
-        sc = ref.Scenario(scene.length, scene.resolution, pos=scene.pos, odom_z=scene.odom_z, cfg=cfg)
-        for _ in range(scene.frames):
-            sc.filter_cloud(scene.cloud, scene.origin, scene.base_z)
-        frames = [rs.frame_digest(r["out_points"], r["layers"]) for r in ref.run(sc)]
+        # (rs.run_reference: the configuration goes to the scenario as plain numbers -- ref.Scenario's defaults edited, no oracle involved --
+        # and a scene that carries a pair of the two compile-time constants runs through the binary compiled with that pair)
+        frames = [rs.frame_digest(out, layers) for out, layers in rs.run_reference(scene)]
         scenes[name] = {"input": rs.input_digest(scene), "points": int(len(scene.cloud)), "frames": frames}
         print(f"{name}: {len(scene.cloud)} points, {len(frames)} frames", flush=True)
     return {

@@ -60,7 +60,7 @@ def trunc_int(v):
 
 
 class PyRef:
-    def __init__(self, length=120.0, resolution=0.33, pos=(0.0, 0.0), odom_z=0.0, cfg=None):
+    def __init__(self, length=120.0, resolution=0.33, pos=(0.0, 0.0), odom_z=0.0, cfg=None, vertical_point_ang_dist=0.0, min_dist_squared=0.0):
         res_f = f32(resolution)
         self.res = f64(res_f)
         n = int(round(float(f64(f32(length)) / self.res)))
@@ -69,8 +69,9 @@ class PyRef:
         self.n = n
         self.length = f64(n) * self.res
         self.pos = (f64(pos[0]), f64(pos[1]))
-        self.vpad = f32(0.00174532925 * 2)
-        self.min_dist_sq = f32(12.0)
+        # include/groundgrid/GroundSegmentation.h:69-70 (0 = the reference's value)
+        self.vpad = f32(vertical_point_ang_dist) if f32(vertical_point_ang_dist) != 0 else f32(0.00174532925 * 2)
+        self.min_dist_sq = f32(min_dist_squared) if f32(min_dist_squared) != 0 else f32(12.0)
         self.cfg = cfg or dict(
             point_count_cell_variance_threshold=10, max_ring=1024, distance_factor=0.0001,
             minimum_distance_factor=0.0005, miminum_point_height_threshold=0.3,

@@ -3,7 +3,11 @@ unit compiled against stand-ins (oracle/ref_build.py).  A plain h
 writes tests/golden/ref_build_digests.json from the reference binary alone), tests/test_reference_build_cpu.py and
 tests/test_reference_vectors_gpu.py.  The product never imports it, and nothing here reads the reference.
 
-A scene is an edge_scenes.Scene: the same cloud for `frames` consecutive filter_cloud calls on one map.  Every generator is seeded.
+A scene is an edge_scenes.Scene: the same cloud for `frames` consecutive filter_cloud calls on one map (the geom/ scenes: a shorter
+prefix of it in every frame, tests/geom_sets.py).  Every generator is seeded.
+
+The geom/ scenes carry a pair of the reference's two compile-time constants (include/groundgrid/GroundSegmentation.h:69-70) in
+Scene.extra; run_reference runs them through the variant binary compiled with that pair (oracle/ref_build.py VARIANTS).
 """
 from __future__ import annotations
 
@@ -16,6 +20,7 @@ import numpy as np
 
 from groundgrid_amd import synth
 from tests import edge_scenes as es
+from tests import geom_sets as gs
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
@@ -113,6 +118,28 @@ def config_scene(field=None, value=None) -> es.Scene:
                     cfg_edit=None if field is None else config_edit(field, value))
 
 
+# ---------------------------------------------------------------- the two sensor constants off their defaults (constant sets A and B)
+GEOM_VARIANTS = {"A": "gg_ref_run_geomA", "B": "gg_ref_run_geomB"}   # set -> the reference binary compiled with its pair
+
+
+def geom_scene(name) -> es.Scene:
+    """the shrinking-cloud scene of a constant set, as the GPU file runs it"""
+    sc = gs.scene(name)
+    return es.Scene(sc.name, sc.cloud, sc.branch, length=sc.length, resolution=sc.resolution, origin=sc.origin, base_z=sc.base_z,
+                    frames=sc.frames, extra={**sc.extra, "variant": GEOM_VARIANTS[name]})
+
+
+def geom_ignore_scene(name) -> es.Scene:
+    """the set's ignore-test cloud (points whose squared distance is exactly the constant, the float below and the float above)"""
+    cloud, origin, _, L, R, vpad, mds = gs.ignore_cloud(name)
+    return es.Scene(f"geom/{name}_ignore", cloud, "the ignore test of :237 at the constant's own float", length=L, resolution=R, origin=origin,
+                    frames=2, extra={"vertical_point_ang_dist": vpad, "min_dist_squared": mds, "variant": GEOM_VARIANTS[name]})
+
+
+def variant_of(scene) -> str:
+    return scene.extra.get("variant", "gg_ref_run")
+
+
 # ---------------------------------------------------------------- the catalogue
 @functools.lru_cache(maxsize=None)
 def _adversarial():
@@ -138,6 +165,9 @@ def builders() -> dict:
     out["config/default"] = config_scene
     for field, value in CONFIG_EDITS + CONFIG_UNUSED:
         out[config_name(field, value)] = functools.partial(config_scene, field, value)
+    for name in GEOM_VARIANTS:
+        out["geom/" + name] = functools.partial(geom_scene, name)
+        out[f"geom/{name}_ignore"] = functools.partial(geom_ignore_scene, name)
     return out
 
 
@@ -164,6 +194,8 @@ def input_digest(scene) -> str:
     """everything a run depends on except the configuration edit (which the scene's name carries)"""
     head = json.dumps([float(np.float32(scene.length)), float(np.float32(scene.resolution)), [float(v) for v in scene.pos],
                        [float(np.float32(v)) for v in scene.origin], float(scene.base_z), float(np.float32(scene.odom_z)), int(scene.frames)])
+    if "variant" in scene.extra:   # (only the scenes that carry constants: every older scene keeps its recorded digest)
+        head += json.dumps([float(np.float32(v)) for v in gs.scene_constants(scene)] + [scene.extra.get("frame_points")])
     return sha(head.encode() + cloud_bytes(scene.cloud).tobytes())
 
 
@@ -228,16 +260,22 @@ def dump_digests(doc, path=DIGESTS):
 
 
 # ---------------------------------------------------------------- the two CPU sides
-def run_reference(scene, binary="gg_ref_run", time_limit=None):
-    """the scene through the reference binary: one process, `frames` filter_cloud steps; returns [(out_points bytes, layers)]"""
-    from oracle import ref
+def run_reference(scene, binary=None, time_limit=None):
+    """the scene through the reference binary (default: the one compiled with the scene's constants): one process, `frames` filter_cloud
+    steps; returns [(out_points bytes, layers)]"""
+    from oracle import ref, ref_build
+
+    binary = binary or variant_of(scene)
+    want = ref_build.VARIANTS.get(binary, (0.0, 0.0))
+    have = gs.scene_constants(scene)
+    assert [np.float32(v) for v in want] == [np.float32(v) for v in have], f"{scene.name}: {binary} was compiled with {want}, the scene asks for {have}"
 
     cfg = ref.default_config()
     if scene.cfg_edit:
         scene.cfg_edit(cfg)
     sc = ref.Scenario(scene.length, scene.resolution, pos=scene.pos, odom_z=scene.odom_z, cfg=cfg)
-    for _ in range(scene.frames):
-        sc.filter_cloud(scene.cloud, scene.origin, scene.base_z)
+    for f in range(scene.frames):
+        sc.filter_cloud(gs.frame_cloud(scene, f), scene.origin, scene.base_z)
     rs = ref.run(sc, binary=binary, time_limit=time_limit or ref.TIME_LIMIT_S)
     return [(r["out_points"], r["layers"]) for r in rs]
 
@@ -248,12 +286,13 @@ def run_oracle(scene, eigen_reduction=0):
 
     oracle.set_eigen_reduction(eigen_reduction)
     try:
-        m = oracle.OracleMap(scene.length, scene.resolution, pos=scene.pos, odom_z=scene.odom_z)
+        vpad, mds = gs.scene_constants(scene)
+        m = oracle.OracleMap(scene.length, scene.resolution, pos=scene.pos, odom_z=scene.odom_z, vertical_point_ang_dist=vpad, min_dist_squared=mds)
         if scene.cfg_edit:
             scene.cfg_edit(m.cfg)
         out = []
-        for _ in range(scene.frames):
-            r = m.filter_cloud(scene.cloud, scene.origin, scene.base_z)
+        for f in range(scene.frames):
+            r = m.filter_cloud(gs.frame_cloud(scene, f), scene.origin, scene.base_z)
             out.append((cloud_bytes(r["out_points"]), m.layers_copy(), r))
         return out
     finally:

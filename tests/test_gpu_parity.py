@@ -34,16 +34,21 @@ def assert_same_state(seg_map, ref, tag=""):
 
 
 def run_pair(cloud, length=120.0, resolution=0.33, pos=(0.0, 0.0), origin=ORIGIN0, base_z=-1.73, frames=2, cfg_edit=None,
-             odom_z=0.0):
-    seg = api.GroundSegmentation().init(length, resolution, n_slots=1, max_points=max(len(cloud), 1))
-    ref = oracle.OracleMap(length, resolution, pos=pos, odom_z=odom_z)
+             odom_z=0.0, geom=(0.0, 0.0), n_points=None):
+    """geom: (vertical_point_ang_dist, min_dist_squared) of gg_geometry, for both sides (0 = the reference's value); n_points(frame, n):
+    how many of the cloud's points frame `frame` uses (default: all)"""
+    seg = api.GroundSegmentation().init(length, resolution, n_slots=1, max_points=max(len(cloud), 1), vertical_point_ang_dist=geom[0],
+                                        min_dist_squared=geom[1])
+    ref = oracle.OracleMap(length, resolution, pos=pos, odom_z=odom_z, vertical_point_ang_dist=geom[0], min_dist_squared=geom[1])
     seg.map(0).reset(odom_z=odom_z, pos=pos)
     if cfg_edit:
         c = seg.getConfig()
         cfg_edit(c)
         seg.setConfig(c)
         cfg_edit(ref.cfg)
+    whole = cloud
     for f in range(frames):
+        cloud = whole if n_points is None else whole[: n_points(f, len(whole))]
         out, labels, index = seg.filter_cloud(cloud, origin, base_z, return_details=True)
         r = ref.filter_cloud(cloud, origin, base_z)
         cls, cell = seg.point_classes(len(cloud))
@@ -230,26 +235,38 @@ def _mixed_small_clouds(count, seed0):
     return [synth.hdl64_cloud(seed=seed0 + k, n_az=(600 if k % 16 == 5 else 100 + (k % 7) * 3)) for k in range(count)]
 
 
-def _check_batch_against_oracle(seg, clouds, pts, origins, base_z, frames, layer_slots, first_slot=0, tag=""):
+def _check_batch_against_oracle(seg, clouds, pts, origins, base_z, frames, layer_slots, first_slot=0, tag="", make_ref=None, n_points=None,
+                                after_call=None):
     """filter_batch `frames` times; labels / emission index / counts of EVERY cloud and all 11 layers of `layer_slots`
-    against one oracle map per cloud."""
+    against one oracle map per cloud.  make_ref(): the oracle map of a cloud (default: 120 m / 0.33 m, the reference's constants);
+    n_points(frame, n): how many of a cloud's n points frame `frame` uses (default: all); after_call(): run after every filter_batch
+    (batch_fence under concurrent halves).  32-byte records: the returned clouds are asked for and compared byte for byte as well."""
     import torch
 
-    refs = [oracle.OracleMap(120.0, 0.33) for _ in clouds]
+    refs = [make_ref() if make_ref else oracle.OracleMap(120.0, 0.33) for _ in clouds]
+    want_clouds = pts.shape[2] == 32
     out = None
     for frame in range(frames):
-        out = seg.filter_batch(pts, [len(c) for c in clouds], origins, base_z, first_slot=first_slot, out=out)
+        used = [len(c) if n_points is None else n_points(frame, len(c)) for c in clouds]
+        out = seg.filter_batch(pts, used, origins, base_z, first_slot=first_slot, out=out, want_clouds=want_clouds)
+        if after_call:
+            after_call()
         torch.cuda.synchronize()
         labels, index, counts = out.labels.cpu().numpy(), out.out_index.cpu().numpy(), out.counts.cpu().numpy()
         for b, c in enumerate(clouds):
-            r = refs[b].filter_cloud(c, tuple(origins[b]), float(base_z[b]))
-            n = len(c)
+            n = used[b]
+            r = refs[b].filter_cloud(c[:n], tuple(origins[b]), float(base_z[b]))
             assert np.array_equal(labels[b, :n], r["label"]), (tag, frame, b)
             assert np.array_equal(index[b, :n], r["index"]), (tag, frame, b)
             assert counts[b, 0] == len(r["out_points"]), (tag, frame, b)
+            emitted = r["index"] >= 0   # (kept and ignored points of the border cells are not returned, :167-168)
+            assert counts[b, 1] == (emitted & (r["cls"] == oracle.KEPT)).sum() and counts[b, 2] == (emitted & (r["cls"] == oracle.IGNORED)).sum(), (tag, frame, b)
             assert counts[b, 3] == (r["cls"] == oracle.OUTLIER).sum(), (tag, frame, b)
+            if want_clouds:
+                assert out.out_clouds[b, : counts[b, 0]].cpu().numpy().tobytes() == r["out_points"].tobytes(), (tag, frame, b)
             if b in layer_slots:
                 assert_same_state(seg.map(first_slot + b), refs[b], f"{tag} frame {frame} cloud {b}")
+    return refs
 
 
 def test_benchmark_launch_geometry_288_slots():

@@ -11,7 +11,7 @@ import pytest
 
 from groundgrid_amd import synth
 from oracle import oracle
-from tests import pyref
+from tests import geom_sets, pyref
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 F32 = np.float32
@@ -238,6 +238,34 @@ def test_oracle_matches_independent_python_restatement(seed, origin, pos):
             assert nan_equal(m.layer(name), p.L[name]), (frame, name)
         assert np.array_equal(r["label"], q["label"]) and np.array_equal(r["index"], q["index"]), frame
     assert (r["cls"] == oracle.OUTLIER).sum() > 0  # the ray march fired
+
+
+@pytest.mark.parametrize("name", sorted(geom_sets.SETS))
+def test_oracle_matches_independent_python_restatement_at_other_sensor_constants(name):
+    """the two constants of GroundSegmentation.h:69-70 off their defaults (tests/geom_sets.py, each set on its own geometry): the C oracle
+    and the Python restatement take them as parameters and still agree in everything, on a shrinking cloud over two frames"""
+    L, R, vpad, mds = geom_sets.geometry(name)
+    sc = geom_sets.scene(name)
+    m = oracle.OracleMap(L, R, vertical_point_ang_dist=vpad, min_dist_squared=mds)
+    p = pyref.PyRef(L, R, vertical_point_ang_dist=vpad, min_dist_squared=mds)
+    assert np.float32(m.min_dist_squared) == p.min_dist_sq and np.float32(m.vertical_point_ang_dist) == p.vpad
+    assert (p.vpad, p.min_dist_sq) == (np.float32(vpad or geom_sets.DEFAULT_VPAD), np.float32(mds or geom_sets.DEFAULT_MDS))
+    far = p.expected < 1e30   # (the centre cell: atan(inf) / vpad, equal as well; the guard is for the relative bound only)
+    assert np.max(np.abs(p.expected[far] - m.expected_points()[far])) <= 1e-4 * np.max(p.expected[far])
+    p.expected = m.expected_points().copy()  # libm atanf vs numpy arctan may differ by an ulp; share the table
+    for frame in range(2):
+        cloud = geom_sets.frame_cloud(sc, 2 * frame)[::6]   # (a sixth of the points: the restatement is plain Python)
+        r = m.filter_cloud(cloud, sc.origin, sc.base_z)
+        q = p.filter_cloud(cloud, sc.origin, sc.base_z)
+        assert np.array_equal(r["cls"], q["cls"]), frame
+        assert np.array_equal(r["cell"], q["cell"]), frame
+        for layer in oracle.LAYERS:
+            assert nan_equal(m.layer(layer), p.L[layer]), (frame, layer)
+        assert np.array_equal(r["label"], q["label"]) and np.array_equal(r["index"], q["index"]), frame
+    if name == "D":
+        assert (r["cls"] != oracle.KEPT).all() and (r["cls"] == oracle.IGNORED).any()
+    else:
+        assert (r["cls"] == oracle.KEPT).any()
 
 
 # ------------------------------------------------------------------ committed regression vectors

@@ -16,6 +16,7 @@ import pytest
 
 from oracle import oracle, ref, ref_build
 from tests import edge_scenes as es
+from tests import geom_sets as gs
 from tests import ref_scenes as rs
 
 TIME_LIMIT_S = 120.0   # per reference process; the slowest scene takes well under a second
@@ -30,7 +31,7 @@ def reference():
     return ref
 
 
-def _compare_scene(name, binary="gg_ref_run", eigen_reduction=0, digests=None):
+def _compare_scene(name, binary=None, eigen_reduction=0, digests=None):
     """'' if every frame of the scene is bit-identical between the reference binary and the oracle, else the first difference;
     `digests`: a list that receives the digests of the reference run's frames"""
     scene = rs.scene(name)
@@ -141,11 +142,12 @@ def test_config_edits_cover_every_field_and_both_sides_of_the_thresholds():
 # ---------------------------------------------------------------- insert_cloud's three lists
 def _insert_state(scene, warm_frames):
     """an oracle map after `warm_frames` frames and the filter_cloud prologue (:61-75): the layers insert_cloud starts from"""
-    m = oracle.OracleMap(scene.length, scene.resolution, pos=scene.pos, odom_z=scene.odom_z)
+    vpad, mds = gs.scene_constants(scene)
+    m = oracle.OracleMap(scene.length, scene.resolution, pos=scene.pos, odom_z=scene.odom_z, vertical_point_ang_dist=vpad, min_dist_squared=mds)
     if scene.cfg_edit:
         scene.cfg_edit(m.cfg)
-    for _ in range(warm_frames):
-        m.filter_cloud(scene.cloud, scene.origin, scene.base_z)
+    for f in range(warm_frames):
+        m.filter_cloud(gs.frame_cloud(scene, f), scene.origin, scene.base_z)
     m.stage_reset()
     return m
 
@@ -162,7 +164,7 @@ def test_insert_cloud_lists_and_cells(reference, name):
         m = _insert_state(scene, warm)
         sc = ref.Scenario(scene.length, scene.resolution, pos=scene.pos, odom_z=scene.odom_z, cfg=ref.single_thread(m.cfg), layers=m.layers_copy())
         sc.insert_cloud(scene.cloud, scene.origin)
-        (r,) = ref.run(sc, time_limit=TIME_LIMIT_S)
+        (r,) = ref.run(sc, binary=rs.variant_of(scene), time_limit=TIME_LIMIT_S)
         cls, cell = m.stage_insert(scene.cloud, scene.origin)
         for kind, code in (("kept", oracle.KEPT), ("ignored", oracle.IGNORED)):
             idx = np.flatnonzero(cls == code)
@@ -310,6 +312,52 @@ def test_init_expected_points(reference, length, resolution, n):
     assert (r["rows"], r["cols"]) == (m.rows, m.cols) == (n, n)
     a, b = m.expected_points().view(np.uint32), r["expected_points"].view(np.uint32)
     assert np.array_equal(a, b), f"expectedPoints differs at {np.argwhere(a != b)[:3].tolist()}"
+
+
+# ---------------------------------------------------------------- the two compile-time constants at other values (constant sets A and B)
+def test_variant_scenes_are_in_the_catalogue_with_their_constants():
+    """every geom/ scene is compared and recorded (none excluded), and the binary it runs through was compiled with its pair"""
+    geom = rs.names("geom/", excluded=True)
+    assert sorted(geom) == sorted(f"geom/{n}{k}" for n in rs.GEOM_VARIANTS for k in ("", "_ignore")) and not set(geom) & set(rs.EXCLUDED)
+    assert set(geom) <= set(rs.load_digests()["scenes"])
+    for n, variant in rs.GEOM_VARIANTS.items():
+        L, R, vpad, mds = gs.geometry(n)
+        assert [np.float32(v) for v in ref_build.VARIANTS[variant]] == [np.float32(vpad), np.float32(mds)]
+        assert np.float32(vpad) != np.float32(gs.DEFAULT_VPAD) and np.float32(mds) != np.float32(gs.DEFAULT_MDS)
+        for k in ("", "_ignore"):
+            sc = rs.scene(f"geom/{n}{k}")
+            assert gs.scene_constants(sc) == (vpad, mds) and rs.variant_of(sc) == variant and (sc.length, sc.resolution) == (L, R)
+
+
+def test_variant_header_differs_from_the_reference_header_in_two_initialisers(reference):
+    """the shadow header of a variant is the reference's header with the two initialisers replaced: exactly two lines differ, one names each
+    member, and what stands there is the set's float"""
+    if not ref_build.have_reference():
+        pytest.skip("the reference is not on this machine (its binaries travelled here): nothing to shadow")
+    with open(ref_build.reference_header()) as f:
+        original = f.read().split("\n")
+    for variant, pair in ref_build.VARIANTS.items():
+        with open(ref_build.write_shadow_header(variant) + "/groundgrid/GroundSegmentation.h") as f:
+            shadow = f.read().split("\n")
+        assert len(shadow) == len(original)
+        diff = [(a, b) for a, b in zip(original, shadow) if a != b]
+        assert len(diff) == 2
+        for (a, b), member, value in zip(diff, ref_build._MEMBERS, pair):
+            assert member in a and member in b
+            assert np.float32(float.fromhex(b.split("=")[1].split(";")[0].strip().rstrip("f"))) == np.float32(value)
+
+
+def test_variant_constants_reach_the_reference_result():
+    """recorded digests: the terrain of geom/A and geom/B is not what the same scene leaves at the default constants (oracle, here)"""
+    d = rs.load_digests()["scenes"]
+    for n in rs.GEOM_VARIANTS:
+        sc = rs.scene(f"geom/{n}")
+        plain = es.Scene(sc.name, sc.cloud, sc.branch, length=sc.length, resolution=sc.resolution, origin=sc.origin, base_z=sc.base_z,
+                         frames=sc.frames, extra={"frame_points": sc.extra["frame_points"]})
+        last = rs.run_oracle(plain)[-1]
+        got = rs.frame_digest(last[0], last[1])
+        rec = d[f"geom/{n}"]["frames"][-1]
+        assert all(got[k] != rec[k] for k in ("ground", "groundpatch", "labels")), n
 
 
 # ---------------------------------------------------------------- the comparison can see one convention apart

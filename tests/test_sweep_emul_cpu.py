@@ -13,6 +13,7 @@ import pytest
 
 from groundgrid_amd import _lib, build
 from oracle import oracle
+from tests import geom_sets as gs
 
 
 @pytest.fixture(scope="module")
@@ -197,3 +198,68 @@ def test_fresh_map_sweep_reads_only_marked_cells(lib, length, resolution):
         assert not np.isnan(g).any() and not np.isnan(w).any(), (seed, "poison came through", np.argwhere(np.isnan(g))[:5].tolist())
         assert np.array_equal(g, ref.layer("ground")), (seed, np.argwhere(g != ref.layer("ground"))[:5].tolist())
         assert np.array_equal(w, ref.layer("groundpatch")), seed
+
+
+# ---------------------------------------------------------------- the decay threshold r2min in every class (tests/geom_sets.py)
+# min_dist_squared becomes the integer P.r2min on the host and `dx^2 + dy^2 >= P.r2min` with another index expression at every place a
+# sweep visits a cell (chains, their first steps, the corner lanes' 2 r^2 and r^2 + (r - 1)^2).  At the default 12 m^2 the boundary sits
+# near ring 10 of every map; these cases put it on a ring-group hand-over (set A), exactly on the strict `>` (set B), into the corner
+# triangles alone, beyond the map and at 1 (gs.R2MIN_CASES).
+def decay_state(n, seed):
+    """random_state with confidences that a decay visibly moves everywhere (no zeros: max(w - w / f, 0.001) changes every cell it reaches)"""
+    ground, conf = random_state(n, seed)
+    conf[conf == 0.0] = np.float32(0.25)
+    return ground, conf
+
+
+@pytest.mark.parametrize("tag,length,resolution", gs.R2MIN_CASES)
+def test_ring_sweep_at_every_class_of_decay_threshold(lib, monkeypatch, tag, length, resolution):
+    """the ring sweep in one work-group and cut into parts of one ring group each (set A's boundary then lies on a hand-over between two
+    work-groups), early and late loads, against the oracle's spiral stage created with the same constant"""
+    mds, r2, ref = gs.r2min_case(tag, length, resolution)
+    n = ref.rows
+    ground, conf = decay_state(n, 7 * n + len(tag))
+    ref.set_layer("ground", ground)
+    ref.set_layer("groundpatch", conf)
+    ref.stage_spiral(-1.73)
+    decayed = int((ref.layer("groundpatch") != conf).sum())
+    for gpw in (0, 1):
+        if gpw:
+            monkeypatch.setenv("GG_SWEEP_GPW", str(gpw))
+        for seed in (0, 3):
+            for late in (False, True):
+                g, w, stats = emulate(lib, n, ref.resolution, ground, conf, -1.73, 5.0, seed, late, min_dist_sq=mds)
+                assert stats[7] == r2, (stats[7], r2)
+                assert np.array_equal(g, ref.layer("ground")), (gpw, seed, late, np.argwhere(g != ref.layer("ground"))[:5].tolist())
+                assert np.array_equal(w, ref.layer("groundpatch")), (gpw, seed, late, np.argwhere(w != ref.layer("groundpatch"))[:5].tolist())
+    # the class shows in the oracle's own result: how many confidences the sweep moved (the centre cell is set, not decayed)
+    c = n // 2 - 1
+    visited = (2 * c - 1) ** 2
+    if tag == "nothing_decays":
+        assert decayed <= 1
+    elif tag == "everything_decays":
+        assert decayed >= visited - 2
+    else:
+        assert 0 < decayed < visited - 2
+
+
+@pytest.mark.parametrize("tag,length,resolution", gs.R2MIN_CASES)
+def test_fresh_map_sweep_at_every_class_of_decay_threshold(lib, tag, length, resolution):
+    """step_a<.., FRESH>: unwritten cells come from the padding element and decay (or not) like any other"""
+    mds, r2, ref = gs.r2min_case(tag, length, resolution)
+    n = ref.rows
+    rng = np.random.default_rng(2000 + n + len(tag))
+    fresh_ground = np.float32(rng.uniform(-0.5, 0.5))
+    ground, conf = decay_state(n, n + 2)
+    patched = rng.random((n, n)) < 0.35
+    patched[:2, :] = patched[n - 2:, :] = False
+    patched[:, :2] = patched[:, n - 2:] = False
+    ref.set_layer("ground", np.where(patched, ground, fresh_ground).astype(np.float32))
+    ref.set_layer("groundpatch", np.where(patched, conf, np.float32(0.0000001)).astype(np.float32))
+    ref.stage_spiral(-1.73)
+    for seed in (0, 2):
+        g, w, stats = emulate_fresh(lib, n, ref.resolution, ground, conf, patched, float(fresh_ground), -1.73, 5.0, seed, min_dist_sq=mds)
+        assert stats[7] == r2
+        assert not np.isnan(g).any() and not np.isnan(w).any(), (seed, "poison came through")
+        assert np.array_equal(g, ref.layer("ground")), (seed, np.argwhere(g != ref.layer("ground"))[:5].tolist())
+        assert np.array_equal(w, ref.layer("groundpatch")), (seed, np.argwhere(w != ref.layer("groundpatch"))[:5].tolist())

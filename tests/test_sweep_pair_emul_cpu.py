@@ -12,6 +12,7 @@ import pytest
 
 from groundgrid_amd import _lib, build
 from oracle import oracle
+from tests import geom_sets as gs
 
 
 @pytest.fixture(scope="module")
@@ -160,3 +161,29 @@ def test_throughput_pair_sweep_special_values_and_decay_factors(lib):
         ref.stage_spiral(-1.0)
         g, w, _ = emulate_batch(lib, n, ref.resolution, ground, conf, -1.0, decrease, 4, True)
         assert np.array_equal(g, ref.layer("ground"), equal_nan=True) and np.array_equal(w, ref.layer("groundpatch"), equal_nan=True), decrease
+
+
+# ---------------------------------------------------------------- the decay threshold r2min in every class (tests/geom_sets.py)
+@pytest.mark.parametrize("tag,length,resolution", gs.R2MIN_CASES)
+def test_pair_sweeps_at_every_class_of_decay_threshold(lib, tag, length, resolution):
+    """sweep_pair.h (records: one and two work-groups, fewer wavefronts than groups) and sweep_pairb.h (in place: early and late loads)
+    restate the decay test with index expressions of their own; r2min on a 64-ring boundary (set A: also a boundary of their 32-ring
+    groups), exactly on the strict compare (set B), in the corner triangles alone, beyond the map, at 1 -- against the oracle's spiral
+    stage created with the same constant.  (These two emulations do not report r2min: it is computed by gs.r2min, the host's formula.)"""
+    mds, r2, ref = gs.r2min_case(tag, length, resolution)
+    n = ref.rows
+    ground, conf = random_state(n, 9 * n + len(tag))
+    conf[conf == 0.0] = np.float32(0.25)   # (no zeros: a decay visibly moves every cell it reaches)
+    ref.set_layer("ground", ground)
+    ref.set_layer("groundpatch", conf)
+    ref.stage_spiral(-1.73)
+    assert tag == "nothing_decays" or (ref.layer("groundpatch") != conf).sum() > 1
+    for seed in (0, 4):
+        for wgs, waves in ((1, 0), (2, 0), (2, 2)):
+            g, w, _ = emulate(lib, n, ref.resolution, ground, conf, -1.73, 5.0, seed, wgs, waves, min_dist_sq=mds)
+            assert np.array_equal(g, ref.layer("ground")), ("pair", seed, wgs, waves, np.argwhere(g != ref.layer("ground"))[:5].tolist())
+            assert np.array_equal(w, ref.layer("groundpatch")), ("pair", seed, wgs, waves, np.argwhere(w != ref.layer("groundpatch"))[:5].tolist())
+        for late, waves in ((False, 0), (True, 0), (True, 1)):
+            g, w, _ = emulate_batch(lib, n, ref.resolution, ground, conf, -1.73, 5.0, seed, late, waves, min_dist_sq=mds)
+            assert np.array_equal(g, ref.layer("ground")), ("throughput", seed, late, waves, np.argwhere(g != ref.layer("ground"))[:5].tolist())
+            assert np.array_equal(w, ref.layer("groundpatch")), ("throughput", seed, late, waves, np.argwhere(w != ref.layer("groundpatch"))[:5].tolist())

@@ -179,8 +179,7 @@ def libm_section() -> dict:
         x = F32(g.wide_float() * F32(0.01))
         y = F32(g.wide_float() * F32(0.01))
         hyp.append(hex32(L.ggo_hypotf(C.c_float(float(x)), C.c_float(float(y)))))
-    m = oracle.OracleMap(120.0, 0.33)  # (kept alive: expected_points() is a view of the map's own memory)
-    e = m.expected_points().copy()
+    e = oracle.OracleMap(120.0, 0.33).expected_points()
     exp = [hex32(e[i, j]) for i in range(0, 364, 7) for j in range(0, 364, 11)]
     return {"hypotf": hyp, "expected_points": exp}
 
