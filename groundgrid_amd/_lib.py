@@ -45,6 +45,7 @@ SYMBOLS = [
     "gg_collective_available", "gg_comm_unique_id", "gg_comm_init_rank", "gg_comm_init_rank_for", "gg_comm_destroy", "gg_allgather_label_masks",
     "gg_set_score_labels", "gg_set_slot_scoring", "gg_get_slot_scores", "gg_reset_slot_scores", "gg_get_score_kernel_time",
     "gg_export_layers",
+    "gg_import_layers",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -179,6 +180,7 @@ def load():
     L.gg_move_map.argtypes = [vp, C.c_int, C.c_double, C.c_double, P(C.c_double), P(C.c_int)]
     L.gg_move_maps.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, P(C.c_double), P(C.c_double), P(C.c_int32), vp]
     L.gg_export_layers.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
+    L.gg_import_layers.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

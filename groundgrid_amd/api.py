@@ -363,6 +363,67 @@ class GroundSegmentation:
         _check(self._L, self._ctx, rc, "gg_export_layers")
         return out
 
+    def import_layers(self, planes, names=None, *, slots=None, first_slot: int = 0, n: Optional[int] = None, row_major: bool = False,
+                      stream=None, own_stream: bool = False, plane_stride: Optional[int] = None):
+        """The inverse of export_layers (gg_import_layers): `planes`, a contiguous CUDA torch.float32 tensor of exactly the shape
+        export_layers returns for the same arguments ([n, K, cols, rows], [n, K, rows, cols] with row_major, or the flat
+        [n * K * plane_stride] tensor), becomes the named layers (default: all eleven, in gg_layer order) of the maps -- bit for bit what
+        map(slot).set(name, plane) would leave for every one of them, without a host round trip.  Layers that are not named keep their
+        values; positions, configurations and scores are untouched.  Enqueued on the current torch stream (or on `stream`) without
+        synchronising: `planes` must stay unmodified until that stream has passed the call, which torch ops enqueued there afterwards
+        do by themselves.  own_stream: on the context's own stream instead (the caller orders its own streams around the call)."""
+        import torch
+
+        self._torch_used = True
+        names = list(LAYERS) if names is None else list(names)
+        mask = 0
+        for k in names:
+            mask |= 1 << LAYERS.index(k)
+        if bin(mask).count("1") != len(names) or [k for k in LAYERS if k in names] != names:
+            raise ValueError("import_layers: names must be distinct and in gg_layer order")
+        cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
+        shape = (cnt, len(names), self.rows, self.cols) if row_major else (cnt, len(names), self.cols, self.rows)
+        if plane_stride is not None:
+            shape = (cnt * len(names) * int(plane_stride),)
+        if not (torch.is_tensor(planes) and planes.is_cuda and planes.dtype == torch.float32 and planes.is_contiguous()):
+            raise ValueError("import_layers: planes must be a contiguous CUDA float32 tensor")
+        if tuple(planes.shape) != shape:
+            raise ValueError(f"import_layers: planes has shape {tuple(planes.shape)}, these arguments need {shape}")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._L.gg_import_layers(self._ctx, cnt, ptr, first, mask, _lib.GG_PLANES_ROWMAJOR if row_major else _lib.GG_PLANES_COLMAJOR,
+                                      C.c_void_p(planes.data_ptr()), self.rows * self.cols if plane_stride is None else int(plane_stride),
+                                      None if own_stream else C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
+        _check(self._L, self._ctx, rc, "gg_import_layers")
+
+    def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:
+        """A checkpoint of the named maps: {"planes": export_layers() of all eleven layers [n, 11, cols, rows] (on the device, enqueued on
+        the current torch stream), "positions": their map positions, float64 [n, 2]}.  restore_maps puts it back -- into these maps, other
+        maps, or the maps of another GroundSegmentation of the same geometry."""
+        cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
+        planes = self.export_layers(slots=slots, first_slot=first_slot, n=n)
+        positions = np.empty((cnt, 2), dtype=np.float64)
+        for k in range(cnt):
+            slot = int(keep[k]) if keep is not None else first + k
+            x, y = C.c_double(), C.c_double()
+            _check(self._L, self._ctx, self._L.gg_get_map_position(self._ctx, slot, C.byref(x), C.byref(y)), "gg_get_map_position")
+            positions[k] = (x.value, y.value)
+        return {"planes": planes, "positions": positions}
+
+    def restore_maps(self, state: dict, slots=None, first_slot: int = 0):
+        """Put a snapshot_maps state into map k = slots[k], or first_slot + k: all eleven layers (import_layers, on the current torch
+        stream) and the map positions.  What runs on these maps afterwards continues as if it had run where the state was taken."""
+        planes, positions = state["planes"], np.asarray(state["positions"], dtype=np.float64)
+        if planes.dim() != 4 or tuple(planes.shape[1:]) != (len(LAYERS), self.cols, self.rows):
+            raise ValueError(f"restore_maps: planes of shape {tuple(planes.shape)} do not fit maps of {self.rows} x {self.cols} cells")
+        cnt = int(planes.shape[0])
+        if positions.shape != (cnt, 2) or (slots is not None and len(slots) != cnt):
+            raise ValueError("restore_maps: planes, positions and slots differ in length")
+        if planes.device.index != self.device:  # (a map that changes its GPU)
+            planes = planes.to(f"cuda:{self.device}")
+        self.import_layers(planes.contiguous(), slots=slots, first_slot=first_slot, n=cnt)
+        for k in range(cnt):
+            self._maps[int(slots[k]) if slots is not None else first_slot + k].setPosition(positions[k, 0], positions[k, 1])
+
     # -- GroundSegmentation::setConfig (src/GroundSegmentation.cpp:468-471)
     def setConfig(self, config: GGConfig):
         _check(self._L, self._ctx, self._L.gg_set_config(self._ctx, C.byref(config)), "gg_set_config")

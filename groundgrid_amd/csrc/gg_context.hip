@@ -35,6 +35,7 @@ namespace {
 
 constexpr int PARAM_RING = 4;
 constexpr int EXPORT_VARIANT_DEFAULT = 0; // gg_export_layers: 0 = k_export_tiled, 1 = k_export_gather; the measured winner
+constexpr int IMPORT_VARIANT_DEFAULT = 0; // gg_import_layers: 0 = k_import_tiled, 1 = a batched materialise + k_import_scatter; the measured winner
 constexpr int K_SCORE = GG_NUM_KERNELS; // k_score's entry of the profiler's sums, behind the seven kernels of the path
 
 // one timed kernel of a profiled launch sequence (GG_FLAG_PROFILE).  Consecutive kernels of a sequence SHARE the event between them -- the
@@ -192,6 +193,7 @@ struct gg_context {
     bool export_used[PARAM_RING]{};
     int export_next = 0;
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
+    int import_variant = IMPORT_VARIANT_DEFAULT; // tuning "import_variant": 0 = k_import_tiled, 1 = k_import_scatter (the A/B of tools/bench_import.py)
     float *d_image = nullptr;          // 3 * C floats (wire-format images)
     float *d_planes = nullptr;         // GG_NUM_LAYERS * Cpad floats: dense planes of gg_get_layers (allocated on first use)
     float *h_planes = nullptr;         // ... and their pinned landing zone on the host (one download for all requested layers)
@@ -2154,6 +2156,93 @@ int gg_export_layers(gg_context *ctx, int n, const int32_t *slots, int first_slo
     return GG_OK;
 }
 
+// The inverse of gg_export_layers, on the same table, rings and events (ensure_export_scratch).  Host-side flags are committed at the end,
+// when every launch of the call has been enqueued.
+int gg_import_layers(gg_context *ctx, int n, const int32_t *slots, int first_slot, unsigned layer_mask, int order, const float *d_src,
+                     size_t plane_stride, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    if (n < 0) return fail(ctx, GG_ERR_INVALID, "gg_import_layers: n < 0");
+    if (n == 0) return GG_OK;
+    if (layer_mask == 0u || (layer_mask >> GG_NUM_LAYERS) != 0u) return fail(ctx, GG_ERR_INVALID, "gg_import_layers: layer_mask");
+    if (order != GG_PLANES_COLMAJOR && order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, "gg_import_layers: order");
+    if (!d_src) return fail(ctx, GG_ERR_INVALID, "gg_import_layers: d_src is null");
+    if (plane_stride < (size_t)ctx->arena.g.C) return fail(ctx, GG_ERR_INVALID, "gg_import_layers: plane_stride is smaller than rows * cols");
+    if (const int rc = check_slot_list(ctx, "gg_import_layers", n, slots, first_slot)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = pick_stream(ctx, stream);
+    if (const int rc = ensure_export_scratch(ctx, st)) return rc;
+    const Arena &a = ctx->arena;
+    auto slot_of = [&](int i) { return slots ? slots[i] : first_slot + i; };
+    const int g = ctx->export_next;
+    ctx->export_next = (g + 1) % PARAM_RING;
+    if (ctx->export_used[g]) HIPCHK(ctx, hipEventSynchronize(ctx->export_done[g]));
+    ctx->export_used[g] = false;
+    ExportMap *hm = ctx->h_export_maps + (size_t)g * ctx->n_slots, *dm = ctx->d_export_maps + (size_t)g * ctx->n_slots;
+    CloudParams *hl = ctx->h_export_lazy + (size_t)g * ctx->n_slots, *dl = ctx->d_export_lazy + (size_t)g * ctx->n_slots;
+    const unsigned gp_mask = layer_mask & ((1u << GG_LAYER_GROUND) | (1u << GG_LAYER_GROUNDPATCH));
+    const unsigned percall_mask = layer_mask & ~gp_mask;
+    const unsigned lazy_mask = (1u << GG_LAYER_MAXGROUNDHEIGHT) | (1u << GG_LAYER_GROUNDCANDIDATES) | (1u << GG_LAYER_PLANEDIST);
+    // The import makes all nine per-call layers of a map dense, after which the three lazily kept ones can no longer be computed into the
+    // half columns their cloud wrote: a listed map that still misses them gets them first -- unless all three are imported anyway
+    const bool lazy_first = percall_mask != 0u && (layer_mask & lazy_mask) != lazy_mask;
+    int n_lazy = 0;
+    for (int i = 0; i < n; ++i) {
+        const int slot = slot_of(i);
+        hm[i].slot = slot;
+        hm[i].fresh = ctx->fresh[slot] ? 1 : 0; // (with ground / groundpatch named, the kernel writes the whole pair: no fill)
+        hm[i].fresh_z = ctx->fresh_z[slot];
+        hm[i].reserved = 0;
+        if (lazy_first && ctx->lazy_pending[slot]) hl[n_lazy++] = ctx->lazy_params[slot];
+    }
+    // `st` follows every earlier map mutation, batch and export of the context, and both halves of a divided batch
+    if (st == ctx->stream) {
+        if (const int rc = own_stream_waits_for_batches(ctx, false)) return rc;
+    } else {
+        if (ctx->map_event_pending) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->map_event, 0));
+        if (ctx->have_batch_event && ctx->last_batch_stream != st && !ctx->probe_unordered_streams) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->batch_event, 0));
+        if (const int rc = stream_waits_for_second_half(ctx, st)) return rc;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(dm, hm, sizeof(ExportMap) * n, hipMemcpyHostToDevice, st));
+    if (n_lazy) {
+        HIPCHK(ctx, hipMemcpyAsync(dl, hl, sizeof(CloudParams) * n_lazy, hipMemcpyHostToDevice, st));
+        launch_reduce_lazy_batch(a, dl, n_lazy, st);
+    }
+    ImportArgs x;
+    x.maps = dm;
+    x.block_off = ctx->d_export_off;
+    x.elem = ctx->d_export_elem;
+    x.cell = ctx->d_export_cell;
+    x.blocks_r = (a.g.rows + EXPORT_TILE - 1) / EXPORT_TILE;
+    x.blocks_c = (a.g.cols + EXPORT_TILE - 1) / EXPORT_TILE;
+    x.mask = layer_mask;
+    x.n_planes = __builtin_popcount(layer_mask);
+    x.order = order;
+    x.src = d_src;
+    x.plane_stride = plane_stride;
+    launch_import(a, x, n, ctx->import_variant, st);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->export_done[g], st));
+    ctx->export_used[g] = true;
+    // whatever reads or writes one of these maps next on another stream waits for the import
+    if (st == ctx->stream) {
+        if (const int rc = own_stream_mutated_map(ctx)) return rc;
+    } else {
+        HIPCHK(ctx, hipEventRecord(ctx->batch_event, st));
+        ctx->have_batch_event = true;
+        ctx->last_batch_stream = st;
+        ctx->map_event_pending = false; // (this stream has waited; later batches anywhere follow batch_event)
+    }
+    // every launch is enqueued: the listed maps' flags follow (no other map's change)
+    for (int i = 0; i < n; ++i) {
+        const int slot = slot_of(i);
+        if (gp_mask) ctx->fresh[slot] = 0; // (the kernel wrote the pair of every cell)
+        if (layer_mask & (1u << GG_LAYER_GROUNDPATCH)) ctx->no_confidence[slot] = 0;
+        if (percall_mask) ctx->lazy_pending[slot] = 0; // (computed above, or all three imported)
+    }
+    return GG_OK;
+}
+
 int gg_get_map_position(const gg_context *ctx, int slot, double *pos_x, double *pos_y)
 {
     if (!slot_ok(ctx, slot)) return GG_ERR_CAPACITY;
@@ -3046,6 +3135,7 @@ extern "C" int gg_debug_set_tuning(gg_context *ctx, const char *key, int value)
         return c;
     }
     if (!strcmp(key, "export_variant_default")) return EXPORT_VARIANT_DEFAULT; // (read-only: the kernel gg_export_layers ships with)
+    if (!strcmp(key, "import_variant_default")) return IMPORT_VARIANT_DEFAULT; // (read-only: the kernel gg_import_layers ships with)
     if (!strcmp(key, "graphs")) { // 0 = every call launches eagerly, 1 = one cloud per call replays a captured graph (the default)
         ctx->graphs_enabled = value != 0;
         drop_graphs(ctx);
@@ -3068,6 +3158,7 @@ extern "C" int gg_debug_set_tuning(gg_context *ctx, const char *key, int value)
     else if (!strcmp(key, "halves_min_clouds")) ctx->halves_min_clouds = std::max(2, value); // (tests: GG_FLAG_CONCURRENT_HALVES on small batches)
     else if (!strcmp(key, "move_chunk")) ctx->move_chunk_tune = value;
     else if (!strcmp(key, "export_variant")) ctx->export_variant = value ? 1 : 0; // (A/B: 1 = gg_export_layers gathers in destination order, k_export_gather)
+    else if (!strcmp(key, "import_variant")) ctx->import_variant = value ? 1 : 0; // (A/B: 1 = gg_import_layers scatters in source order, k_import_scatter)
     else if (!strcmp(key, "halves_no_fork")) ctx->probe_no_fork = value != 0; // (measurement only: the side stream does not wait for the caller's)
     else if (!strcmp(key, "scan_fault")) ctx->arena.tune_scan_fault = value;
     else if (!strcmp(key, "sweep_fault")) ctx->arena.tune_sweep_fault = value;

@@ -300,6 +300,18 @@ struct ExportArgs {
     float *dst;
     size_t plane_stride;
 };
+// gg_import_layers (k10_import.hip): the same map entries, table and addressing, read instead of written
+struct ImportArgs {
+    const ExportMap *maps;
+    const uint32_t *block_off, *elem;
+    const uint16_t *cell;
+    int blocks_r, blocks_c;
+    unsigned mask; // bit per gg_layer
+    int n_planes;  // its popcount
+    int order;     // GG_PLANES_*
+    const float *src;
+    size_t plane_stride;
+};
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
@@ -339,6 +351,7 @@ void launch_stage_insert(const Arena &a, const CloudParams *d_params, hipStream_
 void launch_reduce_lazy(const Arena &a, const CloudParams &cp, hipStream_t s); // (GG_FLAG_MINIMAL_LAYERS: the other three layers, one slot)
 void launch_reduce_lazy_batch(const Arena &a, const CloudParams *d_params, int n_clouds, hipStream_t s); // (... of n slots in one launch: gg_export_layers)
 void launch_export(const Arena &a, const ExportArgs &x, int n_maps, int variant, hipStream_t s); // k9_export.hip; variant 0 = k_export_tiled, 1 = k_export_gather
+void launch_import(const Arena &a, const ImportArgs &x, int n_maps, int variant, hipStream_t s); // k10_import.hip; variant 0 = k_import_tiled, 1 = a batched materialise + k_import_scatter
 void launch_patch(const Arena &a, const CloudParams *d_params, int n_clouds, hipStream_t s);
 void launch_patch_stage(const Arena &a, const CloudParams *d_params, int slot, int section, hipStream_t s); // gg_run_stage: :323 + one quadrant (-1: all) on the slot's layers as they stand
 void launch_stage_cell(const Arena &a, int slot, int stage, int i, int j, hipStream_t s);                    // gg_run_stage: detect_ground_patch<S> / interpolate_cell of one cell

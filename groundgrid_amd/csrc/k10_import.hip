@@ -1,0 +1,228 @@
+// K10 -- gg_import_layers: dense planes in device memory into the layers of MANY maps, one launch (include/groundgrid_hip.h).  The inverse
+// of K9 (k9_export.hip), with the same addressing, the same per-context table and the same block shape.
+//
+// The destinations are not planes (k9_export.hip): `ground` / `groundpatch` are interleaved float2 pairs in the sheared ring order of
+// gp_layout.h, the nine per-call layers are 16 x 16 tile blocks behind per-tile liveness words (gg_internal.h tile_live).
+//
+// k_import_tiled gives every work-group one 64 x 64 block of cells of one map and
+//   * reads each named source plane in runs of 64 consecutive floats per wavefront -- 4-byte loads: the source needs no more than float
+//     alignment and plane_stride may be odd -- for either order (the row-major planes are the transposed walk of the same LDS block),
+//   * stages the block in LDS (row + 65 * column),
+//   * writes the pairs of the block in ELEMENT order through the export table: consecutive lanes store consecutive elements wherever
+//     the layout has them.  Both components named: one 8-byte store per cell.  One named on a real map: a 4-byte store of that component,
+//     the other is not read.  One named on a FRESH map (gg_context::fresh): the pair, with the reset's constant for the other -- every
+//     cell of the map is written, so the map is real afterwards without a fill,
+//   * writes a per-call layer tile by tile, 1 KiB contiguous per wavefront, tile and layer, as float4 stores, and makes the tile DENSE
+//     on the way: one liveness word covers all nine layers of a tile, so a layer that is not imported keeps its values in the live half
+//     columns and receives its reset value in the dead ones, and the tile's word becomes all ones.  A tile belongs to exactly one block
+//     (64 = 4 x 16): the wavefront that owns it reads its word first and rewrites it last, nobody else looks at it in this launch.
+//     Cells of an edge tile that lie outside the map keep their bytes where the half column was live (what k_materialise /
+//     k_layer_insert leave alone) and get the reset value where it was dead.
+//
+// k_import_scatter is the straightforward form (source order, cell by cell, gp_idx / percall_index_of), kept for the A/B of
+// tools/bench_import.py (gg_debug_set_tuning "import_variant" = 1).  It cannot own a tile's liveness word -- the cells of a tile are spread
+// over many work-groups -- so a batched materialise over the listed maps runs in front of it.
+#include "gg_device.h"
+
+#include <algorithm>
+
+namespace gg {
+
+constexpr int IMP_LD = EXPORT_TILE + 1; // LDS pitch of a block: element (row, col) at row + IMP_LD * col
+constexpr unsigned IMP_GP_MASK = (1u << GG_LAYER_GROUND) | (1u << GG_LAYER_GROUNDPATCH);
+
+__device__ __forceinline__ int import_plane_index(unsigned mask, int layer) { return __popc(mask & ((1u << layer) - 1u)); }
+
+__global__ __launch_bounds__(256) void k_import_tiled(const Arena a, const ImportArgs x)
+{
+    __shared__ float lds[2][EXPORT_TILE * IMP_LD];
+    const int tid = threadIdx.x;
+    const ExportMap m = x.maps[blockIdx.y];
+    const int mt = (int)blockIdx.x, mtr = mt % x.blocks_r, mtc = mt / x.blocks_r;
+    const int r0 = mtr * EXPORT_TILE, c0 = mtc * EXPORT_TILE;
+    const int rows = a.g.rows, cols = a.g.cols;
+    const int nr = min(EXPORT_TILE, rows - r0), nc = min(EXPORT_TILE, cols - c0);
+    const float *in = x.src + (size_t)blockIdx.y * (size_t)x.n_planes * x.plane_stride;
+    const bool row_major = x.order == GG_PLANES_ROWMAJOR;
+
+    // one source plane -> the block: a wavefront covers 64 consecutive floats of the plane in either order
+    auto load = [&](const float *plane, float *blk) {
+#pragma unroll 4
+        for (int idx = tid; idx < EXPORT_TILE * EXPORT_TILE; idx += 256) {
+            const int fast = idx & (EXPORT_TILE - 1), slow = idx >> 6;
+            const int ri = row_major ? slow : fast, ci = row_major ? fast : slow;
+            if (ri >= nr || ci >= nc) continue;
+            const size_t at = row_major ? (size_t)(r0 + ri) * cols + (size_t)(c0 + ci) : (size_t)(r0 + ri) + (size_t)(c0 + ci) * rows;
+            blk[ri + ci * IMP_LD] = plane[at];
+        }
+    };
+
+    const unsigned gp_mask = x.mask & IMP_GP_MASK;
+    if (gp_mask) {
+        const float *p_ground = in + (size_t)import_plane_index(x.mask, GG_LAYER_GROUND) * x.plane_stride;
+        const float *p_conf = in + (size_t)import_plane_index(x.mask, GG_LAYER_GROUNDPATCH) * x.plane_stride;
+        float2 *gp2 = gp2_ptr(a, m.slot);
+        const uint32_t first = x.block_off[mt], end = x.block_off[mt + 1];
+        auto lds_of = [](uint32_t c) { return (int)(c & 63u) + (int)(c >> 6) * IMP_LD; }; // row in block | column in block << 6
+        if (gp_mask == IMP_GP_MASK) {
+            load(p_ground, lds[0]);
+            load(p_conf, lds[1]);
+            __syncthreads();
+            for (uint32_t i = first + tid; i < end; i += 256) {
+                const int at = lds_of(x.cell[i]);
+                gp2[x.elem[i]] = make_float2(lds[0][at], lds[1][at]);
+            }
+        } else {
+            const int comp = gp_mask == (1u << GG_LAYER_GROUNDPATCH) ? 1 : 0;
+            load(comp ? p_conf : p_ground, lds[0]);
+            __syncthreads();
+            if (m.fresh) { // the layer holds the reset's values by definition and nothing in memory: the pair, the other half from the reset
+                const float z = m.fresh_z, w = (float)0.0000001;
+                for (uint32_t i = first + tid; i < end; i += 256) {
+                    const float v = lds[0][lds_of(x.cell[i])];
+                    gp2[x.elem[i]] = comp ? make_float2(z, v) : make_float2(v, w);
+                }
+            } else {
+                float *gpf = reinterpret_cast<float *>(gp2);
+                for (uint32_t i = first + tid; i < end; i += 256) gpf[(size_t)x.elem[i] * 2 + comp] = lds[0][lds_of(x.cell[i])];
+            }
+        }
+    }
+    if (!(x.mask & ~gp_mask)) return; // (uniform)
+
+    // the per-call layers: wavefront w owns tiles 4 w .. 4 w + 3 of the block's 4 x 4 tiles; a lane owns four consecutive rows of one
+    // column of a tile (16 bytes, half of one liveness bit's half column)
+    const int wave = tid >> 6, lane = tid & 63;
+    float *percall = percall_ptr(a, m.slot);
+    uint32_t *tile_live = a.tile_live + (size_t)m.slot * a.tile_live_stride;
+    int rank[4];
+    bool live[4];
+    int lds_at[4];
+    unsigned inside[4]; // bit q: row 4 (lane & 3) + q of the lane's column is a cell of the map
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = wave * 4 + j, ltr = t & 3, ltc = t >> 2;
+        const int tr = mtr * (EXPORT_TILE / TILE) + ltr, tc = mtc * (EXPORT_TILE / TILE) + ltc;
+        rank[j] = -1;
+        live[j] = false;
+        inside[j] = 0u;
+        const int ri = ltr * TILE + (lane & 3) * 4, ci = ltc * TILE + (lane >> 2);
+        lds_at[j] = ri + ci * IMP_LD;
+        if (tr < a.g.tiles_r && tc < a.g.tiles_c) {
+            rank[j] = (int)a.tile_rank[tr + tc * a.g.tiles_r];
+            live[j] = ((tile_live[rank[j]] >> live_bit(lane * 4)) & 1u) != 0u;
+            if (ci < nc)
+                for (int q = 0; q < 4; ++q) inside[j] |= ri + q < nr ? 1u << q : 0u;
+        }
+    }
+    __syncthreads(); // (the stores of the pairs above have read both LDS blocks)
+    int buf = 0;     // the two blocks alternate: a layer's staging never meets the reads of the layer before it, one barrier per layer
+    for (int l = 0; l < GG_NUM_LAYERS; ++l) {
+        const int position = percall_position(l);
+        if (position < 0) continue; // (uniform)
+        const float dead = layer_reset_value(l);
+        if (!((x.mask >> l) & 1u)) { // not imported: its values stay where the half column holds them, the reset value where it does not
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (rank[j] >= 0 && !live[j]) *reinterpret_cast<float4 *>(percall + percall_index(rank[j], position, lane * 4)) = make_float4(dead, dead, dead, dead);
+            continue;
+        }
+        float *blk = lds[buf];
+        load(in + (size_t)import_plane_index(x.mask, l) * x.plane_stride, blk);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (rank[j] < 0) continue;
+            float4 *dst = reinterpret_cast<float4 *>(percall + percall_index(rank[j], position, lane * 4));
+            float4 v = make_float4(dead, dead, dead, dead);
+            if (inside[j] != 15u && live[j]) v = *dst; // (an edge tile: the cells outside the map keep what a live half column holds)
+            if (inside[j] & 1u) v.x = blk[lds_at[j] + 0];
+            if (inside[j] & 2u) v.y = blk[lds_at[j] + 1];
+            if (inside[j] & 4u) v.z = blk[lds_at[j] + 2];
+            if (inside[j] & 8u) v.w = blk[lds_at[j] + 3];
+            *dst = v;
+        }
+        buf ^= 1;
+    }
+    // every half column of the wavefront's tiles holds its values now (the words were read above by this wavefront alone)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (lane == j && rank[j] >= 0) tile_live[rank[j]] = 0xFFFFFFFFu;
+}
+
+// Reset values into every dead half column of the per-call layers of the listed maps (k_materialise with the map in blockIdx.y) ...
+__global__ __launch_bounds__(256) void k_materialise_maps(const Arena a, const ExportMap *__restrict__ maps)
+{
+    const int slot = maps[blockIdx.y].slot;
+    const int rows = a.g.rows;
+    float *L = percall_ptr(a, slot);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.g.C; i += gridDim.x * blockDim.x) {
+        if (cell_is_live(a, slot, i % rows, i / rows)) continue;
+        const size_t at = percall_index_of(a, 0, i % rows, i / rows);
+        for (int l = 0; l < GG_NUM_LAYERS; ++l)
+            if (percall_position(l) >= 0) L[at + (size_t)percall_position(l) * (TILE * TILE)] = layer_reset_value(l);
+    }
+}
+// ... and, in the launch behind it, every half column of those maps marked live
+__global__ __launch_bounds__(256) void k_live_all_maps(const Arena a, const ExportMap *__restrict__ maps)
+{
+    uint32_t *tile_live = a.tile_live + (size_t)maps[blockIdx.y].slot * a.tile_live_stride;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < a.g.T; t += gridDim.x * blockDim.x) tile_live[t] = 0xFFFFFFFFu;
+}
+
+// source order, cell by cell (k_plane_insert / k_layer_insert with the map in blockIdx.y, both orders and the fresh maps)
+__global__ __launch_bounds__(256) void k_import_scatter(const Arena a, const ImportArgs x)
+{
+    const ExportMap m = x.maps[blockIdx.y];
+    float *dst = percall_ptr(a, m.slot);
+    float2 *gp2 = gp2_ptr(a, m.slot);
+    float *gpf = reinterpret_cast<float *>(gp2);
+    const int rows = a.g.rows, cols = a.g.cols;
+    const float *in = x.src + (size_t)blockIdx.y * (size_t)x.n_planes * x.plane_stride;
+    const bool row_major = x.order == GG_PLANES_ROWMAJOR;
+    const unsigned gp_mask = x.mask & IMP_GP_MASK;
+    const bool any_percall = (x.mask & ~IMP_GP_MASK) != 0u;
+    const float *in_conf = in + (size_t)import_plane_index(x.mask, GG_LAYER_GROUNDPATCH) * x.plane_stride;
+    const float *in_ground = in + (size_t)import_plane_index(x.mask, GG_LAYER_GROUND) * x.plane_stride;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.g.C; i += gridDim.x * blockDim.x) {
+        const int r = row_major ? i / cols : i % rows, c = row_major ? i % cols : i / rows;
+        if (gp_mask) {
+            const int e = gp_idx(a, r, c);
+            if (gp_mask == IMP_GP_MASK) gp2[e] = make_float2(in_ground[i], in_conf[i]);
+            else if (m.fresh) gp2[e] = gp_mask == (1u << GG_LAYER_GROUND) ? make_float2(in_ground[i], (float)0.0000001) : make_float2(m.fresh_z, in_conf[i]);
+            else if (gp_mask == (1u << GG_LAYER_GROUND)) gpf[(size_t)e * 2] = in_ground[i];
+            else gpf[(size_t)e * 2 + 1] = in_conf[i];
+        }
+        if (!any_percall) continue;
+        const size_t at = percall_index_of(a, 0, r, c);
+        int k = 0;
+#pragma unroll
+        for (int l = 0; l < GG_NUM_LAYERS; ++l) {
+            if (!((x.mask >> l) & 1u)) continue; // (uniform)
+            if (percall_position(l) >= 0) dst[at + (size_t)percall_position(l) * (TILE * TILE)] = in[(size_t)k * x.plane_stride + i];
+            ++k;
+        }
+    }
+}
+
+void launch_import(const Arena &a, const ImportArgs &x, int n_maps, int variant, hipStream_t s)
+{
+    const bool any_percall = (x.mask & ~IMP_GP_MASK) != 0u;
+    for (int first = 0; first < n_maps; first += 32768) { // (gridDim.y: one launch for every context of up to 32768 maps)
+        const int count = std::min(32768, n_maps - first);
+        ImportArgs part = x;
+        part.maps = x.maps + first;
+        part.src = x.src + (size_t)first * (size_t)x.n_planes * x.plane_stride;
+        if (variant == 1) {
+            const int blocks = std::min((a.g.C + 255) / 256, count >= 64 ? 64 : 2048);
+            if (any_percall) {
+                hipLaunchKernelGGL(k_materialise_maps, dim3(blocks, count), dim3(256), 0, s, a, part.maps);
+                hipLaunchKernelGGL(k_live_all_maps, dim3((a.g.T + 255) / 256, count), dim3(256), 0, s, a, part.maps);
+            }
+            hipLaunchKernelGGL(k_import_scatter, dim3(blocks, count), dim3(256), 0, s, a, part);
+        } else
+            hipLaunchKernelGGL(k_import_tiled, dim3(x.blocks_r * x.blocks_c, count), dim3(256), 0, s, a, part);
+    }
+}
+
+} // namespace gg

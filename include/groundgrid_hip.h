@@ -284,6 +284,35 @@ enum { GG_PLANES_COLMAJOR = 0,   /* cell (row, col) at row + col * rows: Eigen's
 int gg_export_layers(gg_context *ctx, int n, const int32_t *slots, int first_slot, unsigned layer_mask, int order, float *d_dst,
                      size_t plane_stride, void *stream);
 #define GG_HAS_EXPORT_LAYERS 1
+/* The other direction: dense planes in DEVICE memory into the layers of n maps, one launch, no synchronisation.  Addressing mirrors
+ * gg_export_layers exactly: map i = slots ? slots[i] : first_slot + i (distinct), K = popcount(layer_mask), the k-th named layer (in
+ * gg_layer order) of map i is read from d_src + (i * K + k) * plane_stride, `order` is GG_PLANES_COLMAJOR or GG_PLANES_ROWMAJOR,
+ * plane_stride is in floats (>= rows * cols) and the floats between rows * cols and plane_stride are never read.  d_src needs 4-byte
+ * alignment only, and plane_stride may be odd.
+ * After the call everything observable -- getters, exports, images, the gridmap message, gg_filter_*, gg_run_stage, gg_insert_cloud,
+ * gg_move_map(s) -- is what it would be after gg_set_layer(ctx, slot_i, l, plane) for every named layer of every map, bit for bit
+ * (NaN payloads and infinities included).  Layers that are not named keep their values; map positions, configurations, score counters
+ * and conventions are untouched.  So gg_export_layers -> gg_import_layers -> continue is indistinguishable from never having left: a
+ * checkpoint and roll-back, a map moved to another context or GPU, K candidates started from one warmed-up terrain.
+ * `stream` follows the gg_filter_batch convention.  The call enqueues and returns: `slots` may be freed on return, d_src must stay valid
+ * and unmodified until `stream` has passed the call.  The import is a map mutation and the library orders it like one: it waits for every
+ * earlier mutation, batch and export of the context on other streams (both halves under GG_FLAG_CONCURRENT_HALVES), runs wholly on
+ * `stream`, and every later entry point that reads or writes one of the maps on another stream waits for it.
+ * A FRESH map (gg_reset_maps, nothing since) whose mask names ground and / or groundpatch becomes real by the import alone: the pair of
+ * every cell is written, the component that is not named gets the reset's constant (odom_z / 1e-7f), nothing is filled first.  A fresh map
+ * whose mask names neither, and every fresh map that is not listed, stays fresh.  The nine other layers share one set of liveness
+ * marks per map: when the mask names any of them, all nine of a listed map become dense (imported ones take the plane, the others keep
+ * their values and hold their per-call reset values wherever the last cloud wrote nothing).  Listed maps whose last cloud left
+ * maxGroundHeight / groundCandidates / planeDist out (GG_FLAG_MINIMAL_LAYERS) get them computed first, in one launch over exactly those
+ * maps on `stream` -- unless the mask names all three.
+ * Argument errors write nothing and change nothing: GG_ERR_CAPACITY (a slot outside the context), GG_ERR_INVALID (null ctx, n < 0,
+ * repeated slots, layer_mask == 0 or with a bit at or above GG_NUM_LAYERS, unknown order, null d_src, plane_stride < rows * cols -- the
+ * last five only with n > 0).  n == 0 is GG_OK.  (A GG_ERR_HIP from the runtime in the middle of the call is not covered by that.)
+ * The call shares its table, parameter rings and events with gg_export_layers: the first of the two in a context allocates and
+ * blocks, later calls only enqueue.  Capture into a caller's graph is not supported, as for the export. */
+int gg_import_layers(gg_context *ctx, int n, const int32_t *slots, int first_slot, unsigned layer_mask, int order, const float *d_src,
+                     size_t plane_stride, void *stream);
+#define GG_HAS_IMPORT_LAYERS 1
 /* GroundSegmentation::expectedPoints (src/GroundSegmentation.cpp:40-46), host copy */
 int gg_get_expected_points(const gg_context *ctx, float *dst);
 
