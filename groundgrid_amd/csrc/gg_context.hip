@@ -47,6 +47,57 @@ struct EventPair {
     bool owns_start;
 };
 
+// A ring of PARAM_RING pinned parameter blocks (each with a device copy): a call takes the next entry, fills it on the host, uploads it and
+// records `done` behind the last copy that reads it -- and `done2` on the side stream when the call ran as two halves
+// (GG_FLAG_CONCURRENT_HALVES).  acquire() waits on the host for whichever of the two the entry's last user recorded, so a pinned entry is
+// rewritten only when the copies that read it have run.
+struct ParamRing {
+    hipEvent_t done[PARAM_RING]{}, done2[PARAM_RING]{};
+    bool used[PARAM_RING]{}, used2[PARAM_RING]{};
+    int next = 0;
+    hipError_t create()
+    {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < PARAM_RING && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
+        for (int i = 0; i < PARAM_RING && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&done2[i], hipEventDisableTiming);
+        return e;
+    }
+    void destroy()
+    {
+        for (int i = 0; i < PARAM_RING; ++i) {
+            if (done[i]) hipEventDestroy(done[i]);
+            if (done2[i]) hipEventDestroy(done2[i]);
+            done[i] = done2[i] = nullptr;
+        }
+    }
+    hipError_t acquire(int *g)
+    {
+        *g = next;
+        next = (next + 1) % PARAM_RING;
+        hipError_t e = used[*g] ? hipEventSynchronize(done[*g]) : hipSuccess;
+        if (e == hipSuccess && used2[*g]) e = hipEventSynchronize(done2[*g]);
+        if (e == hipSuccess) used[*g] = used2[*g] = false;
+        return e;
+    }
+    hipError_t recorded(int g, hipStream_t st)
+    {
+        const hipError_t e = hipEventRecord(done[g], st);
+        if (e == hipSuccess) used[g] = true;
+        return e;
+    }
+    hipError_t recorded2(int g, hipStream_t half_stream)
+    {
+        const hipError_t e = hipEventRecord(done2[g], half_stream);
+        if (e == hipSuccess) used2[g] = true;
+        return e;
+    }
+};
+
+// what a many-map call allocates at its first use (alloc_call_scratch): one device block and one pinned host block
+struct CallScratch {
+    void *dev = nullptr, *pinned = nullptr;
+};
+
 } // namespace
 
 struct gg_context {
@@ -65,7 +116,7 @@ struct gg_context {
     size_t arena_bytes = 0;
     std::vector<float> h_expected;
     std::vector<double> pos_x, pos_y; // per slot map position
-    std::vector<char> slot_seen;      // scratch of gg_filter_batch's check of gg_batch.slots
+    std::vector<char> slot_seen;      // scratch of check_slot_list
     std::vector<char> no_confidence;  // per slot: groundpatch <= 0.01 everywhere for sure (set by gg_reset_map, cleared by any writer)
     // per slot: the map is FRESH -- gg_reset_maps left the interior of its (ground, confidence) layer unwritten (gg_internal.h Arena::gp_bits);
     // a batch of at least FRESH_MIN_CLOUDS fresh maps sweeps them as they are, anything else that touches the layer fills it first (make_real)
@@ -128,8 +179,6 @@ struct gg_context {
                            // measured 1 / 2 / 3 / 4 pieces: 0.472 / 0.478 / 0.488 / 0.494 ms per synchronous call -- a piece's split and copy
                            // call cost more than its overlap gives)
     bool probe_no_fork = false;
-    hipEvent_t ring_done2[4]{};
-    bool ring_used2[4]{};
 
     // pipelined host entry point (gg_filter_cloud_async / _wait): GG_ASYNC_DEPTH staging sets + a copy stream each way
     struct AsyncSlot {
@@ -155,9 +204,7 @@ struct gg_context {
     // per-call parameter ring (pinned host + device)
     CloudParams *h_params = nullptr; // [PARAM_RING][n_slots] pinned
     CloudParams *d_params = nullptr; // [PARAM_RING][n_slots]
-    hipEvent_t ring_done[PARAM_RING]{};
-    bool ring_used[PARAM_RING]{};
-    int ring_next = 0;
+    ParamRing ring;
 
     // staging for the host-buffer entry point
     gg_point16 *h_stage_pts = nullptr; // pinned [max_points]
@@ -173,25 +220,22 @@ struct gg_context {
     float *d_scroll_scratch = nullptr; // 2 layers
     // gg_move_maps (allocated at its first call; contexts that never call it do not pay): one device block holding the cell table (element,
     // row | col << 16 of every cell in element order), the parameter ring [PARAM_RING][n_slots] and move_cap scratch rows of C cells
-    void *d_move_block = nullptr;
+    CallScratch move_mem;
     const int2 *d_move_cells = nullptr;
-    MoveParams *d_move_params = nullptr, *h_move_params = nullptr; // (h_: pinned)
+    MoveParams *d_move_params = nullptr, *h_move_params = nullptr; // (h_: pinned, the whole of move_mem.pinned)
     float2 *d_move_scratch = nullptr;
     int move_cap = 0;        // scratch rows: maps per chunk (half of them per stream when the call runs as two halves)
     int move_chunk_tune = 0; // tuning "move_chunk": at most this many maps per chunk (tests: several chunks in a small call)
-    hipEvent_t move_done[PARAM_RING]{}, move_done2[PARAM_RING]{};
-    bool move_used[PARAM_RING]{}, move_used2[PARAM_RING]{};
-    int move_next = 0;
+    ParamRing move_ring;
     // gg_export_layers (allocated at its first call): one device block holding the export table (gg_internal.h ExportArgs), a ring of map
     // tables [PARAM_RING][n_slots] and a ring of parameter records for the batched launch of the lazily kept layers; their pinned host copies
-    void *d_export_block = nullptr, *h_export_block = nullptr;
+    // (gg_import_layers runs on the same table, rings and events)
+    CallScratch export_mem;
     const uint32_t *d_export_off = nullptr, *d_export_elem = nullptr;
     const uint16_t *d_export_cell = nullptr;
     ExportMap *d_export_maps = nullptr, *h_export_maps = nullptr;
     CloudParams *d_export_lazy = nullptr, *h_export_lazy = nullptr;
-    hipEvent_t export_done[PARAM_RING]{};
-    bool export_used[PARAM_RING]{};
-    int export_next = 0;
+    ParamRing export_ring;
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
     int import_variant = IMPORT_VARIANT_DEFAULT; // tuning "import_variant": 0 = k_import_tiled, 1 = k_import_scatter (the A/B of tools/bench_import.py)
     float *d_image = nullptr;          // 3 * C floats (wire-format images)
@@ -256,6 +300,8 @@ int fail(gg_context *ctx, int code, const char *what, hipError_t e = hipSuccess)
     }
     return code;
 }
+
+int fail(gg_context *ctx, int code, const char *who, const char *what) { return fail(ctx, code, (std::string(who) + ": " + what).c_str()); }
 
 #define HIPCHK(ctx, call)                                                      \
     do {                                                                       \
@@ -378,6 +424,39 @@ int own_stream_mutated_map(gg_context *ctx)
 {
     HIPCHK(ctx, hipEventRecord(ctx->map_event, ctx->stream));
     ctx->map_event_pending = true;
+    return GG_OK;
+}
+
+// The ordering pair of the many-map calls (gg_reset_maps, gg_move_maps, gg_export_layers, gg_import_layers) on stream `st`.
+// call_follows_context, in front of what the call enqueues: `st` follows every earlier map mutation, batch and second half of the context.
+// call_recorded, behind it: whatever touches these maps next on another stream waits for the call.
+//                      skip_half_join                                        clears_map_pending
+//   gg_reset_maps      the call is itself divided into the two halves        false
+//   gg_move_maps       the call is itself divided into the two halves        false
+//   gg_export_layers   false (it reads maps of either half)                  true
+//   gg_import_layers   false (it writes maps of either half)                 true
+// skip_half_join: a divided call right behind a batch (or divided call) on the same caller stream does not wait for the side stream -- a slot
+// is only ever touched from its half's stream, so the halves of consecutive calls need not meet (as in enqueue_batch).
+// clears_map_pending: on a caller stream, `st` has waited for map_event and later batches anywhere follow batch_event, so the pending mark
+// is dropped (as enqueue_batch does).  Reset and move leave it set, which costs the next batch on another stream one wait for an event that
+// batch_event already implies.
+// (enqueue_batch keeps its own prologue and epilogue: it joins the halves by its output-row history, applies probe_unordered_streams on the
+// context's stream too and records batch_event there as well)
+int call_follows_context(gg_context *ctx, hipStream_t st, bool skip_half_join)
+{
+    if (st == ctx->stream) return own_stream_waits_for_batches(ctx, false);
+    if (ctx->map_event_pending) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->map_event, 0));
+    if (ctx->have_batch_event && ctx->last_batch_stream != st && !ctx->probe_unordered_streams) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->batch_event, 0));
+    if (skip_half_join && ctx->last_batch_stream == st) return GG_OK;
+    return stream_waits_for_second_half(ctx, st);
+}
+int call_recorded(gg_context *ctx, hipStream_t st, bool clears_map_pending)
+{
+    if (st == ctx->stream) return own_stream_mutated_map(ctx);
+    HIPCHK(ctx, hipEventRecord(ctx->batch_event, st));
+    ctx->have_batch_event = true;
+    ctx->last_batch_stream = st;
+    if (clears_map_pending) ctx->map_event_pending = false;
     return GG_OK;
 }
 
@@ -655,6 +734,39 @@ int launch_or_replay(gg_context *ctx, const Arena &a, const CloudParams *hp, Clo
     return GG_OK;
 }
 
+bool slot_ok(const gg_context *ctx, int slot) { return ctx && slot >= 0 && slot < ctx->n_slots; }
+
+// The slots a call names -- slots[0 .. n), or the run first_slot .. first_slot + n - 1 when `slots` is null --: GG_ERR_CAPACITY for one
+// outside the context, GG_ERR_INVALID for one named twice, whichever comes first in the list (gg_context::slot_seen is the scratch)
+int check_slot_list(gg_context *ctx, const char *who, int n, const int32_t *slots, int first_slot)
+{
+    if (!slots) // (a run names no slot twice)
+        return first_slot < 0 || (long long)first_slot + n > ctx->n_slots ? fail(ctx, GG_ERR_CAPACITY, who, "slot outside the context") : GG_OK;
+    ctx->slot_seen.assign((size_t)ctx->n_slots, 0);
+    for (int k = 0; k < n; ++k) {
+        if (slots[k] < 0 || slots[k] >= ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "slot outside the context");
+        if (ctx->slot_seen[(size_t)slots[k]]++) return fail(ctx, GG_ERR_INVALID, who, "a slot is named twice");
+    }
+    return GG_OK;
+}
+inline int slot_of(const int32_t *slots, int first_slot, int i) { return slots ? slots[i] : first_slot + i; }
+
+// the fields ExportArgs and ImportArgs share (gg_internal.h: the same map entries, table and addressing)
+template <class PlaneArgs>
+void fill_plane_args(PlaneArgs &x, const gg_context *ctx, const ExportMap *dm, unsigned layer_mask, int order, size_t plane_stride)
+{
+    x.maps = dm;
+    x.block_off = ctx->d_export_off;
+    x.elem = ctx->d_export_elem;
+    x.cell = ctx->d_export_cell;
+    x.blocks_r = (ctx->arena.g.rows + EXPORT_TILE - 1) / EXPORT_TILE;
+    x.blocks_c = (ctx->arena.g.cols + EXPORT_TILE - 1) / EXPORT_TILE;
+    x.mask = layer_mask;
+    x.n_planes = __builtin_popcount(layer_mask);
+    x.order = order;
+    x.plane_stride = plane_stride;
+}
+
 // which half of a context's slots a map belongs to (GG_FLAG_CONCURRENT_HALVES): the upper half runs on the library's side stream
 bool second_half_slot(const gg_context *ctx, int slot) { return slot >= (ctx->n_slots + 1) / 2; }
 bool halves_enabled(const gg_context *ctx)
@@ -672,11 +784,8 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
     const int nb = b->n_clouds;
     if (nb == 0) return GG_OK;
     // parameter ring slot
-    const int g = ctx->ring_next;
-    ctx->ring_next = (g + 1) % PARAM_RING;
-    if (ctx->ring_used[g]) HIPCHK(ctx, hipEventSynchronize(ctx->ring_done[g]));
-    if (ctx->ring_used2[g]) HIPCHK(ctx, hipEventSynchronize(ctx->ring_done2[g]));
-    ctx->ring_used2[g] = false;
+    int g;
+    HIPCHK(ctx, ctx->ring.acquire(&g));
     CloudParams *hp = ctx->h_params + (size_t)g * ctx->n_slots;
     CloudParams *dp = ctx->d_params + (size_t)g * ctx->n_slots;
     // Two halves side by side?  The clouds of the lower slots first in the parameter array, then the others: each half is a batch of its own
@@ -686,13 +795,13 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
     const bool split_wanted = halves_enabled(ctx) && !plan && nb >= ctx->halves_min_clouds && s != ctx->half_stream && s != nullptr;
     if (split_wanted) {
         n_first = 0;
-        for (int i = 0; i < nb; ++i) n_first += second_half_slot(ctx, b->slots ? b->slots[i] : b->first_slot + i) ? 0 : 1;
+        for (int i = 0; i < nb; ++i) n_first += second_half_slot(ctx, slot_of(b->slots, b->first_slot, i)) ? 0 : 1;
     }
     const bool split = split_wanted && n_first > 0 && n_first < nb;
     if (!split) n_first = nb;
     int max_n[2] = {0, 0}, at[2] = {0, n_first};
     for (int i = 0; i < nb; ++i) {
-        const int slot = b->slots ? b->slots[i] : b->first_slot + i;
+        const int slot = slot_of(b->slots, b->first_slot, i);
         const int half = split && second_half_slot(ctx, slot) ? 1 : 0;
         CloudParams &p = hp[at[half]++];
         p.slot = slot;
@@ -763,7 +872,7 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
                                   (size_t)nb * ((per + 3) / 4)};
         for (int k = 0; k < 7; ++k) now.lo[k] = p6[k], now.hi[k] = p6[k] ? p6[k] + bytes6[k] : nullptr;
         uint64_t h = 1469598103934665603ull;
-        for (int i = 0; i < nb; ++i) h = (h ^ (uint64_t)(second_half_slot(ctx, b->slots ? b->slots[i] : b->first_slot + i) ? 2 * i + 1 : 2 * i)) * 1099511628211ull;
+        for (int i = 0; i < nb; ++i) h = (h ^ (uint64_t)(second_half_slot(ctx, slot_of(b->slots, b->first_slot, i)) ? 2 * i + 1 : 2 * i)) * 1099511628211ull;
         now.map_hash = h ^ (uint64_t)nb;
         bool clash = false;
         for (int r = 0; r < ctx->halves_hist_n && !joined && !clash; ++r) {
@@ -836,8 +945,7 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
         launch_sequence(ctx, a, dp, score_half[0] ? io_score : io, n_first, max_n[0], s, nullptr, hp[0].slot, false, score_half[0]);
         launch_sequence(ctx, a2, dp + n_first, score_half[1] ? io_score : io, nb - n_first, max_n[1], ctx->half_stream, nullptr, hp[n_first].slot, false, score_half[1]);
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipEventRecord(ctx->ring_done2[g], ctx->half_stream));
-        ctx->ring_used2[g] = true;
+        HIPCHK(ctx, ctx->ring.recorded2(g, ctx->half_stream));
         HIPCHK(ctx, hipEventRecord(ctx->half_done, ctx->half_stream));
         ctx->have_half_event = true;
     } else {
@@ -846,8 +954,7 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
         if (const int rc = launch_or_replay(ctx, a, hp, dp, score_half[0] ? io_score : io, nb, max_n[0], s, plan, score_half[0])) return rc;
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ring_done[g], s));
-    ctx->ring_used[g] = true;
+    HIPCHK(ctx, ctx->ring.recorded(g, s));
     HIPCHK(ctx, hipEventRecord(ctx->batch_event, s));
     ctx->last_batch_stream = s;
     ctx->have_batch_event = true;
@@ -855,7 +962,60 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
     return GG_OK;
 }
 
-bool slot_ok(const gg_context *ctx, int slot) { return ctx && slot >= 0 && slot < ctx->n_slots; }
+void free_call_scratch(CallScratch &m, ParamRing &r)
+{
+    if (m.dev) hipFree(m.dev);
+    if (m.pinned) hipHostFree(m.pinned);
+    m = CallScratch{};
+    r.destroy();
+}
+
+// The first-call allocation of a many-map call (`who`): a device block, a pinned host block and the events of its parameter ring, and the
+// tables the call's kernels read uploaded into the device block (synchronously: they are there before any stream can launch on them).  Not
+// while `st` is being captured into a graph: an allocation cannot be captured.  `mem` and `ring` are written when everything is in place:
+// nothing of the context changes when this fails (GG_ERR_NOMEM for the two blocks, GG_ERR_HIP for the events and uploads).
+struct TableUpload {
+    size_t offset;
+    const void *src;
+    size_t bytes;
+};
+int alloc_call_scratch(gg_context *ctx, const char *who, hipStream_t st, size_t dev_bytes, size_t pinned_bytes, std::initializer_list<TableUpload> tables, CallScratch *mem,
+                       ParamRing *ring)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(ctx, GG_ERR_INVALID, who, "the first call allocates its scratch and cannot be captured into a graph");
+    (void)hipGetLastError();
+    CallScratch m;
+    ParamRing r;
+    int code = GG_ERR_NOMEM;
+    const char *what = "device scratch";
+    hipError_t e = hipMalloc(&m.dev, dev_bytes);
+    if (e != hipSuccess) m.dev = nullptr;
+    if (e == hipSuccess) {
+        what = "pinned parameter ring";
+        e = hipHostMalloc(&m.pinned, pinned_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) m.pinned = nullptr;
+    }
+    if (e == hipSuccess) {
+        code = GG_ERR_HIP;
+        what = "events";
+        e = r.create();
+    }
+    for (const TableUpload &t : tables)
+        if (e == hipSuccess) {
+            what = "table upload";
+            e = hipMemcpy((char *)m.dev + t.offset, t.src, t.bytes, hipMemcpyHostToDevice);
+        }
+    if (e != hipSuccess) {
+        free_call_scratch(m, r);
+        (void)hipGetLastError();
+        return fail(ctx, code, (std::string(who) + ": " + what).c_str(), e);
+    }
+    *mem = m;
+    *ring = r;
+    return GG_OK;
+}
 
 // GroundGrid::update's host arithmetic (gg_move_map, gg_move_maps): grid_map_core getIndexShiftFromPositionShift -- round half away from
 // zero, map frame -> buffer order (sign flip) -- and getPositionShiftFromIndexShift: the position advances by whole cells, not to the
@@ -1286,8 +1446,7 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
     CREATE_CHK(hipHostMalloc((void **)&ctx->h_stage_labels, max_points, hipHostMallocDefault));
     CREATE_CHK(hipHostMalloc((void **)&ctx->h_stage_index, max_points * 4, hipHostMallocDefault));
     CREATE_CHK(hipHostMalloc((void **)&ctx->h_stage_counts, 64, hipHostMallocDefault));
-    for (int i = 0; i < PARAM_RING; ++i) CREATE_CHK(hipEventCreateWithFlags(&ctx->ring_done[i], hipEventDisableTiming));
-    for (int i = 0; i < PARAM_RING; ++i) CREATE_CHK(hipEventCreateWithFlags(&ctx->ring_done2[i], hipEventDisableTiming));
+    CREATE_CHK(ctx->ring.create());
     for (int k = 0; k < GG_ASYNC_DEPTH; ++k) {
         gg_context::AsyncSlot &as = ctx->async_slot[k];
         CREATE_CHK(hipHostMalloc((void **)&as.h_pts, max_points * sizeof(gg_point16), hipHostMallocDefault));
@@ -1339,10 +1498,7 @@ void gg_destroy(gg_context *ctx)
         hipEventDestroy(p.stop);
     }
     for (hipEvent_t e : ctx->free_single_events) hipEventDestroy(e);
-    for (int i = 0; i < PARAM_RING; ++i)
-        if (ctx->ring_done[i]) hipEventDestroy(ctx->ring_done[i]);
-    for (int i = 0; i < PARAM_RING; ++i)
-        if (ctx->ring_done2[i]) hipEventDestroy(ctx->ring_done2[i]);
+    ctx->ring.destroy();
     if (ctx->half_fork) hipEventDestroy(ctx->half_fork);
     if (ctx->half_done) hipEventDestroy(ctx->half_done);
     if (ctx->half_stream) hipStreamDestroy(ctx->half_stream);
@@ -1372,16 +1528,8 @@ void gg_destroy(gg_context *ctx)
     if (ctx->h_stage_index) hipHostFree(ctx->h_stage_index);
     if (ctx->h_stage_counts) hipHostFree(ctx->h_stage_counts);
     if (ctx->d_planes) hipFree(ctx->d_planes);
-    if (ctx->d_move_block) hipFree(ctx->d_move_block);
-    if (ctx->h_move_params) hipHostFree(ctx->h_move_params);
-    for (int i = 0; i < PARAM_RING; ++i) {
-        if (ctx->move_done[i]) hipEventDestroy(ctx->move_done[i]);
-        if (ctx->move_done2[i]) hipEventDestroy(ctx->move_done2[i]);
-    }
-    if (ctx->d_export_block) hipFree(ctx->d_export_block);
-    if (ctx->h_export_block) hipHostFree(ctx->h_export_block);
-    for (int i = 0; i < PARAM_RING; ++i)
-        if (ctx->export_done[i]) hipEventDestroy(ctx->export_done[i]);
+    free_call_scratch(ctx->move_mem, ctx->move_ring);
+    free_call_scratch(ctx->export_mem, ctx->export_ring);
     if (ctx->d_pc2) hipFree(ctx->d_pc2);
     if (ctx->h_pc2) hipHostFree(ctx->h_pc2);
     if (ctx->h_planes) hipHostFree(ctx->h_planes);
@@ -1466,12 +1614,7 @@ int gg_set_slot_configs(gg_context *ctx, int n, const int32_t *slots, int first_
 {
     if (!ctx || n < 0) return fail(ctx, GG_ERR_INVALID, "gg_set_slot_configs: null context or n < 0");
     if (n == 0) return GG_OK;
-    std::vector<char> seen((size_t)ctx->n_slots, 0);
-    for (int k = 0; k < n; ++k) {
-        const long long slot = slots ? (long long)slots[k] : (long long)first_slot + k;
-        if (slot < 0 || slot >= ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, "gg_set_slot_configs: slot outside the context");
-        if (seen[(size_t)slot]++) return fail(ctx, GG_ERR_INVALID, "gg_set_slot_configs: a slot is named twice");
-    }
+    if (const int rc = check_slot_list(ctx, "gg_set_slot_configs", n, slots, first_slot)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!ctx->d_slot_cfg) {
         void *p = nullptr;
@@ -1485,7 +1628,7 @@ int gg_set_slot_configs(gg_context *ctx, int n, const int32_t *slots, int first_
     std::vector<gg_config> cfg = ctx->slot_cfg;
     std::vector<DevConfig> dev = ctx->slot_dev;
     for (int k = 0; k < n; ++k) {
-        const int slot = slots ? slots[k] : first_slot + k;
+        const int slot = slot_of(slots, first_slot, k);
         own[slot] = cfgs ? 1 : 0;
         cfg[slot] = cfgs ? cfgs[k] : gg_config{};
         dev[slot] = DevConfig{};
@@ -1513,18 +1656,6 @@ int gg_get_slot_config(const gg_context *ctx, int slot, gg_config *cfg, int *own
 }
 
 // ---- evaluator counters (include/groundgrid_hip.h "the score of a labelled cloud", k8_score.hip) ----
-
-// the slots a call names, checked like gg_set_slot_configs': GG_ERR_CAPACITY outside the context, GG_ERR_INVALID for duplicates
-static int check_slot_list(gg_context *ctx, const char *who, int n, const int32_t *slots, int first_slot)
-{
-    std::vector<char> seen((size_t)ctx->n_slots, 0);
-    for (int k = 0; k < n; ++k) {
-        const long long slot = slots ? (long long)slots[k] : (long long)first_slot + k;
-        if (slot < 0 || slot >= ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, (std::string(who) + ": slot outside the context").c_str());
-        if (seen[(size_t)slot]++) return fail(ctx, GG_ERR_INVALID, (std::string(who) + ": a slot is named twice").c_str());
-    }
-    return GG_OK;
-}
 
 int gg_set_score_labels(gg_context *ctx, int n_ids, const int32_t *ids)
 {
@@ -1573,7 +1704,7 @@ int gg_set_slot_scoring(gg_context *ctx, int n, const int32_t *slots, int first_
     if (const int rc = check_slot_list(ctx, "gg_set_slot_scoring", n, slots, first_slot)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<char> on = ctx->score_on;
-    for (int k = 0; k < n; ++k) on[slots ? slots[k] : first_slot + k] = enable ? 1 : 0;
+    for (int k = 0; k < n; ++k) on[slot_of(slots, first_slot, k)] = enable ? 1 : 0;
     if (const int rc = wait_for_batches_in_flight(ctx)) return rc;
     HIPCHK(ctx, hipMemcpy(const_cast<uint8_t *>(ctx->score.slot_on), on.data(), on.size(), hipMemcpyHostToDevice));
     ctx->score_on.swap(on);
@@ -1593,7 +1724,7 @@ int gg_get_slot_scores(gg_context *ctx, int n, const int32_t *slots, int first_s
     if (const int rc = own_stream_waits_for_batches(ctx, false)) return rc;
     int lo = ctx->n_slots, hi = 0;
     for (int k = 0; k < n; ++k) {
-        const int slot = slots ? slots[k] : first_slot + k;
+        const int slot = slot_of(slots, first_slot, k);
         lo = std::min(lo, slot), hi = std::max(hi, slot + 1);
     }
     if (!slots) { // a run of slots: straight into the caller's array
@@ -1723,7 +1854,8 @@ const char *gg_last_error(const gg_context *ctx) { return ctx ? ctx->last_error.
 int gg_reset_maps(gg_context *ctx, int first_slot, int n, double pos_x, double pos_y, float odom_z, int persistent_only, void *stream)
 {
     if (!ctx) return GG_ERR_INVALID;
-    if (n < 0 || first_slot < 0 || first_slot + n > ctx->n_slots) return GG_ERR_CAPACITY;
+    if (n < 0) return fail(ctx, GG_ERR_CAPACITY, "gg_reset_maps: n < 0");
+    if (const int rc = check_slot_list(ctx, "gg_reset_maps", n, nullptr, first_slot)) return rc; // (in front of n == 0: an empty run outside the context is an error too)
     if (n == 0) return GG_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = pick_stream(ctx, stream);
@@ -1732,14 +1864,7 @@ int gg_reset_maps(gg_context *ctx, int first_slot, int n, double pos_x, double p
     // their batches run -- the caller's stream never has to wait for the second half of the batch before
     const int boundary = (ctx->n_slots + 1) / 2;
     const bool split = halves_enabled(ctx) && st != ctx->stream && st != ctx->half_stream && st != nullptr && first_slot < boundary && first_slot + n > boundary;
-    if (st == ctx->stream) {
-        if (const int rc = own_stream_waits_for_batches(ctx, false)) return rc;
-    } else { // ordered like a batch on the caller's stream
-        if (ctx->map_event_pending) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->map_event, 0));
-        if (ctx->have_batch_event && ctx->last_batch_stream != st && !ctx->probe_unordered_streams) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->batch_event, 0));
-        if (!(split && ctx->last_batch_stream == st))
-            if (const int rc = stream_waits_for_second_half(ctx, st)) return rc;
-    }
+    if (const int rc = call_follows_context(ctx, st, split)) return rc; // (on a caller's stream: ordered like a batch there)
     const Arena &a = ctx->arena;
     for (int s = first_slot; s < first_slot + n; ++s) {
         ctx->no_confidence[s] = 1; // groundpatch := 1e-7 everywhere (scrolling keeps that: exposed cells get 0)
@@ -1779,11 +1904,7 @@ int gg_reset_maps(gg_context *ctx, int first_slot, int n, double pos_x, double p
         fill(first_slot, n, st);
         HIPCHK(ctx, hipGetLastError());
     }
-    if (st == ctx->stream) return own_stream_mutated_map(ctx);
-    HIPCHK(ctx, hipEventRecord(ctx->batch_event, st));
-    ctx->have_batch_event = true;
-    ctx->last_batch_stream = st;
-    return GG_OK;
+    return call_recorded(ctx, st, false);
 }
 
 int gg_reset_map(gg_context *ctx, int slot, double pos_x, double pos_y, float odom_z)
@@ -1821,23 +1942,18 @@ int gg_move_map(gg_context *ctx, int slot, double odom_x, double odom_y, const d
     return own_stream_mutated_map(ctx);
 }
 
-// gg_move_maps' device block and pinned parameter ring, at its first call (not while `st` is being captured into a graph: an allocation
-// cannot be captured).  Nothing of the context changes when this fails.
+// gg_move_maps' device block and pinned parameter ring, at its first call (alloc_call_scratch: nothing of the context changes when it fails)
 static int ensure_move_scratch(gg_context *ctx, hipStream_t st)
 {
-    if (ctx->d_move_block) return GG_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        return fail(ctx, GG_ERR_INVALID, "gg_move_maps: the first call allocates its scratch and cannot be captured into a graph");
-    (void)hipGetLastError();
+    if (ctx->move_mem.dev) return GG_OK;
     const Arena &a = ctx->arena;
     const size_t row = (size_t)a.g.C * sizeof(float2);
     // scratch rows: one per slot, at most 256 MB (at least 2: the two halves of a divided call each need one)
     const int cap = (int)std::max<size_t>(2, std::min<size_t>((size_t)ctx->n_slots, ((size_t)256 << 20) / row));
+    const size_t ring_bytes = (size_t)PARAM_RING * ctx->n_slots * sizeof(MoveParams);
     const size_t o_cells = 0;
     const size_t o_params = align_up(o_cells + (size_t)a.g.C * sizeof(int2), 256);
-    const size_t o_scratch = align_up(o_params + (size_t)PARAM_RING * ctx->n_slots * sizeof(MoveParams), 256);
-    const size_t bytes = o_scratch + (size_t)cap * row;
+    const size_t o_scratch = align_up(o_params + ring_bytes, 256);
     std::vector<int2> cells;
     cells.reserve((size_t)a.g.C);
     for (int e = 0; e < a.gpl.elems; ++e) {
@@ -1845,46 +1961,15 @@ static int ensure_move_scratch(gg_context *ctx, hipStream_t st)
         if (gp_cell_of(a.gpl, e, r, c)) cells.push_back(make_int2(e, r | (c << 16)));
     }
     if ((int)cells.size() != a.g.C) return fail(ctx, GG_ERR_GEOMETRY, "gg_move_maps: the layer's cell elements do not cover the map");
-    void *block = nullptr;
-    MoveParams *h = nullptr;
-    hipEvent_t ev[2 * PARAM_RING]{};
-    hipError_t e = hipMalloc(&block, bytes);
-    int code = GG_ERR_NOMEM;
-    const char *what = "gg_move_maps: device scratch";
-    if (e != hipSuccess) block = nullptr;
-    if (e == hipSuccess) {
-        what = "gg_move_maps: pinned parameter ring";
-        e = hipHostMalloc((void **)&h, (size_t)PARAM_RING * ctx->n_slots * sizeof(MoveParams), hipHostMallocDefault);
-        if (e != hipSuccess) h = nullptr;
-    }
-    for (int i = 0; i < 2 * PARAM_RING && e == hipSuccess; ++i) {
-        code = GG_ERR_HIP;
-        what = "gg_move_maps: events";
-        e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
-        if (e != hipSuccess) ev[i] = nullptr;
-    }
-    if (e == hipSuccess) { // (synchronous: the table is on the device before any stream can launch a scroll)
-        what = "gg_move_maps: cell table";
-        e = hipMemcpy(block, cells.data(), cells.size() * sizeof(int2), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        for (hipEvent_t x : ev)
-            if (x) hipEventDestroy(x);
-        if (h) hipHostFree(h);
-        if (block) hipFree(block);
-        (void)hipGetLastError();
-        return fail(ctx, code, what, e);
-    }
-    ctx->d_move_block = block;
-    ctx->d_move_cells = (const int2 *)((char *)block + o_cells);
-    ctx->d_move_params = (MoveParams *)((char *)block + o_params);
-    ctx->d_move_scratch = (float2 *)((char *)block + o_scratch);
-    ctx->h_move_params = h;
+    if (const int rc = alloc_call_scratch(ctx, "gg_move_maps", st, o_scratch + (size_t)cap * row, ring_bytes, {{o_cells, cells.data(), cells.size() * sizeof(int2)}},
+                                          &ctx->move_mem, &ctx->move_ring))
+        return rc;
+    char *block = (char *)ctx->move_mem.dev;
+    ctx->d_move_cells = (const int2 *)(block + o_cells);
+    ctx->d_move_params = (MoveParams *)(block + o_params);
+    ctx->d_move_scratch = (float2 *)(block + o_scratch);
+    ctx->h_move_params = (MoveParams *)ctx->move_mem.pinned;
     ctx->move_cap = cap;
-    for (int i = 0; i < PARAM_RING; ++i) {
-        ctx->move_done[i] = ev[i];
-        ctx->move_done2[i] = ev[PARAM_RING + i];
-    }
     return GG_OK;
 }
 
@@ -1896,17 +1981,9 @@ int gg_move_maps(gg_context *ctx, int n, const int32_t *slots, int first_slot, c
     if (n == 0) return GG_OK;
     if (!odom_xy || !base_planes) return fail(ctx, GG_ERR_INVALID, "gg_move_maps: odom_xy and base_planes are required");
     if (n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, "gg_move_maps: more maps than the context has");
-    if (!slots && (first_slot < 0 || first_slot > ctx->n_slots - n)) return fail(ctx, GG_ERR_CAPACITY, "gg_move_maps: slot range");
-    if (slots) { // distinct and in range: two scrolls of one map in one launch would race
-        std::vector<char> &seen = ctx->slot_seen;
-        seen.assign((size_t)ctx->n_slots, 0);
-        for (int i = 0; i < n; ++i) {
-            const int s = slots[i];
-            if (s < 0 || s >= ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, "gg_move_maps: slot outside the context");
-            if (seen[(size_t)s]) return fail(ctx, GG_ERR_INVALID, "gg_move_maps: slots must be distinct");
-            seen[(size_t)s] = 1;
-        }
-    }
+    // (distinct and in range: two scrolls of one map in one launch would race.  The check above stays in front: a list longer than the context
+    // has a duplicate by necessity, and is GG_ERR_CAPACITY all the same)
+    if (const int rc = check_slot_list(ctx, "gg_move_maps", n, slots, first_slot)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = pick_stream(ctx, stream);
     const Arena &a = ctx->arena;
@@ -1916,45 +1993,33 @@ int gg_move_maps(gg_context *ctx, int n, const int32_t *slots, int first_slot, c
     std::vector<int> order; // the maps that move: those of the lower half of the slots first when the call runs as two halves
     order.reserve((size_t)n);
     for (int i = 0; i < n; ++i) {
-        const int slot = slots ? slots[i] : first_slot + i;
+        const int slot = slot_of(slots, first_slot, i);
         map_shift(a.g.resolution, ctx->pos_x[slot], ctx->pos_y[slot], odom_xy[2 * i], odom_xy[2 * i + 1], &sh[(size_t)2 * i], &moved[(size_t)2 * i]);
         if (sh[(size_t)2 * i] != 0 || sh[(size_t)2 * i + 1] != 0) order.push_back(i);
     }
-    auto slot_of = [&](int i) { return slots ? slots[i] : first_slot + i; };
     if (!order.empty()) {
         if (const int rc = ensure_move_scratch(ctx, st)) return rc;
         // GG_FLAG_CONCURRENT_HALVES: on a caller stream the maps of the upper half of the slots scroll on the side stream, where their
         // batches run (as gg_reset_maps divides its fills): a loop of moves and batches on one stream keeps both halves concurrent
-        std::stable_partition(order.begin(), order.end(), [&](int i) { return !second_half_slot(ctx, slot_of(i)); });
+        std::stable_partition(order.begin(), order.end(), [&](int i) { return !second_half_slot(ctx, slot_of(slots, first_slot, i)); });
         int n_lo = 0;
-        while (n_lo < (int)order.size() && !second_half_slot(ctx, slot_of(order[(size_t)n_lo]))) ++n_lo;
+        while (n_lo < (int)order.size() && !second_half_slot(ctx, slot_of(slots, first_slot, order[(size_t)n_lo]))) ++n_lo;
         const int nm = (int)order.size();
         const bool split = halves_enabled(ctx) && st != ctx->stream && st != ctx->half_stream && st != nullptr && n_lo > 0 && n_lo < nm;
         // parameter ring slot (the pinned entries are rewritten only when the copy that read them last has run)
-        const int g = ctx->move_next;
-        ctx->move_next = (g + 1) % PARAM_RING;
-        if (ctx->move_used[g]) HIPCHK(ctx, hipEventSynchronize(ctx->move_done[g]));
-        if (ctx->move_used2[g]) HIPCHK(ctx, hipEventSynchronize(ctx->move_done2[g]));
-        ctx->move_used[g] = ctx->move_used2[g] = false;
+        int g;
+        HIPCHK(ctx, ctx->move_ring.acquire(&g));
         MoveParams *hp = ctx->h_move_params + (size_t)g * ctx->n_slots;
         MoveParams *dp = ctx->d_move_params + (size_t)g * ctx->n_slots;
         for (int k = 0; k < nm; ++k) {
-            const int i = order[(size_t)k], slot = slot_of(i);
+            const int i = order[(size_t)k], slot = slot_of(slots, first_slot, i);
             MoveParams &p = hp[k];
             p.sp = make_scroll_params(a, sh[(size_t)2 * i], sh[(size_t)2 * i + 1], moved[(size_t)2 * i], moved[(size_t)2 * i + 1], base_planes + (size_t)4 * i);
             p.slot = slot;
             p.fresh = ctx->fresh[slot] ? 1 : 0;
             p.fresh_z = ctx->fresh_z[slot];
         }
-        // ordered like gg_reset_maps on `st`
-        if (st == ctx->stream) {
-            if (const int rc = own_stream_waits_for_batches(ctx, false)) return rc;
-        } else {
-            if (ctx->map_event_pending) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->map_event, 0));
-            if (ctx->have_batch_event && ctx->last_batch_stream != st && !ctx->probe_unordered_streams) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->batch_event, 0));
-            if (!(split && ctx->last_batch_stream == st))
-                if (const int rc = stream_waits_for_second_half(ctx, st)) return rc;
-        }
+        if (const int rc = call_follows_context(ctx, st, split)) return rc; // (ordered like gg_reset_maps on `st`)
         HIPCHK(ctx, hipMemcpyAsync(dp, hp, sizeof(MoveParams) * nm, hipMemcpyHostToDevice, st));
         // chunks of at most `per` maps through the scratch rows [row0, row0 + per): consecutive chunks on one stream reuse them in order
         auto run = [&](int lo, int hi, int row0, int per, hipStream_t on) {
@@ -1969,26 +2034,18 @@ int gg_move_maps(gg_context *ctx, int n, const int32_t *slots, int first_slot, c
             run(0, n_lo, 0, half, st);
             run(n_lo, nm, half, half, ctx->half_stream);
             HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipEventRecord(ctx->move_done2[g], ctx->half_stream));
+            HIPCHK(ctx, ctx->move_ring.recorded2(g, ctx->half_stream));
             HIPCHK(ctx, hipEventRecord(ctx->half_done, ctx->half_stream));
-            ctx->move_used2[g] = true;
             ctx->have_half_event = true;
         } else {
             run(0, nm, 0, ctx->move_cap, st);
             HIPCHK(ctx, hipGetLastError());
         }
-        HIPCHK(ctx, hipEventRecord(ctx->move_done[g], st));
-        ctx->move_used[g] = true;
-        if (st == ctx->stream) {
-            if (const int rc = own_stream_mutated_map(ctx)) return rc;
-        } else {
-            HIPCHK(ctx, hipEventRecord(ctx->batch_event, st));
-            ctx->have_batch_event = true;
-            ctx->last_batch_stream = st;
-        }
+        HIPCHK(ctx, ctx->move_ring.recorded(g, st));
+        if (const int rc = call_recorded(ctx, st, false)) return rc;
         // every enqueue succeeded: the moved maps are at their new positions, and real (the scroll wrote every cell); no_confidence stays
         for (int i : order) {
-            const int slot = slot_of(i);
+            const int slot = slot_of(slots, first_slot, i);
             ctx->pos_x[slot] = moved[(size_t)2 * i];
             ctx->pos_y[slot] = moved[(size_t)2 * i + 1];
             ctx->fresh[slot] = 0;
@@ -1999,15 +2056,11 @@ int gg_move_maps(gg_context *ctx, int n, const int32_t *slots, int first_slot, c
     return GG_OK;
 }
 
-// gg_export_layers' device block, pinned rings and events, at its first call (not while `st` is being captured into a graph: an allocation
-// cannot be captured).  Nothing of the context changes when this fails.
-static int ensure_export_scratch(gg_context *ctx, hipStream_t st)
+// gg_export_layers' and gg_import_layers' device block and pinned rings, at the first call of either (alloc_call_scratch: nothing of the
+// context changes when it fails)
+static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t st)
 {
-    if (ctx->d_export_block) return GG_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        return fail(ctx, GG_ERR_INVALID, "gg_export_layers: the first call allocates its scratch and cannot be captured into a graph");
-    (void)hipGetLastError();
+    if (ctx->export_mem.dev) return GG_OK;
     const Arena &a = ctx->arena;
     const int C = a.g.C;
     const int br = (a.g.rows + EXPORT_TILE - 1) / EXPORT_TILE, bc = (a.g.cols + EXPORT_TILE - 1) / EXPORT_TILE;
@@ -2024,7 +2077,7 @@ static int ensure_export_scratch(gg_context *ctx, hipStream_t st)
             for (int ri = 0; ri < EXPORT_TILE && r0 + ri < a.g.rows; ++ri) blk.emplace_back((uint32_t)gp_idx(a, r0 + ri, c0 + ci), (uint16_t)(ri | (ci << 6)));
         std::sort(blk.begin(), blk.end());
         for (const auto &e : blk) {
-            if (e.first >= (uint32_t)a.gpl.elems) return fail(ctx, GG_ERR_GEOMETRY, "gg_export_layers: a cell's element lies outside the layer");
+            if (e.first >= (uint32_t)a.gpl.elems) return fail(ctx, GG_ERR_GEOMETRY, who, "a cell's element lies outside the layer");
             elem.push_back(e.first);
             cell.push_back(e.second);
         }
@@ -2036,211 +2089,112 @@ static int ensure_export_scratch(gg_context *ctx, hipStream_t st)
     const size_t o_cell = align_up(o_elem + elem.size() * sizeof(uint32_t), 256);
     const size_t o_maps = align_up(o_cell + cell.size() * sizeof(uint16_t), 256);
     const size_t o_lazy = align_up(o_maps + ring * sizeof(ExportMap), 256);
-    const size_t bytes = o_lazy + ring * sizeof(CloudParams);
-    const size_t h_lazy = align_up(ring * sizeof(ExportMap), 256), h_bytes = h_lazy + ring * sizeof(CloudParams);
-    void *block = nullptr, *h = nullptr;
-    hipEvent_t ev[PARAM_RING]{};
-    hipError_t e = hipMalloc(&block, bytes);
-    int code = GG_ERR_NOMEM;
-    const char *what = "gg_export_layers: device scratch";
-    if (e != hipSuccess) block = nullptr;
-    if (e == hipSuccess) {
-        what = "gg_export_layers: pinned parameter ring";
-        e = hipHostMalloc(&h, h_bytes, hipHostMallocDefault);
-        if (e != hipSuccess) h = nullptr;
-    }
-    for (int i = 0; i < PARAM_RING && e == hipSuccess; ++i) {
-        code = GG_ERR_HIP;
-        what = "gg_export_layers: events";
-        e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
-        if (e != hipSuccess) ev[i] = nullptr;
-    }
-    // (synchronous copies: the table is on the device before any stream can launch an export)
-    what = e == hipSuccess ? "gg_export_layers: export table" : what;
-    if (e == hipSuccess) e = hipMemcpy((char *)block + o_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy((char *)block + o_elem, elem.data(), elem.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy((char *)block + o_cell, cell.data(), cell.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        for (hipEvent_t x : ev)
-            if (x) hipEventDestroy(x);
-        if (h) hipHostFree(h);
-        if (block) hipFree(block);
-        (void)hipGetLastError();
-        return fail(ctx, code, what, e);
-    }
-    ctx->d_export_block = block;
-    ctx->h_export_block = h;
-    ctx->d_export_off = (const uint32_t *)((char *)block + o_off);
-    ctx->d_export_elem = (const uint32_t *)((char *)block + o_elem);
-    ctx->d_export_cell = (const uint16_t *)((char *)block + o_cell);
-    ctx->d_export_maps = (ExportMap *)((char *)block + o_maps);
-    ctx->d_export_lazy = (CloudParams *)((char *)block + o_lazy);
+    const size_t h_lazy = align_up(ring * sizeof(ExportMap), 256);
+    if (const int rc = alloc_call_scratch(ctx, who, st, o_lazy + ring * sizeof(CloudParams), h_lazy + ring * sizeof(CloudParams),
+                                          {{o_off, off.data(), off.size() * sizeof(uint32_t)}, {o_elem, elem.data(), elem.size() * sizeof(uint32_t)}, {o_cell, cell.data(), cell.size() * sizeof(uint16_t)}},
+                                          &ctx->export_mem, &ctx->export_ring))
+        return rc;
+    char *block = (char *)ctx->export_mem.dev, *h = (char *)ctx->export_mem.pinned;
+    ctx->d_export_off = (const uint32_t *)(block + o_off);
+    ctx->d_export_elem = (const uint32_t *)(block + o_elem);
+    ctx->d_export_cell = (const uint16_t *)(block + o_cell);
+    ctx->d_export_maps = (ExportMap *)(block + o_maps);
+    ctx->d_export_lazy = (CloudParams *)(block + o_lazy);
     ctx->h_export_maps = (ExportMap *)h;
-    ctx->h_export_lazy = (CloudParams *)((char *)h + h_lazy);
-    for (int i = 0; i < PARAM_RING; ++i) ctx->export_done[i] = ev[i];
+    ctx->h_export_lazy = (CloudParams *)(h + h_lazy);
+    return GG_OK;
+}
+
+// gg_export_layers and gg_import_layers, its inverse, are one call in two directions on the same table, rings and events; `d_planes` is the
+// destination of the one and the source of the other.  Host-side flags are committed at the end, when every launch has been enqueued.
+static int transfer_layers(gg_context *ctx, bool import, int n, const int32_t *slots, int first_slot, unsigned layer_mask, int order, const float *d_planes,
+                           size_t plane_stride, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = import ? "gg_import_layers" : "gg_export_layers";
+    if (n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (n == 0) return GG_OK;
+    if (layer_mask == 0u || (layer_mask >> GG_NUM_LAYERS) != 0u) return fail(ctx, GG_ERR_INVALID, who, "layer_mask");
+    if (order != GG_PLANES_COLMAJOR && order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (!d_planes) return fail(ctx, GG_ERR_INVALID, who, import ? "d_src is null" : "d_dst is null");
+    if (plane_stride < (size_t)ctx->arena.g.C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
+    if (const int rc = check_slot_list(ctx, who, n, slots, first_slot)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = pick_stream(ctx, stream);
+    if (const int rc = ensure_export_scratch(ctx, who, st)) return rc;
+    const Arena &a = ctx->arena;
+    // ring entry (the pinned tables are rewritten only when the copies that read them last have run)
+    int g;
+    HIPCHK(ctx, ctx->export_ring.acquire(&g));
+    ExportMap *hm = ctx->h_export_maps + (size_t)g * ctx->n_slots, *dm = ctx->d_export_maps + (size_t)g * ctx->n_slots;
+    CloudParams *hl = ctx->h_export_lazy + (size_t)g * ctx->n_slots, *dl = ctx->d_export_lazy + (size_t)g * ctx->n_slots;
+    const unsigned gp_mask = layer_mask & ((1u << GG_LAYER_GROUND) | (1u << GG_LAYER_GROUNDPATCH));
+    const unsigned percall_mask = layer_mask & ~gp_mask;
+    const unsigned lazy_mask = (1u << GG_LAYER_MAXGROUNDHEIGHT) | (1u << GG_LAYER_GROUNDCANDIDATES) | (1u << GG_LAYER_PLANEDIST);
+    // Which listed maps get the three layers GG_FLAG_MINIMAL_LAYERS left out computed first, where they still miss them:
+    // export: those whose lazily kept layers the mask names -- exactly the exported slots that still miss them.
+    // import: the import makes all nine per-call layers of a map dense, after which the three lazily kept ones can no longer be computed into
+    // the half columns their cloud wrote: a listed map that still misses them gets them first -- unless all three are imported anyway
+    const bool lazy_first = percall_mask != 0u && (layer_mask & lazy_mask) != lazy_mask;
+    const bool lazy_wanted = import ? lazy_first : (layer_mask & lazy_mask) != 0u;
+    int n_lazy = 0;
+    for (int i = 0; i < n; ++i) {
+        const int slot = slot_of(slots, first_slot, i);
+        hm[i].slot = slot;
+        // (export: a fresh map stays fresh: its planes are the reset's constants.  import: with ground / groundpatch named, the kernel writes
+        // the whole pair: no fill)
+        hm[i].fresh = ctx->fresh[slot] ? 1 : 0;
+        hm[i].fresh_z = ctx->fresh_z[slot];
+        hm[i].reserved = 0;
+        if (lazy_wanted && ctx->lazy_pending[slot]) hl[n_lazy++] = ctx->lazy_params[slot];
+    }
+    // `st` follows every earlier map mutation, batch, export and import of the context, and both halves of a divided batch: the call reads
+    // (writes) maps of either
+    if (const int rc = call_follows_context(ctx, st, false)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(dm, hm, sizeof(ExportMap) * n, hipMemcpyHostToDevice, st));
+    if (n_lazy) { // one launch
+        HIPCHK(ctx, hipMemcpyAsync(dl, hl, sizeof(CloudParams) * n_lazy, hipMemcpyHostToDevice, st));
+        launch_reduce_lazy_batch(a, dl, n_lazy, st);
+    }
+    if (import) {
+        ImportArgs x;
+        fill_plane_args(x, ctx, dm, layer_mask, order, plane_stride);
+        x.src = d_planes;
+        launch_import(a, x, n, ctx->import_variant, st);
+    } else {
+        ExportArgs x;
+        fill_plane_args(x, ctx, dm, layer_mask, order, plane_stride);
+        x.dst = const_cast<float *>(d_planes);
+        launch_export(a, x, n, ctx->export_variant, st);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, ctx->export_ring.recorded(g, st));
+    // whatever reads or writes one of these maps next on another stream waits for the call (and for the lazily kept layers it computed)
+    if (const int rc = call_recorded(ctx, st, true)) return rc;
+    if (!import) {
+        for (int i = 0; i < n_lazy; ++i) ctx->lazy_pending[hl[i].slot] = 0;
+        return GG_OK;
+    }
+    // import: every launch is enqueued: the listed maps' flags follow (no other map's change)
+    for (int i = 0; i < n; ++i) {
+        const int slot = slot_of(slots, first_slot, i);
+        if (gp_mask) ctx->fresh[slot] = 0; // (the kernel wrote the pair of every cell)
+        if (layer_mask & (1u << GG_LAYER_GROUNDPATCH)) ctx->no_confidence[slot] = 0;
+        if (percall_mask) ctx->lazy_pending[slot] = 0; // (computed above, or all three imported)
+    }
     return GG_OK;
 }
 
 int gg_export_layers(gg_context *ctx, int n, const int32_t *slots, int first_slot, unsigned layer_mask, int order, float *d_dst, size_t plane_stride,
                      void *stream)
 {
-    if (!ctx) return GG_ERR_INVALID;
-    if (n < 0) return fail(ctx, GG_ERR_INVALID, "gg_export_layers: n < 0");
-    if (n == 0) return GG_OK;
-    if (layer_mask == 0u || (layer_mask >> GG_NUM_LAYERS) != 0u) return fail(ctx, GG_ERR_INVALID, "gg_export_layers: layer_mask");
-    if (order != GG_PLANES_COLMAJOR && order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, "gg_export_layers: order");
-    if (!d_dst) return fail(ctx, GG_ERR_INVALID, "gg_export_layers: d_dst is null");
-    if (plane_stride < (size_t)ctx->arena.g.C) return fail(ctx, GG_ERR_INVALID, "gg_export_layers: plane_stride is smaller than rows * cols");
-    if (const int rc = check_slot_list(ctx, "gg_export_layers", n, slots, first_slot)) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const hipStream_t st = pick_stream(ctx, stream);
-    if (const int rc = ensure_export_scratch(ctx, st)) return rc;
-    const Arena &a = ctx->arena;
-    auto slot_of = [&](int i) { return slots ? slots[i] : first_slot + i; };
-    // ring entry (the pinned tables are rewritten only when the copies that read them last have run)
-    const int g = ctx->export_next;
-    ctx->export_next = (g + 1) % PARAM_RING;
-    if (ctx->export_used[g]) HIPCHK(ctx, hipEventSynchronize(ctx->export_done[g]));
-    ctx->export_used[g] = false;
-    ExportMap *hm = ctx->h_export_maps + (size_t)g * ctx->n_slots, *dm = ctx->d_export_maps + (size_t)g * ctx->n_slots;
-    CloudParams *hl = ctx->h_export_lazy + (size_t)g * ctx->n_slots, *dl = ctx->d_export_lazy + (size_t)g * ctx->n_slots;
-    const unsigned lazy_mask = (1u << GG_LAYER_MAXGROUNDHEIGHT) | (1u << GG_LAYER_GROUNDCANDIDATES) | (1u << GG_LAYER_PLANEDIST);
-    int n_lazy = 0;
-    for (int i = 0; i < n; ++i) {
-        const int slot = slot_of(i);
-        hm[i].slot = slot;
-        hm[i].fresh = ctx->fresh[slot] ? 1 : 0; // (a fresh map stays fresh: its planes are the reset's constants)
-        hm[i].fresh_z = ctx->fresh_z[slot];
-        hm[i].reserved = 0;
-        if ((layer_mask & lazy_mask) && ctx->lazy_pending[slot]) hl[n_lazy++] = ctx->lazy_params[slot];
-    }
-    // `st` follows every earlier map mutation and batch of the context, and both halves of a divided batch: the export reads maps of either
-    if (st == ctx->stream) {
-        if (const int rc = own_stream_waits_for_batches(ctx, false)) return rc;
-    } else {
-        if (ctx->map_event_pending) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->map_event, 0));
-        if (ctx->have_batch_event && ctx->last_batch_stream != st && !ctx->probe_unordered_streams) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->batch_event, 0));
-        if (const int rc = stream_waits_for_second_half(ctx, st)) return rc;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(dm, hm, sizeof(ExportMap) * n, hipMemcpyHostToDevice, st));
-    if (n_lazy) { // the three layers GG_FLAG_MINIMAL_LAYERS left out, for exactly the exported slots that still miss them: one launch
-        HIPCHK(ctx, hipMemcpyAsync(dl, hl, sizeof(CloudParams) * n_lazy, hipMemcpyHostToDevice, st));
-        launch_reduce_lazy_batch(a, dl, n_lazy, st);
-    }
-    ExportArgs x;
-    x.maps = dm;
-    x.block_off = ctx->d_export_off;
-    x.elem = ctx->d_export_elem;
-    x.cell = ctx->d_export_cell;
-    x.blocks_r = (a.g.rows + EXPORT_TILE - 1) / EXPORT_TILE;
-    x.blocks_c = (a.g.cols + EXPORT_TILE - 1) / EXPORT_TILE;
-    x.mask = layer_mask;
-    x.n_planes = __builtin_popcount(layer_mask);
-    x.order = order;
-    x.dst = d_dst;
-    x.plane_stride = plane_stride;
-    launch_export(a, x, n, ctx->export_variant, st);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->export_done[g], st));
-    ctx->export_used[g] = true;
-    // whatever writes one of these maps next on another stream waits for the export (and for the lazily kept layers it computed)
-    if (st == ctx->stream) {
-        if (const int rc = own_stream_mutated_map(ctx)) return rc;
-    } else {
-        HIPCHK(ctx, hipEventRecord(ctx->batch_event, st));
-        ctx->have_batch_event = true;
-        ctx->last_batch_stream = st;
-        ctx->map_event_pending = false; // (this stream has waited; later batches anywhere follow batch_event)
-    }
-    for (int i = 0; i < n_lazy; ++i) ctx->lazy_pending[hl[i].slot] = 0;
-    return GG_OK;
+    return transfer_layers(ctx, false, n, slots, first_slot, layer_mask, order, d_dst, plane_stride, stream);
 }
 
-// The inverse of gg_export_layers, on the same table, rings and events (ensure_export_scratch).  Host-side flags are committed at the end,
-// when every launch of the call has been enqueued.
 int gg_import_layers(gg_context *ctx, int n, const int32_t *slots, int first_slot, unsigned layer_mask, int order, const float *d_src,
                      size_t plane_stride, void *stream)
 {
-    if (!ctx) return GG_ERR_INVALID;
-    if (n < 0) return fail(ctx, GG_ERR_INVALID, "gg_import_layers: n < 0");
-    if (n == 0) return GG_OK;
-    if (layer_mask == 0u || (layer_mask >> GG_NUM_LAYERS) != 0u) return fail(ctx, GG_ERR_INVALID, "gg_import_layers: layer_mask");
-    if (order != GG_PLANES_COLMAJOR && order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, "gg_import_layers: order");
-    if (!d_src) return fail(ctx, GG_ERR_INVALID, "gg_import_layers: d_src is null");
-    if (plane_stride < (size_t)ctx->arena.g.C) return fail(ctx, GG_ERR_INVALID, "gg_import_layers: plane_stride is smaller than rows * cols");
-    if (const int rc = check_slot_list(ctx, "gg_import_layers", n, slots, first_slot)) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const hipStream_t st = pick_stream(ctx, stream);
-    if (const int rc = ensure_export_scratch(ctx, st)) return rc;
-    const Arena &a = ctx->arena;
-    auto slot_of = [&](int i) { return slots ? slots[i] : first_slot + i; };
-    const int g = ctx->export_next;
-    ctx->export_next = (g + 1) % PARAM_RING;
-    if (ctx->export_used[g]) HIPCHK(ctx, hipEventSynchronize(ctx->export_done[g]));
-    ctx->export_used[g] = false;
-    ExportMap *hm = ctx->h_export_maps + (size_t)g * ctx->n_slots, *dm = ctx->d_export_maps + (size_t)g * ctx->n_slots;
-    CloudParams *hl = ctx->h_export_lazy + (size_t)g * ctx->n_slots, *dl = ctx->d_export_lazy + (size_t)g * ctx->n_slots;
-    const unsigned gp_mask = layer_mask & ((1u << GG_LAYER_GROUND) | (1u << GG_LAYER_GROUNDPATCH));
-    const unsigned percall_mask = layer_mask & ~gp_mask;
-    const unsigned lazy_mask = (1u << GG_LAYER_MAXGROUNDHEIGHT) | (1u << GG_LAYER_GROUNDCANDIDATES) | (1u << GG_LAYER_PLANEDIST);
-    // The import makes all nine per-call layers of a map dense, after which the three lazily kept ones can no longer be computed into the
-    // half columns their cloud wrote: a listed map that still misses them gets them first -- unless all three are imported anyway
-    const bool lazy_first = percall_mask != 0u && (layer_mask & lazy_mask) != lazy_mask;
-    int n_lazy = 0;
-    for (int i = 0; i < n; ++i) {
-        const int slot = slot_of(i);
-        hm[i].slot = slot;
-        hm[i].fresh = ctx->fresh[slot] ? 1 : 0; // (with ground / groundpatch named, the kernel writes the whole pair: no fill)
-        hm[i].fresh_z = ctx->fresh_z[slot];
-        hm[i].reserved = 0;
-        if (lazy_first && ctx->lazy_pending[slot]) hl[n_lazy++] = ctx->lazy_params[slot];
-    }
-    // `st` follows every earlier map mutation, batch and export of the context, and both halves of a divided batch
-    if (st == ctx->stream) {
-        if (const int rc = own_stream_waits_for_batches(ctx, false)) return rc;
-    } else {
-        if (ctx->map_event_pending) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->map_event, 0));
-        if (ctx->have_batch_event && ctx->last_batch_stream != st && !ctx->probe_unordered_streams) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->batch_event, 0));
-        if (const int rc = stream_waits_for_second_half(ctx, st)) return rc;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(dm, hm, sizeof(ExportMap) * n, hipMemcpyHostToDevice, st));
-    if (n_lazy) {
-        HIPCHK(ctx, hipMemcpyAsync(dl, hl, sizeof(CloudParams) * n_lazy, hipMemcpyHostToDevice, st));
-        launch_reduce_lazy_batch(a, dl, n_lazy, st);
-    }
-    ImportArgs x;
-    x.maps = dm;
-    x.block_off = ctx->d_export_off;
-    x.elem = ctx->d_export_elem;
-    x.cell = ctx->d_export_cell;
-    x.blocks_r = (a.g.rows + EXPORT_TILE - 1) / EXPORT_TILE;
-    x.blocks_c = (a.g.cols + EXPORT_TILE - 1) / EXPORT_TILE;
-    x.mask = layer_mask;
-    x.n_planes = __builtin_popcount(layer_mask);
-    x.order = order;
-    x.src = d_src;
-    x.plane_stride = plane_stride;
-    launch_import(a, x, n, ctx->import_variant, st);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->export_done[g], st));
-    ctx->export_used[g] = true;
-    // whatever reads or writes one of these maps next on another stream waits for the import
-    if (st == ctx->stream) {
-        if (const int rc = own_stream_mutated_map(ctx)) return rc;
-    } else {
-        HIPCHK(ctx, hipEventRecord(ctx->batch_event, st));
-        ctx->have_batch_event = true;
-        ctx->last_batch_stream = st;
-        ctx->map_event_pending = false; // (this stream has waited; later batches anywhere follow batch_event)
-    }
-    // every launch is enqueued: the listed maps' flags follow (no other map's change)
-    for (int i = 0; i < n; ++i) {
-        const int slot = slot_of(i);
-        if (gp_mask) ctx->fresh[slot] = 0; // (the kernel wrote the pair of every cell)
-        if (layer_mask & (1u << GG_LAYER_GROUNDPATCH)) ctx->no_confidence[slot] = 0;
-        if (percall_mask) ctx->lazy_pending[slot] = 0; // (computed above, or all three imported)
-    }
-    return GG_OK;
+    return transfer_layers(ctx, true, n, slots, first_slot, layer_mask, order, d_src, plane_stride, stream);
 }
 
 int gg_get_map_position(const gg_context *ctx, int slot, double *pos_x, double *pos_y)
@@ -2575,16 +2529,8 @@ int gg_filter_batch(gg_context *ctx, const gg_batch *b, void *stream)
     if (b->n_clouds < 0 || b->n_clouds > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, "slot range");
     if (!b->slots && (b->first_slot < 0 || b->first_slot + b->n_clouds > ctx->n_slots)) return fail(ctx, GG_ERR_CAPACITY, "slot range");
     if (b->n_clouds == 0) return GG_OK;
-    if (b->slots) { // distinct and in range: two clouds of one launch on one map would race
-        std::vector<char> &seen = ctx->slot_seen;
-        seen.assign((size_t)ctx->n_slots, 0);
-        for (int i = 0; i < b->n_clouds; ++i) {
-            const int s = b->slots[i];
-            if (s < 0 || s >= ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, "gg_batch.slots entry outside the context");
-            if (seen[(size_t)s]) return fail(ctx, GG_ERR_INVALID, "gg_batch.slots entries must be distinct");
-            seen[(size_t)s] = 1;
-        }
-    }
+    // (distinct and in range: two clouds of one launch on one map would race)
+    if (const int rc = check_slot_list(ctx, "gg_filter_batch", b->n_clouds, b->slots, b->first_slot)) return rc;
     if (!b->d_points || !b->n_points || !b->origins || !b->base_z) return fail(ctx, GG_ERR_INVALID, "null batch field");
     if (b->point_format != GG_POINT32 && b->point_format != GG_POINT16) return fail(ctx, GG_ERR_INVALID, "point_format");
     if (b->d_out_clouds && b->point_format != GG_POINT32) return fail(ctx, GG_ERR_INVALID, "d_out_clouds needs GG_POINT32 input");
@@ -3025,9 +2971,8 @@ int gg_run_stage(gg_context *ctx, int slot, int stage, const gg_stage_args *args
     if (own) a.cfg = ctx->slot_dev[slot]; // (the single-cell stages read it by value; k_patch takes its SLOT_CFG variant below)
     if (stage == GG_STAGE_DETECT_GROUND_PATCHES || stage == GG_STAGE_SPIRAL_GROUND_INTERPOLATION) {
         // the many-cell stages are the path's own kernels: they take their slot and base_z from a parameter record like a batch of one
-        const int r = ctx->ring_next;
-        ctx->ring_next = (r + 1) % PARAM_RING;
-        if (ctx->ring_used[r]) HIPCHK(ctx, hipEventSynchronize(ctx->ring_done[r]));
+        int r;
+        HIPCHK(ctx, ctx->ring.acquire(&r));
         CloudParams *hp = ctx->h_params + (size_t)r * ctx->n_slots, *dp = ctx->d_params + (size_t)r * ctx->n_slots;
         hp[0] = CloudParams{};
         hp[0].slot = slot;
@@ -3048,8 +2993,7 @@ int gg_run_stage(gg_context *ctx, int slot, int stage, const gg_stage_args *args
             launch_sweep(a, sp, dp, 1, s, nullptr);
         }
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipEventRecord(ctx->ring_done[r], s));
-        ctx->ring_used[r] = true;
+        HIPCHK(ctx, ctx->ring.recorded(r, s));
     } else {
         launch_stage_cell(a, slot, stage, args->i, args->j, s);
         HIPCHK(ctx, hipGetLastError());
@@ -3086,9 +3030,8 @@ int gg_insert_cloud(gg_context *ctx, int slot, const gg_point32 *cloud, size_t s
         d.x = p.x, d.y = p.y, d.z = p.z, d.ring = p.ring, d.pad = 0;
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage_pts, ctx->h_stage_pts, n * sizeof(gg_point16), hipMemcpyHostToDevice, s));
-    const int r = ctx->ring_next;
-    ctx->ring_next = (r + 1) % PARAM_RING;
-    if (ctx->ring_used[r]) HIPCHK(ctx, hipEventSynchronize(ctx->ring_done[r]));
+    int r;
+    HIPCHK(ctx, ctx->ring.acquire(&r));
     CloudParams *hp = ctx->h_params + (size_t)r * ctx->n_slots, *dp = ctx->d_params + (size_t)r * ctx->n_slots;
     hp[0] = CloudParams{};
     hp[0].slot = slot;
@@ -3113,8 +3056,7 @@ int gg_insert_cloud(gg_context *ctx, int slot, const gg_point32 *cloud, size_t s
     HIPCHK(ctx, hipGetLastError());
     if (out_class) HIPCHK(ctx, hipMemcpyAsync(out_class, ctx->d_stage_class, n, hipMemcpyDeviceToHost, s));
     if (out_cell) HIPCHK(ctx, hipMemcpyAsync(out_cell, ctx->d_stage_cell, n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipEventRecord(ctx->ring_done[r], s));
-    ctx->ring_used[r] = true;
+    HIPCHK(ctx, ctx->ring.recorded(r, s));
     ctx->lazy_pending[slot] = 0; // (all nine layers are maintained and dense)
     if (const int rc = own_stream_mutated_map(ctx)) return rc;
     SYNCCHK(ctx, hipStreamSynchronize(s));
