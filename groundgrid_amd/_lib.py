@@ -46,10 +46,12 @@ SYMBOLS = [
     "gg_set_score_labels", "gg_set_slot_scoring", "gg_get_slot_scores", "gg_reset_slot_scores", "gg_get_score_kernel_time",
     "gg_export_layers",
     "gg_import_layers",
+    "gg_export_images",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
 GG_PLANES_COLMAJOR, GG_PLANES_ROWMAJOR = 0, 1
+GG_TERRAIN_HWC, GG_TERRAIN_CHW = 0, 1
 GG_ROT_TF2, GG_ROT_KDL = 0, 1
 ROTATION = {"tf2": GG_ROT_TF2, "kdl": GG_ROT_KDL}
 GG_ASYNC_DEPTH = 2
@@ -108,6 +110,23 @@ class GGBatch(C.Structure):
         ("d_label_masks", C.c_void_p),
         ("slots", C.POINTER(C.c_int32)),
         ("d_out_pc2", C.c_void_p),
+    ]
+
+
+class GGImageExport(C.Structure):
+    """gg_image_export: the u8 layer images and the terrain images of many maps, in device memory (gg_export_images)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("first_slot", C.c_int),
+        ("slots", C.POINTER(C.c_int32)),
+        ("layer_mask", C.c_uint),
+        ("d_images", C.c_void_p),
+        ("image_stride", C.c_size_t),
+        ("d_bounds", C.c_void_p),
+        ("d_terrain", C.c_void_p),
+        ("terrain_stride", C.c_size_t),
+        ("terrain_layout", C.c_int),
     ]
 
 
@@ -181,6 +200,7 @@ def load():
     L.gg_move_maps.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, P(C.c_double), P(C.c_double), P(C.c_int32), vp]
     L.gg_export_layers.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
     L.gg_import_layers.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
+    L.gg_export_images.argtypes = [vp, P(GGImageExport), vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

@@ -225,6 +225,15 @@ class BatchOutputs:
     out_pc2: "object" = None      # torch.uint8 [B, stride * 18]: the returned clouds as 18-byte PointCloud2 records
 
 
+@dataclass
+class ImageExport:
+    """what GroundSegmentation.export_images returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    images: "object" = None   # torch.uint8 [n, K, rows, cols]
+    bounds: "object" = None   # torch.float32 [n, K, 2]: lower, upper
+    terrain: "object" = None  # torch.float32 [n, rows, cols, 3], or [n, 3, rows, cols] with chw
+
+
 class GroundSegmentation:
     """Mirror of groundgrid::GroundSegmentation (include/groundgrid/GroundSegmentation.h:48-71)."""
 
@@ -394,6 +403,57 @@ class GroundSegmentation:
                                       C.c_void_p(planes.data_ptr()), self.rows * self.cols if plane_stride is None else int(plane_stride),
                                       None if own_stream else C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
         _check(self._L, self._ctx, rc, "gg_import_layers")
+
+    def export_images(self, names=None, *, terrain: bool = False, chw: bool = False, slots=None, first_slot: int = 0, n: Optional[int] = None,
+                      out=None, on_torch_stream: bool = False) -> ImageExport:
+        """The 8-bit images of the named layers (default: all eleven, in gg_layer order; [] for none) and, with terrain, the 32FC3
+        terrain images of many maps as CUDA torch tensors (gg_export_images): images uint8 [n, K, rows, cols] and bounds float32
+        [n, K, 2] -- per map and layer what map(slot).image_u8(name) returns, byte for byte --, terrain float32 [n, rows, cols, 3] --
+        map(slot).terrain_image() bit for bit -- or [n, 3, rows, cols] with chw.  Map i = slots[i], or first_slot + i for n maps
+        (default: up to the last slot).  `out`: an ImageExport of an earlier call with the same arguments, whose tensors are reused.
+        Enqueued without synchronising, on the context's own stream (torch.cuda.synchronize() before torch reads the tensors; synchronize() fills the fresh maps) or, with
+        on_torch_stream, on the current torch stream, where torch ops enqueued afterwards see them.  Fresh maps stay fresh; the three
+        lazily kept layers are computed first where the names ask for one."""
+        import torch
+
+        self._torch_used = True
+        names = list(LAYERS) if names is None else list(names)
+        mask = 0
+        for k in names:
+            mask |= 1 << LAYERS.index(k)
+        if bin(mask).count("1") != len(names) or [k for k in LAYERS if k in names] != names:
+            raise ValueError("export_images: names must be distinct and in gg_layer order")
+        if not names and not terrain:
+            raise ValueError("export_images: neither a layer nor the terrain image is asked for")
+        cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
+        K, dev = len(names), torch.device("cuda", self.device)
+        res = out if out is not None else ImageExport()
+        want = {"images": ((cnt, K, self.rows, self.cols), torch.uint8) if K else None, "bounds": ((cnt, K, 2), torch.float32) if K else None,
+                "terrain": ((cnt, 3, self.rows, self.cols) if chw else (cnt, self.rows, self.cols, 3), torch.float32) if terrain else None}
+        for field, spec in want.items():
+            t = getattr(res, field)
+            if spec is None:
+                if t is not None:
+                    raise ValueError(f"export_images: out.{field} is given but not asked for")
+                continue
+            if t is None:
+                setattr(res, field, torch.empty(spec[0], dtype=spec[1], device=dev))
+            elif not (t.is_cuda and t.dtype == spec[1] and tuple(t.shape) == spec[0] and t.is_contiguous()):
+                raise ValueError(f"export_images: out.{field} must be a contiguous CUDA {spec[1]} tensor of shape {spec[0]}")
+        x = _lib.GGImageExport()
+        x.n, x.first_slot, x.slots, x.layer_mask = cnt, first, ptr, mask
+        x.d_images = res.images.data_ptr() if K else None
+        x.image_stride = self.rows * self.cols
+        x.d_bounds = res.bounds.data_ptr() if K else None
+        x.d_terrain = res.terrain.data_ptr() if terrain else None
+        x.terrain_stride = 3 * self.rows * self.cols
+        x.terrain_layout = _lib.GG_TERRAIN_CHW if chw else _lib.GG_TERRAIN_HWC
+        stream = None  # the context's own stream
+        if on_torch_stream:
+            h = torch.cuda.current_stream(self.device).cuda_stream
+            stream = C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
+        _check(self._L, self._ctx, self._L.gg_export_images(self._ctx, C.byref(x), stream), "gg_export_images")
+        return res
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:
         """A checkpoint of the named maps: {"planes": export_layers() of all eleven layers [n, 11, cols, rows] (on the device, enqueued on

@@ -36,6 +36,7 @@ namespace {
 constexpr int PARAM_RING = 4;
 constexpr int EXPORT_VARIANT_DEFAULT = 0; // gg_export_layers: 0 = k_export_tiled, 1 = k_export_gather; the measured winner
 constexpr int IMPORT_VARIANT_DEFAULT = 0; // gg_import_layers: 0 = k_import_tiled, 1 = a batched materialise + k_import_scatter; the measured winner
+constexpr int IMAGES_VARIANT_DEFAULT = 0; // gg_export_images: 0 = the tiled kernels of k11_images.hip, 1 = their cell-by-cell forms; the measured winner
 constexpr int K_SCORE = GG_NUM_KERNELS; // k_score's entry of the profiler's sums, behind the seven kernels of the path
 
 // one timed kernel of a profiled launch sequence (GG_FLAG_PROFILE).  Consecutive kernels of a sequence SHARE the event between them -- the
@@ -239,6 +240,11 @@ struct gg_context {
     ParamRing export_ring;
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
     int import_variant = IMPORT_VARIANT_DEFAULT; // tuning "import_variant": 0 = k_import_tiled, 1 = k_import_scatter (the A/B of tools/bench_import.py)
+    // gg_export_images runs on the same table, rings and events; its bounds launch leaves the partial (min, max) pairs of a call in the ring
+    // entry's part of d_image_partials: [PARAM_RING][n_slots][GG_NUM_LAYERS][image_parts_cap][2] floats
+    float *d_image_partials = nullptr;
+    int image_parts_cap = 0;
+    int images_variant = IMAGES_VARIANT_DEFAULT; // tuning "images_variant": 0 = the tiled kernels, 1 = cell by cell (the A/B of tools/bench_images.py)
     float *d_image = nullptr;          // 3 * C floats (wire-format images)
     float *d_planes = nullptr;         // GG_NUM_LAYERS * Cpad floats: dense planes of gg_get_layers (allocated on first use)
     float *h_planes = nullptr;         // ... and their pinned landing zone on the host (one download for all requested layers)
@@ -2117,7 +2123,10 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     const size_t o_maps = align_up(o_cell + cell.size() * sizeof(uint16_t), 256);
     const size_t o_lazy = align_up(o_maps + ring * sizeof(ExportMap), 256);
     const size_t h_lazy = align_up(ring * sizeof(ExportMap), 256);
-    if (const int rc = alloc_call_scratch(ctx, who, st, o_lazy + ring * sizeof(CloudParams), h_lazy + ring * sizeof(CloudParams),
+    // (gg_export_images: the partial bounds of either variant's bounds launch, per ring entry)
+    const int parts_cap = std::max(image_parts(a.g, 0), image_parts(a.g, 1));
+    const size_t o_partials = align_up(o_lazy + ring * sizeof(CloudParams), 256);
+    if (const int rc = alloc_call_scratch(ctx, who, st, o_partials + ring * GG_NUM_LAYERS * (size_t)parts_cap * 2 * sizeof(float), h_lazy + ring * sizeof(CloudParams),
                                           {{o_off, off.data(), off.size() * sizeof(uint32_t)}, {o_elem, elem.data(), elem.size() * sizeof(uint32_t)}, {o_cell, cell.data(), cell.size() * sizeof(uint16_t)}},
                                           &ctx->export_mem, &ctx->export_ring))
         return rc;
@@ -2127,13 +2136,68 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     ctx->d_export_cell = (const uint16_t *)(block + o_cell);
     ctx->d_export_maps = (ExportMap *)(block + o_maps);
     ctx->d_export_lazy = (CloudParams *)(block + o_lazy);
+    ctx->d_image_partials = (float *)(block + o_partials);
+    ctx->image_parts_cap = parts_cap;
     ctx->h_export_maps = (ExportMap *)h;
     ctx->h_export_lazy = (CloudParams *)(h + h_lazy);
     return GG_OK;
 }
 
-// gg_export_layers and gg_import_layers, its inverse, are one call in two directions on the same table, rings and events; `d_planes` is the
-// destination of the one and the source of the other.  Host-side flags are committed at the end, when every launch has been enqueued.
+// The frame of the many-map calls that read or write layers (gg_export_layers, gg_import_layers, gg_export_images), on the shared table,
+// rings and events.  map_call_begin: the slot list is checked, the ring entry `g` taken, the listed maps' entries filled and uploaded, `st`
+// ordered behind the context, and -- lazy_wanted -- the three lazily kept layers computed for the listed maps that still miss them, in one
+// launch.  The caller enqueues its kernels on f.st with f.dm, then map_call_end: the ring entry and the call are recorded.  Host-side flags
+// are committed by the caller behind that, when every launch has been enqueued.
+struct MapCall {
+    hipStream_t st = nullptr;
+    int g = 0;
+    ExportMap *hm = nullptr, *dm = nullptr;
+    CloudParams *hl = nullptr;
+    int n_lazy = 0; // hl[0 .. n_lazy): the maps whose lazily kept layers the call computed
+};
+static int map_call_begin(gg_context *ctx, const char *who, int n, const int32_t *slots, int first_slot, void *stream, bool lazy_wanted, MapCall *f)
+{
+    if (const int rc = check_slot_list(ctx, who, n, slots, first_slot)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    f->st = pick_stream(ctx, stream);
+    if (const int rc = ensure_export_scratch(ctx, who, f->st)) return rc;
+    // ring entry (the pinned tables are rewritten only when the copies that read them last have run)
+    HIPCHK(ctx, ctx->export_ring.acquire(&f->g));
+    f->hm = ctx->h_export_maps + (size_t)f->g * ctx->n_slots;
+    f->dm = ctx->d_export_maps + (size_t)f->g * ctx->n_slots;
+    f->hl = ctx->h_export_lazy + (size_t)f->g * ctx->n_slots;
+    CloudParams *dl = ctx->d_export_lazy + (size_t)f->g * ctx->n_slots;
+    f->n_lazy = 0;
+    for (int i = 0; i < n; ++i) {
+        const int slot = slot_of(slots, first_slot, i);
+        f->hm[i].slot = slot;
+        // (export, images: a fresh map stays fresh: its planes are the reset's constants.  import: with ground / groundpatch named, the kernel
+        // writes the whole pair: no fill)
+        f->hm[i].fresh = ctx->fresh[slot] ? 1 : 0;
+        f->hm[i].fresh_z = ctx->fresh_z[slot];
+        f->hm[i].reserved = 0;
+        if (lazy_wanted && ctx->lazy_pending[slot]) f->hl[f->n_lazy++] = ctx->lazy_params[slot];
+    }
+    // `st` follows every earlier map mutation, batch, export and import of the context, and both halves of a divided batch: the call reads
+    // (writes) maps of either
+    if (const int rc = call_follows_context(ctx, f->st, false)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(f->dm, f->hm, sizeof(ExportMap) * n, hipMemcpyHostToDevice, f->st));
+    if (f->n_lazy) { // one launch
+        HIPCHK(ctx, hipMemcpyAsync(dl, f->hl, sizeof(CloudParams) * f->n_lazy, hipMemcpyHostToDevice, f->st));
+        launch_reduce_lazy_batch(ctx->arena, dl, f->n_lazy, f->st);
+    }
+    return GG_OK;
+}
+static int map_call_end(gg_context *ctx, const MapCall &f)
+{
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, ctx->export_ring.recorded(f.g, f.st));
+    // whatever reads or writes one of these maps next on another stream waits for the call (and for the lazily kept layers it computed)
+    return call_recorded(ctx, f.st, true);
+}
+
+// gg_export_layers and gg_import_layers, its inverse, are one call in two directions; `d_planes` is the destination of the one and the
+// source of the other.
 static int transfer_layers(gg_context *ctx, bool import, int n, const int32_t *slots, int first_slot, unsigned layer_mask, int order, const float *d_planes,
                            size_t plane_stride, void *stream)
 {
@@ -2145,16 +2209,6 @@ static int transfer_layers(gg_context *ctx, bool import, int n, const int32_t *s
     if (order != GG_PLANES_COLMAJOR && order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
     if (!d_planes) return fail(ctx, GG_ERR_INVALID, who, import ? "d_src is null" : "d_dst is null");
     if (plane_stride < (size_t)ctx->arena.g.C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
-    if (const int rc = check_slot_list(ctx, who, n, slots, first_slot)) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const hipStream_t st = pick_stream(ctx, stream);
-    if (const int rc = ensure_export_scratch(ctx, who, st)) return rc;
-    const Arena &a = ctx->arena;
-    // ring entry (the pinned tables are rewritten only when the copies that read them last have run)
-    int g;
-    HIPCHK(ctx, ctx->export_ring.acquire(&g));
-    ExportMap *hm = ctx->h_export_maps + (size_t)g * ctx->n_slots, *dm = ctx->d_export_maps + (size_t)g * ctx->n_slots;
-    CloudParams *hl = ctx->h_export_lazy + (size_t)g * ctx->n_slots, *dl = ctx->d_export_lazy + (size_t)g * ctx->n_slots;
     const unsigned gp_mask = layer_mask & ((1u << GG_LAYER_GROUND) | (1u << GG_LAYER_GROUNDPATCH));
     const unsigned percall_mask = layer_mask & ~gp_mask;
     const unsigned lazy_mask = LAZY_LAYERS;
@@ -2164,34 +2218,14 @@ static int transfer_layers(gg_context *ctx, bool import, int n, const int32_t *s
     // the half columns their cloud wrote: a listed map that still misses them gets them first -- unless all three are imported anyway
     const bool lazy_first = percall_mask != 0u && (layer_mask & lazy_mask) != lazy_mask;
     const bool lazy_wanted = import ? lazy_first : (layer_mask & lazy_mask) != 0u;
-    int n_lazy = 0;
-    for (int i = 0; i < n; ++i) {
-        const int slot = slot_of(slots, first_slot, i);
-        hm[i].slot = slot;
-        // (export: a fresh map stays fresh: its planes are the reset's constants.  import: with ground / groundpatch named, the kernel writes
-        // the whole pair: no fill)
-        hm[i].fresh = ctx->fresh[slot] ? 1 : 0;
-        hm[i].fresh_z = ctx->fresh_z[slot];
-        hm[i].reserved = 0;
-        if (lazy_wanted && ctx->lazy_pending[slot]) hl[n_lazy++] = ctx->lazy_params[slot];
-    }
-    // `st` follows every earlier map mutation, batch, export and import of the context, and both halves of a divided batch: the call reads
-    // (writes) maps of either
-    if (const int rc = call_follows_context(ctx, st, false)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(dm, hm, sizeof(ExportMap) * n, hipMemcpyHostToDevice, st));
-    if (n_lazy) { // one launch
-        HIPCHK(ctx, hipMemcpyAsync(dl, hl, sizeof(CloudParams) * n_lazy, hipMemcpyHostToDevice, st));
-        launch_reduce_lazy_batch(a, dl, n_lazy, st);
-    }
-    const PlaneArgs x = fill_plane_args(ctx, dm, layer_mask, order, const_cast<float *>(d_planes), plane_stride); // (the import only reads them)
-    if (import) launch_import(a, x, n, ctx->import_variant, st);
-    else launch_export(a, x, n, ctx->export_variant, st);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, ctx->export_ring.recorded(g, st));
-    // whatever reads or writes one of these maps next on another stream waits for the call (and for the lazily kept layers it computed)
-    if (const int rc = call_recorded(ctx, st, true)) return rc;
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, n, slots, first_slot, stream, lazy_wanted, &f)) return rc;
+    const PlaneArgs x = fill_plane_args(ctx, f.dm, layer_mask, order, const_cast<float *>(d_planes), plane_stride); // (the import only reads them)
+    if (import) launch_import(ctx->arena, x, n, ctx->import_variant, f.st);
+    else launch_export(ctx->arena, x, n, ctx->export_variant, f.st);
+    if (const int rc = map_call_end(ctx, f)) return rc;
     if (!import) {
-        for (int i = 0; i < n_lazy; ++i) ctx->lazy_pending[hl[i].slot] = 0;
+        for (int i = 0; i < f.n_lazy; ++i) ctx->lazy_pending[f.hl[i].slot] = 0;
         return GG_OK;
     }
     // import: every launch is enqueued: the listed maps' flags follow (no other map's change)
@@ -2214,6 +2248,48 @@ int gg_import_layers(gg_context *ctx, int n, const int32_t *slots, int first_slo
                      size_t plane_stride, void *stream)
 {
     return transfer_layers(ctx, true, n, slots, first_slot, layer_mask, order, d_src, plane_stride, stream);
+}
+
+// The u8 layer images and the terrain images of many maps (k11_images.hip), in the frame of the export: nothing is synchronised, no map is
+// filled, and the lazily kept layers are computed only where the mask names one of them (the terrain image reads none).
+int gg_export_images(gg_context *ctx, const gg_image_export *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_export_images";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_image_export");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    if ((x->layer_mask >> GG_NUM_LAYERS) != 0u) return fail(ctx, GG_ERR_INVALID, who, "layer_mask");
+    if (x->layer_mask && !x->d_images) return fail(ctx, GG_ERR_INVALID, who, "d_images is null");
+    if (!x->layer_mask && !x->d_terrain) return fail(ctx, GG_ERR_INVALID, who, "neither a layer nor the terrain image is asked for");
+    if (x->layer_mask && x->image_stride < C) return fail(ctx, GG_ERR_INVALID, who, "image_stride is smaller than rows * cols");
+    if (x->d_terrain && x->terrain_stride < 3 * C) return fail(ctx, GG_ERR_INVALID, who, "terrain_stride is smaller than 3 * rows * cols");
+    if (x->d_terrain && x->terrain_layout != GG_TERRAIN_HWC && x->terrain_layout != GG_TERRAIN_CHW) return fail(ctx, GG_ERR_INVALID, who, "terrain_layout");
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, x->n, x->slots, x->first_slot, stream, (x->layer_mask & LAZY_LAYERS) != 0u, &f)) return rc;
+    const PlaneArgs table = fill_plane_args(ctx, f.dm, x->layer_mask, GG_PLANES_ROWMAJOR, nullptr, 0);
+    ImageArgs im;
+    im.maps = f.dm;
+    im.block_off = table.block_off;
+    im.elem = table.elem;
+    im.cell = table.cell;
+    im.blocks_r = table.blocks_r;
+    im.blocks_c = table.blocks_c;
+    im.mask = x->layer_mask;
+    im.n_planes = table.n_planes;
+    im.images = x->d_images;
+    im.image_stride = x->image_stride;
+    im.partials = ctx->d_image_partials + (size_t)f.g * ctx->n_slots * GG_NUM_LAYERS * (size_t)ctx->image_parts_cap * 2;
+    im.n_parts = image_parts(ctx->arena.g, ctx->images_variant);
+    im.bounds = x->d_bounds;
+    im.terrain = x->d_terrain;
+    im.terrain_stride = x->terrain_stride;
+    im.terrain_layout = x->terrain_layout;
+    launch_images(ctx->arena, im, x->n, ctx->images_variant, f.st);
+    if (const int rc = map_call_end(ctx, f)) return rc;
+    for (int i = 0; i < f.n_lazy; ++i) ctx->lazy_pending[f.hl[i].slot] = 0;
+    return GG_OK;
 }
 
 int gg_get_map_position(const gg_context *ctx, int slot, double *pos_x, double *pos_y)
@@ -3075,6 +3151,7 @@ extern "C" int gg_debug_set_tuning(gg_context *ctx, const char *key, int value)
     }
     if (!strcmp(key, "export_variant_default")) return EXPORT_VARIANT_DEFAULT; // (read-only: the kernel gg_export_layers ships with)
     if (!strcmp(key, "import_variant_default")) return IMPORT_VARIANT_DEFAULT; // (read-only: the kernel gg_import_layers ships with)
+    if (!strcmp(key, "images_variant_default")) return IMAGES_VARIANT_DEFAULT; // (read-only: the kernels gg_export_images ships with)
     if (!strcmp(key, "graphs")) { // 0 = every call launches eagerly, 1 = one cloud per call replays a captured graph (the default)
         ctx->graphs_enabled = value != 0;
         drop_graphs(ctx);
@@ -3098,6 +3175,7 @@ extern "C" int gg_debug_set_tuning(gg_context *ctx, const char *key, int value)
     else if (!strcmp(key, "move_chunk")) ctx->move_chunk_tune = value;
     else if (!strcmp(key, "export_variant")) ctx->export_variant = value ? 1 : 0; // (A/B: 1 = gg_export_layers gathers in destination order, k_export_gather)
     else if (!strcmp(key, "import_variant")) ctx->import_variant = value ? 1 : 0; // (A/B: 1 = gg_import_layers scatters in source order, k_import_scatter)
+    else if (!strcmp(key, "images_variant")) ctx->images_variant = value ? 1 : 0; // (A/B: 1 = gg_export_images cell by cell, k11_images.hip)
     else if (!strcmp(key, "halves_no_fork")) ctx->probe_no_fork = value != 0; // (measurement only: the side stream does not wait for the caller's)
     else if (!strcmp(key, "scan_fault")) ctx->arena.tune_scan_fault = value;
     else if (!strcmp(key, "sweep_fault")) ctx->arena.tune_sweep_fault = value;

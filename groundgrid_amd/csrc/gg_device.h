@@ -76,6 +76,18 @@ GG_DEV float tree25_eigen34(const float *e)
     return res;
 }
 
+// GridMapCvConverter::toImage<unsigned char, 1> of one cell: imageValue = (uchar)(((clamp(v, lo, hi) - lo) / (hi - lo)) * 255.f), a
+// non-finite cell 0.  The one statement of it: k_layer_to_u8 (k6_wire.hip) and the image kernels of k11_images.hip call this.
+GG_DEV uint8_t layer_value_to_u8(float v, float lo, float hi)
+{
+    uint8_t o = 0;
+    if (isfinite(v)) {
+        const float c = v < lo ? lo : (v > hi ? hi : v);
+        o = (uint8_t)(((c - lo) / (hi - lo)) * 255.0f);
+    }
+    return o;
+}
+
 // x86-64 cvttsd2si: truncation toward zero, INT_MIN for NaN / out of range
 GG_DEV int trunc_to_int(double v)
 {

@@ -303,6 +303,33 @@ struct PlaneArgs {
     size_t plane_stride;
 };
 
+// gg_export_images (k11_images.hip): the u8 layer images and the terrain images of the listed maps.  The same map entries and table as
+// PlaneArgs.  The bounds of a (map, layer) reach the image launch as `n_parts` partial (min, max) pairs the bounds launch wrote:
+// partials[((map * n_planes + k) * n_parts + part) * 2]; a part without a finite cell holds (+inf, -inf).
+constexpr int IMAGE_GATHER_PARTS = 64; // work-groups per map of the cell-by-cell form (variant 1) = its partial pairs per plane
+struct ImageArgs {
+    const ExportMap *maps;
+    const uint32_t *block_off, *elem;
+    const uint16_t *cell;
+    int blocks_r, blocks_c;
+    unsigned mask;        // the u8 images: bit per gg_layer (0: none)
+    int n_planes;         // its popcount
+    uint8_t *images;      // map i's image k at images + (i * n_planes + k) * image_stride, rows x cols row-major bytes
+    size_t image_stride;  // bytes
+    float *partials;      // call scratch (above)
+    int n_parts;
+    float *bounds;        // [map][n_planes][2] lower, upper; null: nobody asked
+    float *terrain;       // map i at terrain + i * terrain_stride; null: no terrain image
+    size_t terrain_stride; // floats
+    int terrain_layout;   // GG_TERRAIN_*
+};
+inline int image_parts(const Geometry &g, int variant) // partial pairs per plane of a call
+{
+    const int blocks = ((g.rows + EXPORT_TILE - 1) / EXPORT_TILE) * ((g.cols + EXPORT_TILE - 1) / EXPORT_TILE);
+    const int gather = (g.C + 255) / 256 < IMAGE_GATHER_PARTS ? (g.C + 255) / 256 : IMAGE_GATHER_PARTS;
+    return variant == 1 ? gather : blocks;
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -342,6 +369,7 @@ void launch_reduce_lazy(const Arena &a, const CloudParams &cp, hipStream_t s); /
 void launch_reduce_lazy_batch(const Arena &a, const CloudParams *d_params, int n_clouds, hipStream_t s); // (... of n slots in one launch: gg_export_layers)
 void launch_export(const Arena &a, const PlaneArgs &x, int n_maps, int variant, hipStream_t s); // k9_export.hip; variant 0 = k_export_tiled, 1 = launch_planes_gather
 void launch_import(const Arena &a, const PlaneArgs &x, int n_maps, int variant, hipStream_t s); // k10_import.hip; variant 0 = k_import_tiled, 1 = launch_planes_scatter
+void launch_images(const Arena &a, const ImageArgs &x, int n_maps, int variant, hipStream_t s);  // k11_images.hip; variant 0 = the tiled kernels, 1 = cell by cell
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

@@ -53,13 +53,7 @@ __global__ __launch_bounds__(256) void k_layer_to_u8(const float *__restrict__ l
     const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (i >= rows || j >= cols) return;
     const float lo = bounds[0], hi = bounds[1];
-    const float v = layer[(size_t)i + (size_t)j * rows];
-    uint8_t o = 0;
-    if (isfinite(v)) {
-        const float c = v < lo ? lo : (v > hi ? hi : v);
-        o = (uint8_t)(((c - lo) / (hi - lo)) * 255.0f);
-    }
-    img[(size_t)i * cols + j] = o;
+    img[(size_t)i * cols + j] = layer_value_to_u8(layer[(size_t)i + (size_t)j * rows], lo, hi);
 }
 
 // Nodelet.cpp:258-268; the reference reads block<3,3>(i-1, j-1) also on the border (UB): border cells get 0 for the flag.

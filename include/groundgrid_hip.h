@@ -536,6 +536,46 @@ int gg_get_layer_image_u8(gg_context *ctx, int slot, int layer, uint8_t *dst, fl
 /* the 32FC3 terrain image (Nodelet.cpp:247-268): rows x cols x 3 floats (ground, 3x3 pointsRaw sum >= 27, pointsRaw) */
 int gg_get_terrain_image(gg_context *ctx, int slot, float *dst);
 
+/* Both images of MANY maps in DEVICE memory, in one call and without a synchronisation: what the two getters above return per map and
+ * layer, where a consumer on the GPU (a model that takes the terrain tensor, a server that forwards BEV images) reads it.
+ * Map i = slots ? slots[i] : first_slot + i (distinct, inside the context), as for gg_export_layers.
+ *   u8 images   layer_mask has one bit per gg_layer (0: none), K = its popcount.  The image of the k-th named layer (in gg_layer order)
+ *               of map i lies at d_images + (i * K + k) * image_stride: rows x cols row-major bytes, byte for byte what
+ *               gg_get_layer_image_u8 writes.  image_stride is in bytes (>= rows * cols); the bytes between rows * cols and the stride
+ *               are never written; neither d_images nor image_stride needs any alignment.  d_bounds (nullable): [n][K][2] floats, the
+ *               lower and upper the getter returns -- (+inf, -inf) for a plane without a finite cell.
+ *   terrain     d_terrain (nullable): the 32FC3 image of map i at d_terrain + i * terrain_stride, terrain_stride in floats
+ *               (>= 3 * rows * cols; the floats behind the image are never written).  terrain_layout: GG_TERRAIN_HWC = rows x cols x 3
+ *               interleaved -- what gg_get_terrain_image returns, bit for bit, a cv::Mat of type 32FC3 -- or GG_TERRAIN_CHW = three
+ *               row-major rows x cols planes (ground, flag, pointsRaw), what a model takes.
+ * `stream` follows the gg_filter_batch convention; the call enqueues and returns, `slots` may be freed on return, and work enqueued on
+ * `stream` afterwards sees the images.  The library orders the call exactly like gg_export_layers (both halves under
+ * GG_FLAG_CONCURRENT_HALVES included), and later writers of these maps on other streams wait for it.
+ * A FRESH map (gg_reset_maps, nothing since) is neither read nor filled: its ground plane is the constant odom_z and its groundpatch
+ * plane 1e-7f -- their u8 images are what the getter gives for a constant plane --, its terrain channel 0 is odom_z, and it and every other
+ * fresh map stay fresh.  When layer_mask names maxGroundHeight, groundCandidates or planeDist, the listed maps whose last cloud left
+ * them out get them computed first, in one launch over exactly those maps on `stream`; the terrain image needs none of the three.
+ * Argument errors write nothing and change nothing: GG_ERR_CAPACITY (a slot outside the context), GG_ERR_INVALID (null ctx, null x,
+ * n < 0, repeated slots; and with n > 0: a mask bit at or above GG_NUM_LAYERS, layer_mask != 0 with null d_images, layer_mask == 0 with
+ * null d_terrain -- nothing asked for --, image_stride < rows * cols, terrain_stride < 3 * rows * cols, an unknown terrain_layout).
+ * n == 0 is GG_OK.  The call shares its table, parameter rings and events with gg_export_layers / gg_import_layers: the first of the
+ * three in a context allocates and blocks, later calls only enqueue.  Capture into a caller's graph is not supported. */
+enum { GG_TERRAIN_HWC = 0, GG_TERRAIN_CHW = 1 };
+typedef struct gg_image_export {
+    int n;                 /* maps */
+    int first_slot;        /* map i = first_slot + i when slots == NULL */
+    const int32_t *slots;  /* host [n], nullable */
+    unsigned layer_mask;   /* the u8 images: bit per gg_layer, may be 0 */
+    uint8_t *d_images;     /* [n][K] images, image_stride bytes apart; needed when layer_mask != 0 */
+    size_t image_stride;   /* bytes, >= rows * cols */
+    float *d_bounds;       /* [n][K][2] lower, upper; nullable */
+    float *d_terrain;      /* [n] terrain images, terrain_stride floats apart; nullable */
+    size_t terrain_stride; /* floats, >= 3 * rows * cols */
+    int terrain_layout;    /* GG_TERRAIN_HWC / GG_TERRAIN_CHW */
+} gg_image_export;
+int gg_export_images(gg_context *ctx, const gg_image_export *x, void *stream);
+#define GG_HAS_EXPORT_IMAGES 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
