@@ -47,6 +47,7 @@ SYMBOLS = [
     "gg_export_layers",
     "gg_import_layers",
     "gg_export_images",
+    "gg_split_clouds",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -130,6 +131,32 @@ class GGImageExport(C.Structure):
     ]
 
 
+class GGSplitSet(C.Structure):
+    """gg_split_set: one selected set of every cloud (gg_split_clouds); each pointer nullable"""
+
+    _fields_ = [("d_points", C.c_void_p), ("d_height", C.c_void_p), ("d_source", C.c_void_p)]
+
+
+class GGCloudSplit(C.Structure):
+    """gg_cloud_split: the ground and the non-ground points of many labelled clouds as dense clouds, in device memory (gg_split_clouds)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("first_slot", C.c_int),
+        ("slots", C.POINTER(C.c_int32)),
+        ("point_format", C.c_int),
+        ("d_points", C.c_void_p),
+        ("cloud_stride", C.c_size_t),
+        ("n_points", C.POINTER(C.c_int32)),
+        ("transforms", C.POINTER(C.c_double)),
+        ("d_labels", C.c_void_p),
+        ("d_label_masks", C.c_void_p),
+        ("ground", GGSplitSet),
+        ("nonground", GGSplitSet),
+        ("d_counts", C.c_void_p),
+    ]
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -201,6 +228,7 @@ def load():
     L.gg_export_layers.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
     L.gg_import_layers.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
     L.gg_export_images.argtypes = [vp, P(GGImageExport), vp]
+    L.gg_split_clouds.argtypes = [vp, P(GGCloudSplit), vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

@@ -234,6 +234,28 @@ class ImageExport:
     terrain: "object" = None  # torch.float32 [n, rows, cols, 3], or [n, 3, rows, cols] with chw
 
 
+@dataclass
+class SplitOutputs:
+    """what GroundSegmentation.split_clouds returns (CUDA torch tensors; None where nothing was asked for).  Row i of every tensor belongs to
+    cloud i; only its first counts[i, 0] (ground) / counts[i, 1] (nonground) elements are written."""
+
+    counts: "object" = None            # torch.int32 [n, 2]: points in ground, in nonground
+    ground_points: "object" = None     # torch.uint8 [n, stride, 16]: packed gg_point16 (x, y, z in the map frame, ring, pad = 0)
+    ground_height: "object" = None     # torch.float32 [n, stride]: z - ground(cell of the point)
+    ground_source: "object" = None     # torch.int32 [n, stride]: index of the point in its input cloud
+    nonground_points: "object" = None
+    nonground_height: "object" = None
+    nonground_source: "object" = None
+
+    def clouds(self, which: str = "nonground"):
+        """The rows of set `which` ("ground" / "nonground") trimmed to their counts: a list of (points, height, source) views, one per
+        cloud (None for a tensor that was not asked for).  The ONE place that synchronises: it reads `counts` on the host."""
+        col = {"ground": 0, "nonground": 1}[which]
+        sizes = self.counts[:, col].cpu().tolist()
+        fields = [getattr(self, f"{which}_{k}") for k in ("points", "height", "source")]
+        return [tuple(None if t is None else t[i, :m] for t in fields) for i, m in enumerate(sizes)]
+
+
 class GroundSegmentation:
     """Mirror of groundgrid::GroundSegmentation (include/groundgrid/GroundSegmentation.h:48-71)."""
 
@@ -453,6 +475,70 @@ class GroundSegmentation:
             h = torch.cuda.current_stream(self.device).cuda_stream
             stream = C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
         _check(self._L, self._ctx, self._L.gg_export_images(self._ctx, C.byref(x), stream), "gg_export_images")
+        return res
+
+    def split_clouds(self, points, n_points: Sequence[int], *, labels=None, masks=None, transforms=None, slots=None, first_slot: int = 0,
+                     ground: bool = True, nonground: bool = True, heights: bool = True, sources: bool = True, out: Optional[SplitOutputs] = None,
+                     on_torch_stream: bool = True) -> SplitOutputs:
+        """The ground (label 49) and the non-ground (label 99) points of many labelled clouds as dense clouds on the device
+        (gg_split_clouds): per set the packed 16-byte records uint8 [B, stride, 16] in the map frame, float32 [B, stride] heights above the
+        map's `ground` layer as it stands, int32 [B, stride] indices into the input cloud, and counts int32 [B, 2] -- in the cloud's own
+        order, what points[b][labels[b] == 99] gives, without a synchronisation: the sizes stay on the device (SplitOutputs.clouds() reads
+        them).  points / n_points / transforms / slots / first_slot as for filter_batch; exactly one of labels (uint8 [B, stride], BatchOutputs.labels)
+        and masks (uint8 [B, stride // 4], BatchOutputs.label_masks).  ground / nonground: which sets are written; heights / sources:
+        whether their height and source tensors are.  `out`: a SplitOutputs of an earlier call with the same arguments, whose tensors are
+        reused.  Enqueued on the current torch stream (where filter_batch runs and torch ops enqueued afterwards see the outputs) or, with
+        on_torch_stream=False, on the context's own stream.  No map changes; fresh maps stay fresh."""
+        import torch
+
+        self._torch_used = True
+        assert points.is_cuda and points.dtype == torch.uint8 and points.dim() == 3 and points.is_contiguous()
+        B, stride, rec = points.shape
+        assert rec in (16, 32)
+        if (labels is None) == (masks is None):
+            raise ValueError("split_clouds: exactly one of labels and masks")
+        given = labels if labels is not None else masks
+        want_shape = (B, stride) if labels is not None else (B, (stride + 3) // 4)
+        if not (torch.is_tensor(given) and given.is_cuda and given.dtype == torch.uint8 and given.is_contiguous() and tuple(given.shape) == want_shape):
+            raise ValueError(f"split_clouds: {'labels' if labels is not None else 'masks'} must be a contiguous CUDA uint8 tensor of shape {want_shape}")
+        res = out if out is not None else SplitOutputs()
+        want = {"counts": ((B, 2), torch.int32)}
+        for name, on in (("ground", ground), ("nonground", nonground)):
+            want[f"{name}_points"] = ((B, stride, 16), torch.uint8) if on else None
+            want[f"{name}_height"] = ((B, stride), torch.float32) if on and heights else None
+            want[f"{name}_source"] = ((B, stride), torch.int32) if on and sources else None
+        for field, spec in want.items():
+            t = getattr(res, field)
+            if spec is None:
+                if t is not None:
+                    raise ValueError(f"split_clouds: out.{field} is given but not asked for")
+                continue
+            if t is None:
+                setattr(res, field, torch.empty(spec[0], dtype=spec[1], device=points.device))
+            elif not (t.is_cuda and t.dtype == spec[1] and tuple(t.shape) == spec[0] and t.is_contiguous()):
+                raise ValueError(f"split_clouds: out.{field} must be a contiguous CUDA {spec[1]} tensor of shape {spec[0]}")
+        npts = (C.c_int32 * max(B, 1))(*[int(v) for v in n_points])
+        x = _lib.GGCloudSplit()
+        x.n, x.first_slot, x.point_format = B, int(first_slot), _lib.GG_POINT16 if rec == 16 else _lib.GG_POINT32
+        x.d_points, x.cloud_stride, x.n_points = points.data_ptr(), stride, npts
+        if slots is not None:
+            sl = (C.c_int32 * max(B, 1))(*[int(v) for v in slots])
+            x.slots = sl
+        if transforms is not None:  # [B, 3, 4] map <- cloud frame, as for filter_batch
+            tfs = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(B, 12))
+            x.transforms = tfs.ctypes.data_as(C.POINTER(C.c_double))
+        x.d_labels = labels.data_ptr() if labels is not None else None
+        x.d_label_masks = masks.data_ptr() if masks is not None else None
+        for name, dst in (("ground", x.ground), ("nonground", x.nonground)):
+            for k in ("points", "height", "source"):
+                t = getattr(res, f"{name}_{k}")
+                setattr(dst, f"d_{k}", t.data_ptr() if t is not None else None)
+        x.d_counts = res.counts.data_ptr()
+        stream = None  # the context's own stream
+        if on_torch_stream:
+            h = torch.cuda.current_stream(points.device).cuda_stream
+            stream = C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
+        _check(self._L, self._ctx, self._L.gg_split_clouds(self._ctx, C.byref(x), stream), "gg_split_clouds")
         return res
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:

@@ -245,6 +245,12 @@ struct gg_context {
     float *d_image_partials = nullptr;
     int image_parts_cap = 0;
     int images_variant = IMAGES_VARIANT_DEFAULT; // tuning "images_variant": 0 = the tiled kernels, 1 = cell by cell (the A/B of tools/bench_images.py)
+    // gg_split_clouds (allocated at its first call): the per-cloud records [PARAM_RING][n_slots] (device and pinned) and the chunk counters
+    // of its two launches, [PARAM_RING][n_slots][NCH] pairs.  The call runs in the export's frame: an entry of export_ring is an entry here,
+    // so it has no ring of its own
+    CallScratch split_mem;
+    SplitCloud *d_split_clouds = nullptr, *h_split_clouds = nullptr;
+    uint2 *d_split_counts = nullptr;
     float *d_image = nullptr;          // 3 * C floats (wire-format images)
     float *d_planes = nullptr;         // GG_NUM_LAYERS * Cpad floats: dense planes of gg_get_layers (allocated on first use)
     float *h_planes = nullptr;         // ... and their pinned landing zone on the host (one download for all requested layers)
@@ -1001,18 +1007,23 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
     return GG_OK;
 }
 
-void free_call_scratch(CallScratch &m, ParamRing &r)
+void free_call_scratch(CallScratch &m)
 {
     if (m.dev) hipFree(m.dev);
     if (m.pinned) hipHostFree(m.pinned);
     m = CallScratch{};
+}
+void free_call_scratch(CallScratch &m, ParamRing &r)
+{
+    free_call_scratch(m);
     r.destroy();
 }
 
 // The first-call allocation of a many-map call (`who`): a device block, a pinned host block and the events of its parameter ring, and the
 // tables the call's kernels read uploaded into the device block (synchronously: they are there before any stream can launch on them).  Not
 // while `st` is being captured into a graph: an allocation cannot be captured.  `mem` and `ring` are written when everything is in place:
-// nothing of the context changes when this fails (GG_ERR_NOMEM for the two blocks, GG_ERR_HIP for the events and uploads).
+// nothing of the context changes when this fails (GG_ERR_NOMEM for the two blocks, GG_ERR_HIP for the events and uploads).  `ring` is null
+// for a call that runs in another call's frame and takes its ring entries from there: then no events are created.
 struct TableUpload {
     size_t offset;
     const void *src;
@@ -1036,8 +1047,8 @@ int alloc_call_scratch(gg_context *ctx, const char *who, hipStream_t st, size_t 
         e = hipHostMalloc(&m.pinned, pinned_bytes, hipHostMallocDefault);
         if (e != hipSuccess) m.pinned = nullptr;
     }
-    if (e == hipSuccess) {
-        code = GG_ERR_HIP;
+    if (e == hipSuccess) code = GG_ERR_HIP;
+    if (e == hipSuccess && ring) {
         what = "events";
         e = r.create();
     }
@@ -1052,7 +1063,7 @@ int alloc_call_scratch(gg_context *ctx, const char *who, hipStream_t st, size_t 
         return fail(ctx, code, (std::string(who) + ": " + what).c_str(), e);
     }
     *mem = m;
-    *ring = r;
+    if (ring) *ring = r;
     return GG_OK;
 }
 
@@ -1563,6 +1574,7 @@ void gg_destroy(gg_context *ctx)
     if (ctx->d_planes) hipFree(ctx->d_planes);
     free_call_scratch(ctx->move_mem, ctx->move_ring);
     free_call_scratch(ctx->export_mem, ctx->export_ring);
+    free_call_scratch(ctx->split_mem);
     if (ctx->d_pc2) hipFree(ctx->d_pc2);
     if (ctx->h_pc2) hipHostFree(ctx->h_pc2);
     if (ctx->h_planes) hipHostFree(ctx->h_planes);
@@ -2290,6 +2302,76 @@ int gg_export_images(gg_context *ctx, const gg_image_export *x, void *stream)
     if (const int rc = map_call_end(ctx, f)) return rc;
     for (int i = 0; i < f.n_lazy; ++i) ctx->lazy_pending[f.hl[i].slot] = 0;
     return GG_OK;
+}
+
+// gg_split_clouds' device block and pinned records, at its first call (alloc_call_scratch: nothing of the context changes when it fails)
+static int ensure_split_scratch(gg_context *ctx, const char *who, hipStream_t st)
+{
+    if (ctx->split_mem.dev) return GG_OK;
+    const size_t ring = (size_t)PARAM_RING * ctx->n_slots;
+    const size_t o_counts = align_up(ring * sizeof(SplitCloud), 256);
+    const size_t n_pairs = ring * (size_t)std::max(ctx->arena.NCH, 1);
+    if (const int rc = alloc_call_scratch(ctx, who, st, o_counts + n_pairs * sizeof(uint2), ring * sizeof(SplitCloud), {}, &ctx->split_mem, nullptr)) return rc;
+    ctx->d_split_clouds = (SplitCloud *)ctx->split_mem.dev;
+    ctx->d_split_counts = (uint2 *)((char *)ctx->split_mem.dev + o_counts);
+    ctx->h_split_clouds = (SplitCloud *)ctx->split_mem.pinned;
+    return GG_OK;
+}
+
+// The ground and the non-ground points of many labelled clouds as dense clouds (k12_split.hip), in the frame of the export: nothing is
+// synchronised, no map is filled, no per-call layer is read (the lazily kept ones stay pending) and no host-side flag changes.
+int gg_split_clouds(gg_context *ctx, const gg_cloud_split *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_split_clouds";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_cloud_split");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    if (!x->d_points || !x->n_points || !x->d_counts) return fail(ctx, GG_ERR_INVALID, who, "d_points, n_points and d_counts are required");
+    if (x->point_format != GG_POINT32 && x->point_format != GG_POINT16) return fail(ctx, GG_ERR_INVALID, who, "point_format");
+    if ((x->d_labels != nullptr) == (x->d_label_masks != nullptr)) return fail(ctx, GG_ERR_INVALID, who, "exactly one of d_labels and d_label_masks");
+    if (x->d_label_masks && x->cloud_stride % 4 != 0) return fail(ctx, GG_ERR_INVALID, who, "d_label_masks needs a cloud_stride that is a multiple of 4");
+    if (x->cloud_stride > ctx->max_points) return fail(ctx, GG_ERR_CAPACITY, who, "cloud_stride is larger than max_points");
+    if (const int rc = check_slot_list(ctx, who, x->n, x->slots, x->first_slot)) return rc;
+    int max_n = 0;
+    for (int i = 0; i < x->n; ++i) {
+        if (x->n_points[i] < 0) return fail(ctx, GG_ERR_INVALID, who, "n_points[i] < 0");
+        if ((size_t)x->n_points[i] > ctx->max_points) return fail(ctx, GG_ERR_CAPACITY, who, "a cloud is larger than max_points");
+        if ((size_t)x->n_points[i] > x->cloud_stride) return fail(ctx, GG_ERR_INVALID, who, "n_points[i] is larger than cloud_stride");
+        max_n = std::max(max_n, (int)x->n_points[i]);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = ensure_split_scratch(ctx, who, pick_stream(ctx, stream))) return rc;
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, x->n, x->slots, x->first_slot, stream, false, &f)) return rc;
+    SplitCloud *hc = ctx->h_split_clouds + (size_t)f.g * ctx->n_slots, *dc = ctx->d_split_clouds + (size_t)f.g * ctx->n_slots;
+    for (int i = 0; i < x->n; ++i) {
+        SplitCloud &c = hc[i];
+        c.slot = f.hm[i].slot;
+        c.n_points = x->n_points[i];
+        c.fresh = f.hm[i].fresh;
+        c.fresh_z = f.hm[i].fresh_z;
+        c.has_tf = x->transforms ? 1 : 0;
+        c.io_index = i;
+        c.pos_x = ctx->pos_x[c.slot];
+        c.pos_y = ctx->pos_y[c.slot];
+        for (int k = 0; k < 12; ++k) c.tf[k] = x->transforms ? x->transforms[(size_t)12 * i + k] : 0.0;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(dc, hc, sizeof(SplitCloud) * x->n, hipMemcpyHostToDevice, f.st));
+    SplitArgs sa;
+    sa.clouds = dc;
+    sa.point_format = x->point_format;
+    sa.points = x->d_points;
+    sa.cloud_stride = x->cloud_stride;
+    sa.labels = x->d_labels;
+    sa.masks = x->d_label_masks;
+    sa.set[0] = SplitSet{x->ground.d_points, x->ground.d_height, x->ground.d_source};
+    sa.set[1] = SplitSet{x->nonground.d_points, x->nonground.d_height, x->nonground.d_source};
+    sa.counts = x->d_counts;
+    sa.chunk_counts = ctx->d_split_counts + (size_t)f.g * ctx->n_slots * (size_t)std::max(ctx->arena.NCH, 1);
+    sa.nch = std::max(1, (max_n + ctx->arena.PW - 1) / ctx->arena.PW); // (<= NCH: n_points <= max_points.  At least one: an empty cloud still gets its counts)
+    launch_split(ctx->arena, sa, x->n, f.st);
+    return map_call_end(ctx, f);
 }
 
 int gg_get_map_position(const gg_context *ctx, int slot, double *pos_x, double *pos_y)
@@ -3147,6 +3229,11 @@ extern "C" int gg_debug_set_tuning(gg_context *ctx, const char *key, int value)
     if (!strcmp(key, "fresh_count")) { // (read-only: how many maps are fresh -- gg_reset_maps left their layer unwritten and nothing has filled it since)
         int c = 0;
         for (int k = 0; k < ctx->n_slots; ++k) c += ctx->fresh[k] ? 1 : 0;
+        return c;
+    }
+    if (!strcmp(key, "lazy_count")) { // (read-only: how many maps still owe the three lazily kept layers of their last cloud)
+        int c = 0;
+        for (int k = 0; k < ctx->n_slots; ++k) c += ctx->lazy_pending[k] ? 1 : 0;
         return c;
     }
     if (!strcmp(key, "export_variant_default")) return EXPORT_VARIANT_DEFAULT; // (read-only: the kernel gg_export_layers ships with)

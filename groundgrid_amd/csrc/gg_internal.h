@@ -330,6 +330,34 @@ inline int image_parts(const Geometry &g, int variant) // partial pairs per plan
     return variant == 1 ? gather : blocks;
 }
 
+// gg_split_clouds (k12_split.hip): one entry per cloud of a call (a pinned ring entry, like ExportMap), and what its two launches share
+struct SplitCloud {
+    int slot;
+    int n_points;
+    int fresh;       // the map is fresh (gg_context::fresh): the ground under every point is fresh_z, its layer is not read
+    float fresh_z;
+    int has_tf;      // the points are in the sensor frame: p_map = transform_point(tf, p) first
+    int io_index;    // the cloud's row of the caller's buffers and of the call's chunk counters: its position in gg_cloud_split
+    double pos_x, pos_y; // the map's position when the call was made
+    double tf[12];
+};
+struct SplitSet {
+    gg_point16 *points;
+    float *height;
+    int32_t *source;
+};
+struct SplitArgs {
+    const SplitCloud *clouds;
+    int point_format;
+    const void *points;
+    size_t cloud_stride;
+    const uint8_t *labels, *masks; // exactly one of the two
+    SplitSet set[2];               // ground, nonground
+    int32_t *counts;               // [cloud][2]
+    uint2 *chunk_counts;           // call scratch: [cloud][nch] (points in ground, in nonground) of the chunk, written by k_split_count
+    int nch;                       // chunks per cloud of this call: ceil(max n_points / PW), at least 1
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -370,6 +398,7 @@ void launch_reduce_lazy_batch(const Arena &a, const CloudParams *d_params, int n
 void launch_export(const Arena &a, const PlaneArgs &x, int n_maps, int variant, hipStream_t s); // k9_export.hip; variant 0 = k_export_tiled, 1 = launch_planes_gather
 void launch_import(const Arena &a, const PlaneArgs &x, int n_maps, int variant, hipStream_t s); // k10_import.hip; variant 0 = k_import_tiled, 1 = launch_planes_scatter
 void launch_images(const Arena &a, const ImageArgs &x, int n_maps, int variant, hipStream_t s);  // k11_images.hip; variant 0 = the tiled kernels, 1 = cell by cell
+void launch_split(const Arena &a, const SplitArgs &x, int n_clouds, hipStream_t s);              // k12_split.hip: k_split_count, then k_split_scatter
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

@@ -576,6 +576,62 @@ typedef struct gg_image_export {
 int gg_export_images(gg_context *ctx, const gg_image_export *x, void *stream);
 #define GG_HAS_EXPORT_IMAGES 1
 
+/* The point side of a batch in DEVICE memory: the ground and the non-ground points of MANY labelled clouds as two dense clouds per input
+ * cloud, every point with its height above the estimated terrain and its index in the input -- what `points[labels == 99]` gives per
+ * cloud, without the launch and the device -> host synchronisation per cloud that a data-dependent size costs: the counts stay on the
+ * device.  Cloud i meets map slots ? slots[i] : first_slot + i (distinct, inside the context).
+ *   selection   point p < n_points[i] of cloud i goes into `ground` when its label is 49 (GG_LABEL_GROUND) and into `nonground` when it
+ *               is 99 (GG_LABEL_NONGROUND); any other label byte selects nothing.  The labels come as bytes (d_labels) or as the 2-bit masks
+ *               of gg_batch.d_label_masks (d_label_masks; codes 1 and 2) -- exactly one of the two.
+ *   order       ascending p, the cloud's own order: what cloud[labels == 99] gives, NOT the kept / ignored / outlier order of the
+ *               returned cloud (gg_batch.d_out_clouds).
+ *   addressing  row i of every output starts at i * cloud_stride elements.  d_counts[i] = {points in ground, points in nonground}.
+ *               Never written: the elements at and beyond a row's count, and the rows of a set none of whose three pointers is given.
+ *               Each of the three pointers of a set may be null on its own.
+ *   records     x, y, z are the input's -- with `transforms`, the map-frame point the path computes from it (tf2::doTransform in double,
+ *               cast to float, as for gg_batch.transforms): the bits of gg_batch.d_out_clouds / d_out_pc2.  ring is copied (gg_point16.ring,
+ *               or offset 20 of a 32-byte point), pad is 0.
+ *   height      one float subtraction, z_map - g: g is the `ground` layer of the cloud's map AS IT STANDS WHEN THE CALL RUNS, at the cell of
+ *               the map-frame (x, y) under the map's current position (the path's own inside test and index arithmetic, :222-231).  Right
+ *               behind gg_filter_batch on the same stream g is the value the label loop compared the point with
+ *               (src/GroundSegmentation.cpp:162).  A selected point outside the map -- possible only when the caller's labels do not belong
+ *               to these points and maps -- gets the quiet NaN 0x7FC00000 and reads nothing: the call is memory-safe for any label bytes.
+ * The call is stateless with respect to the last cloud: it reads the caller's buffers, the maps' `ground` layer and their positions, and no
+ * record a batch left behind -- any time, any maps, any labels.  A FRESH map (gg_reset_maps, nothing since) is neither read nor filled: its g
+ * is the constant odom_z, and it and every other fresh map stay fresh.  None of the nine per-call layers is read (the three lazily kept ones
+ * stay pending), and no layer, position, configuration, score or liveness flag changes.
+ * `stream` follows the gg_filter_batch convention; the call enqueues and returns, the host arrays may be freed on return, and work enqueued
+ * on `stream` afterwards sees the outputs.  The library orders the call exactly like gg_export_layers: it waits for every earlier map
+ * mutation, batch, export and import of the context (both halves under GG_FLAG_CONCURRENT_HALVES), and later writers of these maps on
+ * other streams wait for it.  The caller's buffers must stay valid and unmodified until `stream` has passed the call.
+ * Argument errors write nothing and change nothing: GG_ERR_CAPACITY (a slot outside the context, cloud_stride or an n_points[i] above
+ * max_points), GG_ERR_INVALID (null ctx, null x, n < 0, repeated slots; and with n > 0: null d_points, n_points or d_counts, an unknown
+ * point_format, both or neither of d_labels / d_label_masks, masks with a cloud_stride that is not a multiple of 4, n_points[i] < 0 or
+ * > cloud_stride).  n == 0 is GG_OK.  The first call of a context may allocate (GG_ERR_NOMEM) and block; later calls only enqueue.
+ * Capture into a caller's graph is not supported. */
+typedef struct gg_split_set {      /* one selected set of every cloud; each pointer nullable */
+    gg_point16 *d_points;          /* [n][cloud_stride] x, y, z in the MAP frame, ring, pad = 0 */
+    float      *d_height;          /* [n][cloud_stride] z - ground(cell of the point) */
+    int32_t    *d_source;          /* [n][cloud_stride] index of the point in its input cloud */
+} gg_split_set;
+typedef struct gg_cloud_split {
+    int n;                         /* clouds */
+    int first_slot;                /* cloud i meets map first_slot + i when slots == NULL */
+    const int32_t *slots;          /* host [n], nullable, distinct */
+    int point_format;              /* GG_POINT32 / GG_POINT16 */
+    const void *d_points;          /* [n][cloud_stride], as gg_batch.d_points */
+    size_t cloud_stride;           /* points */
+    const int32_t *n_points;       /* host [n] */
+    const double *transforms;      /* host [n][12], nullable, as gg_batch.transforms */
+    const uint8_t *d_labels;       /* [n][cloud_stride] GG_LABEL_*  -- exactly one of these two */
+    const uint8_t *d_label_masks;  /* [n][(cloud_stride + 3) / 4] 2-bit masks, as gg_batch.d_label_masks */
+    gg_split_set ground;           /* label 49 */
+    gg_split_set nonground;        /* label 99 */
+    int32_t *d_counts;             /* [n][2]: points in ground, in nonground; required */
+} gg_cloud_split;
+int gg_split_clouds(gg_context *ctx, const gg_cloud_split *x, void *stream);
+#define GG_HAS_SPLIT_CLOUDS 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
