@@ -48,10 +48,16 @@ SYMBOLS = [
     "gg_import_layers",
     "gg_export_images",
     "gg_split_clouds",
+    "gg_rasterize_clouds",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
 GG_PLANES_COLMAJOR, GG_PLANES_ROWMAJOR = 0, 1
+# gg_rasterize_clouds: the channels in GG_RASTER_* order (a channel's bit of channel_mask is its position here)
+RASTER_CHANNELS = ("nonground_count", "nonground_max_height", "nonground_min_height", "ground_count", "ground_max_height", "ground_min_height")
+(GG_RASTER_NONGROUND_COUNT, GG_RASTER_NONGROUND_MAX_HEIGHT, GG_RASTER_NONGROUND_MIN_HEIGHT, GG_RASTER_GROUND_COUNT, GG_RASTER_GROUND_MAX_HEIGHT,
+ GG_RASTER_GROUND_MIN_HEIGHT) = range(6)
+GG_NUM_RASTER_CHANNELS = 6
 GG_TERRAIN_HWC, GG_TERRAIN_CHW = 0, 1
 GG_ROT_TF2, GG_ROT_KDL = 0, 1
 ROTATION = {"tf2": GG_ROT_TF2, "kdl": GG_ROT_KDL}
@@ -157,6 +163,27 @@ class GGCloudSplit(C.Structure):
     ]
 
 
+class GGCloudRaster(C.Structure):
+    """gg_cloud_raster: the obstacle grid of many labelled clouds as dense planes, in device memory (gg_rasterize_clouds)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("first_slot", C.c_int),
+        ("slots", C.POINTER(C.c_int32)),
+        ("point_format", C.c_int),
+        ("d_points", C.c_void_p),
+        ("cloud_stride", C.c_size_t),
+        ("n_points", C.POINTER(C.c_int32)),
+        ("transforms", C.POINTER(C.c_double)),
+        ("d_labels", C.c_void_p),
+        ("d_label_masks", C.c_void_p),
+        ("channel_mask", C.c_uint),
+        ("order", C.c_int),
+        ("d_dst", C.c_void_p),
+        ("plane_stride", C.c_size_t),
+    ]
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -229,6 +256,7 @@ def load():
     L.gg_import_layers.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
     L.gg_export_images.argtypes = [vp, P(GGImageExport), vp]
     L.gg_split_clouds.argtypes = [vp, P(GGCloudSplit), vp]
+    L.gg_rasterize_clouds.argtypes = [vp, P(GGCloudRaster), vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

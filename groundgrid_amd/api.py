@@ -541,6 +541,65 @@ class GroundSegmentation:
         _check(self._L, self._ctx, self._L.gg_split_clouds(self._ctx, C.byref(x), stream), "gg_split_clouds")
         return res
 
+    def rasterize_clouds(self, points, n_points: Sequence[int], *, labels=None, masks=None, transforms=None, slots=None, first_slot: int = 0,
+                         channels: Sequence[str] = ("nonground_count", "nonground_max_height"), order: str = "row", out=None,
+                         on_torch_stream: bool = True):
+        """The obstacle grid of many labelled clouds on the device (gg_rasterize_clouds): a CUDA torch.float32 tensor [B, K, rows, cols]
+        (order="row"; [B, K, cols, rows], Eigen's column-major planes, with order="col" -- the shapes of export_layers) whose plane k is the
+        k-th of `channels`: per cell of cloud b's map the number of its non-ground (label 99) / ground (label 49) points there as a float
+        ("nonground_count", "ground_count"), and the largest and the smallest height of them above the map's `ground` layer as it stands
+        ("..._max_height", "..._min_height"; NaN where the cell holds no such point).  channels: distinct names of _lib.RASTER_CHANNELS in
+        that order.  points / n_points / transforms / slots / first_slot and labels / masks as for split_clouds.  `out` (same shape,
+        contiguous) is reused and returned when given.  Independent of the order in which points arrive: bit-identical from run to run.
+        Enqueued on the current torch stream (where filter_batch runs and torch ops enqueued afterwards see the planes) or, with
+        on_torch_stream=False, on the context's own stream.  No map changes; fresh maps stay fresh."""
+        import torch
+
+        self._torch_used = True
+        assert points.is_cuda and points.dtype == torch.uint8 and points.dim() == 3 and points.is_contiguous()
+        B, stride, rec = points.shape
+        assert rec in (16, 32)
+        if (labels is None) == (masks is None):
+            raise ValueError("rasterize_clouds: exactly one of labels and masks")
+        given = labels if labels is not None else masks
+        want_shape = (B, stride) if labels is not None else (B, (stride + 3) // 4)
+        if not (torch.is_tensor(given) and given.is_cuda and given.dtype == torch.uint8 and given.is_contiguous() and tuple(given.shape) == want_shape):
+            raise ValueError(f"rasterize_clouds: {'labels' if labels is not None else 'masks'} must be a contiguous CUDA uint8 tensor of shape {want_shape}")
+        channels = list(channels)
+        unknown = [k for k in channels if k not in _lib.RASTER_CHANNELS]
+        if unknown:
+            raise ValueError(f"rasterize_clouds: unknown channels {unknown}; known: {list(_lib.RASTER_CHANNELS)}")
+        if not channels or [k for k in _lib.RASTER_CHANNELS if k in channels] != channels:
+            raise ValueError("rasterize_clouds: channels must be distinct, in GG_RASTER_* order, and at least one")
+        if order not in ("row", "col"):
+            raise ValueError("rasterize_clouds: order is 'row' or 'col'")
+        shape = (B, len(channels), self.rows, self.cols) if order == "row" else (B, len(channels), self.cols, self.rows)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=points.device)
+        elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+            raise ValueError(f"rasterize_clouds: out must be a contiguous CUDA float32 tensor of shape {shape}")
+        npts = (C.c_int32 * max(B, 1))(*[int(v) for v in n_points])
+        x = _lib.GGCloudRaster()
+        x.n, x.first_slot, x.point_format = B, int(first_slot), _lib.GG_POINT16 if rec == 16 else _lib.GG_POINT32
+        x.d_points, x.cloud_stride, x.n_points = points.data_ptr(), stride, npts
+        if slots is not None:
+            sl = (C.c_int32 * max(B, 1))(*[int(v) for v in slots])
+            x.slots = sl
+        if transforms is not None:  # [B, 3, 4] map <- cloud frame, as for filter_batch
+            tfs = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(B, 12))
+            x.transforms = tfs.ctypes.data_as(C.POINTER(C.c_double))
+        x.d_labels = labels.data_ptr() if labels is not None else None
+        x.d_label_masks = masks.data_ptr() if masks is not None else None
+        x.channel_mask = sum(1 << _lib.RASTER_CHANNELS.index(k) for k in channels)
+        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.d_dst, x.plane_stride = out.data_ptr(), self.rows * self.cols
+        stream = None  # the context's own stream
+        if on_torch_stream:
+            h = torch.cuda.current_stream(points.device).cuda_stream
+            stream = C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
+        _check(self._L, self._ctx, self._L.gg_rasterize_clouds(self._ctx, C.byref(x), stream), "gg_rasterize_clouds")
+        return out
+
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:
         """A checkpoint of the named maps: {"planes": export_layers() of all eleven layers [n, 11, cols, rows] (on the device, enqueued on
         the current torch stream), "positions": their map positions, float64 [n, 2]}.  restore_maps puts it back -- into these maps, other

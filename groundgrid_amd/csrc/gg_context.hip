@@ -245,9 +245,9 @@ struct gg_context {
     float *d_image_partials = nullptr;
     int image_parts_cap = 0;
     int images_variant = IMAGES_VARIANT_DEFAULT; // tuning "images_variant": 0 = the tiled kernels, 1 = cell by cell (the A/B of tools/bench_images.py)
-    // gg_split_clouds (allocated at its first call): the per-cloud records [PARAM_RING][n_slots] (device and pinned) and the chunk counters
-    // of its two launches, [PARAM_RING][n_slots][NCH] pairs.  The call runs in the export's frame: an entry of export_ring is an entry here,
-    // so it has no ring of its own
+    // gg_split_clouds and gg_rasterize_clouds (allocated at the first call of either): the per-cloud records [PARAM_RING][n_slots] (device
+    // and pinned) and the chunk counters of the split's two launches, [PARAM_RING][n_slots][NCH] pairs.  The calls run in the export's frame:
+    // an entry of export_ring is an entry here, so they have no ring of their own
     CallScratch split_mem;
     SplitCloud *d_split_clouds = nullptr, *h_split_clouds = nullptr;
     uint2 *d_split_counts = nullptr;
@@ -2304,7 +2304,8 @@ int gg_export_images(gg_context *ctx, const gg_image_export *x, void *stream)
     return GG_OK;
 }
 
-// gg_split_clouds' device block and pinned records, at its first call (alloc_call_scratch: nothing of the context changes when it fails)
+// gg_split_clouds' and gg_rasterize_clouds' device block and pinned records, at the first call of either (alloc_call_scratch: nothing of the
+// context changes when it fails)
 static int ensure_split_scratch(gg_context *ctx, const char *who, hipStream_t st)
 {
     if (ctx->split_mem.dev) return GG_OK;
@@ -2318,6 +2319,57 @@ static int ensure_split_scratch(gg_context *ctx, const char *who, hipStream_t st
     return GG_OK;
 }
 
+// What gg_split_clouds and gg_rasterize_clouds take in: the leading members of gg_cloud_split and gg_cloud_raster
+struct LabelledClouds {
+    int n, first_slot;
+    const int32_t *slots;
+    int point_format;
+    const void *d_points;
+    size_t cloud_stride;
+    const int32_t *n_points;
+    const double *transforms;
+    const uint8_t *d_labels, *d_label_masks;
+};
+
+// Their frame, the export's: the arguments are checked before anything is touched (in.n > 0), then the call's ring entry is taken, `f->st`
+// ordered behind the context and one SplitCloud per cloud uploaded (*dc).  The caller enqueues its kernels on f->st, then map_call_end.
+static int labelled_clouds_begin(gg_context *ctx, const char *who, const LabelledClouds &in, void *stream, MapCall *f, SplitCloud **dc, int *nch)
+{
+    if (!in.d_points || !in.n_points) return fail(ctx, GG_ERR_INVALID, who, "d_points and n_points are required");
+    if (in.point_format != GG_POINT32 && in.point_format != GG_POINT16) return fail(ctx, GG_ERR_INVALID, who, "point_format");
+    if ((in.d_labels != nullptr) == (in.d_label_masks != nullptr)) return fail(ctx, GG_ERR_INVALID, who, "exactly one of d_labels and d_label_masks");
+    if (in.d_label_masks && in.cloud_stride % 4 != 0) return fail(ctx, GG_ERR_INVALID, who, "d_label_masks needs a cloud_stride that is a multiple of 4");
+    if (in.cloud_stride > ctx->max_points) return fail(ctx, GG_ERR_CAPACITY, who, "cloud_stride is larger than max_points");
+    if (const int rc = check_slot_list(ctx, who, in.n, in.slots, in.first_slot)) return rc;
+    int max_n = 0;
+    for (int i = 0; i < in.n; ++i) {
+        if (in.n_points[i] < 0) return fail(ctx, GG_ERR_INVALID, who, "n_points[i] < 0");
+        if ((size_t)in.n_points[i] > ctx->max_points) return fail(ctx, GG_ERR_CAPACITY, who, "a cloud is larger than max_points");
+        if ((size_t)in.n_points[i] > in.cloud_stride) return fail(ctx, GG_ERR_INVALID, who, "n_points[i] is larger than cloud_stride");
+        max_n = std::max(max_n, (int)in.n_points[i]);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = ensure_split_scratch(ctx, who, pick_stream(ctx, stream))) return rc;
+    if (const int rc = map_call_begin(ctx, who, in.n, in.slots, in.first_slot, stream, false, f)) return rc;
+    SplitCloud *hc = ctx->h_split_clouds + (size_t)f->g * ctx->n_slots;
+    *dc = ctx->d_split_clouds + (size_t)f->g * ctx->n_slots;
+    for (int i = 0; i < in.n; ++i) {
+        SplitCloud &c = hc[i];
+        c.slot = f->hm[i].slot;
+        c.n_points = in.n_points[i];
+        c.fresh = f->hm[i].fresh;
+        c.fresh_z = f->hm[i].fresh_z;
+        c.has_tf = in.transforms ? 1 : 0;
+        c.io_index = i;
+        c.pos_x = ctx->pos_x[c.slot];
+        c.pos_y = ctx->pos_y[c.slot];
+        for (int k = 0; k < 12; ++k) c.tf[k] = in.transforms ? in.transforms[(size_t)12 * i + k] : 0.0;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(*dc, hc, sizeof(SplitCloud) * in.n, hipMemcpyHostToDevice, f->st));
+    *nch = std::max(1, (max_n + ctx->arena.PW - 1) / ctx->arena.PW); // (<= NCH: n_points <= max_points.  At least one: the split writes an empty cloud's counts)
+    return GG_OK;
+}
+
 // The ground and the non-ground points of many labelled clouds as dense clouds (k12_split.hip), in the frame of the export: nothing is
 // synchronised, no map is filled, no per-call layer is read (the lazily kept ones stay pending) and no host-side flag changes.
 int gg_split_clouds(gg_context *ctx, const gg_cloud_split *x, void *stream)
@@ -2327,38 +2379,12 @@ int gg_split_clouds(gg_context *ctx, const gg_cloud_split *x, void *stream)
     if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_cloud_split");
     if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
     if (x->n == 0) return GG_OK;
-    if (!x->d_points || !x->n_points || !x->d_counts) return fail(ctx, GG_ERR_INVALID, who, "d_points, n_points and d_counts are required");
-    if (x->point_format != GG_POINT32 && x->point_format != GG_POINT16) return fail(ctx, GG_ERR_INVALID, who, "point_format");
-    if ((x->d_labels != nullptr) == (x->d_label_masks != nullptr)) return fail(ctx, GG_ERR_INVALID, who, "exactly one of d_labels and d_label_masks");
-    if (x->d_label_masks && x->cloud_stride % 4 != 0) return fail(ctx, GG_ERR_INVALID, who, "d_label_masks needs a cloud_stride that is a multiple of 4");
-    if (x->cloud_stride > ctx->max_points) return fail(ctx, GG_ERR_CAPACITY, who, "cloud_stride is larger than max_points");
-    if (const int rc = check_slot_list(ctx, who, x->n, x->slots, x->first_slot)) return rc;
-    int max_n = 0;
-    for (int i = 0; i < x->n; ++i) {
-        if (x->n_points[i] < 0) return fail(ctx, GG_ERR_INVALID, who, "n_points[i] < 0");
-        if ((size_t)x->n_points[i] > ctx->max_points) return fail(ctx, GG_ERR_CAPACITY, who, "a cloud is larger than max_points");
-        if ((size_t)x->n_points[i] > x->cloud_stride) return fail(ctx, GG_ERR_INVALID, who, "n_points[i] is larger than cloud_stride");
-        max_n = std::max(max_n, (int)x->n_points[i]);
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (const int rc = ensure_split_scratch(ctx, who, pick_stream(ctx, stream))) return rc;
+    if (!x->d_counts) return fail(ctx, GG_ERR_INVALID, who, "d_counts is required");
     MapCall f;
-    if (const int rc = map_call_begin(ctx, who, x->n, x->slots, x->first_slot, stream, false, &f)) return rc;
-    SplitCloud *hc = ctx->h_split_clouds + (size_t)f.g * ctx->n_slots, *dc = ctx->d_split_clouds + (size_t)f.g * ctx->n_slots;
-    for (int i = 0; i < x->n; ++i) {
-        SplitCloud &c = hc[i];
-        c.slot = f.hm[i].slot;
-        c.n_points = x->n_points[i];
-        c.fresh = f.hm[i].fresh;
-        c.fresh_z = f.hm[i].fresh_z;
-        c.has_tf = x->transforms ? 1 : 0;
-        c.io_index = i;
-        c.pos_x = ctx->pos_x[c.slot];
-        c.pos_y = ctx->pos_y[c.slot];
-        for (int k = 0; k < 12; ++k) c.tf[k] = x->transforms ? x->transforms[(size_t)12 * i + k] : 0.0;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(dc, hc, sizeof(SplitCloud) * x->n, hipMemcpyHostToDevice, f.st));
+    SplitCloud *dc = nullptr;
     SplitArgs sa;
+    const LabelledClouds in{x->n, x->first_slot, x->slots, x->point_format, x->d_points, x->cloud_stride, x->n_points, x->transforms, x->d_labels, x->d_label_masks};
+    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &dc, &sa.nch)) return rc;
     sa.clouds = dc;
     sa.point_format = x->point_format;
     sa.points = x->d_points;
@@ -2369,8 +2395,41 @@ int gg_split_clouds(gg_context *ctx, const gg_cloud_split *x, void *stream)
     sa.set[1] = SplitSet{x->nonground.d_points, x->nonground.d_height, x->nonground.d_source};
     sa.counts = x->d_counts;
     sa.chunk_counts = ctx->d_split_counts + (size_t)f.g * ctx->n_slots * (size_t)std::max(ctx->arena.NCH, 1);
-    sa.nch = std::max(1, (max_n + ctx->arena.PW - 1) / ctx->arena.PW); // (<= NCH: n_points <= max_points.  At least one: an empty cloud still gets its counts)
     launch_split(ctx->arena, sa, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
+// The obstacle grid of many labelled clouds as dense planes (k13_raster.hip), in the same frame and with the same per-cloud records: nothing
+// is synchronised, no map is filled or read beyond its `ground` layer, and no host-side flag (fresh, lazy_pending, liveness) changes.
+int gg_rasterize_clouds(gg_context *ctx, const gg_cloud_raster *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_rasterize_clouds";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_cloud_raster");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    if (!x->d_dst) return fail(ctx, GG_ERR_INVALID, who, "d_dst is null");
+    if (x->channel_mask == 0u || (x->channel_mask >> GG_NUM_RASTER_CHANNELS) != 0u) return fail(ctx, GG_ERR_INVALID, who, "channel_mask");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->plane_stride < (size_t)ctx->arena.g.C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
+    MapCall f;
+    SplitCloud *dc = nullptr;
+    RasterArgs ra;
+    const LabelledClouds in{x->n, x->first_slot, x->slots, x->point_format, x->d_points, x->cloud_stride, x->n_points, x->transforms, x->d_labels, x->d_label_masks};
+    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &dc, &ra.nch)) return rc;
+    ra.clouds = dc;
+    ra.point_format = x->point_format;
+    ra.points = x->d_points;
+    ra.cloud_stride = x->cloud_stride;
+    ra.labels = x->d_labels;
+    ra.masks = x->d_label_masks;
+    ra.channel_mask = x->channel_mask;
+    ra.n_planes = 0;
+    for (int ch = 0; ch < GG_NUM_RASTER_CHANNELS; ++ch) ra.plane_of[ch] = ((x->channel_mask >> ch) & 1u) ? ra.n_planes++ : -1;
+    ra.order = x->order;
+    ra.planes = reinterpret_cast<uint32_t *>(x->d_dst);
+    ra.plane_stride = x->plane_stride;
+    launch_raster(ctx->arena, ra, x->n, f.st);
     return map_call_end(ctx, f);
 }
 

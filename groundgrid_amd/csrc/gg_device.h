@@ -150,6 +150,18 @@ GG_DEV void transform_point(const double (&tf)[12], float &x, float &y, float &z
     z = (float)oz;
 }
 
+// The set a caller's label selects (gg_split_clouds, gg_rasterize_clouds): 0: the point goes nowhere, 1: `ground` (label 49 / mask code 1),
+// 2: `nonground` (label 99 / mask code 2).  row: the cloud's label bytes, or its 2-bit masks (gg_batch.d_label_masks)
+template <bool MASKS> GG_DEV uint32_t split_code(const uint8_t *row, int p)
+{
+    if (MASKS) {
+        const uint32_t c = ((uint32_t)row[p >> 2] >> (2 * (p & 3))) & 3u;
+        return c == 3u ? 0u : c;
+    }
+    const uint32_t l = row[p];
+    return l == GG_LABEL_GROUND ? 1u : l == GG_LABEL_NONGROUND ? 2u : 0u;
+}
+
 GG_DEV int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 // number of set bits of `mask` below this lane

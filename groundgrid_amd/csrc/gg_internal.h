@@ -358,6 +358,22 @@ struct SplitArgs {
     int nch;                       // chunks per cloud of this call: ceil(max n_points / PW), at least 1
 };
 
+// gg_rasterize_clouds (k13_raster.hip): what its three launches share.  The per-cloud records are gg_split_clouds' (SplitCloud, the same ring)
+struct RasterArgs {
+    const SplitCloud *clouds;
+    int point_format;
+    const void *points;
+    size_t cloud_stride;
+    const uint8_t *labels, *masks; // exactly one of the two
+    unsigned channel_mask;         // bit per GG_RASTER_*
+    int n_planes;                  // its popcount
+    int plane_of[GG_NUM_RASTER_CHANNELS]; // channel -> its plane among a cloud's n_planes (-1: not named)
+    int order;                     // GG_PLANES_*
+    uint32_t *planes;              // the caller's d_dst as 32-bit words: cloud i's plane k at planes + (i * n_planes + k) * plane_stride
+    size_t plane_stride;
+    int nch;                       // chunks per cloud of this call: ceil(max n_points / PW), at least 1
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -399,6 +415,7 @@ void launch_export(const Arena &a, const PlaneArgs &x, int n_maps, int variant, 
 void launch_import(const Arena &a, const PlaneArgs &x, int n_maps, int variant, hipStream_t s); // k10_import.hip; variant 0 = k_import_tiled, 1 = launch_planes_scatter
 void launch_images(const Arena &a, const ImageArgs &x, int n_maps, int variant, hipStream_t s);  // k11_images.hip; variant 0 = the tiled kernels, 1 = cell by cell
 void launch_split(const Arena &a, const SplitArgs &x, int n_clouds, hipStream_t s);              // k12_split.hip: k_split_count, then k_split_scatter
+void launch_raster(const Arena &a, const RasterArgs &x, int n_clouds, hipStream_t s);            // k13_raster.hip: k_raster_init, k_raster_scatter, k_raster_finalise
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

@@ -21,16 +21,6 @@
 
 namespace gg {
 
-// 0: the point goes nowhere, 1: into `ground` (label 49 / mask code 1), 2: into `nonground` (label 99 / mask code 2)
-template <bool MASKS> GG_DEV uint32_t split_code(const uint8_t *row, int p)
-{
-    if (MASKS) {
-        const uint32_t c = ((uint32_t)row[p >> 2] >> (2 * (p & 3))) & 3u;
-        return c == 3u ? 0u : c;
-    }
-    const uint32_t l = row[p];
-    return l == GG_LABEL_GROUND ? 1u : l == GG_LABEL_NONGROUND ? 2u : 0u;
-}
 template <bool MASKS> GG_DEV const uint8_t *split_label_row(const SplitArgs &x, int io)
 {
     return MASKS ? x.masks + (size_t)io * ((x.cloud_stride + 3) / 4) : x.labels + (size_t)io * x.cloud_stride;

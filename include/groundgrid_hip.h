@@ -632,6 +632,62 @@ typedef struct gg_cloud_split {
 int gg_split_clouds(gg_context *ctx, const gg_cloud_split *x, void *stream);
 #define GG_HAS_SPLIT_CLOUDS 1
 
+/* The OBSTACLE GRID of a batch in DEVICE memory: per cell of every map how many non-ground points of the map's cloud fell there and how far
+ * the highest and the lowest of them stand above the estimated terrain -- and the same three planes for the ground points (the height
+ * residual of the terrain estimate) -- what a planner or a BEV model takes from a ground segmenter.  The reference keeps only the count
+ * (the `points` layer, src/GroundSegmentation.cpp:147,176) and never a height.  One call for many maps, one pass over the points; cloud i
+ * meets map slots ? slots[i] : first_slot + i (distinct, inside the context).
+ *   selection   as gg_split_clouds: point p < n_points[i] belongs to the ground set when its label is 49 (mask code 1) and to the non-ground
+ *               set when it is 99 (mask code 2); any other label byte selects nothing.  Labels as bytes or as 2-bit masks, exactly one.
+ *   cell        of the map-frame (x, y) -- with `transforms`, of the point the path computes (tf2::doTransform in double, cast to float) --
+ *               under the map's current position: the path's own inside test and index arithmetic (:222-231).  A selected point outside
+ *               the map contributes to nothing: the call is memory-safe for any label bytes and any coordinates.
+ *   height      h = z_map - g, one float subtraction; g is the `ground` layer of the cloud's map AS IT STANDS WHEN THE CALL RUNS.
+ *   count       GG_RASTER_*_COUNT: the number of points of the set in the cell, as a float (exact: counts stay far below 2^24); an empty
+ *               cell holds 0.0f.  Right behind gg_filter_batch on the same stream the non-ground count is the `points` layer bit for bit.
+ *   max, min    GG_RASTER_*_MAX_HEIGHT / _MIN_HEIGHT: over the set's points in the cell whose h is not NaN, by IEEE totalOrder on the
+ *               non-NaN values (-0.0 < +0.0, +-inf take part).  A cell without such a point holds the quiet NaN 0x7FC00000.  A point whose
+ *               h is NaN (a NaN z, a NaN ground, inf - inf) is still counted.
+ *   addressing  with K = popcount(channel_mask), the k-th named channel (in GG_RASTER_* order) of cloud i is the plane of rows * cols floats
+ *               at d_dst + (i * K + k) * plane_stride, cell (row, col) where `order` (GG_PLANES_*) puts it.  EVERY cell of every named plane
+ *               of every listed cloud is written, those of an empty cloud (n_points[i] == 0) included; the floats between rows * cols and
+ *               plane_stride never are.  d_dst needs 4-byte alignment only.  While the call runs the planes hold intermediate words.
+ *   determinism the result does not depend on the order in which points arrive: counts are integer atomic adds, heights integer atomic
+ *               max / min on an order-preserving key of the float's bits; no float is ever added.  Bit-identical from run to run.
+ * The call is stateless with respect to the last cloud, exactly as gg_split_clouds: it reads the caller's buffers, the maps' `ground` layer
+ * and their positions, and no record a batch left behind.  A FRESH map is neither read nor filled: its g is the constant odom_z, and it and
+ * every other fresh map stay fresh.  None of the nine per-call layers is read (the three lazily kept ones stay pending), and no layer,
+ * position, configuration, score or liveness flag changes.
+ * `stream` and ordering are those of gg_split_clouds: the call enqueues and returns, the host arrays may be freed on return, it waits for
+ * every earlier map mutation, batch, export and import of the context (both halves under GG_FLAG_CONCURRENT_HALVES), and later writers of
+ * these maps on other streams wait for it.  The caller's buffers must stay valid and unmodified until `stream` has passed the call.
+ * Argument errors write nothing and change nothing: GG_ERR_CAPACITY (a slot outside the context, cloud_stride or an n_points[i] above
+ * max_points), GG_ERR_INVALID (null ctx, null x, n < 0, repeated slots; and with n > 0: null d_points, n_points or d_dst, an unknown
+ * point_format or order, both or neither of d_labels / d_label_masks, masks with a cloud_stride that is not a multiple of 4, n_points[i] < 0
+ * or > cloud_stride, channel_mask == 0 or with a bit at or above GG_NUM_RASTER_CHANNELS, plane_stride < rows * cols).  n == 0 is GG_OK.  The
+ * first call of a context may allocate (GG_ERR_NOMEM) and block; later calls only enqueue.  Capture into a caller's graph is not supported. */
+enum { GG_RASTER_NONGROUND_COUNT = 0, GG_RASTER_NONGROUND_MAX_HEIGHT = 1, GG_RASTER_NONGROUND_MIN_HEIGHT = 2,
+       GG_RASTER_GROUND_COUNT = 3,    GG_RASTER_GROUND_MAX_HEIGHT = 4,    GG_RASTER_GROUND_MIN_HEIGHT = 5,
+       GG_NUM_RASTER_CHANNELS = 6 };
+typedef struct gg_cloud_raster {
+    int n;                         /* clouds */
+    int first_slot;                /* cloud i meets map first_slot + i when slots == NULL */
+    const int32_t *slots;          /* host [n], nullable, distinct */
+    int point_format;              /* GG_POINT32 / GG_POINT16 */
+    const void *d_points;          /* [n][cloud_stride], as gg_batch.d_points */
+    size_t cloud_stride;           /* points */
+    const int32_t *n_points;       /* host [n] */
+    const double *transforms;      /* host [n][12], nullable, as gg_batch.transforms */
+    const uint8_t *d_labels;       /* [n][cloud_stride] GG_LABEL_*  -- exactly one of these two */
+    const uint8_t *d_label_masks;  /* [n][(cloud_stride + 3) / 4] 2-bit masks, as gg_batch.d_label_masks */
+    unsigned channel_mask;         /* bit per GG_RASTER_*; K = its popcount, != 0 */
+    int order;                     /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR */
+    float *d_dst;                  /* [n][K] planes, plane_stride floats apart */
+    size_t plane_stride;           /* floats, >= rows * cols */
+} gg_cloud_raster;
+int gg_rasterize_clouds(gg_context *ctx, const gg_cloud_raster *x, void *stream);
+#define GG_HAS_RASTERIZE_CLOUDS 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);

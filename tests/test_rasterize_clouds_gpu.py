@@ -1,0 +1,521 @@
+"""gg_rasterize_clouds (the obstacle grid of many labelled clouds -- per cell the number of non-ground / ground points and the largest and
+smallest height of them above the terrain -- as dense planes in device memory, one call) on the device.  Expected values come from the CPU
+oracle and numpy alone: OracleMap.filter_cloud gives the labels and the `ground` layer afterwards, OracleMap.get_index the cell,
+np.float32(z) - ground[row, col] the height, np.add.at the counts and np.maximum.at / np.minimum.at on the order-preserving uint32 keys
+the extremes.  Every comparison is on bits; there is no tolerance."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from groundgrid_amd import _lib, api, kitti, synth  # noqa: E402
+from groundgrid_amd._lib import LAYERS  # noqa: E402
+from oracle import oracle  # noqa: E402
+from tests.test_export_layers_gpu import SENTINEL, batch_points, fresh_count, same_bits, stride_of, warm_maps  # noqa: E402
+from tests.test_split_clouds_gpu import GEOMETRY, PARAM_RING, lazy_count, masks_of, points_tensor, transform_of  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+INVALID, CAPACITY = -1, -5
+QUIET_NAN = 0x7FC00000
+ALL = (1 << _lib.GG_NUM_RASTER_CHANNELS) - 1
+ROW, COL = _lib.GG_PLANES_ROWMAJOR, _lib.GG_PLANES_COLMAJOR
+SIGNED_SENTINEL = SENTINEL - (1 << 32) if SENTINEL >= (1 << 31) else SENTINEL
+
+
+# ---------------------------------------------------------------- helpers
+
+def keys_of(h):
+    """the order-preserving uint32 key of non-NaN float32 values: IEEE totalOrder as unsigned order"""
+    b = np.ascontiguousarray(h, dtype=np.float32).view(np.uint32)
+    return b ^ np.where(b >> 31, np.uint32(0xFFFFFFFF), np.uint32(0x80000000)).astype(np.uint32)
+
+
+def floats_of(keys):
+    return np.where(keys >> 31, keys ^ np.uint32(0x80000000), ~keys).astype(np.uint32)
+
+
+def expected_planes(ref, cloud_map, labels, ground=None):
+    """uint32 [6, rows, cols]: the bits of the six channels of one cloud in GG_RASTER_* order, from the oracle: ref's position and `ground`
+    layer as they stand (or the constant `ground` of a fresh map), cloud_map the points in the map frame, labels one byte per point"""
+    rows, cols = ref.rows, ref.cols
+    layer = ref.layer("ground")
+    out = np.empty((6, rows * cols), dtype=np.uint32)
+    for s, code in enumerate((99, 49)):
+        idx = np.nonzero(labels[: len(cloud_map)] == code)[0]
+        cells, hs = [], []
+        for p in idx:
+            inside, r, c = ref.get_index(float(cloud_map["x"][p]), float(cloud_map["y"][p]))
+            if inside and 0 <= r < rows and 0 <= c < cols:
+                cells.append(r * cols + c)
+                with np.errstate(invalid="ignore", over="ignore"):
+                    hs.append(np.float32(cloud_map["z"][p]) - (layer[r, c] if ground is None else np.float32(ground)))
+        cells, hs = np.array(cells, dtype=np.int64), np.array(hs, dtype=np.float32)
+        count = np.zeros(rows * cols, dtype=np.uint32)
+        np.add.at(count, cells, 1)
+        ok = ~np.isnan(hs)
+        hi, lo = np.zeros(rows * cols, dtype=np.uint32), np.full(rows * cols, 0xFFFFFFFF, dtype=np.uint32)
+        np.maximum.at(hi, cells[ok], keys_of(hs[ok]))
+        np.minimum.at(lo, cells[ok], keys_of(hs[ok]))
+        out[3 * s] = count.astype(np.float32).view(np.uint32)
+        out[3 * s + 1] = np.where(hi == 0, np.uint32(QUIET_NAN), floats_of(hi))
+        out[3 * s + 2] = np.where(lo == 0xFFFFFFFF, np.uint32(QUIET_NAN), floats_of(lo))
+    return out.reshape(6, rows, cols)
+
+
+def channels_of(mask):
+    return [ch for ch in range(6) if (mask >> ch) & 1]
+
+
+class Planes:
+    """a sentinel-filled destination of one call: n * K planes plane_stride words apart, and `slack` words behind the last one"""
+
+    def __init__(self, n, K, plane_stride, slack=0):
+        import torch
+
+        self.n, self.K, self.stride, self.slack = n, K, plane_stride, slack
+        self.t = torch.full((n * K * plane_stride + slack,), SIGNED_SENTINEL, dtype=torch.int32, device="cuda")
+
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def host(self):
+        return self.t.cpu().numpy().view(np.uint32)
+
+
+def raw_raster(seg, n, slots, first_slot, fmt, points, stride, n_points, dst, plane_stride, labels=0, masks=0, transforms=None, mask=ALL, order=ROW,
+               stream=None, own=False):
+    """gg_rasterize_clouds as the C ABI has it (device addresses as integers, 0 = null); returns the status"""
+    import torch
+
+    x = _lib.GGCloudRaster()
+    sl = None if slots is None else (C.c_int32 * max(len(slots), 1))(*[int(s) for s in slots])
+    npts = None if n_points is None else (C.c_int32 * max(len(n_points), 1))(*[int(v) for v in n_points])
+    x.n, x.first_slot, x.slots, x.point_format = n, first_slot, sl, fmt
+    x.d_points, x.cloud_stride, x.n_points = points or None, stride, npts
+    tfs = None
+    if transforms is not None:
+        tfs = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(-1, 12))
+        x.transforms = tfs.ctypes.data_as(C.POINTER(C.c_double))
+    x.d_labels, x.d_label_masks = labels or None, masks or None
+    x.channel_mask, x.order, x.d_dst, x.plane_stride = mask, order, dst or None, plane_stride
+    h = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    return seg._L.gg_rasterize_clouds(seg._ctx, C.byref(x), None if own else C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT))
+
+
+def check_planes(host, i, want, mask, order, plane_stride, tag):
+    """cloud i of a downloaded Planes against expected_planes: the named channels in enum order, and the words behind every plane untouched"""
+    rows, cols = want.shape[1:]
+    chans = channels_of(mask)
+    for k, ch in enumerate(chans):
+        at = (i * len(chans) + k) * plane_stride
+        got = host[at: at + rows * cols]
+        got = got.reshape(rows, cols) if order == ROW else got.reshape((rows, cols), order="F")
+        bad = int((got != want[ch]).sum())
+        assert bad == 0, f"{tag}: cloud {i} plane {k} ({_lib.RASTER_CHANNELS[ch]}): {bad} cells differ"
+        assert np.all(host[at + rows * cols: at + plane_stride] == SENTINEL), f"{tag}: cloud {i} plane {k}: the words behind the plane were written"
+
+
+def raster_scene(size, fmt, use_tf, small_chunks):
+    """The scene of test_split_clouds_gpu.lengths_scene with denser clouds in front (with its own two, fewer than 200 cells of a 79 x 79 map
+    hold two non-ground points of different heights: seen on the CPU oracle before the seeds were fixed).  Eleven maps through a
+    non-consecutive slot list -- five warmed by two scrolled batches, six as the reset left them --, then one batch of distinct clouds of the
+    lengths full (a 64-ring scan), full (a random cloud whose extent exceeds the map), 4 * 128 + 1, 129, 128, 127, 65, 64, 63, 1, 0.
+    Returns the context, the batch's device tensors and per cloud the oracle's expected_planes (`grids`)."""
+    import torch
+
+    length, res = GEOMETRY[size]
+    slots = [11, 2, 7, 0, 9, 4, 12, 1, 6, 10, 3]
+    with pytest.MonkeyPatch.context() as mp:
+        if small_chunks:
+            mp.setenv("GG_PW", "128")  # (read at gg_create: the 18006-point cloud spans 141 chunks and 36 work-groups)
+        seg = api.GroundSegmentation().init(length, res, n_slots=13, max_points=20000)
+    if small_chunks:
+        assert seg.debug_set_tuning("pw", 0) == 128
+    assert seg.rows == seg.cols == size
+    seg.reset_maps(odom_z=0.2)
+    refs = [oracle.OracleMap(length, res, odom_z=0.2) for _ in slots]
+    warm_maps(seg, slots[:5], seed=3100, refs=refs[:5])
+    assert fresh_count(seg) == 13 - 5
+    extent = 0.6 * length
+    clouds = [synth.hdl64_cloud(seed=3150, n_az=300), synth.random_cloud(12000, seed=3151, extent=extent)]
+    clouds += [synth.random_cloud(m, seed=3160 + m, extent=extent) for m in (4 * 128 + 1, 129, 128, 127, 65, 64, 63, 1)]
+    clouds.append(synth.empty_cloud(0))
+    n_pts = [len(c) for c in clouds]
+    assert n_pts[1:] == [12000, 513, 129, 128, 127, 65, 64, 63, 1, 0] and n_pts[0] > 12000
+    stride = stride_of(clouds)
+    R, t, tf = transform_of()
+    maps = [kitti.transform_cloud(c, R, t) if len(c) else c for c in clouds] if use_tf else clouds  # what the nodelet computes on the CPU (Nodelet.cpp:166-181)
+    origin = tuple(np.float32(v) for v in t) if use_tf else (0.0, 0.0, 0.0)
+    pts = points_tensor(clouds, stride, fmt)
+    out = seg.filter_batch(pts, n_pts, [origin] * len(slots), np.full(len(slots), -1.73), slots=slots, want_masks=True,
+                           transforms=[tf] * len(slots) if use_tf else None)
+    torch.cuda.synchronize()
+    labels = out.labels.cpu().numpy()
+    grids = []
+    for i in range(len(slots)):
+        r = refs[i].filter_cloud(maps[i], origin, -1.73)
+        assert np.array_equal(labels[i, : n_pts[i]], r["label"]), f"cloud {i}: the batch's labels are not the oracle's"
+        grids.append(expected_planes(refs[i], maps[i], r["label"]))
+    # the 2-bit masks of the same labels, as lengths_scene has them: with GG_PW=128 (k_label's mask stores of a chunk shorter than 256 points
+    # reach into the next chunk) packed on the host, else the batch's own after the same packing has been held against them
+    host_masks = masks_of(np.where(np.arange(stride)[None, :] < np.array(n_pts)[:, None], labels, 0).astype(np.uint8), stride)
+    if small_chunks:
+        masks = torch.from_numpy(host_masks).cuda()
+    else:
+        got_masks = out.label_masks.cpu().numpy()
+        for i in range(len(slots)):
+            assert np.array_equal(got_masks[i, : (n_pts[i] + 3) // 4], host_masks[i, : (n_pts[i] + 3) // 4]), f"cloud {i}: the batch's masks are not its labels"
+        masks = out.label_masks
+    return dict(seg=seg, slots=slots, pts=pts, n_pts=n_pts, stride=stride, out=out, masks=masks, grids=grids, tf=[tf] * len(slots) if use_tf else None, fmt=fmt)
+
+
+@pytest.fixture(scope="module")
+def scenes():
+    """raster_scene per (size, format, transforms), made once and shared: no call of this file changes a map"""
+    cache = {}
+
+    def get(size, fmt, use_tf, small_chunks):
+        key = (size, fmt, use_tf, small_chunks)
+        if key not in cache:
+            cache[key] = raster_scene(size, fmt, use_tf, small_chunks)
+        return cache[key]
+
+    yield get
+    for sc in cache.values():
+        sc["seg"].close()
+
+
+# ---------------------------------------------------------------- 1. parity with the oracle
+
+@pytest.mark.parametrize("order", [ROW, COL])
+@pytest.mark.parametrize("use_tf", [False, True])
+@pytest.mark.parametrize("use_masks", [False, True])
+@pytest.mark.parametrize("fmt", [_lib.GG_POINT16, _lib.GG_POINT32])
+@pytest.mark.parametrize("size,small_chunks", [(79, True), (364, False)])
+def test_parity_with_the_oracle(scenes, size, small_chunks, fmt, use_masks, use_tf, order):
+    import torch
+
+    sc = scenes(size, fmt, use_tf, small_chunks)
+    seg, n = sc["seg"], len(sc["slots"])
+    assert n == 11 and sc["n_pts"][2:] == [513, 129, 128, 127, 65, 64, 63, 1, 0] and fresh_count(seg) == 2  # (the batch made all eleven real)
+    # the scene holds what the extremes and the empty cells need (on the oracle's expectation)
+    grids = np.stack(sc["grids"])
+    f = grids.view(np.float32)
+    contended = (f[:, 0] >= 2.0) & (grids[:, 1] != grids[:, 2])
+    assert int(contended.sum()) >= 200, int(contended.sum())
+    assert int(((f[:, 0] == 0.0) & (f[:, 3] == 0.0)).sum()) >= 200
+    assert np.all(grids[:, 1][f[:, 0] == 0.0] == QUIET_NAN) and np.all(grids[-1, [0, 3]] == 0)  # (the empty cloud's planes are written too)
+    fresh_before = fresh_count(seg)
+    stride = seg.rows * seg.cols + 3
+    dst = Planes(n, 6, stride)
+    lab = dict(masks=sc["masks"].data_ptr()) if use_masks else dict(labels=sc["out"].labels.data_ptr())
+    rc = raw_raster(seg, n, sc["slots"], 0, fmt, sc["pts"].data_ptr(), sc["stride"], sc["n_pts"], dst.ptr(), stride, transforms=sc["tf"], order=order, **lab)
+    assert rc == 0, seg._L.gg_last_error(seg._ctx)
+    torch.cuda.synchronize()
+    assert fresh_count(seg) == fresh_before
+    host = dst.host()
+    tag = f"{size} {'point16' if fmt else 'point32'} {'masks' if use_masks else 'labels'} {'tf' if use_tf else 'map frame'} {'row' if order == ROW else 'col'}"
+    for i in range(n):
+        check_planes(host, i, sc["grids"][i], ALL, order, stride, tag)
+
+
+# ---------------------------------------------------------------- 2. agreement with the path itself
+
+def test_agreement_with_the_points_layer():
+    import torch
+
+    slots = [3, 0, 2]
+    seg = api.GroundSegmentation().init(120.0, 0.33, n_slots=4, max_points=20000)
+    seg.reset_maps(odom_z=0.1)
+    warm_maps(seg, slots, seed=4200)
+    clouds = [synth.hdl64_cloud(seed=4250 + k, n_az=140 + 11 * k) for k in range(3)]
+    stride, n_pts = stride_of(clouds), [len(c) for c in clouds]
+    pts = batch_points(clouds, stride)
+    out = seg.filter_batch(pts, n_pts, np.zeros((3, 3), np.float32), np.full(3, -1.73), slots=slots, want_masks=True)
+    row = seg.rasterize_clouds(pts, n_pts, labels=out.labels, slots=slots, channels=["nonground_count"])
+    col = seg.rasterize_clouds(pts, n_pts, masks=out.label_masks, slots=slots, channels=["nonground_count"], order="col")
+    layer_row = seg.export_layers(["points"], slots=slots, row_major=True)
+    layer_col = seg.export_layers(["points"], slots=slots)
+    torch.cuda.synchronize()
+    assert row.shape == layer_row.shape and col.shape == layer_col.shape
+    assert float(row.sum()) > 1000
+    assert same_bits(row.cpu().numpy(), layer_row.cpu().numpy())
+    assert same_bits(col.cpu().numpy(), layer_col.cpu().numpy())
+    seg.close()
+
+
+# ---------------------------------------------------------------- 3. contention and the ordering rule
+
+def test_contention_and_the_ordering_rule(monkeypatch):
+    import torch
+
+    length, res = GEOMETRY[79]
+    monkeypatch.setenv("GG_PW", "128")  # (read at gg_create: the 3000 points of one cell come from 24 chunks and 6 work-groups)
+    seg = api.GroundSegmentation().init(length, res, n_slots=1, max_points=4096)
+    assert seg.debug_set_tuning("pw", 0) == 128
+    seg.reset_maps(odom_z=0.0, on_torch_stream=True)
+    assert fresh_count(seg) == 1
+    ref = oracle.OracleMap(length, res, odom_z=0.0)
+    rng = np.random.default_rng(4300)
+    tiny = np.array([1, 2, 0x007FFFFF, 0x80000001, 0x80000003], dtype=np.uint32).view(np.float32)  # denormals of both signs
+    special = np.concatenate([np.array([0.0, -0.0, np.inf, -np.inf, np.nan, -3.0e38, 3.0e38, -1.5e30, 2.5e30, 1.25, 1.25, -7.5, -7.5], dtype=np.float32), tiny])
+    z_big = np.concatenate([np.tile(special, 40), rng.normal(0.0, 50.0, 3000 - 40 * len(special)).astype(np.float32)])
+    groups = [((1.0, 2.0), z_big),                                                       # ONE cell, 3000 points
+              ((-3.0, 0.5), np.full(40, np.nan, dtype=np.float32)),                      # a cell of NaN heights only
+              ((4.0, -6.0), np.tile(np.array([0.0, -0.0], dtype=np.float32), 16)),       # only the two zeros
+              ((1000.0, 0.0), np.ones(12, dtype=np.float32)),                            # outside the map
+              ((np.nan, 1.0), np.ones(4, dtype=np.float32)), ((2.0, np.inf), np.ones(4, dtype=np.float32)), ((-np.inf, np.nan), np.ones(4, dtype=np.float32))]
+    n = sum(len(z) for _, z in groups)
+    cloud = synth.empty_cloud(n)
+    at = 0
+    for (x, y), z in groups:
+        cloud["x"][at: at + len(z)], cloud["y"][at: at + len(z)], cloud["z"][at: at + len(z)] = x, y, z
+        at += len(z)
+    order = rng.permutation(n)
+    cloud = cloud[order]
+    stride = stride_of([cloud])
+    labels = np.zeros((1, stride), dtype=np.uint8)
+    labels[0] = np.tile(np.array([49, 99, 0, 7], dtype=np.uint8), stride // 4)
+    outside = order >= 3000 + 40 + 32
+    labels[0, :n][outside] = 99  # (every point outside the map is a selected one)
+    cells = [ref.get_index(*xy)[1:] for xy, _ in groups[:3]]
+    assert all(ref.get_index(*xy)[0] for xy, _ in groups[:3]) and len(set(cells)) == 3
+    assert not any(ref.get_index(float(x), float(y))[0] for (x, y), _ in groups[3:])
+    want = expected_planes(ref, cloud, labels[0], ground=0.0)
+    f = want.view(np.float32)
+    (r0, c0), (r1, c1), (r2, c2) = cells
+    assert f[0, r0, c0] + f[3, r0, c0] > 1400 and f[0, r1, c1] > 0 and f[3, r1, c1] > 0
+    assert want[1, r1, c1] == want[2, r1, c1] == want[4, r1, c1] == want[5, r1, c1] == QUIET_NAN
+    assert want[1, r2, c2] == 0x00000000 and want[2, r2, c2] == 0x80000000  # -0.0 < +0.0
+    assert f[0].sum() + f[3].sum() == f[0, r0, c0] + f[3, r0, c0] + f[0, r1, c1] + f[3, r1, c1] + f[0, r2, c2] + f[3, r2, c2]  # the outside points are counted nowhere
+    pts = points_tensor([cloud], stride, _lib.GG_POINT16)
+    d_labels = torch.from_numpy(labels).cuda()
+    plane_stride = seg.rows * seg.cols + 3
+    dsts = [Planes(1, 6, plane_stride) for _ in range(2)]
+    for d in dsts:
+        assert raw_raster(seg, 1, None, 0, _lib.GG_POINT16, pts.data_ptr(), stride, [n], d.ptr(), plane_stride, labels=d_labels.data_ptr()) == 0
+    torch.cuda.synchronize()
+    assert fresh_count(seg) == 1
+    hosts = [d.host() for d in dsts]
+    assert np.array_equal(hosts[0], hosts[1])
+    for h in hosts:
+        check_planes(h, 0, want, ALL, ROW, plane_stride, "contention")
+    seg.close()
+
+
+# ---------------------------------------------------------------- 4. subsets and what is not written
+
+def test_subsets_and_what_is_not_written(scenes):
+    import torch
+
+    sc = scenes(79, _lib.GG_POINT16, False, True)
+    seg, n = sc["seg"], len(sc["slots"])
+    stride = seg.rows * seg.cols + 3
+    masks = [1 << 0, 1 << 4, 0b111000, (1 << 1) | (1 << 4)]
+    dsts = [Planes(n, len(channels_of(m)), stride, slack=257) for m in masks]
+    for m, d in zip(masks, dsts):
+        rc = raw_raster(seg, n, sc["slots"], 0, sc["fmt"], sc["pts"].data_ptr(), sc["stride"], sc["n_pts"], d.ptr(), stride, labels=sc["out"].labels.data_ptr(), mask=m)
+        assert rc == 0, seg._L.gg_last_error(seg._ctx)
+    torch.cuda.synchronize()
+    for m, d in zip(masks, dsts):
+        host = d.host()
+        assert np.all(host[n * d.K * stride:] == SENTINEL), f"mask {m:#b}: words beyond n * K * plane_stride were written"
+        for i in range(n):
+            check_planes(host, i, sc["grids"][i], m, ROW, stride, f"mask {m:#b}")
+
+
+# ---------------------------------------------------------------- 5. nothing changes
+
+def test_nothing_changes():
+    import torch
+
+    slots = [4, 1, 5, 2]
+    K = len(slots)
+    segs = [api.GroundSegmentation().init(120.0, 0.33, n_slots=6, max_points=20000) for _ in range(2)]
+    base = [synth.hdl64_cloud(seed=4500 + k, n_az=150 + 7 * k) for k in range(K)]
+    stride = stride_of(base)
+    pts = [batch_points(base, stride), batch_points(base[::-1], stride)]
+    n_pts = [[len(c) for c in base], [len(c) for c in base[::-1]]]
+    origins, base_z = np.zeros((K, 3), np.float32), np.full(K, -1.73)
+    lazy = ["maxGroundHeight", "groundCandidates", "planeDist"]
+    results = []
+    for which, seg in enumerate(segs):
+        seg.reset_maps(odom_z=0.1)
+        seg.set_scoring(slots=slots)
+        first = seg.filter_batch(pts[0], n_pts[0], origins, base_z, slots=slots, want_masks=True)
+        assert lazy_count(seg) == K
+        if which == 0:  # the raster between the two batches, on every map of the context (two of them fresh)
+            all_pts = torch.zeros((6, stride, 16), dtype=torch.uint8, device="cuda")
+            all_labels = torch.full((6, stride), 99, dtype=torch.uint8, device="cuda")
+            grid = seg.rasterize_clouds(all_pts, [stride] * 6, labels=all_labels, slots=list(range(6)), channels=_lib.RASTER_CHANNELS)
+            seg.rasterize_clouds(pts[0], n_pts[0], masks=first.label_masks, slots=slots)
+        # the lazily kept layers are still pending behind the raster: their first reader computes them, to the values of the twin
+        assert lazy_count(seg) == K
+        pending = seg.export_layers(lazy, slots=slots)
+        assert lazy_count(seg) == 0
+        second = seg.filter_batch(pts[1], n_pts[1], origins, base_z, slots=slots)
+        planes = seg.export_layers()
+        torch.cuda.synchronize()
+        if which == 0:  # (every point at the origin: one cell per map holds them all)
+            assert np.array_equal(grid[:, 0].sum(dim=(1, 2)).cpu().numpy(), np.full(6, stride, np.float32))
+        results.append(dict(fresh=fresh_count(seg), pending=pending.cpu().numpy(), planes=planes.cpu().numpy(), labels=second.labels.cpu().numpy(),
+                            index=second.out_index.cpu().numpy(), counts=second.counts.cpu().numpy(), scores=seg.scores_raw(),
+                            positions=[seg.map(s).getPosition() for s in range(6)]))
+    a, b = results
+    assert a["fresh"] == b["fresh"] == 2
+    assert same_bits(a["pending"], b["pending"]) and same_bits(a["planes"], b["planes"])
+    assert a["planes"].shape[1] == len(LAYERS) == 11
+    assert np.array_equal(a["counts"], b["counts"]) and a["positions"] == b["positions"]
+    for k in range(K):
+        assert np.array_equal(a["labels"][k, : n_pts[1][k]], b["labels"][k, : n_pts[1][k]]) and np.array_equal(a["index"][k, : n_pts[1][k]], b["index"][k, : n_pts[1][k]])
+    assert np.array_equal(a["scores"][0], b["scores"][0]) and np.array_equal(a["scores"][1], b["scores"][1]) and a["scores"][0].sum() == 2 * K
+    for seg in segs:
+        seg.close()
+
+
+# ---------------------------------------------------------------- 6. a caller's stream, past the ring, no host synchronisation
+
+@pytest.mark.parametrize("halves", [False, True])
+def test_on_a_caller_stream_past_the_ring(halves):
+    import torch
+
+    n_slots, slots = 4, [2, 1, 3, 0]  # both halves (boundary 2)
+    K, rounds = len(slots), PARAM_RING + 2
+    base = [synth.hdl64_cloud(seed=4600 + k, n_az=60 + 5 * k) for k in range(K)]
+    stride = stride_of(base)
+    seg = api.GroundSegmentation().init(120.0, 0.33, n_slots=n_slots, max_points=stride)
+    if halves:
+        seg.set_flags(concurrent_halves=True)
+        seg.debug_set_tuning("halves_min_clouds", 2)
+    sets = [base, base[::-1]]
+    pts = [batch_points(c, stride) for c in sets]
+    n_pts = [[len(c) for c in cs] for cs in sets]
+    origins, base_z = np.zeros((K, 3), np.float32), np.full(K, -1.73)
+    plane_stride = seg.rows * seg.cols + 3
+    dsts = [Planes(K, 6, plane_stride) for _ in range(rounds)]
+    torch.cuda.synchronize()  # (the uploads and the fills ran on torch's default stream)
+    stream = torch.cuda.Stream()
+    batches = []
+    with torch.cuda.stream(stream):
+        seg.reset_maps(odom_z=0.0, on_torch_stream=True)
+        for r in range(rounds):  # no synchronisation anywhere: every batch has its own label tensor, every raster its own planes
+            batches.append(seg.filter_batch(pts[r % 2], n_pts[r % 2], origins, base_z, slots=slots))
+            rc = raw_raster(seg, K, slots, 0, _lib.GG_POINT16, pts[r % 2].data_ptr(), stride, n_pts[r % 2], dsts[r].ptr(), plane_stride,
+                            labels=batches[r].labels.data_ptr())
+            assert rc == 0, seg._L.gg_last_error(seg._ctx)
+    torch.cuda.synchronize()
+    refs = [oracle.OracleMap(120.0, 0.33) for _ in slots]
+    for r in range(rounds):
+        host = dsts[r].host()
+        for i in range(K):
+            cloud = sets[r % 2][i]
+            lab = refs[i].filter_cloud(cloud, (0.0, 0.0, 0.0), -1.73)["label"]
+            check_planes(host, i, expected_planes(refs[i], cloud, lab), ALL, ROW, plane_stride, f"round {r}, halves {halves}")
+    seg.close()
+
+
+# ---------------------------------------------------------------- 7. errors change nothing
+
+def test_errors_change_nothing():
+    import torch
+
+    seg = api.GroundSegmentation().init(120.0, 0.33, n_slots=6, max_points=4096)
+    seg.reset_maps(odom_z=0.4)
+    clouds = [synth.hdl64_cloud(seed=4700 + k, n_az=40) for k in range(2)]
+    stride, n_pts = stride_of(clouds), [len(c) for c in clouds]
+    assert stride <= 4096
+    warm_maps(seg, [4, 1], seed=4710, frames=1, n_az=40)
+    before = seg.export_layers(["ground", "groundpatch"])
+    torch.cuda.synchronize()
+    fresh_before = fresh_count(seg)
+    assert fresh_before == 4
+    pts = points_tensor(clouds, stride, _lib.GG_POINT16)
+    labels = torch.full((2, stride), 99, dtype=torch.uint8, device="cuda")
+    cells = seg.rows * seg.cols
+    dst = Planes(2, 6, cells)
+    P, Lb, D = pts.data_ptr(), labels.data_ptr(), dst.ptr()
+
+    def call(n=2, slots=None, first=0, fmt=_lib.GG_POINT16, points=P, stride=stride, n_points=n_pts, labels=Lb, masks=0, d=D, plane_stride=cells, mask=ALL, order=ROW):
+        return raw_raster(seg, n, slots, first, fmt, points, stride, n_points, d, plane_stride, labels=labels, masks=masks, mask=mask, order=order)
+
+    x = _lib.GGCloudRaster()
+    x.n = 2
+    assert seg._L.gg_rasterize_clouds(None, C.byref(x), None) == INVALID
+    assert seg._L.gg_rasterize_clouds(seg._ctx, None, None) == INVALID
+    assert call(n=-1) == INVALID
+    assert call(slots=[1, 1]) == INVALID
+    assert call(points=0) == INVALID
+    assert call(n_points=None) == INVALID
+    assert call(d=0) == INVALID
+    assert call(fmt=2) == INVALID
+    assert call(fmt=-1) == INVALID
+    assert call(order=2) == INVALID
+    assert call(order=-1) == INVALID
+    assert call(masks=Lb) == INVALID                 # both
+    assert call(labels=0) == INVALID                 # neither
+    assert call(labels=0, masks=Lb, stride=stride - 2, n_points=[10, 10]) == INVALID  # masks with a stride that is no multiple of 4
+    assert call(n_points=[-1, 5]) == INVALID
+    assert call(n_points=[5, stride + 1]) == INVALID
+    assert call(mask=0) == INVALID
+    assert call(mask=1 << 6) == INVALID
+    assert call(mask=ALL | (1 << 31)) == INVALID
+    assert call(plane_stride=cells - 1) == INVALID
+    assert call(n_points=[5, 4097]) == CAPACITY      # above max_points (and above the stride: the capacity is what is reported)
+    assert call(stride=4096, n_points=[5, 4097]) == CAPACITY
+    assert call(stride=4097) == CAPACITY
+    assert call(slots=[1, 6]) == CAPACITY
+    assert call(slots=[-1, 2]) == CAPACITY
+    assert call(first=5) == CAPACITY
+    assert call(first=-1) == CAPACITY
+    assert call(n=0, points=0, n_points=None, labels=0, d=0, fmt=9, stride=10 ** 9, mask=0, order=7, plane_stride=0) == 0  # n == 0: nothing to do, nothing to check
+    torch.cuda.synchronize()
+    assert np.all(dst.host() == SENTINEL)
+    assert fresh_count(seg) == fresh_before
+    after = seg.export_layers(["ground", "groundpatch"])
+    torch.cuda.synchronize()
+    assert same_bits(before.cpu().numpy(), after.cpu().numpy())
+    assert call(slots=[4, 1]) == 0, seg._L.gg_last_error(seg._ctx)  # ... and the same arguments without a mistake are accepted
+    torch.cuda.synchronize()
+    host = dst.host().view(np.float32).reshape(2, 6, cells)
+    assert fresh_count(seg) == fresh_before
+    assert 0 < host[0, 0].sum() <= n_pts[0] and 0 < host[1, 0].sum() <= n_pts[1] and not host[:, 3].any()
+    assert np.all(host[:, 4:].view(np.uint32) == QUIET_NAN)
+    seg.close()
+
+
+# ---------------------------------------------------------------- 8. the Python entry point
+
+def test_python_entry_point(scenes):
+    import torch
+
+    sc = scenes(79, _lib.GG_POINT16, False, True)
+    seg, n, slots = sc["seg"], len(sc["slots"]), sc["slots"]
+    grids = np.stack(sc["grids"])
+    a = seg.rasterize_clouds(sc["pts"], sc["n_pts"], labels=sc["out"].labels, slots=slots)
+    assert a.shape == (n, 2, seg.rows, seg.cols) and a.dtype == torch.float32 and a.is_cuda and a.is_contiguous()
+    b = seg.rasterize_clouds(sc["pts"], sc["n_pts"], masks=sc["masks"], slots=slots, channels=_lib.RASTER_CHANNELS, order="col")
+    assert b.shape == (n, 6, seg.cols, seg.rows)
+    again = seg.rasterize_clouds(sc["pts"], sc["n_pts"], masks=sc["masks"], slots=slots, channels=_lib.RASTER_CHANNELS, order="col", out=b)
+    assert again is b
+    own = seg.rasterize_clouds(sc["pts"], sc["n_pts"], labels=sc["out"].labels, slots=slots, channels=["ground_min_height"], on_torch_stream=False)
+    with pytest.raises(ValueError):
+        seg.rasterize_clouds(sc["pts"], sc["n_pts"], slots=slots)
+    with pytest.raises(ValueError):
+        seg.rasterize_clouds(sc["pts"], sc["n_pts"], labels=sc["out"].labels, masks=sc["masks"], slots=slots)
+    with pytest.raises(ValueError):
+        seg.rasterize_clouds(sc["pts"], sc["n_pts"], labels=sc["out"].labels, slots=slots, channels=["nonground_count", "obstacle_mean"])
+    with pytest.raises(ValueError):
+        seg.rasterize_clouds(sc["pts"], sc["n_pts"], labels=sc["out"].labels, slots=slots, out=b)  # (the wrong shape)
+    with pytest.raises(ValueError):
+        seg.rasterize_clouds(sc["pts"], sc["n_pts"], labels=sc["out"].labels, slots=slots, out=torch.empty(a.shape, dtype=torch.float64, device="cuda"))
+    torch.cuda.synchronize()
+    assert same_bits(a.cpu().numpy(), grids[:, :2].view(np.float32))
+    assert same_bits(b.cpu().numpy().transpose(0, 1, 3, 2), grids.view(np.float32))
+    assert same_bits(own.cpu().numpy(), grids[:, 5:6].view(np.float32))
