@@ -49,6 +49,7 @@ SYMBOLS = [
     "gg_export_images",
     "gg_split_clouds",
     "gg_rasterize_clouds",
+    "gg_export_slopes",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -58,6 +59,10 @@ RASTER_CHANNELS = ("nonground_count", "nonground_max_height", "nonground_min_hei
 (GG_RASTER_NONGROUND_COUNT, GG_RASTER_NONGROUND_MAX_HEIGHT, GG_RASTER_NONGROUND_MIN_HEIGHT, GG_RASTER_GROUND_COUNT, GG_RASTER_GROUND_MAX_HEIGHT,
  GG_RASTER_GROUND_MIN_HEIGHT) = range(6)
 GG_NUM_RASTER_CHANNELS = 6
+# gg_export_slopes: the channels in GG_SLOPE_* order (a channel's bit of channel_mask is its position here)
+SLOPE_CHANNELS = ["grad_x", "grad_y", "tangent", "normal_z", "step", "min_confidence"]
+GG_SLOPE_GRAD_X, GG_SLOPE_GRAD_Y, GG_SLOPE_TANGENT, GG_SLOPE_NORMAL_Z, GG_SLOPE_STEP, GG_SLOPE_MIN_CONFIDENCE = range(6)
+GG_NUM_SLOPE_CHANNELS = 6
 GG_TERRAIN_HWC, GG_TERRAIN_CHW = 0, 1
 GG_ROT_TF2, GG_ROT_KDL = 0, 1
 ROTATION = {"tf2": GG_ROT_TF2, "kdl": GG_ROT_KDL}
@@ -257,6 +262,7 @@ def load():
     L.gg_export_images.argtypes = [vp, P(GGImageExport), vp]
     L.gg_split_clouds.argtypes = [vp, P(GGCloudSplit), vp]
     L.gg_rasterize_clouds.argtypes = [vp, P(GGCloudRaster), vp]
+    L.gg_export_slopes.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

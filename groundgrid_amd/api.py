@@ -394,6 +394,41 @@ class GroundSegmentation:
         _check(self._L, self._ctx, rc, "gg_export_layers")
         return out
 
+    def export_slopes(self, names=None, *, slots=None, first_slot: int = 0, n: Optional[int] = None, out=None, row_major: bool = False,
+                      stream=None, own_stream: bool = False, plane_stride: Optional[int] = None):
+        """The shape of the terrain of many maps (gg_export_slopes): the named channels of _lib.SLOPE_CHANNELS (default: all six; distinct
+        and in that order) as one CUDA torch.float32 tensor with the shapes of export_layers -- [n, K, cols, rows] (element [i, k, c, r] is
+        cell (r, c)), [n, K, rows, cols] with row_major, or the flat [n * K * plane_stride] tensor.  grad_x / grad_y are dz/dx and dz/dy in
+        the map frame (rows grow towards -x, columns towards -y; central differences, one-sided on the border), tangent and normal_z the
+        tangent and the cosine of the slope angle, step the largest height difference to one of the up to eight neighbours,
+        min_confidence the smallest groundpatch value of the cell and its neighbours; include/groundgrid_hip.h defines them to the bit.
+        Computed from the maps' ground / groundpatch layers as they stand, in one launch, without synchronising; nothing of a map
+        changes, fresh maps stay fresh and the lazily kept layers stay pending.  Map selection, `out`, `stream`, `own_stream` and
+        `plane_stride` are those of export_layers."""
+        import torch
+
+        self._torch_used = True
+        names = list(_lib.SLOPE_CHANNELS) if names is None else list(names)
+        unknown = [k for k in names if k not in _lib.SLOPE_CHANNELS]
+        if unknown:
+            raise ValueError(f"export_slopes: unknown channels {unknown}; known: {list(_lib.SLOPE_CHANNELS)}")
+        if not names or [k for k in _lib.SLOPE_CHANNELS if k in names] != names:
+            raise ValueError("export_slopes: names must be distinct and in GG_SLOPE_* order")
+        mask = sum(1 << _lib.SLOPE_CHANNELS.index(k) for k in names)
+        cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
+        shape = (cnt, len(names), self.rows, self.cols) if row_major else (cnt, len(names), self.cols, self.rows)
+        if plane_stride is not None:
+            shape = (cnt * len(names) * int(plane_stride),)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", self.device))
+        assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._L.gg_export_slopes(self._ctx, cnt, ptr, first, mask, _lib.GG_PLANES_ROWMAJOR if row_major else _lib.GG_PLANES_COLMAJOR,
+                                      C.c_void_p(out.data_ptr()), self.rows * self.cols if plane_stride is None else int(plane_stride),
+                                      None if own_stream else C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
+        _check(self._L, self._ctx, rc, "gg_export_slopes")
+        return out
+
     def import_layers(self, planes, names=None, *, slots=None, first_slot: int = 0, n: Optional[int] = None, row_major: bool = False,
                       stream=None, own_stream: bool = False, plane_stride: Optional[int] = None):
         """The inverse of export_layers (gg_import_layers): `planes`, a contiguous CUDA torch.float32 tensor of exactly the shape

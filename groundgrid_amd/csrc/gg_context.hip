@@ -238,6 +238,7 @@ struct gg_context {
     const ExportMap *d_slot_maps = nullptr; // [n_slots] in the arena: entry s lists slot s alone -- the single-map getters' and setters' list of one map (gg_create)
     CloudParams *d_export_lazy = nullptr, *h_export_lazy = nullptr;
     ParamRing export_ring;
+    int slopes_variant = 0; // tuning "slopes_variant": 0 = k_slopes_tiled, 1 = k_slopes_gather (the A/B of tools/bench_slopes.py)
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
     int import_variant = IMPORT_VARIANT_DEFAULT; // tuning "import_variant": 0 = k_import_tiled, 1 = k_import_scatter (the A/B of tools/bench_import.py)
     // gg_export_images runs on the same table, rings and events; its bounds launch leaves the partial (min, max) pairs of a call in the ring
@@ -2262,6 +2263,25 @@ int gg_import_layers(gg_context *ctx, int n, const int32_t *slots, int first_slo
     return transfer_layers(ctx, true, n, slots, first_slot, layer_mask, order, d_src, plane_stride, stream);
 }
 
+// The slope, step and normal planes of many maps (k14_slopes.hip), in the frame of the export with its checks in its order: stateless, nothing
+// is synchronised, no map is filled, the lazily kept layers stay pending and no host flag is committed.
+int gg_export_slopes(gg_context *ctx, int n, const int32_t *slots, int first_slot, unsigned channel_mask, int order, float *d_dst, size_t plane_stride,
+                     void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_export_slopes";
+    if (n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (n == 0) return GG_OK;
+    if (channel_mask == 0u || (channel_mask >> GG_NUM_SLOPE_CHANNELS) != 0u) return fail(ctx, GG_ERR_INVALID, who, "channel_mask");
+    if (order != GG_PLANES_COLMAJOR && order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (!d_dst) return fail(ctx, GG_ERR_INVALID, who, "d_dst is null");
+    if (plane_stride < (size_t)ctx->arena.g.C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, n, slots, first_slot, stream, false, &f)) return rc;
+    launch_slopes(ctx->arena, fill_plane_args(ctx, f.dm, channel_mask, order, d_dst, plane_stride), n, ctx->slopes_variant, f.st);
+    return map_call_end(ctx, f);
+}
+
 // The u8 layer images and the terrain images of many maps (k11_images.hip), in the frame of the export: nothing is synchronised, no map is
 // filled, and the lazily kept layers are computed only where the mask names one of them (the terrain image reads none).
 int gg_export_images(gg_context *ctx, const gg_image_export *x, void *stream)
@@ -3320,6 +3340,7 @@ extern "C" int gg_debug_set_tuning(gg_context *ctx, const char *key, int value)
     else if (!strcmp(key, "halves_min_clouds")) ctx->halves_min_clouds = std::max(2, value); // (tests: GG_FLAG_CONCURRENT_HALVES on small batches)
     else if (!strcmp(key, "move_chunk")) ctx->move_chunk_tune = value;
     else if (!strcmp(key, "export_variant")) ctx->export_variant = value ? 1 : 0; // (A/B: 1 = gg_export_layers gathers in destination order, k_export_gather)
+    else if (!strcmp(key, "slopes_variant")) ctx->slopes_variant = value ? 1 : 0; // (A/B: 1 = gg_export_slopes cell by cell, k_slopes_gather)
     else if (!strcmp(key, "import_variant")) ctx->import_variant = value ? 1 : 0; // (A/B: 1 = gg_import_layers scatters in source order, k_import_scatter)
     else if (!strcmp(key, "images_variant")) ctx->images_variant = value ? 1 : 0; // (A/B: 1 = gg_export_images cell by cell, k11_images.hip)
     else if (!strcmp(key, "halves_no_fork")) ctx->probe_no_fork = value != 0; // (measurement only: the side stream does not wait for the caller's)

@@ -296,7 +296,7 @@ struct PlaneArgs {
     const uint32_t *block_off, *elem;
     const uint16_t *cell;
     int blocks_r, blocks_c;
-    unsigned mask; // bit per gg_layer
+    unsigned mask; // bit per gg_layer (launch_slopes: per GG_SLOPE_*)
     int n_planes;  // its popcount
     int order;     // GG_PLANES_*
     float *planes; // map i's plane k (the k-th layer of `mask` in gg_layer order) at planes + (i * n_planes + k) * plane_stride
@@ -413,6 +413,7 @@ void launch_reduce_lazy(const Arena &a, const CloudParams &cp, hipStream_t s); /
 void launch_reduce_lazy_batch(const Arena &a, const CloudParams *d_params, int n_clouds, hipStream_t s); // (... of n slots in one launch: gg_export_layers)
 void launch_export(const Arena &a, const PlaneArgs &x, int n_maps, int variant, hipStream_t s); // k9_export.hip; variant 0 = k_export_tiled, 1 = launch_planes_gather
 void launch_import(const Arena &a, const PlaneArgs &x, int n_maps, int variant, hipStream_t s); // k10_import.hip; variant 0 = k_import_tiled, 1 = launch_planes_scatter
+void launch_slopes(const Arena &a, const PlaneArgs &x, int n_maps, int variant, hipStream_t s); // k14_slopes.hip; x.mask: bit per GG_SLOPE_*; variant 0 = k_slopes_tiled, 1 = k_slopes_gather (cell by cell)
 void launch_images(const Arena &a, const ImageArgs &x, int n_maps, int variant, hipStream_t s);  // k11_images.hip; variant 0 = the tiled kernels, 1 = cell by cell
 void launch_split(const Arena &a, const SplitArgs &x, int n_clouds, hipStream_t s);              // k12_split.hip: k_split_count, then k_split_scatter
 void launch_raster(const Arena &a, const RasterArgs &x, int n_clouds, hipStream_t s);            // k13_raster.hip: k_raster_init, k_raster_scatter, k_raster_finalise

@@ -688,6 +688,42 @@ typedef struct gg_cloud_raster {
 int gg_rasterize_clouds(gg_context *ctx, const gg_cloud_raster *x, void *stream);
 #define GG_HAS_RASTERIZE_CLOUDS 1
 
+/* The SHAPE of the terrain of n maps as dense planes in DEVICE memory, one launch, no synchronisation: per cell how steep the ground is and
+ * in which direction, how large the step to a neighbour is and how far the estimate can be trusted there -- what a planner otherwise builds
+ * from gg_export_layers(ground, groundpatch) and two dozen passes of shifted slices.
+ * Addressing, `order`, `plane_stride`, `stream`, slot lists and the ordering guarantees are exactly those of gg_export_layers: map i =
+ * slots ? slots[i] : first_slot + i (distinct), K = popcount(channel_mask), the k-th named channel (in GG_SLOPE_* order) of map i goes to
+ * d_dst + (i * K + k) * plane_stride; d_dst needs 4-byte alignment only and plane_stride (floats, >= rows * cols) may be odd; the floats
+ * between rows * cols and plane_stride are not written; order is GG_PLANES_COLMAJOR or GG_PLANES_ROWMAJOR.
+ * The call is stateless: it reads the `ground` and `groundpatch` layer of the listed maps as they stand, reads none of the nine per-call
+ * layers, launches nothing for the three lazily kept ones (they stay pending), and changes no map, no flag, no score, no position.
+ * DEFINITION.  With g = ground, w = groundpatch, res = the `float` resolution of gg_geometry, and for cell (r, c):
+ *   r_lo = max(r-1, 0), r_hi = min(r+1, rows-1), c_lo = max(c-1, 0), c_hi = min(c+1, cols-1).
+ *   All arithmetic is float32, with no contraction, IEEE division and square root, and denormals kept.
+ *   GRAD_X          gx = (g(r_lo,c) - g(r_hi,c)) / ((float)(r_hi - r_lo) * res).  This is dz/dx in the map frame, because rows grow towards
+ *                   -x.  It is one-sided on the border rows.
+ *   GRAD_Y          gy = (g(r,c_lo) - g(r,c_hi)) / ((float)(c_hi - c_lo) * res)   (columns grow towards -y)
+ *   TANGENT         sqrtf(gx*gx + gy*gy), the tangent of the slope angle.
+ *   NORMAL_Z        1.0f / sqrtf((gx*gx + gy*gy) + 1.0f), the z component of the unit normal, equal to the cosine of the slope angle.
+ *   STEP            m = 0.0f, then over the cells (r', c') of {r_lo..r_hi} x {c_lo..c_hi} other than (r, c), in any order:
+ *                   m = fmaxf(m, fabsf(g(r',c') - g(r,c))).  A NaN difference is skipped, so the result is never NaN and its sign bit is
+ *                   clear.
+ *   MIN_CONFIDENCE  fminf of w over all cells of {r_lo..r_hi} x {c_lo..c_hi}, centre included, starting from w(r,c).  NaNs are skipped
+ *                   unless all are NaN.
+ * The first four channels are NaN where their stencil holds a NaN, or where inf - inf arises.  Which NaN is not specified.  Everything else
+ * is specified to the bit.
+ * A FRESH map (gg_reset_maps, nothing since) gets +0, +0, +0, 1.0f, +0, 1e-7f.  Its layer is not read or filled, and it and every other
+ * fresh map stays fresh.
+ * Argument errors write nothing and change nothing: GG_ERR_CAPACITY (a slot outside the context), GG_ERR_INVALID (null ctx, n < 0, repeated
+ * slots, channel_mask == 0 or with a bit at or above GG_NUM_SLOPE_CHANNELS, unknown order, null d_dst, plane_stride < rows * cols -- the last
+ * five only with n > 0).  n == 0 is GG_OK.  The call shares its table, parameter rings and events with gg_export_layers: the first of them
+ * in a context allocates and blocks, later calls only enqueue.  Capture into a caller's graph is not supported, as for the export. */
+enum { GG_SLOPE_GRAD_X = 0, GG_SLOPE_GRAD_Y = 1, GG_SLOPE_TANGENT = 2, GG_SLOPE_NORMAL_Z = 3,
+       GG_SLOPE_STEP = 4, GG_SLOPE_MIN_CONFIDENCE = 5, GG_NUM_SLOPE_CHANNELS = 6 };
+int gg_export_slopes(gg_context *ctx, int n, const int32_t *slots, int first_slot, unsigned channel_mask, int order,
+                     float *d_dst, size_t plane_stride, void *stream);
+#define GG_HAS_EXPORT_SLOPES 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
