@@ -50,6 +50,7 @@ SYMBOLS = [
     "gg_split_clouds",
     "gg_rasterize_clouds",
     "gg_export_slopes",
+    "gg_cluster_clouds",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -189,6 +190,49 @@ class GGCloudRaster(C.Structure):
     ]
 
 
+class GGCluster(C.Structure):
+    """gg_cluster: one obstacle cluster of a cloud (gg_cluster_clouds), 32 bytes"""
+
+    _fields_ = [
+        ("cells", C.c_int32),
+        ("points", C.c_int32),
+        ("row_min", C.c_int32),
+        ("row_max", C.c_int32),
+        ("col_min", C.c_int32),
+        ("col_max", C.c_int32),
+        ("height_max", C.c_float),
+        ("first_cell", C.c_int32),
+    ]
+
+
+class GGCloudClusters(C.Structure):
+    """gg_cloud_clusters: the obstacle clusters of many labelled clouds, in device memory (gg_cluster_clouds)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("first_slot", C.c_int),
+        ("slots", C.POINTER(C.c_int32)),
+        ("point_format", C.c_int),
+        ("d_points", C.c_void_p),
+        ("cloud_stride", C.c_size_t),
+        ("n_points", C.POINTER(C.c_int32)),
+        ("transforms", C.POINTER(C.c_double)),
+        ("d_labels", C.c_void_p),
+        ("d_label_masks", C.c_void_p),
+        ("min_points", C.c_int),
+        ("min_height", C.c_float),
+        ("max_height", C.c_float),
+        ("connectivity", C.c_int),
+        ("order", C.c_int),
+        ("d_cell_cluster", C.c_void_p),
+        ("plane_stride", C.c_size_t),
+        ("d_point_cluster", C.c_void_p),
+        ("d_n_clusters", C.c_void_p),
+        ("d_clusters", C.c_void_p),
+        ("max_clusters", C.c_int),
+    ]
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -263,6 +307,7 @@ def load():
     L.gg_split_clouds.argtypes = [vp, P(GGCloudSplit), vp]
     L.gg_rasterize_clouds.argtypes = [vp, P(GGCloudRaster), vp]
     L.gg_export_slopes.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
+    L.gg_cluster_clouds.argtypes = [vp, P(GGCloudClusters), vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

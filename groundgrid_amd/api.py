@@ -256,6 +256,27 @@ class SplitOutputs:
         return [tuple(None if t is None else t[i, :m] for t in fields) for i, m in enumerate(sizes)]
 
 
+# gg_cluster as a numpy record (ClusterOutputs.table)
+CLUSTER_DTYPE = np.dtype([("cells", "<i4"), ("points", "<i4"), ("row_min", "<i4"), ("row_max", "<i4"), ("col_min", "<i4"), ("col_max", "<i4"),
+                          ("height_max", "<f4"), ("first_cell", "<i4")])
+
+
+@dataclass
+class ClusterOutputs:
+    """what GroundSegmentation.cluster_clouds returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    cell_cluster: "object" = None   # torch.int32 [B, rows, cols] ([B, cols, rows] with order="col"): -1 or the cell's cluster id
+    n_clusters: "object" = None     # torch.int32 [B]: the true number of clusters of every cloud
+    clusters: "object" = None       # torch.int32 [B, max_clusters, 8]: gg_cluster records (word 6 holds the bits of the float height_max)
+    point_cluster: "object" = None  # torch.int32 [B, stride]: -1 or the id of the point's cell, for p < n_points[b]
+
+    def table(self, b: int):
+        """The first min(K, max_clusters) records of cloud b as a numpy structured array (CLUSTER_DTYPE, height_max as float32).  The ONE
+        place that synchronises: it reads the count on the host."""
+        k = min(int(self.n_clusters[b].item()), int(self.clusters.shape[1]))
+        return self.clusters[b, :k].cpu().numpy().copy().view(CLUSTER_DTYPE).reshape(k)
+
+
 class GroundSegmentation:
     """Mirror of groundgrid::GroundSegmentation (include/groundgrid/GroundSegmentation.h:48-71)."""
 
@@ -634,6 +655,79 @@ class GroundSegmentation:
             stream = C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
         _check(self._L, self._ctx, self._L.gg_rasterize_clouds(self._ctx, C.byref(x), stream), "gg_rasterize_clouds")
         return out
+
+    def cluster_clouds(self, points, n_points: Sequence[int], *, labels=None, masks=None, transforms=None, slots=None, first_slot: int = 0,
+                       min_points: int = 1, min_height: float = -math.inf, max_height: float = math.inf, connectivity: int = 8,
+                       max_clusters: int = 256, order: str = "row", point_clusters: bool = True, out: Optional[ClusterOutputs] = None,
+                       on_torch_stream: bool = True) -> ClusterOutputs:
+        """The obstacle clusters of many labelled clouds on the device (gg_cluster_clouds): the connected components (connectivity 4 or 8)
+        of the cells that hold at least min_points non-ground (label 99) points whose height above the map's `ground` layer as it stands
+        lies in [min_height, max_height].  ClusterOutputs: cell_cluster int32 [B, rows, cols] (order="row"; [B, cols, rows] with
+        order="col") with -1 or the cell's cluster id, the clusters of a map numbered by their smallest linear cell index of `order` (with
+        "row": scipy.ndimage.label(occupied)[0] - 1); n_clusters int32 [B], the true counts; clusters int32 [B, max_clusters, 8], the
+        gg_cluster records of the first max_clusters clusters (None with max_clusters=0; ClusterOutputs.table(b) reads them as a numpy
+        structured array); point_cluster int32 [B, stride], the id of every point's cell or -1 (None with point_clusters=False; elements
+        behind n_points[b] are not written).  points / n_points / transforms / slots / first_slot and labels / masks as for
+        rasterize_clouds.  `out`: a ClusterOutputs of an earlier call with the same arguments, whose tensors are reused.  Only integer
+        atomics: bit-identical from run to run.  Enqueued on the current torch stream or, with on_torch_stream=False, on the context's own
+        stream; nothing synchronises.  No map changes; fresh maps stay fresh."""
+        import torch
+
+        self._torch_used = True
+        assert points.is_cuda and points.dtype == torch.uint8 and points.dim() == 3 and points.is_contiguous()
+        B, stride, rec = points.shape
+        assert rec in (16, 32)
+        if (labels is None) == (masks is None):
+            raise ValueError("cluster_clouds: exactly one of labels and masks")
+        given = labels if labels is not None else masks
+        want_shape = (B, stride) if labels is not None else (B, (stride + 3) // 4)
+        if not (torch.is_tensor(given) and given.is_cuda and given.dtype == torch.uint8 and given.is_contiguous() and tuple(given.shape) == want_shape):
+            raise ValueError(f"cluster_clouds: {'labels' if labels is not None else 'masks'} must be a contiguous CUDA uint8 tensor of shape {want_shape}")
+        if connectivity not in (4, 8):
+            raise ValueError("cluster_clouds: connectivity is 4 or 8")
+        if order not in ("row", "col"):
+            raise ValueError("cluster_clouds: order is 'row' or 'col'")
+        max_clusters = int(max_clusters)
+        if max_clusters < 0:
+            raise ValueError("cluster_clouds: max_clusters < 0")
+        res = out if out is not None else ClusterOutputs()
+        want = {"cell_cluster": (B, self.rows, self.cols) if order == "row" else (B, self.cols, self.rows), "n_clusters": (B,),
+                "clusters": (B, max_clusters, 8) if max_clusters else None, "point_cluster": (B, stride) if point_clusters else None}
+        for field, shape in want.items():
+            t = getattr(res, field)
+            if shape is None:
+                if t is not None:
+                    raise ValueError(f"cluster_clouds: out.{field} is given but not asked for")
+                continue
+            if t is None:
+                setattr(res, field, torch.empty(shape, dtype=torch.int32, device=points.device))
+            elif not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"cluster_clouds: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {shape}")
+        npts = (C.c_int32 * max(B, 1))(*[int(v) for v in n_points])
+        x = _lib.GGCloudClusters()
+        x.n, x.first_slot, x.point_format = B, int(first_slot), _lib.GG_POINT16 if rec == 16 else _lib.GG_POINT32
+        x.d_points, x.cloud_stride, x.n_points = points.data_ptr(), stride, npts
+        if slots is not None:
+            sl = (C.c_int32 * max(B, 1))(*[int(v) for v in slots])
+            x.slots = sl
+        if transforms is not None:  # [B, 3, 4] map <- cloud frame, as for filter_batch
+            tfs = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(B, 12))
+            x.transforms = tfs.ctypes.data_as(C.POINTER(C.c_double))
+        x.d_labels = labels.data_ptr() if labels is not None else None
+        x.d_label_masks = masks.data_ptr() if masks is not None else None
+        x.min_points, x.min_height, x.max_height, x.connectivity = int(min_points), float(min_height), float(max_height), int(connectivity)
+        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.d_cell_cluster, x.plane_stride = res.cell_cluster.data_ptr(), self.rows * self.cols
+        x.d_point_cluster = res.point_cluster.data_ptr() if point_clusters else None
+        x.d_n_clusters = res.n_clusters.data_ptr()
+        x.d_clusters = res.clusters.data_ptr() if max_clusters else None
+        x.max_clusters = max_clusters
+        stream = None  # the context's own stream
+        if on_torch_stream:
+            h = torch.cuda.current_stream(points.device).cuda_stream
+            stream = C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
+        _check(self._L, self._ctx, self._L.gg_cluster_clouds(self._ctx, C.byref(x), stream), "gg_cluster_clouds")
+        return res
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:
         """A checkpoint of the named maps: {"planes": export_layers() of all eleven layers [n, 11, cols, rows] (on the device, enqueued on

@@ -252,6 +252,11 @@ struct gg_context {
     CallScratch split_mem;
     SplitCloud *d_split_clouds = nullptr, *h_split_clouds = nullptr;
     uint2 *d_split_counts = nullptr;
+    // gg_cluster_clouds (allocated at its first call): the root counters of its cell launches, [PARAM_RING][n_slots][cluster_cell_chunks]
+    // words, in the same frame: an entry of export_ring is an entry here
+    CallScratch cluster_mem;
+    uint32_t *d_cluster_counts = nullptr;
+    int cluster_cell_chunks = 0;
     float *d_image = nullptr;          // 3 * C floats (wire-format images)
     float *d_planes = nullptr;         // GG_NUM_LAYERS * Cpad floats: dense planes of gg_get_layers (allocated on first use)
     float *h_planes = nullptr;         // ... and their pinned landing zone on the host (one download for all requested layers)
@@ -1576,6 +1581,7 @@ void gg_destroy(gg_context *ctx)
     free_call_scratch(ctx->move_mem, ctx->move_ring);
     free_call_scratch(ctx->export_mem, ctx->export_ring);
     free_call_scratch(ctx->split_mem);
+    free_call_scratch(ctx->cluster_mem);
     if (ctx->d_pc2) hipFree(ctx->d_pc2);
     if (ctx->h_pc2) hipHostFree(ctx->h_pc2);
     if (ctx->h_planes) hipHostFree(ctx->h_planes);
@@ -2353,7 +2359,8 @@ struct LabelledClouds {
 
 // Their frame, the export's: the arguments are checked before anything is touched (in.n > 0), then the call's ring entry is taken, `f->st`
 // ordered behind the context and one SplitCloud per cloud uploaded (*dc).  The caller enqueues its kernels on f->st, then map_call_end.
-static int labelled_clouds_begin(gg_context *ctx, const char *who, const LabelledClouds &in, void *stream, MapCall *f, SplitCloud **dc, int *nch)
+static int labelled_clouds_begin(gg_context *ctx, const char *who, const LabelledClouds &in, void *stream, MapCall *f, SplitCloud **dc, int *nch,
+                                 int (*ensure_more)(gg_context *, const char *, hipStream_t) = nullptr)
 {
     if (!in.d_points || !in.n_points) return fail(ctx, GG_ERR_INVALID, who, "d_points and n_points are required");
     if (in.point_format != GG_POINT32 && in.point_format != GG_POINT16) return fail(ctx, GG_ERR_INVALID, who, "point_format");
@@ -2370,6 +2377,8 @@ static int labelled_clouds_begin(gg_context *ctx, const char *who, const Labelle
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (const int rc = ensure_split_scratch(ctx, who, pick_stream(ctx, stream))) return rc;
+    if (ensure_more) // (a call with scratch of its own: checked arguments first, and no ring entry taken yet)
+        if (const int rc = ensure_more(ctx, who, pick_stream(ctx, stream))) return rc;
     if (const int rc = map_call_begin(ctx, who, in.n, in.slots, in.first_slot, stream, false, f)) return rc;
     SplitCloud *hc = ctx->h_split_clouds + (size_t)f->g * ctx->n_slots;
     *dc = ctx->d_split_clouds + (size_t)f->g * ctx->n_slots;
@@ -2450,6 +2459,63 @@ int gg_rasterize_clouds(gg_context *ctx, const gg_cloud_raster *x, void *stream)
     ra.planes = reinterpret_cast<uint32_t *>(x->d_dst);
     ra.plane_stride = x->plane_stride;
     launch_raster(ctx->arena, ra, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
+// gg_cluster_clouds' root counters, at its first call (alloc_call_scratch: nothing of the context changes when it fails)
+static int ensure_cluster_scratch(gg_context *ctx, const char *who, hipStream_t st)
+{
+    if (ctx->cluster_mem.dev) return GG_OK;
+    const int chunks = (ctx->arena.g.C + CLUSTER_CHUNK_CELLS - 1) / CLUSTER_CHUNK_CELLS;
+    const size_t words = (size_t)PARAM_RING * ctx->n_slots * (size_t)chunks;
+    if (const int rc = alloc_call_scratch(ctx, who, st, words * sizeof(uint32_t), 64, {}, &ctx->cluster_mem, nullptr)) return rc;
+    ctx->d_cluster_counts = (uint32_t *)ctx->cluster_mem.dev;
+    ctx->cluster_cell_chunks = chunks;
+    return GG_OK;
+}
+
+// The obstacle clusters of many labelled clouds (k15_cluster.hip), in the frame of gg_rasterize_clouds and with the same per-cloud records:
+// nothing is synchronised, no map is filled or read beyond its `ground` layer, and no host-side flag (fresh, lazy_pending, liveness) changes.
+int gg_cluster_clouds(gg_context *ctx, const gg_cloud_clusters *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_cluster_clouds";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_cloud_clusters");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    if (!x->d_cell_cluster || !x->d_n_clusters) return fail(ctx, GG_ERR_INVALID, who, "d_cell_cluster and d_n_clusters are required");
+    if (x->min_points < 1) return fail(ctx, GG_ERR_INVALID, who, "min_points < 1");
+    if (x->min_height != x->min_height || x->max_height != x->max_height) return fail(ctx, GG_ERR_INVALID, who, "min_height or max_height is NaN");
+    if (x->connectivity != 4 && x->connectivity != 8) return fail(ctx, GG_ERR_INVALID, who, "connectivity is 4 or 8");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->plane_stride < (size_t)ctx->arena.g.C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
+    if (x->max_clusters < 0) return fail(ctx, GG_ERR_INVALID, who, "max_clusters < 0");
+    if (x->d_clusters && x->max_clusters == 0) return fail(ctx, GG_ERR_INVALID, who, "d_clusters is given with max_clusters == 0");
+    MapCall f;
+    SplitCloud *dc = nullptr;
+    ClusterArgs ca;
+    const LabelledClouds in{x->n, x->first_slot, x->slots, x->point_format, x->d_points, x->cloud_stride, x->n_points, x->transforms, x->d_labels, x->d_label_masks};
+    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &dc, &ca.nch, ensure_cluster_scratch)) return rc;
+    ca.clouds = dc;
+    ca.point_format = x->point_format;
+    ca.points = x->d_points;
+    ca.cloud_stride = x->cloud_stride;
+    ca.labels = x->d_labels;
+    ca.masks = x->d_label_masks;
+    ca.min_points = x->min_points;
+    ca.min_height = x->min_height;
+    ca.max_height = x->max_height;
+    ca.connectivity = x->connectivity;
+    ca.order = x->order;
+    ca.planes = reinterpret_cast<uint32_t *>(x->d_cell_cluster);
+    ca.plane_stride = x->plane_stride;
+    ca.point_cluster = x->d_point_cluster;
+    ca.n_clusters = x->d_n_clusters;
+    ca.records = reinterpret_cast<uint32_t *>(x->d_clusters);
+    ca.max_clusters = x->d_clusters ? x->max_clusters : 0; // (without a table the kernels rank and count only)
+    ca.cell_chunks = ctx->cluster_cell_chunks;
+    ca.chunk_counts = ctx->d_cluster_counts + (size_t)f.g * ctx->n_slots * (size_t)ctx->cluster_cell_chunks;
+    launch_cluster(ctx->arena, ca, x->n, f.st);
     return map_call_end(ctx, f);
 }
 

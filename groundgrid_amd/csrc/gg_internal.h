@@ -374,6 +374,29 @@ struct RasterArgs {
     int nch;                       // chunks per cloud of this call: ceil(max n_points / PW), at least 1
 };
 
+// gg_cluster_clouds (k15_cluster.hip): what its launches share.  The per-cloud records are gg_split_clouds' (SplitCloud, the same ring)
+constexpr int CLUSTER_CHUNK_CELLS = 256; // cells per work-group of the cell launches = per root counter of the call scratch
+struct ClusterArgs {
+    const SplitCloud *clouds;
+    int point_format;
+    const void *points;
+    size_t cloud_stride;
+    const uint8_t *labels, *masks; // exactly one of the two
+    int min_points;
+    float min_height, max_height;
+    int connectivity;              // 4 or 8
+    int order;                     // GG_PLANES_*
+    uint32_t *planes;              // the caller's d_cell_cluster as 32-bit words: cloud i's plane at planes + i * plane_stride
+    size_t plane_stride;
+    int32_t *point_cluster;        // [cloud][cloud_stride]; null: nobody asked
+    int32_t *n_clusters;           // [cloud]
+    uint32_t *records;             // the caller's d_clusters as 32-bit words, eight per gg_cluster: [cloud][max_clusters]; null: no table
+    int max_clusters;
+    uint32_t *chunk_counts;        // call scratch: [cloud][cell_chunks] roots of the chunk (k_cluster_flatten), then their exclusive prefix (k_cluster_scan)
+    int cell_chunks;               // ceil(rows * cols / CLUSTER_CHUNK_CELLS)
+    int nch;                       // chunks per cloud of this call: ceil(max n_points / PW), at least 1
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -417,6 +440,7 @@ void launch_slopes(const Arena &a, const PlaneArgs &x, int n_maps, int variant, 
 void launch_images(const Arena &a, const ImageArgs &x, int n_maps, int variant, hipStream_t s);  // k11_images.hip; variant 0 = the tiled kernels, 1 = cell by cell
 void launch_split(const Arena &a, const SplitArgs &x, int n_clouds, hipStream_t s);              // k12_split.hip: k_split_count, then k_split_scatter
 void launch_raster(const Arena &a, const RasterArgs &x, int n_clouds, hipStream_t s);            // k13_raster.hip: k_raster_init, k_raster_scatter, k_raster_finalise
+void launch_cluster(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s);          // k15_cluster.hip: count, seed, merge, flatten, scan, rank, apply, points, finalise
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

@@ -724,6 +724,79 @@ int gg_export_slopes(gg_context *ctx, int n, const int32_t *slots, int first_slo
                      float *d_dst, size_t plane_stride, void *stream);
 #define GG_HAS_EXPORT_SLOPES 1
 
+/* The OBSTACLE CLUSTERS of a batch in DEVICE memory: the connected components of the occupied cells of every cloud's obstacle grid -- the
+ * objects -- as a plane of cluster ids, a table of the clusters and a cluster id per point: the step that follows a ground segmenter, which
+ * a caller otherwise composes from gg_rasterize_clouds, a download, a connected-components pass per map on the host and an upload.  One call
+ * for many maps; cloud i meets map slots ? slots[i] : first_slot + i (distinct, inside the context).  The ten leading members are those of
+ * gg_cloud_raster, with the same meaning and the same checks.
+ *   participation  point p < n_points[i] of cloud i participates when (1) its label is 99 (mask code 2; any other byte selects nothing),
+ *               (2) it lies inside its map by the path's own inside test and index arithmetic (:222-231) under the map's current position --
+ *               with `transforms`, tested on the map-frame point the path computes -- and (3) its height h = z_map - g satisfies
+ *               !(h < min_height) && !(h > max_height).
+ *   height      h is one float subtraction against the `ground` layer of the cloud's map AS IT STANDS WHEN THE CALL RUNS.  A NaN h
+ *               participates; min_height = -INFINITY and max_height = +INFINITY admit everything.  A FRESH map's g is its constant odom_z.
+ *   occupied    a cell is occupied when at least min_points points participate in it.
+ *   cluster     a connected component of occupied cells.  Under connectivity 4 the neighbours of (r, c) are (r +- 1, c) and (r, c +- 1);
+ *               under connectivity 8 the four diagonals as well.  Nothing wraps at the border: (r, cols - 1) and (r + 1, 0) are not
+ *               neighbours, although their row-major indices are consecutive.
+ *   numbering   the clusters of a map are numbered 0 .. K-1 in ascending order of their smallest linear cell index, the index being that of
+ *               `order`: r * cols + c for GG_PLANES_ROWMAJOR, r + c * rows for GG_PLANES_COLMAJOR.  With row-major order the plane is what
+ *               scipy.ndimage.label(occupied, structure)[0] - 1 gives.  The partition does not depend on `order`; the numbering does.
+ *   d_cell_cluster  cloud i's plane of rows * cols int32 at d_cell_cluster + i * plane_stride, cell (row, col) where `order` puts it.  EVERY
+ *               cell of every listed plane is written: -1 where the cell is not occupied, else its cluster id.  The words between
+ *               rows * cols and plane_stride never are.  4-byte alignment.  While the call runs the planes hold intermediate words.
+ *   d_n_clusters[i]  K_i, the true count, also when it exceeds max_clusters.
+ *   d_point_cluster[i][p]  for p < n_points[i] the id of the point's cell when the point participates and the cell is occupied, else -1.
+ *               Elements at and beyond n_points[i] are never written.
+ *   d_clusters[i][k]  written for k < min(K_i, max_clusters), every field; records at and beyond that never are.  cells: the cluster's
+ *               occupied cells; points: the participating points in them; the four bounds: over its cells; first_cell: its smallest linear
+ *               cell index, in `order`; height_max: the largest h of the cluster's participating points, by IEEE totalOrder on the non-NaN
+ *               values (-0.0 < +0.0, +-inf take part), and the quiet NaN 0x7FC00000 when none of them has a non-NaN h.
+ *   determinism only integer atomics (add, min, max) are used -- heights go through an order-preserving key of the float's bits -- and no
+ *               float is ever added: the outputs are bit-identical from run to run and independent of scheduling.
+ * The call is stateless exactly as gg_rasterize_clouds is: it reads the caller's buffers, the maps' `ground` layer and their positions, and
+ * no record a batch left behind.  A FRESH map is neither read nor filled, and it and every other fresh map stay fresh.  None of the nine
+ * per-call layers is read (the three lazily kept ones stay pending), and no layer, position, configuration, score or liveness flag changes.
+ * `stream` and ordering are those of gg_rasterize_clouds: the call enqueues and returns, the host arrays may be freed on return, it waits for
+ * every earlier map mutation, batch, export and import of the context (both halves under GG_FLAG_CONCURRENT_HALVES), and later writers of
+ * these maps on other streams wait for it.  The caller's buffers must stay valid and unmodified until `stream` has passed the call.
+ * Argument errors write nothing and change nothing: every error of gg_rasterize_clouds for the ten shared members, and GG_ERR_INVALID for
+ * null ctx (before the device is touched), null x, n < 0; and with n > 0: null d_cell_cluster or d_n_clusters, min_points < 1, a
+ * connectivity that is not 4 or 8, an unknown order, plane_stride < rows * cols, max_clusters < 0, d_clusters given with max_clusters == 0,
+ * a NaN min_height or max_height.  n == 0 is GG_OK before anything else is looked at.  The first call of a context may allocate
+ * (GG_ERR_NOMEM) and block; later calls only enqueue.  Capture into a caller's graph is not supported. */
+typedef struct gg_cluster {        /* 32 bytes */
+    int32_t cells;                 /* occupied cells of the cluster */
+    int32_t points;                /* participating points in those cells */
+    int32_t row_min, row_max, col_min, col_max;
+    float   height_max;            /* largest height of its participating points; 0x7FC00000: none that is not NaN */
+    int32_t first_cell;            /* smallest linear cell index of the cluster, in `order` */
+} gg_cluster;
+typedef struct gg_cloud_clusters {
+    int n;                         /* clouds */
+    int first_slot;                /* cloud i meets map first_slot + i when slots == NULL */
+    const int32_t *slots;          /* host [n], nullable, distinct */
+    int point_format;              /* GG_POINT32 / GG_POINT16 */
+    const void *d_points;          /* [n][cloud_stride], as gg_batch.d_points */
+    size_t cloud_stride;           /* points */
+    const int32_t *n_points;       /* host [n] */
+    const double *transforms;      /* host [n][12], nullable, as gg_batch.transforms */
+    const uint8_t *d_labels;       /* [n][cloud_stride] GG_LABEL_*  -- exactly one of these two */
+    const uint8_t *d_label_masks;  /* [n][(cloud_stride + 3) / 4] 2-bit masks, as gg_batch.d_label_masks */
+    int min_points;                /* >= 1: participating points that make a cell occupied */
+    float min_height, max_height;  /* the height band (not NaN; -INFINITY / +INFINITY: open) */
+    int connectivity;              /* 4 or 8 */
+    int order;                     /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR */
+    int32_t *d_cell_cluster;       /* [n] planes of rows * cols int32, plane_stride apart; required */
+    size_t plane_stride;           /* int32 words, >= rows * cols */
+    int32_t *d_point_cluster;      /* [n][cloud_stride], nullable */
+    int32_t *d_n_clusters;         /* [n], required */
+    gg_cluster *d_clusters;        /* [n][max_clusters], nullable */
+    int max_clusters;              /* >= 0; must be > 0 when d_clusters is given */
+} gg_cloud_clusters;
+int gg_cluster_clouds(gg_context *ctx, const gg_cloud_clusters *x, void *stream);
+#define GG_HAS_CLUSTER_CLOUDS 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
