@@ -149,20 +149,25 @@ class GGSplitSet(C.Structure):
     _fields_ = [("d_points", C.c_void_p), ("d_height", C.c_void_p), ("d_source", C.c_void_p)]
 
 
+# the labelled clouds of a call: the ten leading members of gg_cloud_split, gg_cloud_raster and gg_cloud_clusters
+_LABELLED_CLOUDS = [
+    ("n", C.c_int),
+    ("first_slot", C.c_int),
+    ("slots", C.POINTER(C.c_int32)),
+    ("point_format", C.c_int),
+    ("d_points", C.c_void_p),
+    ("cloud_stride", C.c_size_t),
+    ("n_points", C.POINTER(C.c_int32)),
+    ("transforms", C.POINTER(C.c_double)),
+    ("d_labels", C.c_void_p),
+    ("d_label_masks", C.c_void_p),
+]
+
+
 class GGCloudSplit(C.Structure):
     """gg_cloud_split: the ground and the non-ground points of many labelled clouds as dense clouds, in device memory (gg_split_clouds)"""
 
-    _fields_ = [
-        ("n", C.c_int),
-        ("first_slot", C.c_int),
-        ("slots", C.POINTER(C.c_int32)),
-        ("point_format", C.c_int),
-        ("d_points", C.c_void_p),
-        ("cloud_stride", C.c_size_t),
-        ("n_points", C.POINTER(C.c_int32)),
-        ("transforms", C.POINTER(C.c_double)),
-        ("d_labels", C.c_void_p),
-        ("d_label_masks", C.c_void_p),
+    _fields_ = _LABELLED_CLOUDS + [
         ("ground", GGSplitSet),
         ("nonground", GGSplitSet),
         ("d_counts", C.c_void_p),
@@ -172,17 +177,7 @@ class GGCloudSplit(C.Structure):
 class GGCloudRaster(C.Structure):
     """gg_cloud_raster: the obstacle grid of many labelled clouds as dense planes, in device memory (gg_rasterize_clouds)"""
 
-    _fields_ = [
-        ("n", C.c_int),
-        ("first_slot", C.c_int),
-        ("slots", C.POINTER(C.c_int32)),
-        ("point_format", C.c_int),
-        ("d_points", C.c_void_p),
-        ("cloud_stride", C.c_size_t),
-        ("n_points", C.POINTER(C.c_int32)),
-        ("transforms", C.POINTER(C.c_double)),
-        ("d_labels", C.c_void_p),
-        ("d_label_masks", C.c_void_p),
+    _fields_ = _LABELLED_CLOUDS + [
         ("channel_mask", C.c_uint),
         ("order", C.c_int),
         ("d_dst", C.c_void_p),
@@ -208,17 +203,7 @@ class GGCluster(C.Structure):
 class GGCloudClusters(C.Structure):
     """gg_cloud_clusters: the obstacle clusters of many labelled clouds, in device memory (gg_cluster_clouds)"""
 
-    _fields_ = [
-        ("n", C.c_int),
-        ("first_slot", C.c_int),
-        ("slots", C.POINTER(C.c_int32)),
-        ("point_format", C.c_int),
-        ("d_points", C.c_void_p),
-        ("cloud_stride", C.c_size_t),
-        ("n_points", C.POINTER(C.c_int32)),
-        ("transforms", C.POINTER(C.c_double)),
-        ("d_labels", C.c_void_p),
-        ("d_label_masks", C.c_void_p),
+    _fields_ = _LABELLED_CLOUDS + [
         ("min_points", C.c_int),
         ("min_height", C.c_float),
         ("max_height", C.c_float),

@@ -334,14 +334,8 @@ class GroundSegmentation:
         persistent_only just ground / groundpatch, the state that outlives a cloud (a "cold" start).  on_torch_stream: enqueue on
         the current torch stream (where filter_batch runs) instead of the context's own."""
         n = self.n_slots - first_slot if n_slots is None else n_slots
-        stream = None
-        if on_torch_stream:
-            import torch
-
-            h = torch.cuda.current_stream(self.device).cuda_stream
-            stream = C.c_void_p(h) if h else C.c_void_p(-1)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
         _check(self._L, self._ctx, self._L.gg_reset_maps(self._ctx, first_slot, n, float(pos[0]), float(pos[1]), C.c_float(odom_z),
-                                                          1 if persistent_only else 0, stream), "gg_reset_maps")
+                                                          1 if persistent_only else 0, self._stream_arg(on_torch_stream)), "gg_reset_maps")
         for s in range(first_slot, first_slot + n):
             self._maps[s]._pos = (float(pos[0]), float(pos[1]))
 
@@ -526,10 +520,7 @@ class GroundSegmentation:
         x.d_terrain = res.terrain.data_ptr() if terrain else None
         x.terrain_stride = 3 * self.rows * self.cols
         x.terrain_layout = _lib.GG_TERRAIN_CHW if chw else _lib.GG_TERRAIN_HWC
-        stream = None  # the context's own stream
-        if on_torch_stream:
-            h = torch.cuda.current_stream(self.device).cuda_stream
-            stream = C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
+        stream = self._stream_arg(on_torch_stream)
         _check(self._L, self._ctx, self._L.gg_export_images(self._ctx, C.byref(x), stream), "gg_export_images")
         return res
 
@@ -548,15 +539,8 @@ class GroundSegmentation:
         import torch
 
         self._torch_used = True
-        assert points.is_cuda and points.dtype == torch.uint8 and points.dim() == 3 and points.is_contiguous()
-        B, stride, rec = points.shape
-        assert rec in (16, 32)
-        if (labels is None) == (masks is None):
-            raise ValueError("split_clouds: exactly one of labels and masks")
-        given = labels if labels is not None else masks
-        want_shape = (B, stride) if labels is not None else (B, (stride + 3) // 4)
-        if not (torch.is_tensor(given) and given.is_cuda and given.dtype == torch.uint8 and given.is_contiguous() and tuple(given.shape) == want_shape):
-            raise ValueError(f"split_clouds: {'labels' if labels is not None else 'masks'} must be a contiguous CUDA uint8 tensor of shape {want_shape}")
+        x = _lib.GGCloudSplit()
+        B, stride, keep = self._labelled_clouds("split_clouds", x, points, n_points, labels, masks, transforms, slots, first_slot)
         res = out if out is not None else SplitOutputs()
         want = {"counts": ((B, 2), torch.int32)}
         for name, on in (("ground", ground), ("nonground", nonground)):
@@ -573,27 +557,12 @@ class GroundSegmentation:
                 setattr(res, field, torch.empty(spec[0], dtype=spec[1], device=points.device))
             elif not (t.is_cuda and t.dtype == spec[1] and tuple(t.shape) == spec[0] and t.is_contiguous()):
                 raise ValueError(f"split_clouds: out.{field} must be a contiguous CUDA {spec[1]} tensor of shape {spec[0]}")
-        npts = (C.c_int32 * max(B, 1))(*[int(v) for v in n_points])
-        x = _lib.GGCloudSplit()
-        x.n, x.first_slot, x.point_format = B, int(first_slot), _lib.GG_POINT16 if rec == 16 else _lib.GG_POINT32
-        x.d_points, x.cloud_stride, x.n_points = points.data_ptr(), stride, npts
-        if slots is not None:
-            sl = (C.c_int32 * max(B, 1))(*[int(v) for v in slots])
-            x.slots = sl
-        if transforms is not None:  # [B, 3, 4] map <- cloud frame, as for filter_batch
-            tfs = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(B, 12))
-            x.transforms = tfs.ctypes.data_as(C.POINTER(C.c_double))
-        x.d_labels = labels.data_ptr() if labels is not None else None
-        x.d_label_masks = masks.data_ptr() if masks is not None else None
         for name, dst in (("ground", x.ground), ("nonground", x.nonground)):
             for k in ("points", "height", "source"):
                 t = getattr(res, f"{name}_{k}")
                 setattr(dst, f"d_{k}", t.data_ptr() if t is not None else None)
         x.d_counts = res.counts.data_ptr()
-        stream = None  # the context's own stream
-        if on_torch_stream:
-            h = torch.cuda.current_stream(points.device).cuda_stream
-            stream = C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
+        stream = self._stream_arg(on_torch_stream, points.device)
         _check(self._L, self._ctx, self._L.gg_split_clouds(self._ctx, C.byref(x), stream), "gg_split_clouds")
         return res
 
@@ -612,15 +581,8 @@ class GroundSegmentation:
         import torch
 
         self._torch_used = True
-        assert points.is_cuda and points.dtype == torch.uint8 and points.dim() == 3 and points.is_contiguous()
-        B, stride, rec = points.shape
-        assert rec in (16, 32)
-        if (labels is None) == (masks is None):
-            raise ValueError("rasterize_clouds: exactly one of labels and masks")
-        given = labels if labels is not None else masks
-        want_shape = (B, stride) if labels is not None else (B, (stride + 3) // 4)
-        if not (torch.is_tensor(given) and given.is_cuda and given.dtype == torch.uint8 and given.is_contiguous() and tuple(given.shape) == want_shape):
-            raise ValueError(f"rasterize_clouds: {'labels' if labels is not None else 'masks'} must be a contiguous CUDA uint8 tensor of shape {want_shape}")
+        x = _lib.GGCloudRaster()
+        B, stride, keep = self._labelled_clouds("rasterize_clouds", x, points, n_points, labels, masks, transforms, slots, first_slot)
         channels = list(channels)
         unknown = [k for k in channels if k not in _lib.RASTER_CHANNELS]
         if unknown:
@@ -634,25 +596,10 @@ class GroundSegmentation:
             out = torch.empty(shape, dtype=torch.float32, device=points.device)
         elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
             raise ValueError(f"rasterize_clouds: out must be a contiguous CUDA float32 tensor of shape {shape}")
-        npts = (C.c_int32 * max(B, 1))(*[int(v) for v in n_points])
-        x = _lib.GGCloudRaster()
-        x.n, x.first_slot, x.point_format = B, int(first_slot), _lib.GG_POINT16 if rec == 16 else _lib.GG_POINT32
-        x.d_points, x.cloud_stride, x.n_points = points.data_ptr(), stride, npts
-        if slots is not None:
-            sl = (C.c_int32 * max(B, 1))(*[int(v) for v in slots])
-            x.slots = sl
-        if transforms is not None:  # [B, 3, 4] map <- cloud frame, as for filter_batch
-            tfs = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(B, 12))
-            x.transforms = tfs.ctypes.data_as(C.POINTER(C.c_double))
-        x.d_labels = labels.data_ptr() if labels is not None else None
-        x.d_label_masks = masks.data_ptr() if masks is not None else None
         x.channel_mask = sum(1 << _lib.RASTER_CHANNELS.index(k) for k in channels)
         x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
         x.d_dst, x.plane_stride = out.data_ptr(), self.rows * self.cols
-        stream = None  # the context's own stream
-        if on_torch_stream:
-            h = torch.cuda.current_stream(points.device).cuda_stream
-            stream = C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
+        stream = self._stream_arg(on_torch_stream, points.device)
         _check(self._L, self._ctx, self._L.gg_rasterize_clouds(self._ctx, C.byref(x), stream), "gg_rasterize_clouds")
         return out
 
@@ -674,15 +621,8 @@ class GroundSegmentation:
         import torch
 
         self._torch_used = True
-        assert points.is_cuda and points.dtype == torch.uint8 and points.dim() == 3 and points.is_contiguous()
-        B, stride, rec = points.shape
-        assert rec in (16, 32)
-        if (labels is None) == (masks is None):
-            raise ValueError("cluster_clouds: exactly one of labels and masks")
-        given = labels if labels is not None else masks
-        want_shape = (B, stride) if labels is not None else (B, (stride + 3) // 4)
-        if not (torch.is_tensor(given) and given.is_cuda and given.dtype == torch.uint8 and given.is_contiguous() and tuple(given.shape) == want_shape):
-            raise ValueError(f"cluster_clouds: {'labels' if labels is not None else 'masks'} must be a contiguous CUDA uint8 tensor of shape {want_shape}")
+        x = _lib.GGCloudClusters()
+        B, stride, keep = self._labelled_clouds("cluster_clouds", x, points, n_points, labels, masks, transforms, slots, first_slot)
         if connectivity not in (4, 8):
             raise ValueError("cluster_clouds: connectivity is 4 or 8")
         if order not in ("row", "col"):
@@ -703,18 +643,6 @@ class GroundSegmentation:
                 setattr(res, field, torch.empty(shape, dtype=torch.int32, device=points.device))
             elif not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()):
                 raise ValueError(f"cluster_clouds: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {shape}")
-        npts = (C.c_int32 * max(B, 1))(*[int(v) for v in n_points])
-        x = _lib.GGCloudClusters()
-        x.n, x.first_slot, x.point_format = B, int(first_slot), _lib.GG_POINT16 if rec == 16 else _lib.GG_POINT32
-        x.d_points, x.cloud_stride, x.n_points = points.data_ptr(), stride, npts
-        if slots is not None:
-            sl = (C.c_int32 * max(B, 1))(*[int(v) for v in slots])
-            x.slots = sl
-        if transforms is not None:  # [B, 3, 4] map <- cloud frame, as for filter_batch
-            tfs = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(B, 12))
-            x.transforms = tfs.ctypes.data_as(C.POINTER(C.c_double))
-        x.d_labels = labels.data_ptr() if labels is not None else None
-        x.d_label_masks = masks.data_ptr() if masks is not None else None
         x.min_points, x.min_height, x.max_height, x.connectivity = int(min_points), float(min_height), float(max_height), int(connectivity)
         x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
         x.d_cell_cluster, x.plane_stride = res.cell_cluster.data_ptr(), self.rows * self.cols
@@ -722,10 +650,7 @@ class GroundSegmentation:
         x.d_n_clusters = res.n_clusters.data_ptr()
         x.d_clusters = res.clusters.data_ptr() if max_clusters else None
         x.max_clusters = max_clusters
-        stream = None  # the context's own stream
-        if on_torch_stream:
-            h = torch.cuda.current_stream(points.device).cuda_stream
-            stream = C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)  # (0 = torch's default stream = GG_STREAM_DEFAULT)
+        stream = self._stream_arg(on_torch_stream, points.device)
         _check(self._L, self._ctx, self._L.gg_cluster_clouds(self._ctx, C.byref(x), stream), "gg_cluster_clouds")
         return res
 
@@ -797,6 +722,46 @@ class GroundSegmentation:
         return c, bool(own.value)
 
     # -- the score of a labelled cloud: per-map evaluator counters on the device (scripts/eval_groundpoint_classifier.py:95-132)
+    def _stream_arg(self, on_torch_stream: bool, device=None, handle=None):
+        """The `stream` argument of a C call: None, the context's own stream, or with on_torch_stream the caller's `handle` or, without
+        one, the current torch stream of `device` (default: the context's).  0 = torch's default stream = GG_STREAM_DEFAULT: NULL would
+        mean the context's own stream to the library."""
+        if not on_torch_stream:
+            return None
+        if handle is None:
+            import torch
+
+            handle = torch.cuda.current_stream(self.device if device is None else device).cuda_stream
+        return C.c_void_p(handle if handle else _lib.GG_STREAM_DEFAULT)
+
+    def _labelled_clouds(self, who, x, points, n_points, labels, masks, transforms, slots, first_slot):
+        """What split_clouds, rasterize_clouds and cluster_clouds (`who`) share: checks points and labels / masks and fills the ten leading
+        members of the fresh gg_cloud_* structure `x`.  Returns (B, stride, keep): `keep` holds the host arrays `x` points to, and the
+        caller keeps it referenced until the C call has returned."""
+        import torch
+
+        assert points.is_cuda and points.dtype == torch.uint8 and points.dim() == 3 and points.is_contiguous()
+        B, stride, rec = points.shape
+        assert rec in (16, 32)
+        if (labels is None) == (masks is None):
+            raise ValueError(f"{who}: exactly one of labels and masks")
+        given = labels if labels is not None else masks
+        want_shape = (B, stride) if labels is not None else (B, (stride + 3) // 4)
+        if not (torch.is_tensor(given) and given.is_cuda and given.dtype == torch.uint8 and given.is_contiguous() and tuple(given.shape) == want_shape):
+            raise ValueError(f"{who}: {'labels' if labels is not None else 'masks'} must be a contiguous CUDA uint8 tensor of shape {want_shape}")
+        keep = [(C.c_int32 * max(B, 1))(*[int(v) for v in n_points])]
+        x.n, x.first_slot, x.point_format = B, int(first_slot), _lib.GG_POINT16 if rec == 16 else _lib.GG_POINT32
+        x.d_points, x.cloud_stride, x.n_points = points.data_ptr(), stride, keep[0]
+        if slots is not None:
+            keep.append((C.c_int32 * max(B, 1))(*[int(v) for v in slots]))
+            x.slots = keep[-1]
+        if transforms is not None:  # [B, 3, 4] map <- cloud frame, as for filter_batch
+            keep.append(np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(B, 12)))
+            x.transforms = keep[-1].ctypes.data_as(C.POINTER(C.c_double))
+        x.d_labels = labels.data_ptr() if labels is not None else None
+        x.d_label_masks = masks.data_ptr() if masks is not None else None
+        return B, stride, keep
+
     def _slot_args(self, slots, first_slot, n):
         if slots is not None:
             sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
@@ -1049,10 +1014,7 @@ class GroundSegmentation:
     def batch_fence(self, stream=None):
         """GG_FLAG_CONCURRENT_HALVES: order the current torch stream (or `stream`) after both halves of the batches enqueued so far --
         before anything the caller enqueues itself reads their outputs."""
-        import torch
-
-        h = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
-        _check(self._L, self._ctx, self._L.gg_batch_fence(self._ctx, C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT)), "gg_batch_fence")
+        _check(self._L, self._ctx, self._L.gg_batch_fence(self._ctx, self._stream_arg(True, handle=stream)), "gg_batch_fence")
 
     def kernel_times(self, reset: bool = True):
         """(ms[7], launches[7]) accumulated under set_flags(profile=True)."""

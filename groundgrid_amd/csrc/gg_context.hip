@@ -2358,8 +2358,8 @@ struct LabelledClouds {
 };
 
 // Their frame, the export's: the arguments are checked before anything is touched (in.n > 0), then the call's ring entry is taken, `f->st`
-// ordered behind the context and one SplitCloud per cloud uploaded (*dc).  The caller enqueues its kernels on f->st, then map_call_end.
-static int labelled_clouds_begin(gg_context *ctx, const char *who, const LabelledClouds &in, void *stream, MapCall *f, SplitCloud **dc, int *nch,
+// ordered behind the context, one SplitCloud per cloud uploaded and *cl filled.  The caller enqueues its kernels on f->st, then map_call_end.
+static int labelled_clouds_begin(gg_context *ctx, const char *who, const LabelledClouds &in, void *stream, MapCall *f, CloudArgs *cl,
                                  int (*ensure_more)(gg_context *, const char *, hipStream_t) = nullptr)
 {
     if (!in.d_points || !in.n_points) return fail(ctx, GG_ERR_INVALID, who, "d_points and n_points are required");
@@ -2381,7 +2381,7 @@ static int labelled_clouds_begin(gg_context *ctx, const char *who, const Labelle
         if (const int rc = ensure_more(ctx, who, pick_stream(ctx, stream))) return rc;
     if (const int rc = map_call_begin(ctx, who, in.n, in.slots, in.first_slot, stream, false, f)) return rc;
     SplitCloud *hc = ctx->h_split_clouds + (size_t)f->g * ctx->n_slots;
-    *dc = ctx->d_split_clouds + (size_t)f->g * ctx->n_slots;
+    SplitCloud *dc = ctx->d_split_clouds + (size_t)f->g * ctx->n_slots;
     for (int i = 0; i < in.n; ++i) {
         SplitCloud &c = hc[i];
         c.slot = f->hm[i].slot;
@@ -2394,8 +2394,9 @@ static int labelled_clouds_begin(gg_context *ctx, const char *who, const Labelle
         c.pos_y = ctx->pos_y[c.slot];
         for (int k = 0; k < 12; ++k) c.tf[k] = in.transforms ? in.transforms[(size_t)12 * i + k] : 0.0;
     }
-    HIPCHK(ctx, hipMemcpyAsync(*dc, hc, sizeof(SplitCloud) * in.n, hipMemcpyHostToDevice, f->st));
-    *nch = std::max(1, (max_n + ctx->arena.PW - 1) / ctx->arena.PW); // (<= NCH: n_points <= max_points.  At least one: the split writes an empty cloud's counts)
+    HIPCHK(ctx, hipMemcpyAsync(dc, hc, sizeof(SplitCloud) * in.n, hipMemcpyHostToDevice, f->st));
+    const int nch = std::max(1, (max_n + ctx->arena.PW - 1) / ctx->arena.PW); // (<= NCH: n_points <= max_points.  At least one: the split writes an empty cloud's counts)
+    *cl = CloudArgs{dc, in.point_format, in.d_points, in.cloud_stride, in.d_labels, in.d_label_masks, nch};
     return GG_OK;
 }
 
@@ -2410,16 +2411,9 @@ int gg_split_clouds(gg_context *ctx, const gg_cloud_split *x, void *stream)
     if (x->n == 0) return GG_OK;
     if (!x->d_counts) return fail(ctx, GG_ERR_INVALID, who, "d_counts is required");
     MapCall f;
-    SplitCloud *dc = nullptr;
     SplitArgs sa;
     const LabelledClouds in{x->n, x->first_slot, x->slots, x->point_format, x->d_points, x->cloud_stride, x->n_points, x->transforms, x->d_labels, x->d_label_masks};
-    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &dc, &sa.nch)) return rc;
-    sa.clouds = dc;
-    sa.point_format = x->point_format;
-    sa.points = x->d_points;
-    sa.cloud_stride = x->cloud_stride;
-    sa.labels = x->d_labels;
-    sa.masks = x->d_label_masks;
+    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &sa.cl)) return rc;
     sa.set[0] = SplitSet{x->ground.d_points, x->ground.d_height, x->ground.d_source};
     sa.set[1] = SplitSet{x->nonground.d_points, x->nonground.d_height, x->nonground.d_source};
     sa.counts = x->d_counts;
@@ -2442,16 +2436,9 @@ int gg_rasterize_clouds(gg_context *ctx, const gg_cloud_raster *x, void *stream)
     if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
     if (x->plane_stride < (size_t)ctx->arena.g.C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
     MapCall f;
-    SplitCloud *dc = nullptr;
     RasterArgs ra;
     const LabelledClouds in{x->n, x->first_slot, x->slots, x->point_format, x->d_points, x->cloud_stride, x->n_points, x->transforms, x->d_labels, x->d_label_masks};
-    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &dc, &ra.nch)) return rc;
-    ra.clouds = dc;
-    ra.point_format = x->point_format;
-    ra.points = x->d_points;
-    ra.cloud_stride = x->cloud_stride;
-    ra.labels = x->d_labels;
-    ra.masks = x->d_label_masks;
+    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &ra.cl)) return rc;
     ra.channel_mask = x->channel_mask;
     ra.n_planes = 0;
     for (int ch = 0; ch < GG_NUM_RASTER_CHANNELS; ++ch) ra.plane_of[ch] = ((x->channel_mask >> ch) & 1u) ? ra.n_planes++ : -1;
@@ -2492,16 +2479,9 @@ int gg_cluster_clouds(gg_context *ctx, const gg_cloud_clusters *x, void *stream)
     if (x->max_clusters < 0) return fail(ctx, GG_ERR_INVALID, who, "max_clusters < 0");
     if (x->d_clusters && x->max_clusters == 0) return fail(ctx, GG_ERR_INVALID, who, "d_clusters is given with max_clusters == 0");
     MapCall f;
-    SplitCloud *dc = nullptr;
     ClusterArgs ca;
     const LabelledClouds in{x->n, x->first_slot, x->slots, x->point_format, x->d_points, x->cloud_stride, x->n_points, x->transforms, x->d_labels, x->d_label_masks};
-    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &dc, &ca.nch, ensure_cluster_scratch)) return rc;
-    ca.clouds = dc;
-    ca.point_format = x->point_format;
-    ca.points = x->d_points;
-    ca.cloud_stride = x->cloud_stride;
-    ca.labels = x->d_labels;
-    ca.masks = x->d_label_masks;
+    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &ca.cl, ensure_cluster_scratch)) return rc;
     ca.min_points = x->min_points;
     ca.min_height = x->min_height;
     ca.max_height = x->max_height;

@@ -346,42 +346,37 @@ struct SplitSet {
     float *height;
     int32_t *source;
 };
-struct SplitArgs {
+// the labelled clouds of a call, the first member of every labelled-cloud call's arguments (cloud_walk.h walks them): labelled_clouds_begin fills it
+struct CloudArgs {
     const SplitCloud *clouds;
     int point_format;
     const void *points;
     size_t cloud_stride;
     const uint8_t *labels, *masks; // exactly one of the two
+    int nch;                       // chunks per cloud of this call: ceil(max n_points / PW), at least 1
+};
+struct SplitArgs {
+    CloudArgs cl;
     SplitSet set[2];               // ground, nonground
     int32_t *counts;               // [cloud][2]
     uint2 *chunk_counts;           // call scratch: [cloud][nch] (points in ground, in nonground) of the chunk, written by k_split_count
-    int nch;                       // chunks per cloud of this call: ceil(max n_points / PW), at least 1
 };
 
 // gg_rasterize_clouds (k13_raster.hip): what its three launches share.  The per-cloud records are gg_split_clouds' (SplitCloud, the same ring)
 struct RasterArgs {
-    const SplitCloud *clouds;
-    int point_format;
-    const void *points;
-    size_t cloud_stride;
-    const uint8_t *labels, *masks; // exactly one of the two
+    CloudArgs cl;
     unsigned channel_mask;         // bit per GG_RASTER_*
     int n_planes;                  // its popcount
     int plane_of[GG_NUM_RASTER_CHANNELS]; // channel -> its plane among a cloud's n_planes (-1: not named)
     int order;                     // GG_PLANES_*
     uint32_t *planes;              // the caller's d_dst as 32-bit words: cloud i's plane k at planes + (i * n_planes + k) * plane_stride
     size_t plane_stride;
-    int nch;                       // chunks per cloud of this call: ceil(max n_points / PW), at least 1
 };
 
 // gg_cluster_clouds (k15_cluster.hip): what its launches share.  The per-cloud records are gg_split_clouds' (SplitCloud, the same ring)
 constexpr int CLUSTER_CHUNK_CELLS = 256; // cells per work-group of the cell launches = per root counter of the call scratch
 struct ClusterArgs {
-    const SplitCloud *clouds;
-    int point_format;
-    const void *points;
-    size_t cloud_stride;
-    const uint8_t *labels, *masks; // exactly one of the two
+    CloudArgs cl;
     int min_points;
     float min_height, max_height;
     int connectivity;              // 4 or 8
@@ -394,7 +389,6 @@ struct ClusterArgs {
     int max_clusters;
     uint32_t *chunk_counts;        // call scratch: [cloud][cell_chunks] roots of the chunk (k_cluster_flatten), then their exclusive prefix (k_cluster_scan)
     int cell_chunks;               // ceil(rows * cols / CLUSTER_CHUNK_CELLS)
-    int nch;                       // chunks per cloud of this call: ceil(max n_points / PW), at least 1
 };
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
@@ -439,7 +433,7 @@ void launch_import(const Arena &a, const PlaneArgs &x, int n_maps, int variant, 
 void launch_slopes(const Arena &a, const PlaneArgs &x, int n_maps, int variant, hipStream_t s); // k14_slopes.hip; x.mask: bit per GG_SLOPE_*; variant 0 = k_slopes_tiled, 1 = k_slopes_gather (cell by cell)
 void launch_images(const Arena &a, const ImageArgs &x, int n_maps, int variant, hipStream_t s);  // k11_images.hip; variant 0 = the tiled kernels, 1 = cell by cell
 void launch_split(const Arena &a, const SplitArgs &x, int n_clouds, hipStream_t s);              // k12_split.hip: k_split_count, then k_split_scatter
-void launch_raster(const Arena &a, const RasterArgs &x, int n_clouds, hipStream_t s);            // k13_raster.hip: k_raster_init, k_raster_scatter, k_raster_finalise
+void launch_raster(const Arena &a, const RasterArgs &x, int n_clouds, hipStream_t s);            // k13_raster.hip: k_raster_planes<false>, k_raster_scatter, k_raster_planes<true>
 void launch_cluster(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s);          // k15_cluster.hip: count, seed, merge, flatten, scan, rank, apply, points, finalise
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone

@@ -3,8 +3,7 @@
 // gets today with `points[labels == 99]` per cloud -- a launch and a device -> host synchronisation per cloud, the output size being data
 // dependent -- in two launches for the whole batch and with the counts left on the device.
 //
-// Both launches use the wave <-> chunk mapping of K1 / K5 / K8 (a.PW points per wavefront, four wavefronts per work-group, grid
-// (ceil(nch / 4), clouds), xcd_contiguous_item: the chunks of a cloud share an L2):
+// Both launches walk the clouds as cloud_walk.h describes (one wavefront per a.PW-point chunk; their bodies hold to its convergence contract):
 //   k_split_count     the number of 49s and of 99s among the labels of every (cloud, chunk) -> one pair in call scratch.  Ballots and
 //                     popcounts: no atomics, nothing depends on an arrival order.
 //   k_split_scatter   a wavefront sums the pairs of its cloud's EARLIER chunks (at most max_points / PW of them: a strided read and a wave
@@ -17,75 +16,43 @@
 //
 // Algorithmic bytes per input point: 1 (labels; 0.25 with masks) in the count, 1 + 16 (32: GG_POINT32) in the scatter, plus per selected
 // point 8 gathered (the (ground, confidence) pair) and 16 + 4 + 4 written.
-#include "gg_device.h"
+#include "cloud_walk.h"
 
 namespace gg {
-
-template <bool MASKS> GG_DEV const uint8_t *split_label_row(const SplitArgs &x, int io)
-{
-    return MASKS ? x.masks + (size_t)io * ((x.cloud_stride + 3) / 4) : x.labels + (size_t)io * x.cloud_stride;
-}
-
-GG_DEV uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-    return v;
-}
 
 template <bool MASKS>
 __global__ __launch_bounds__(256) void k_split_count(const Arena a, const SplitArgs x)
 {
-    const uint32_t item = xcd_contiguous_item(blockIdx.x + blockIdx.y * gridDim.x, gridDim.x * gridDim.y);
-    const int cloud = (int)(item / gridDim.x), bx = (int)(item % gridDim.x);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int chunk = bx * 4 + wave;
-    if (chunk >= x.nch) return; // (uniform over the wavefront)
-    const int n = x.clouds[cloud].n_points, io = x.clouds[cloud].io_index;
-    const int base = min(chunk * a.PW, n);
-    const int end = min(base + a.PW, n);
-    const uint8_t *row = split_label_row<MASKS>(x, io);
-
+    CloudChunk k;
+    if (!cloud_chunk(a, x.cl, k)) return;
     uint32_t n_ground = 0u, n_nonground = 0u;
-    constexpr int ITEMS = 4;
-    for (int p0 = base; p0 < end; p0 += 64 * ITEMS) {
-        uint32_t code[ITEMS];
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) code[j] = split_code<MASKS>(row, min(p0 + j * 64 + lane, end - 1)); // (clamped: the loads do not wait for a test)
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const bool valid = p0 + j * 64 + lane < end;
-            n_ground += (uint32_t)__popcll(__ballot(valid && code[j] == 1u));
-            n_nonground += (uint32_t)__popcll(__ballot(valid && code[j] == 2u));
-        }
-    }
-    if (lane == 0) x.chunk_counts[(size_t)io * x.nch + chunk] = make_uint2(n_ground, n_nonground); // (every chunk of every cloud: an empty one holds (0, 0))
+    walk_chunk<GG_POINT16, MASKS, WALK_CODE>(x.cl, k, [&](int, uint32_t code, const uint4 &, uint32_t) GG_INLINE_LAMBDA {
+        n_ground += (uint32_t)__popcll(__ballot(code == 1u));
+        n_nonground += (uint32_t)__popcll(__ballot(code == 2u));
+    });
+    if (k.lane == 0) x.chunk_counts[(size_t)k.io * x.cl.nch + k.chunk] = make_uint2(n_ground, n_nonground); // (every chunk of every cloud: an empty one holds (0, 0))
 }
 
 template <int FMT, bool MASKS, bool HEIGHTS>
 __global__ __launch_bounds__(256) void k_split_scatter(const Arena a, const SplitArgs x)
 {
-    const uint32_t item = xcd_contiguous_item(blockIdx.x + blockIdx.y * gridDim.x, gridDim.x * gridDim.y);
-    const int cloud = (int)(item / gridDim.x), bx = (int)(item % gridDim.x);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int chunk = bx * 4 + wave;
-    if (chunk >= x.nch) return; // (uniform over the wavefront; there is no barrier below)
-    const SplitCloud &c = x.clouds[cloud];
-    const int n = c.n_points, io = c.io_index;
+    CloudChunk k;
+    if (!cloud_chunk(a, x.cl, k)) return; // (there is no barrier below)
+    const int lane = k.lane, n = k.n;
 
     // the sets' sizes in front of this chunk; the first wavefront of a cloud goes on to the end and leaves the totals
-    const uint2 *pairs = x.chunk_counts + (size_t)io * x.nch;
+    const uint2 *pairs = x.chunk_counts + (size_t)k.io * x.cl.nch;
     uint32_t at[2] = {0u, 0u};
-    for (int q = lane; q < chunk; q += 64) {
+    for (int q = lane; q < k.chunk; q += 64) {
         const uint2 v = pairs[q];
         at[0] += v.x;
         at[1] += v.y;
     }
     at[0] = wave_sum(at[0]);
     at[1] = wave_sum(at[1]);
-    if (chunk == 0) {
+    if (k.chunk == 0) {
         uint32_t t0 = 0u, t1 = 0u;
-        for (int q = lane; q < x.nch; q += 64) {
+        for (int q = lane; q < x.cl.nch; q += 64) {
             const uint2 v = pairs[q];
             t0 += v.x;
             t1 += v.y;
@@ -93,95 +60,48 @@ __global__ __launch_bounds__(256) void k_split_scatter(const Arena a, const Spli
         t0 = wave_sum(t0);
         t1 = wave_sum(t1);
         if (lane == 0) {
-            x.counts[(size_t)io * 2] = (int32_t)t0;
-            x.counts[(size_t)io * 2 + 1] = (int32_t)t1;
+            x.counts[(size_t)k.io * 2] = (int32_t)t0;
+            x.counts[(size_t)k.io * 2 + 1] = (int32_t)t1;
         }
     }
 
-    const int base = min(chunk * a.PW, n);
-    const int end = min(base + a.PW, n);
-    if (base >= end) return;
-    const uint8_t *row = split_label_row<MASKS>(x, io);
-    const uint4 *pts = reinterpret_cast<const uint4 *>(x.points) + (size_t)io * x.cloud_stride * (FMT == GG_POINT16 ? 1 : 2);
-    const size_t out0 = (size_t)io * x.cloud_stride;
-    const bool has_tf = c.has_tf != 0, fresh = c.fresh != 0;
-    const float fresh_z = c.fresh_z;
-    const double pos_x = c.pos_x, pos_y = c.pos_y;
-    double tf[12];
-    if (has_tf) { // (uniform)
-#pragma unroll
-        for (int k = 0; k < 12; ++k) tf[k] = c.tf[k];
-    }
-    const float2 *gp2 = gp2_ptr(a, c.slot);
-
-    constexpr int ITEMS = 4;
-    for (int p0 = base; p0 < end; p0 += 64 * ITEMS) {
-        uint4 v[ITEMS];
-        uint32_t ring[ITEMS], code[ITEMS];
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) { // all windows' loads in flight together (unconditional, at clamped indices)
-            const int p = min(p0 + j * 64 + lane, end - 1);
-            code[j] = split_code<MASKS>(row, p);
-            if (FMT == GG_POINT16) {
-                v[j] = pts[p];
-                ring[j] = v[j].w & 0xFFFFu;
-            } else {
-                v[j] = pts[(size_t)p * 2];                    // x, y, z, pad0
-                ring[j] = pts[(size_t)p * 2 + 1].y & 0xFFFFu; // intensity, ring | pad1 << 16, pad2
+    if (k.base >= k.end) return;
+    const size_t out0 = (size_t)k.io * x.cl.cloud_stride;
+    CloudFrame f;
+    load_cloud_frame(a, x.cl.clouds[k.cloud], f);
+    walk_chunk<FMT, MASKS, WALK_POINT_RING>(x.cl, k, [&](int p, uint32_t sel, const uint4 &v, uint32_t ring) GG_INLINE_LAMBDA {
+        const unsigned long long m0 = __ballot(sel == 1u), m1 = __ballot(sel == 2u);
+        const int s = sel == 2u ? 1 : 0;
+        const uint32_t place = at[s] + (uint32_t)rank_below(s ? m1 : m0); // the point's place in its set: below the set's size, at most n_points <= cloud_stride
+        if (sel && place < (uint32_t)n) { // (place >= n: the labels changed between the two launches -- nothing is written outside the row)
+            const size_t o = out0 + place;
+            const SplitSet &set = x.set[s];
+            float px = __uint_as_float(v.x), py = __uint_as_float(v.y), pz = __uint_as_float(v.z);
+            to_map_frame(f, px, py, pz);
+            if (set.points) reinterpret_cast<uint4 *>(set.points)[o] = make_uint4(__float_as_uint(px), __float_as_uint(py), __float_as_uint(pz), ring);
+            if (set.source) set.source[o] = p;
+            if (HEIGHTS && set.height) {
+                int r, cc; // a selected point outside the map: the caller's labels are not this cloud's
+                set.height[o] = cell_of_point(a, f, px, py, r, cc) ? height_above_ground(a, f, pz, r, cc) : __uint_as_float(QUIET_NAN_BITS);
             }
         }
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const int p = p0 + j * 64 + lane;
-            const uint32_t sel = p < end ? code[j] : 0u;
-            const unsigned long long m0 = __ballot(sel == 1u), m1 = __ballot(sel == 2u);
-            const int s = sel == 2u ? 1 : 0;
-            const uint32_t k = at[s] + (uint32_t)rank_below(s ? m1 : m0); // the point's place in its set: below the set's size, at most n_points <= cloud_stride
-            if (sel && k < (uint32_t)n) { // (k >= n: the labels changed between the two launches -- nothing is written outside the row)
-                const size_t o = out0 + k;
-                const SplitSet &set = x.set[s];
-                float px = __uint_as_float(v[j].x), py = __uint_as_float(v[j].y), pz = __uint_as_float(v[j].z);
-                if (has_tf) transform_point(tf, px, py, pz);
-                if (set.points) reinterpret_cast<uint4 *>(set.points)[o] = make_uint4(__float_as_uint(px), __float_as_uint(py), __float_as_uint(pz), ring[j]);
-                if (set.source) set.source[o] = p;
-                if (HEIGHTS && set.height) {
-                    float h = __uint_as_float(0x7FC00000u); // a selected point outside the map: the caller's labels are not this cloud's
-                    int r, cc;
-                    const bool inside = position_inside(a.g, pos_x, pos_y, (double)px, (double)py);
-                    index_from_position(a.g, pos_x, pos_y, (double)px, (double)py, r, cc);
-                    if (inside && r >= 0 && cc >= 0 && r < a.g.rows && cc < a.g.cols) h = pz - (fresh ? fresh_z : gp2[gp_idx(a, r, cc)].x);
-                    set.height[o] = h;
-                }
-            }
-            at[0] += (uint32_t)__popcll(m0);
-            at[1] += (uint32_t)__popcll(m1);
-        }
-    }
-}
-
-template <int FMT, bool MASKS> static void launch_split_scatter(const Arena &a, const SplitArgs &x, dim3 grid, hipStream_t s)
-{
-    if (x.set[0].height || x.set[1].height)
-        hipLaunchKernelGGL((k_split_scatter<FMT, MASKS, true>), grid, dim3(256), 0, s, a, x);
-    else
-        hipLaunchKernelGGL((k_split_scatter<FMT, MASKS, false>), grid, dim3(256), 0, s, a, x);
+        at[0] += (uint32_t)__popcll(m0);
+        at[1] += (uint32_t)__popcll(m1);
+    });
 }
 
 void launch_split(const Arena &a, const SplitArgs &x, int n_clouds, hipStream_t s)
 {
-    const dim3 grid((x.nch + 3) / 4, n_clouds); // (one launch for the whole call, as K1 / K5 / K8 launch a batch)
-    const bool masks = x.masks != nullptr;
-    if (masks)
-        hipLaunchKernelGGL((k_split_count<true>), grid, dim3(256), 0, s, a, x);
-    else
-        hipLaunchKernelGGL((k_split_count<false>), grid, dim3(256), 0, s, a, x);
-    if (x.point_format == GG_POINT16) {
-        if (masks) launch_split_scatter<GG_POINT16, true>(a, x, grid, s);
-        else launch_split_scatter<GG_POINT16, false>(a, x, grid, s);
-    } else {
-        if (masks) launch_split_scatter<GG_POINT32, true>(a, x, grid, s);
-        else launch_split_scatter<GG_POINT32, false>(a, x, grid, s);
-    }
+    const dim3 grid((x.cl.nch + 3) / 4, n_clouds); // (one launch for the whole call, as K1 / K5 / K8 launch a batch)
+    dispatch_cloud_variant(x.cl, [&](auto fmt, auto masks) {
+        constexpr int FMT = decltype(fmt)::value;
+        constexpr bool MASKS = decltype(masks)::value;
+        hipLaunchKernelGGL((k_split_count<MASKS>), grid, dim3(256), 0, s, a, x);
+        if (x.set[0].height || x.set[1].height)
+            hipLaunchKernelGGL((k_split_scatter<FMT, MASKS, true>), grid, dim3(256), 0, s, a, x);
+        else
+            hipLaunchKernelGGL((k_split_scatter<FMT, MASKS, false>), grid, dim3(256), 0, s, a, x);
+    });
 }
 
 } // namespace gg

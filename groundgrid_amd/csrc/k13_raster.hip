@@ -3,16 +3,13 @@
 // terrain.  What a caller composes today from gg_split_clouds and a scatter-reduce over cell indices it computes itself, in one pass over
 // the points and with the library's own inside test and index arithmetic.
 //
-// Nothing depends on the order in which points arrive: a count is an integer atomic add, a height an integer atomic max / min on the key
-//   key(h) = bits(h) ^ (sign(h) ? 0xFFFFFFFF : 0x80000000)
-// which orders the non-NaN floats as IEEE totalOrder does (-0.0 below +0.0, the infinities at the ends) and maps none of them to 0 or to
-// 0xFFFFFFFF (those would be the bits 0xFFFFFFFF and 0x7FFFFFFF, both NaNs): the two values mark "no point yet".  No float is added.
+// Nothing depends on the order in which points arrive: a count is an integer atomic add, a height an integer atomic max / min on its
+// height_key (cloud_walk.h), which is never 0 or 0xFFFFFFFF: the two values mark "no point yet".  No float is added.
 // Three launches on the caller's planes, no scratch:
 //   k_raster_planes<false>  every word of every named plane := 0 (a count, a max key) or 0xFFFFFFFF (a min key); 16-byte stores.
-//   k_raster_scatter        the wave <-> chunk mapping of K1 / K5 / K12 (a.PW points per wavefront, four wavefronts per work-group, grid
-//                           (ceil(nch / 4), clouds), xcd_contiguous_item), four 64-point windows' loads in flight; per selected point inside
-//                           the map at most one atomic add, one atomic max and one atomic min into its cloud's planes, none of them
-//                           returning a value.  The ground under a point is gathered only where a height channel of its set is named.
+//   k_raster_scatter        the walk of cloud_walk.h (one wavefront per a.PW-point chunk); per selected point inside the map at most one
+//                           atomic add, one atomic max and one atomic min into its cloud's planes, none of them returning a value.  The
+//                           ground under a point is gathered only where a height channel of its set is named.
 //   k_raster_planes<true>   in place: a counter becomes its float, a key its float or the quiet NaN 0x7FC00000 where it still holds the
 //                           initial value.
 // No work-group waits for another, and nothing a batch left behind is read.
@@ -20,25 +17,16 @@
 // Algorithmic bytes: per input point 1 (labels; 0.25 with masks) + 16 (32: GG_POINT32); per selected point inside the map 8 gathered (the
 // (ground, confidence) pair, height channels only) and one 4-byte atomic per named channel of its set; per cell and named plane 4 written by
 // the first launch and 4 read + 4 written by the third.
-#include "gg_device.h"
+#include "cloud_walk.h"
 
 namespace gg {
-
-constexpr uint32_t RASTER_NAN = 0x7FC00000u;
-
-GG_DEV uint32_t height_key(float h)
-{
-    const uint32_t b = __float_as_uint(h);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-GG_DEV uint32_t height_of_key(uint32_t key) { return (key >> 31) ? key ^ 0x80000000u : ~key; }
 
 // kind of a channel: 0 count, 1 max height, 2 min height (GG_RASTER_* come as two such triples)
 GG_DEV uint32_t raster_initial_word(int kind) { return kind == 2 ? 0xFFFFFFFFu : 0u; }
 GG_DEV uint32_t raster_final_word(int kind, uint32_t w)
 {
     if (kind == 0) return __float_as_uint((float)w);
-    return w == raster_initial_word(kind) ? RASTER_NAN : height_of_key(w);
+    return w == raster_initial_word(kind) ? QUIET_NAN_BITS : height_of_key(w);
 }
 
 // Every word of every named plane once, one plane per `parts` consecutive work-groups: 16-byte accesses over the 16-byte aligned body of the
@@ -74,76 +62,32 @@ __global__ __launch_bounds__(256) void k_raster_planes(const Arena a, const Rast
 template <int FMT, bool MASKS, bool HEIGHTS>
 __global__ __launch_bounds__(256) void k_raster_scatter(const Arena a, const RasterArgs x)
 {
-    const uint32_t item = xcd_contiguous_item(blockIdx.x + blockIdx.y * gridDim.x, gridDim.x * gridDim.y);
-    const int cloud = (int)(item / gridDim.x), bx = (int)(item % gridDim.x);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int chunk = bx * 4 + wave;
-    if (chunk >= x.nch) return; // (uniform over the wavefront; there is no barrier below)
-    const SplitCloud &c = x.clouds[cloud];
-    const int n = c.n_points, io = c.io_index;
-    const int base = min(chunk * a.PW, n);
-    const int end = min(base + a.PW, n);
-    if (base >= end) return;
-    const uint8_t *row = MASKS ? x.masks + (size_t)io * ((x.cloud_stride + 3) / 4) : x.labels + (size_t)io * x.cloud_stride;
-    const uint4 *pts = reinterpret_cast<const uint4 *>(x.points) + (size_t)io * x.cloud_stride * (FMT == GG_POINT16 ? 1 : 2);
-    uint32_t *planes = x.planes + (size_t)io * x.n_planes * x.plane_stride;
-    const bool has_tf = c.has_tf != 0, fresh = c.fresh != 0;
-    const float fresh_z = c.fresh_z;
-    const double pos_x = c.pos_x, pos_y = c.pos_y;
-    double tf[12];
-    if (has_tf) { // (uniform)
-#pragma unroll
-        for (int k = 0; k < 12; ++k) tf[k] = c.tf[k];
-    }
-    const float2 *gp2 = gp2_ptr(a, c.slot);
+    CloudChunk k;
+    if (!cloud_chunk(a, x.cl, k) || k.base >= k.end) return; // (uniform over the wavefront; there is no barrier below)
+    uint32_t *planes = x.planes + (size_t)k.io * x.n_planes * x.plane_stride;
     const bool row_major = x.order == GG_PLANES_ROWMAJOR;
-
-    constexpr int ITEMS = 4;
-    for (int p0 = base; p0 < end; p0 += 64 * ITEMS) {
-        uint4 v[ITEMS];
-        uint32_t code[ITEMS];
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) { // all windows' loads in flight together (unconditional, at clamped indices)
-            const int p = min(p0 + j * 64 + lane, end - 1);
-            code[j] = split_code<MASKS>(row, p);
-            v[j] = pts[FMT == GG_POINT16 ? (size_t)p : (size_t)p * 2]; // x, y, z, (ring | pad0)
-        }
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const uint32_t sel = p0 + j * 64 + lane < end ? code[j] : 0u;
-            // the planes of the point's set (-1: not named)
-            const int k_count = sel == 2u ? x.plane_of[GG_RASTER_NONGROUND_COUNT] : x.plane_of[GG_RASTER_GROUND_COUNT];
-            const int k_max = sel == 2u ? x.plane_of[GG_RASTER_NONGROUND_MAX_HEIGHT] : x.plane_of[GG_RASTER_GROUND_MAX_HEIGHT];
-            const int k_min = sel == 2u ? x.plane_of[GG_RASTER_NONGROUND_MIN_HEIGHT] : x.plane_of[GG_RASTER_GROUND_MIN_HEIGHT];
-            if (!sel || (k_count & k_max & k_min) < 0) continue; // (all three -1)
-            float px = __uint_as_float(v[j].x), py = __uint_as_float(v[j].y), pz = __uint_as_float(v[j].z);
-            if (has_tf) transform_point(tf, px, py, pz);
-            int r, cc;
-            const bool inside = position_inside(a.g, pos_x, pos_y, (double)px, (double)py);
-            index_from_position(a.g, pos_x, pos_y, (double)px, (double)py, r, cc);
-            if (!(inside && r >= 0 && cc >= 0 && r < a.g.rows && cc < a.g.cols)) continue; // the caller's labels are not this cloud's: nothing is touched
-            const int cell = row_major ? r * a.g.cols + cc : r + cc * a.g.rows; // < rows * cols <= plane_stride
-            if (k_count >= 0) atomicAdd(planes + (size_t)k_count * x.plane_stride + cell, 1u);
-            if (HEIGHTS && (k_max & k_min) >= 0) {
-                const float h = pz - (fresh ? fresh_z : gp2[gp_idx(a, r, cc)].x);
-                if (h == h) { // (a NaN height is counted and takes part in neither extreme)
-                    const uint32_t key = height_key(h);
-                    if (k_max >= 0) atomicMax(planes + (size_t)k_max * x.plane_stride + cell, key);
-                    if (k_min >= 0) atomicMin(planes + (size_t)k_min * x.plane_stride + cell, key);
-                }
+    CloudFrame f;
+    load_cloud_frame(a, x.cl.clouds[k.cloud], f);
+    walk_chunk<FMT, MASKS, WALK_POINT>(x.cl, k, [&](int, uint32_t sel, const uint4 &v, uint32_t) GG_INLINE_LAMBDA { // (no cross-lane operation: the returns are free)
+        // the planes of the point's set (-1: not named)
+        const int k_count = sel == 2u ? x.plane_of[GG_RASTER_NONGROUND_COUNT] : x.plane_of[GG_RASTER_GROUND_COUNT];
+        const int k_max = sel == 2u ? x.plane_of[GG_RASTER_NONGROUND_MAX_HEIGHT] : x.plane_of[GG_RASTER_GROUND_MAX_HEIGHT];
+        const int k_min = sel == 2u ? x.plane_of[GG_RASTER_NONGROUND_MIN_HEIGHT] : x.plane_of[GG_RASTER_GROUND_MIN_HEIGHT];
+        if (!sel || (k_count & k_max & k_min) < 0) return; // (all three -1)
+        float px = __uint_as_float(v.x), py = __uint_as_float(v.y), pz = __uint_as_float(v.z);
+        int r, cc;
+        if (!locate_point(a, f, px, py, pz, r, cc)) return; // the caller's labels are not this cloud's: nothing is touched
+        const int cell = linear_cell(a, row_major, r, cc);
+        if (k_count >= 0) atomicAdd(planes + (size_t)k_count * x.plane_stride + cell, 1u);
+        if (HEIGHTS && (k_max & k_min) >= 0) {
+            const float h = height_above_ground(a, f, pz, r, cc);
+            if (h == h) { // (a NaN height is counted and takes part in neither extreme)
+                const uint32_t key = height_key(h);
+                if (k_max >= 0) atomicMax(planes + (size_t)k_max * x.plane_stride + cell, key);
+                if (k_min >= 0) atomicMin(planes + (size_t)k_min * x.plane_stride + cell, key);
             }
         }
-    }
-}
-
-template <int FMT, bool MASKS> static void launch_raster_scatter(const Arena &a, const RasterArgs &x, dim3 grid, hipStream_t s)
-{
-    constexpr unsigned heights = (1u << GG_RASTER_NONGROUND_MAX_HEIGHT) | (1u << GG_RASTER_NONGROUND_MIN_HEIGHT) | (1u << GG_RASTER_GROUND_MAX_HEIGHT) |
-                                 (1u << GG_RASTER_GROUND_MIN_HEIGHT);
-    if (x.channel_mask & heights)
-        hipLaunchKernelGGL((k_raster_scatter<FMT, MASKS, true>), grid, dim3(256), 0, s, a, x);
-    else // (a count-only call gathers no ground)
-        hipLaunchKernelGGL((k_raster_scatter<FMT, MASKS, false>), grid, dim3(256), 0, s, a, x);
+    });
 }
 
 void launch_raster(const Arena &a, const RasterArgs &x, int n_clouds, hipStream_t s)
@@ -151,15 +95,17 @@ void launch_raster(const Arena &a, const RasterArgs &x, int n_clouds, hipStream_
     const int parts = (a.g.C / 4 + 1 + 255) / 256; // threads per plane: its 16-byte body, and at least the three single words at either end
     const dim3 plane_grid((uint32_t)parts * (uint32_t)(n_clouds * x.n_planes));
     hipLaunchKernelGGL((k_raster_planes<false>), plane_grid, dim3(256), 0, s, a, x, parts);
-    const dim3 grid((x.nch + 3) / 4, n_clouds);
-    const bool masks = x.masks != nullptr;
-    if (x.point_format == GG_POINT16) {
-        if (masks) launch_raster_scatter<GG_POINT16, true>(a, x, grid, s);
-        else launch_raster_scatter<GG_POINT16, false>(a, x, grid, s);
-    } else {
-        if (masks) launch_raster_scatter<GG_POINT32, true>(a, x, grid, s);
-        else launch_raster_scatter<GG_POINT32, false>(a, x, grid, s);
-    }
+    const dim3 grid((x.cl.nch + 3) / 4, n_clouds);
+    constexpr unsigned heights = (1u << GG_RASTER_NONGROUND_MAX_HEIGHT) | (1u << GG_RASTER_NONGROUND_MIN_HEIGHT) | (1u << GG_RASTER_GROUND_MAX_HEIGHT) |
+                                 (1u << GG_RASTER_GROUND_MIN_HEIGHT);
+    dispatch_cloud_variant(x.cl, [&](auto fmt, auto masks) {
+        constexpr int FMT = decltype(fmt)::value;
+        constexpr bool MASKS = decltype(masks)::value;
+        if (x.channel_mask & heights)
+            hipLaunchKernelGGL((k_raster_scatter<FMT, MASKS, true>), grid, dim3(256), 0, s, a, x);
+        else // (a count-only call gathers no ground)
+            hipLaunchKernelGGL((k_raster_scatter<FMT, MASKS, false>), grid, dim3(256), 0, s, a, x);
+    });
     hipLaunchKernelGGL((k_raster_planes<true>), plane_grid, dim3(256), 0, s, a, x, parts);
 }
 

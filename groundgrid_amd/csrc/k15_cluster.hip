@@ -10,7 +10,7 @@
 // the same component: it costs steps or a retry, because the atomic's return value is the truth, never a wrong union.
 // Ten launches, all on the caller's buffers and one word per 256 cells of call scratch; L = the linear cell index of `order`:
 //   k_cluster_cells<ZERO>     plane[L] := 0
-//   k_cluster_points<COUNT>   the wave <-> chunk mapping of K12 / K13; one atomic add per participating point into its cell
+//   k_cluster_points<COUNT>   the walk of cloud_walk.h; one atomic add per participating point into its cell
 //   k_cluster_cells<SEED>     plane[L] := count >= min_points ? L : 0xFFFFFFFF
 //   k_cluster_merge           every occupied cell is united with the occupied ones of the half of its neighbourhood that precedes it
 //   k_cluster_flatten         plane[L] := find(L); the number of roots of every 256-cell chunk -> scratch
@@ -21,7 +21,7 @@
 //   k_cluster_apply           plane[L] := the rank behind plane[L] (a root decodes its own word, another cell the word of its root, which is
 //                             the encoded or the decoded rank -- both read the same); cells and the four bounds of the records by integer
 //                             atomics, reduced over the lanes of a wavefront that share an id first
-//   k_cluster_points<IDS>     d_point_cluster; points and the height key (the key of k13_raster.hip) of the records, reduced likewise
+//   k_cluster_points<IDS>     d_point_cluster; points and the height_key (cloud_walk.h) of the records, reduced likewise
 //   k_cluster_finalise        a record's key becomes its float, or the quiet NaN 0x7FC00000
 // No work-group waits for another, every loop is bounded by construction, no float is added and only integer atomics (add, min, max) are
 // used: the outputs do not depend on scheduling.
@@ -30,42 +30,14 @@
 // (the (ground, confidence) pair: only with a height band or a table) and one 4-byte atomic (COUNT) / 4 read + 4 written (IDS); per cell 4
 // written by ZERO, 4 + 4 by SEED, 4 + 4 by the flatten, 4 + 4 by the apply, 4 read by the rank; per occupied cell the parents the merge
 // walks; per cluster record 32 written and a handful of atomics per wavefront that touches it.
-#include "gg_device.h"
+#include "cloud_walk.h"
 
 namespace gg {
 
 constexpr uint32_t CLUSTER_EMPTY = 0xFFFFFFFFu; // an unoccupied cell, from the seed on (-1 as the caller reads it)
-constexpr uint32_t CLUSTER_NAN = 0x7FC00000u;
 constexpr int CLUSTER_WAVE_ROUNDS = 4; // ids a wavefront reduces over its lanes before the remaining lanes send their own atomics
 
-// the order-preserving key of k13_raster.hip: never 0 for a non-NaN float, so 0 marks "no such point yet" under atomicMax
-GG_DEV uint32_t cluster_height_key(float h)
-{
-    const uint32_t b = __float_as_uint(h);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-GG_DEV uint32_t cluster_height_of_key(uint32_t key) { return (key >> 31) ? key ^ 0x80000000u : ~key; }
-
 GG_DEV uint32_t cluster_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-GG_DEV int wave_min_i(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-    return v;
-}
-GG_DEV int wave_max_i(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
-}
-GG_DEV uint32_t wave_max_u(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, 64));
-    return v;
-}
 
 // (map, 256-cell chunk) of a work-group of the cell launches, grid (cell_chunks, clouds)
 GG_DEV void cluster_cell_item(int &cloud, int &chunk)
@@ -78,6 +50,24 @@ GG_DEV void cluster_cell_item(int &cloud, int &chunk)
 // a cluster's record as eight words: cells, points, row_min, row_max, col_min, col_max, height_max (its key while the call runs), first_cell
 GG_DEV uint32_t *cluster_record(const ClusterArgs &x, int io, int k) { return x.records + ((size_t)io * x.max_clusters + k) * 8; }
 
+// The lanes of a large cluster's interior all hold one id: one lane speaks for a run of them.  At most CLUSTER_WAVE_ROUNDS times, the first
+// lane that still holds an id (rid >= 0) names it and run(id, mine, count, speaker) is called by ALL lanes (it reduces over the lanes with
+// `mine`, and the `speaker` lane sends the result for the `count` of them); those lanes' rid becomes -1.  A lane whose rid is still >= 0
+// afterwards sends its own.  To be called in wavefront-uniform control flow.
+template <class Run> GG_DEV void cluster_id_runs(int &rid, int lane, Run &&run)
+{
+    unsigned long long todo = __ballot(rid >= 0);
+    for (int round = 0; round < CLUSTER_WAVE_ROUNDS && todo; ++round) {
+        const int src = __ffsll((long long)todo) - 1;
+        const int cur = __shfl(rid, src, 64);
+        const bool mine = rid == cur;
+        const unsigned long long m = __ballot(mine);
+        run(cur, mine, (int)__popcll(m), lane == src);
+        if (mine) rid = -1;
+        todo &= ~m;
+    }
+}
+
 template <bool SEED>
 __global__ __launch_bounds__(256) void k_cluster_cells(const Arena a, const ClusterArgs x)
 {
@@ -85,7 +75,7 @@ __global__ __launch_bounds__(256) void k_cluster_cells(const Arena a, const Clus
     cluster_cell_item(cloud, chunk);
     const int L = chunk * 256 + (int)threadIdx.x;
     if (L >= a.g.C) return;
-    uint32_t *p = x.planes + (size_t)x.clouds[cloud].io_index * x.plane_stride + L;
+    uint32_t *p = x.planes + (size_t)x.cl.clouds[cloud].io_index * x.plane_stride + L;
     *p = SEED ? (*p >= (uint32_t)x.min_points ? (uint32_t)L : CLUSTER_EMPTY) : 0u;
 }
 
@@ -124,7 +114,7 @@ __global__ __launch_bounds__(256) void k_cluster_merge(const Arena a, const Clus
     cluster_cell_item(cloud, chunk);
     const int L = chunk * 256 + (int)threadIdx.x;
     if (L >= a.g.C) return;
-    uint32_t *parent = x.planes + (size_t)x.clouds[cloud].io_index * x.plane_stride;
+    uint32_t *parent = x.planes + (size_t)x.cl.clouds[cloud].io_index * x.plane_stride;
     if (cluster_load(parent + L) == CLUSTER_EMPTY) return;
     const int minors = x.order == GG_PLANES_ROWMAJOR ? a.g.cols : a.g.rows;
     const int major = L / minors, minor = L - major * minors;
@@ -143,7 +133,7 @@ __global__ __launch_bounds__(256) void k_cluster_flatten(const Arena a, const Cl
     __shared__ uint32_t wave_roots[4];
     int cloud, chunk;
     cluster_cell_item(cloud, chunk);
-    const int io = x.clouds[cloud].io_index;
+    const int io = x.cl.clouds[cloud].io_index;
     const int L = chunk * 256 + (int)threadIdx.x;
     uint32_t *parent = x.planes + (size_t)io * x.plane_stride;
     bool root = false;
@@ -161,7 +151,7 @@ __global__ __launch_bounds__(256) void k_cluster_flatten(const Arena a, const Cl
 __global__ __launch_bounds__(256) void k_cluster_scan(const Arena a, const ClusterArgs x)
 {
     __shared__ uint32_t sums[256];
-    const int io = x.clouds[blockIdx.x].io_index;
+    const int io = x.cl.clouds[blockIdx.x].io_index;
     uint32_t *counts = x.chunk_counts + (size_t)io * x.cell_chunks;
     const int t = (int)threadIdx.x;
     const int per = (x.cell_chunks + 255) / 256;
@@ -203,7 +193,7 @@ __global__ __launch_bounds__(256) void k_cluster_rank(const Arena a, const Clust
     __shared__ uint32_t wave_roots[4];
     int cloud, chunk;
     cluster_cell_item(cloud, chunk);
-    const int io = x.clouds[cloud].io_index;
+    const int io = x.cl.clouds[cloud].io_index;
     const int L = chunk * 256 + (int)threadIdx.x;
     const int wave = threadIdx.x >> 6;
     uint32_t *plane = x.planes + (size_t)io * x.plane_stride;
@@ -222,7 +212,7 @@ __global__ __launch_bounds__(256) void k_cluster_apply(const Arena a, const Clus
 {
     int cloud, chunk;
     cluster_cell_item(cloud, chunk);
-    const int io = x.clouds[cloud].io_index;
+    const int io = x.cl.clouds[cloud].io_index;
     const int L = chunk * 256 + (int)threadIdx.x;
     const int lane = threadIdx.x & 63;
     uint32_t *plane = x.planes + (size_t)io * x.plane_stride;
@@ -241,34 +231,20 @@ __global__ __launch_bounds__(256) void k_cluster_apply(const Arena a, const Clus
     const int major = L / minors, minor = L - major * minors;
     const int r = x.order == GG_PLANES_ROWMAJOR ? major : minor, c = x.order == GG_PLANES_ROWMAJOR ? minor : major;
     int rid = id < x.max_clusters ? id : -1;
-    // the lanes of a large cluster's interior all hold one id: one lane speaks for them
-    unsigned long long todo = __ballot(rid >= 0);
-    for (int round = 0; round < CLUSTER_WAVE_ROUNDS && todo; ++round) {
-        const int src = __ffsll((long long)todo) - 1;
-        const int cur = __shfl(rid, src, 64);
-        const bool mine = rid == cur;
-        const unsigned long long m = __ballot(mine);
+    const auto send = [&](int to, int cells, int r_lo, int r_hi, int c_lo, int c_hi) GG_INLINE_LAMBDA {
+        int *rec = reinterpret_cast<int *>(cluster_record(x, io, to));
+        atomicAdd(rec + 0, cells);
+        atomicMin(rec + 2, r_lo);
+        atomicMax(rec + 3, r_hi);
+        atomicMin(rec + 4, c_lo);
+        atomicMax(rec + 5, c_hi);
+    };
+    cluster_id_runs(rid, lane, [&](int to, bool mine, int count, bool speaker) GG_INLINE_LAMBDA {
         const int r_lo = wave_min_i(mine ? r : 0x7FFFFFFF), r_hi = wave_max_i(mine ? r : -1);
         const int c_lo = wave_min_i(mine ? c : 0x7FFFFFFF), c_hi = wave_max_i(mine ? c : -1);
-        if (lane == src) {
-            int *rec = reinterpret_cast<int *>(cluster_record(x, io, cur));
-            atomicAdd(rec + 0, (int)__popcll(m));
-            atomicMin(rec + 2, r_lo);
-            atomicMax(rec + 3, r_hi);
-            atomicMin(rec + 4, c_lo);
-            atomicMax(rec + 5, c_hi);
-        }
-        if (mine) rid = -1;
-        todo &= ~m;
-    }
-    if (rid >= 0) {
-        int *rec = reinterpret_cast<int *>(cluster_record(x, io, rid));
-        atomicAdd(rec + 0, 1);
-        atomicMin(rec + 2, r);
-        atomicMax(rec + 3, r);
-        atomicMin(rec + 4, c);
-        atomicMax(rec + 5, c);
-    }
+        if (speaker) send(to, count, r_lo, r_hi, c_lo, c_hi);
+    });
+    if (rid >= 0) send(rid, 1, r, r, c, c);
 }
 
 // IDS = false: the count launch.  IDS = true: the per-point ids and the records' points and height key.  NEED_H: the height of a point is
@@ -276,92 +252,48 @@ __global__ __launch_bounds__(256) void k_cluster_apply(const Arena a, const Clus
 template <int FMT, bool MASKS, bool NEED_H, bool IDS>
 __global__ __launch_bounds__(256) void k_cluster_points(const Arena a, const ClusterArgs x)
 {
-    const uint32_t item = xcd_contiguous_item(blockIdx.x + blockIdx.y * gridDim.x, gridDim.x * gridDim.y);
-    const int cloud = (int)(item / gridDim.x), bx = (int)(item % gridDim.x);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int chunk = bx * 4 + wave;
-    if (chunk >= x.nch) return; // (uniform over the wavefront; there is no barrier below)
-    const SplitCloud &c = x.clouds[cloud];
-    const int n = c.n_points, io = c.io_index;
-    const int base = min(chunk * a.PW, n);
-    const int end = min(base + a.PW, n);
-    if (base >= end) return;
-    const uint8_t *row = MASKS ? x.masks + (size_t)io * ((x.cloud_stride + 3) / 4) : x.labels + (size_t)io * x.cloud_stride;
-    const uint4 *pts = reinterpret_cast<const uint4 *>(x.points) + (size_t)io * x.cloud_stride * (FMT == GG_POINT16 ? 1 : 2);
+    CloudChunk k;
+    if (!cloud_chunk(a, x.cl, k) || k.base >= k.end) return; // (uniform over the wavefront; there is no barrier below)
+    const int io = k.io;
     uint32_t *plane = x.planes + (size_t)io * x.plane_stride;
-    int32_t *ids = IDS && x.point_cluster ? x.point_cluster + (size_t)io * x.cloud_stride : nullptr;
-    const bool has_tf = c.has_tf != 0, fresh = c.fresh != 0;
-    const float fresh_z = c.fresh_z;
-    const double pos_x = c.pos_x, pos_y = c.pos_y;
-    double tf[12];
-    if (has_tf) { // (uniform)
-#pragma unroll
-        for (int k = 0; k < 12; ++k) tf[k] = c.tf[k];
-    }
-    const float2 *gp2 = gp2_ptr(a, c.slot);
+    int32_t *ids = IDS && x.point_cluster ? x.point_cluster + (size_t)io * x.cl.cloud_stride : nullptr;
     const bool row_major = x.order == GG_PLANES_ROWMAJOR;
-
-    constexpr int ITEMS = 4;
-    for (int p0 = base; p0 < end; p0 += 64 * ITEMS) {
-        uint4 v[ITEMS];
-        uint32_t code[ITEMS];
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) { // all windows' loads in flight together (unconditional, at clamped indices)
-            const int p = min(p0 + j * 64 + lane, end - 1);
-            code[j] = split_code<MASKS>(row, p);
-            v[j] = pts[FMT == GG_POINT16 ? (size_t)p : (size_t)p * 2]; // x, y, z, (ring | pad0)
-        }
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const int p = p0 + j * 64 + lane;
-            const bool valid = p < end;
-            int cell = -1; // the participating point's cell
-            uint32_t key = 0u;
-            if (valid && code[j] == 2u) {
-                float px = __uint_as_float(v[j].x), py = __uint_as_float(v[j].y), pz = __uint_as_float(v[j].z);
-                if (has_tf) transform_point(tf, px, py, pz);
-                int r, cc;
-                const bool inside = position_inside(a.g, pos_x, pos_y, (double)px, (double)py);
-                index_from_position(a.g, pos_x, pos_y, (double)px, (double)py, r, cc);
-                if (inside && r >= 0 && cc >= 0 && r < a.g.rows && cc < a.g.cols) {
-                    cell = row_major ? r * a.g.cols + cc : r + cc * a.g.rows; // < rows * cols <= plane_stride
-                    if (NEED_H) {
-                        const float h = pz - (fresh ? fresh_z : gp2[gp_idx(a, r, cc)].x);
-                        if (h < x.min_height || h > x.max_height) cell = -1; // (a NaN height participates)
-                        else if (h == h) key = cluster_height_key(h);
-                    }
+    CloudFrame f;
+    load_cloud_frame(a, x.cl.clouds[k.cloud], f);
+    walk_chunk<FMT, MASKS, WALK_POINT>(x.cl, k, [&](int p, uint32_t sel, const uint4 &v, uint32_t) GG_INLINE_LAMBDA {
+        int cell = -1; // the participating point's cell
+        uint32_t key = 0u;
+        if (sel == 2u) {
+            float px = __uint_as_float(v.x), py = __uint_as_float(v.y), pz = __uint_as_float(v.z);
+            int r, cc;
+            if (locate_point(a, f, px, py, pz, r, cc)) {
+                cell = linear_cell(a, row_major, r, cc);
+                if (NEED_H) {
+                    const float h = height_above_ground(a, f, pz, r, cc);
+                    if (h < x.min_height || h > x.max_height) cell = -1; // (a NaN height participates)
+                    else if (h == h) key = height_key(h);
                 }
             }
-            if (!IDS) {
-                if (cell >= 0) atomicAdd(plane + cell, 1u);
-                continue;
-            }
-            const int id = cell >= 0 ? (int)plane[cell] : -1; // (-1: its cell is not occupied)
-            if (valid && ids) ids[p] = id;
-            if (!x.records) continue; // (uniform)
-            int rid = id < x.max_clusters ? id : -1;
-            unsigned long long todo = __ballot(rid >= 0);
-            for (int round = 0; round < CLUSTER_WAVE_ROUNDS && todo; ++round) {
-                const int src = __ffsll((long long)todo) - 1;
-                const int cur = __shfl(rid, src, 64);
-                const bool mine = rid == cur;
-                const unsigned long long m = __ballot(mine);
-                const uint32_t top = wave_max_u(mine ? key : 0u);
-                if (lane == src) {
-                    uint32_t *rec = cluster_record(x, io, cur);
-                    atomicAdd(rec + 1, (uint32_t)__popcll(m));
-                    if (top) atomicMax(rec + 6, top);
-                }
-                if (mine) rid = -1;
-                todo &= ~m;
-            }
-            if (rid >= 0) {
-                uint32_t *rec = cluster_record(x, io, rid);
-                atomicAdd(rec + 1, 1u);
-                if (key) atomicMax(rec + 6, key);
-            }
         }
-    }
+        if (!IDS) {
+            if (cell >= 0) atomicAdd(plane + cell, 1u);
+            return;
+        }
+        const int id = cell >= 0 ? (int)plane[cell] : -1; // (-1: its cell is not occupied)
+        if (p < k.end && ids) ids[p] = id;
+        if (!x.records) return; // (uniform: every lane is back for the ballots below)
+        const auto send = [&](int to, uint32_t points, uint32_t top) GG_INLINE_LAMBDA {
+            uint32_t *rec = cluster_record(x, io, to);
+            atomicAdd(rec + 1, points);
+            if (top) atomicMax(rec + 6, top);
+        };
+        int rid = id < x.max_clusters ? id : -1;
+        cluster_id_runs(rid, k.lane, [&](int to, bool mine, int count, bool speaker) GG_INLINE_LAMBDA {
+            const uint32_t top = wave_max_u(mine ? key : 0u);
+            if (speaker) send(to, (uint32_t)count, top);
+        });
+        if (rid >= 0) send(rid, 1u, key);
+    });
 }
 
 __global__ __launch_bounds__(256) void k_cluster_finalise(const ClusterArgs x, int n_clouds)
@@ -371,25 +303,18 @@ __global__ __launch_bounds__(256) void k_cluster_finalise(const ClusterArgs x, i
     const int io = (int)(i / x.max_clusters), k = (int)(i % x.max_clusters);
     if (k >= x.n_clusters[io]) return;
     uint32_t *w = cluster_record(x, io, k) + 6;
-    *w = *w ? cluster_height_of_key(*w) : CLUSTER_NAN;
+    *w = *w ? height_of_key(*w) : QUIET_NAN_BITS;
 }
 
-template <int FMT, bool MASKS, bool IDS> static void launch_cluster_points(const Arena &a, const ClusterArgs &x, bool need_h, dim3 grid, hipStream_t s)
-{
-    if (need_h) hipLaunchKernelGGL((k_cluster_points<FMT, MASKS, true, IDS>), grid, dim3(256), 0, s, a, x);
-    else hipLaunchKernelGGL((k_cluster_points<FMT, MASKS, false, IDS>), grid, dim3(256), 0, s, a, x);
-}
 template <bool IDS> static void launch_cluster_points(const Arena &a, const ClusterArgs &x, bool need_h, int n_clouds, hipStream_t s)
 {
-    const dim3 grid((x.nch + 3) / 4, n_clouds);
-    const bool masks = x.masks != nullptr;
-    if (x.point_format == GG_POINT16) {
-        if (masks) launch_cluster_points<GG_POINT16, true, IDS>(a, x, need_h, grid, s);
-        else launch_cluster_points<GG_POINT16, false, IDS>(a, x, need_h, grid, s);
-    } else {
-        if (masks) launch_cluster_points<GG_POINT32, true, IDS>(a, x, need_h, grid, s);
-        else launch_cluster_points<GG_POINT32, false, IDS>(a, x, need_h, grid, s);
-    }
+    const dim3 grid((x.cl.nch + 3) / 4, n_clouds);
+    dispatch_cloud_variant(x.cl, [&](auto fmt, auto masks) {
+        constexpr int FMT = decltype(fmt)::value;
+        constexpr bool MASKS = decltype(masks)::value;
+        if (need_h) hipLaunchKernelGGL((k_cluster_points<FMT, MASKS, true, IDS>), grid, dim3(256), 0, s, a, x);
+        else hipLaunchKernelGGL((k_cluster_points<FMT, MASKS, false, IDS>), grid, dim3(256), 0, s, a, x);
+    });
 }
 
 void launch_cluster(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s)

@@ -75,6 +75,27 @@ def test_struct_layouts_match_the_header():
                     _lib.GGStageArgs.base_z.offset, C.sizeof(_lib.GGGridMapHeader)]
 
 
+def test_labelled_cloud_struct_layouts_match_the_header():
+    """gg_cloud_split, gg_cloud_raster and gg_cloud_clusters share ten leading members (one list in the binding): their size and the offset
+    of the first member behind the ten, as the C compiler lays the header out, against the ctypes classes."""
+    structs = (("gg_cloud_split", "ground", _lib.GGCloudSplit), ("gg_cloud_raster", "channel_mask", _lib.GGCloudRaster),
+               ("gg_cloud_clusters", "min_points", _lib.GGCloudClusters))
+    args = ", ".join(f"sizeof({c}), offsetof({c}, {m})" for c, m, _ in structs)
+    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "groundgrid_hip.h"\n' \
+           'int main(void){ printf("%zu %zu %zu %zu %zu %zu\\n", ' + args + '); return 0; }\n'
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.c"), "w").write(prog)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
+        vals = list(map(int, subprocess.check_output([os.path.join(d, "t")], text=True).split()))
+    want = []
+    for _, member, cls in structs:
+        assert [name for name, _ in cls._fields_[:10]] == [name for name, _ in _lib.GGCloudSplit._fields_[:10]]
+        assert cls._fields_[10][0] == member
+        want += [C.sizeof(cls), getattr(cls, member).offset]
+    assert vals == want
+
+
 def test_defaults_are_the_reference_cfg(lib):
     c = _lib.GGConfig()
     lib.gg_default_config(C.byref(c))
