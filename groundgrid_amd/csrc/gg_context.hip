@@ -25,6 +25,8 @@
 #include <unistd.h>
 
 #include "gg_internal.h"
+#include "arena_layout.h"
+#include "hip_owned.h"
 #include "host_helper.h"
 #include "scroll_core.h"
 #include "sweep_core.h"
@@ -33,7 +35,6 @@ using namespace gg;
 
 namespace {
 
-constexpr int PARAM_RING = 4;
 constexpr int EXPORT_VARIANT_DEFAULT = 0; // gg_export_layers: 0 = k_export_tiled, 1 = k_export_gather; the measured winner
 constexpr int IMPORT_VARIANT_DEFAULT = 0; // gg_import_layers: 0 = k_import_tiled, 1 = a batched materialise + k_import_scatter; the measured winner
 constexpr int IMAGES_VARIANT_DEFAULT = 0; // gg_export_images: 0 = the tiled kernels of k11_images.hip, 1 = their cell-by-cell forms; the measured winner
@@ -53,23 +54,15 @@ struct EventPair {
 // (GG_FLAG_CONCURRENT_HALVES).  acquire() waits on the host for whichever of the two the entry's last user recorded, so a pinned entry is
 // rewritten only when the copies that read it have run.
 struct ParamRing {
-    hipEvent_t done[PARAM_RING]{}, done2[PARAM_RING]{};
+    Event done[PARAM_RING], done2[PARAM_RING];
     bool used[PARAM_RING]{}, used2[PARAM_RING]{};
     int next = 0;
     hipError_t create()
     {
         hipError_t e = hipSuccess;
-        for (int i = 0; i < PARAM_RING && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
-        for (int i = 0; i < PARAM_RING && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&done2[i], hipEventDisableTiming);
+        for (int i = 0; i < PARAM_RING && e == hipSuccess; ++i) e = done[i].create();
+        for (int i = 0; i < PARAM_RING && e == hipSuccess; ++i) e = done2[i].create();
         return e;
-    }
-    void destroy()
-    {
-        for (int i = 0; i < PARAM_RING; ++i) {
-            if (done[i]) hipEventDestroy(done[i]);
-            if (done2[i]) hipEventDestroy(done2[i]);
-            done[i] = done2[i] = nullptr;
-        }
     }
     hipError_t acquire(int *g)
     {
@@ -96,15 +89,19 @@ struct ParamRing {
 
 // what a many-map call allocates at its first use (alloc_call_scratch): one device block and one pinned host block
 struct CallScratch {
-    void *dev = nullptr, *pinned = nullptr;
+    DeviceBlock<char> dev;
+    PinnedBlock<char> pinned;
 };
 
 } // namespace
 
-struct gg_context {
+struct gg_context : ContextBuffers {
     int device = 0;
     HostHelper helper;
-    hipStream_t stream = nullptr;
+    // the streams come first: members die in reverse order, so a stream outlives every event recorded on it and every block it worked on.
+    // h2d / d2h: a copy stream each way for the pipelined host entry point.  half_stream: GG_FLAG_CONCURRENT_HALVES, below
+    Stream stream, h2d_stream, d2h_stream, half_stream;
+    DeviceBlock<> d_arena; // the one block arena_layout.h lays out: Arena's and ContextBuffers' pointers point into it
     Arena arena{};
     gg_config cfg{};
     gg_geometry geom{};
@@ -113,7 +110,6 @@ struct gg_context {
     unsigned flags = 0;
     std::string last_error;
 
-    void *d_arena = nullptr;
     size_t arena_bytes = 0;
     std::vector<float> h_expected;
     std::vector<double> pos_x, pos_y; // per slot map position
@@ -134,11 +130,11 @@ struct gg_context {
     std::vector<char> slot_own;
     std::vector<gg_config> slot_cfg;
     std::vector<DevConfig> slot_dev;
-    DevConfig *d_slot_cfg = nullptr;
+    DeviceBlock<DevConfig> d_slot_cfg;
     // the evaluator counters (gg_set_score_labels / gg_set_slot_scoring): one device block, allocated by the first label list -- the ring ->
     // bin table, the slots' on / off bytes, the counters and the 2-bit label masks k_label leaves for k_score when the caller passed none
     // (row = position in the batch, like gg_batch.d_label_masks)
-    void *d_score_block = nullptr;
+    DeviceBlock<uint8_t> d_score_block;
     gg::ScoreArgs score{};
     uint8_t *d_score_masks = nullptr;
     size_t score_masks_bytes = 0;
@@ -150,8 +146,8 @@ struct gg_context {
 
     // cross-stream ordering (include/groundgrid_hip.h, gg_filter_batch): `map_event` is recorded on ctx->stream after every
     // map mutation enqueued there, `batch_event` on the launch stream after every batch
-    hipEvent_t map_event = nullptr, batch_event = nullptr;
-    hipEvent_t gather_event = nullptr;       // recorded behind the last gg_allgather_label_masks
+    Event map_event, batch_event;
+    Event gather_event;                      // recorded behind the last gg_allgather_label_masks
     hipStream_t gather_stream = nullptr;
     const uint8_t *gather_lo = nullptr, *gather_hi = nullptr; // ... and the send buffer it reads (null: none pending)
     bool map_event_pending = false;          // a mutation was enqueued on ctx->stream since the last batch waited for it
@@ -159,9 +155,8 @@ struct gg_context {
     bool have_batch_event = false;
     // GG_FLAG_CONCURRENT_HALVES: the clouds (and map re-initialisations) of the upper half of the slots run on half_stream; half_done is
     // recorded there behind each of them, half_fork on the caller's stream in front (the side stream sees what the caller enqueued before)
-    hipStream_t half_stream = nullptr;
     bool layer_copy_failed = false; // a download of the fused filter + layers call could not be enqueued (reported by the call)
-    hipEvent_t half_fork = nullptr, half_done = nullptr;
+    Event half_fork, half_done;
     bool have_half_event = false;
     // Output rows are indexed by a cloud's position in the batch, its half by its slot: two divided batches that are not joined (same caller
     // stream) may write the same row of the same buffer from different streams.  The last few divided batches' output ranges and
@@ -181,21 +176,20 @@ struct gg_context {
                            // call cost more than its overlap gives)
     bool probe_no_fork = false;
 
-    // pipelined host entry point (gg_filter_cloud_async / _wait): GG_ASYNC_DEPTH staging sets + a copy stream each way
-    struct AsyncSlot {
-        gg_point16 *h_pts = nullptr, *d_pts = nullptr;
-        uint8_t *h_labels = nullptr, *d_labels = nullptr;
-        int32_t *h_index = nullptr, *d_index = nullptr;
-        int32_t *h_counts = nullptr, *d_counts = nullptr;
+    // pipelined host entry point (gg_filter_cloud_async / _wait): GG_ASYNC_DEPTH staging sets; the device side of set k is async_set[k]
+    struct __attribute__((visibility("hidden"))) AsyncSlot {
+        PinnedBlock<gg_point16> h_pts;
+        PinnedBlock<int32_t> h_counts; // counts, index and labels in one block, like the device's (ContextBuffers::AsyncSet)
+        uint8_t *h_labels = nullptr;   // (placed per ticket: behind the n index entries)
+        int32_t *h_index = nullptr;
         int32_t *hd_counts = nullptr; // h_counts as the device addresses it (results_direct)
-        hipEvent_t uploaded = nullptr, computed = nullptr, downloaded = nullptr;
+        Event uploaded, computed, downloaded;
         const gg_point32 *cloud = nullptr;
         size_t n = 0;
         bool has_tf = false;
         double tf[12]{};
         int ticket = -1;
     } async_slot[GG_ASYNC_DEPTH];
-    hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
     int next_ticket = 0, oldest_ticket = 0;
     int slot_of_ticket[GG_ASYNC_DEPTH] = {}; // staging set of an outstanding ticket (a synchronous call always takes set 0)
     int next_label_shift = 0;                // enqueue_ticket -> enqueue_batch: CloudParams::label_shift of the one cloud
@@ -203,22 +197,14 @@ struct gg_context {
     long host_calls = 0;
 
     // per-call parameter ring (pinned host + device)
-    CloudParams *h_params = nullptr; // [PARAM_RING][n_slots] pinned
-    CloudParams *d_params = nullptr; // [PARAM_RING][n_slots]
+    PinnedBlock<CloudParams> h_params; // [PARAM_RING][n_slots], the host side of d_params
     ParamRing ring;
 
-    // staging for the host-buffer entry point
-    gg_point16 *h_stage_pts = nullptr; // pinned [max_points]
-    uint8_t *h_stage_labels = nullptr; // pinned
-    int32_t *h_stage_index = nullptr;  // pinned
-    int32_t *h_stage_counts = nullptr; // pinned [4]
-    gg_point16 *d_stage_pts = nullptr;
-    uint8_t *d_stage_labels = nullptr;
-    int32_t *d_stage_index = nullptr;
-    int32_t *d_stage_counts = nullptr;
-    uint8_t *d_stage_class = nullptr;
-    int32_t *d_stage_cell = nullptr;
-    float *d_scroll_scratch = nullptr; // 2 layers
+    // staging for the host-buffer entry point, the host side of d_stage_*
+    PinnedBlock<gg_point16> h_stage_pts; // [max_points]
+    PinnedBlock<uint8_t> h_stage_labels;
+    PinnedBlock<int32_t> h_stage_index;
+    PinnedBlock<int32_t> h_stage_counts; // [4]
     // gg_move_maps (allocated at its first call; contexts that never call it do not pay): one device block holding the cell table (element,
     // row | col << 16 of every cell in element order), the parameter ring [PARAM_RING][n_slots] and move_cap scratch rows of C cells
     CallScratch move_mem;
@@ -235,7 +221,6 @@ struct gg_context {
     const uint32_t *d_export_off = nullptr, *d_export_elem = nullptr;
     const uint16_t *d_export_cell = nullptr;
     ExportMap *d_export_maps = nullptr, *h_export_maps = nullptr;
-    const ExportMap *d_slot_maps = nullptr; // [n_slots] in the arena: entry s lists slot s alone -- the single-map getters' and setters' list of one map (gg_create)
     CloudParams *d_export_lazy = nullptr, *h_export_lazy = nullptr;
     ParamRing export_ring;
     int slopes_variant = 0; // tuning "slopes_variant": 0 = k_slopes_tiled, 1 = k_slopes_gather (the A/B of tools/bench_slopes.py)
@@ -257,13 +242,11 @@ struct gg_context {
     CallScratch cluster_mem;
     uint32_t *d_cluster_counts = nullptr;
     int cluster_cell_chunks = 0;
-    float *d_image = nullptr;          // 3 * C floats (wire-format images)
-    float *d_planes = nullptr;         // GG_NUM_LAYERS * Cpad floats: dense planes of gg_get_layers (allocated on first use)
-    float *h_planes = nullptr;         // ... and their pinned landing zone on the host (one download for all requested layers)
-    float *d_bounds = nullptr;         // 2 floats
-    uint8_t *d_pc2 = nullptr, *h_pc2 = nullptr; // gg_filter_cloud_pc2_out: [64 B counts][max_points * 18 B records], device and pinned host (allocated on first use)
-    volatile uint32_t *h_dev_error = nullptr;  // host view of Arena::dev_error (mapped pinned memory)
-    unsigned long long *d_sweep_dbg = nullptr; // GG_SWEEP_TIMING=1: cycle counters of the sweep's wavefronts (cloud 0 of a batch)
+    DeviceBlock<float> d_planes;       // GG_NUM_LAYERS * Cpad floats: dense planes of gg_get_layers (ensure_plane_staging, at first use)
+    PinnedBlock<float> h_planes;       // ... and their pinned landing zone on the host (one download for all requested layers)
+    DeviceBlock<uint8_t> d_pc2;        // gg_filter_cloud_pc2_out: [64 B counts][max_points * 18 B records], device and pinned host (allocated on first use)
+    PinnedBlock<uint8_t> h_pc2;
+    PinnedBlock<volatile uint32_t> h_dev_error; // host view of Arena::dev_error (mapped pinned memory)
 
     // One cloud per call -- the reference's own call shape (src/GroundGridNodelet.cpp:196) -- replays a captured HIP graph: the seven
     // launches (and, for the fused filter + layers call, the layer extraction and downloads on a side branch) are handed to the device
@@ -293,9 +276,8 @@ struct gg_context {
                                  // against 0.571 (profiles/r05a/host_call_probe*.json): the launches of a call already queue up behind the first
                                  // kernel, there are no gaps left for a graph to close
     long graph_replays = 0, graph_captures = 0;
-    CloudParams *d_gparams = nullptr;
-    hipEvent_t fork_event = nullptr, join_event = nullptr; // the side branch of the fused filter + layers call
-    hipEvent_t layers_event = nullptr;                     // ... and its late layers (behind the results on the context's stream)
+    Event fork_event, join_event; // the side branch of the fused filter + layers call
+    Event layers_event;           // ... and its late layers (behind the results on the context's stream)
     std::vector<std::pair<char *, size_t>> registered;     // gg_host_register: host ranges downloads may land in directly
 
     // profiling
@@ -350,7 +332,12 @@ int device_error(gg_context *ctx)
         if (rc__ != GG_OK) return rc__;                      \
     } while (0)
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// an integer knob of the environment (atoi: text that is no number reads as 0); `fallback` when the variable is not set
+int env_int(const char *name, int fallback)
+{
+    const char *v = getenv(name);
+    return v ? atoi(v) : fallback;
+}
 
 uint32_t morton2(uint32_t x, uint32_t y)
 {
@@ -488,8 +475,7 @@ struct Roctx {
     int (*pop)() = nullptr;
     Roctx()
     {
-        const char *e = getenv("GG_ROCTX");
-        if (e && atoi(e) == 0) return;
+        if (env_int("GG_ROCTX", 1) == 0) return;
         for (const char *name : {"librocprofiler-sdk-roctx.so.1", "libroctx64.so.4", "libroctx64.so"}) {
             void *h = dlopen(name, RTLD_NOW | RTLD_LOCAL);
             if (!h) continue;
@@ -572,6 +558,18 @@ int drain_profile(gg_context *ctx)
     }
     ctx->pending.clear();
     return GG_OK;
+}
+
+// the profiler's events are shared between neighbouring pairs (owns_start) and pooled, so they stay raw handles: gg_destroy releases them here
+void release_profile_events(gg_context *ctx)
+{
+    for (auto &p : ctx->pending) {
+        if (p.owns_start) hipEventDestroy(p.start);
+        hipEventDestroy(p.stop);
+    }
+    for (hipEvent_t e : ctx->free_single_events) hipEventDestroy(e);
+    ctx->pending.clear();
+    ctx->free_single_events.clear();
 }
 
 // the record of one plane call (gg_internal.h); the table is null until gg_export_layers / gg_import_layers built it -- only their tiled kernels read it
@@ -1013,18 +1011,6 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
     return GG_OK;
 }
 
-void free_call_scratch(CallScratch &m)
-{
-    if (m.dev) hipFree(m.dev);
-    if (m.pinned) hipHostFree(m.pinned);
-    m = CallScratch{};
-}
-void free_call_scratch(CallScratch &m, ParamRing &r)
-{
-    free_call_scratch(m);
-    r.destroy();
-}
-
 // The first-call allocation of a many-map call (`who`): a device block, a pinned host block and the events of its parameter ring, and the
 // tables the call's kernels read uploaded into the device block (synchronously: they are there before any stream can launch on them).  Not
 // while `st` is being captured into a graph: an allocation cannot be captured.  `mem` and `ring` are written when everything is in place:
@@ -1046,12 +1032,10 @@ int alloc_call_scratch(gg_context *ctx, const char *who, hipStream_t st, size_t 
     ParamRing r;
     int code = GG_ERR_NOMEM;
     const char *what = "device scratch";
-    hipError_t e = hipMalloc(&m.dev, dev_bytes);
-    if (e != hipSuccess) m.dev = nullptr;
+    hipError_t e = m.dev.create(dev_bytes);
     if (e == hipSuccess) {
         what = "pinned parameter ring";
-        e = hipHostMalloc(&m.pinned, pinned_bytes, hipHostMallocDefault);
-        if (e != hipSuccess) m.pinned = nullptr;
+        e = m.pinned.create(pinned_bytes);
     }
     if (e == hipSuccess) code = GG_ERR_HIP;
     if (e == hipSuccess && ring) {
@@ -1061,15 +1045,14 @@ int alloc_call_scratch(gg_context *ctx, const char *who, hipStream_t st, size_t 
     for (const TableUpload &t : tables)
         if (e == hipSuccess) {
             what = "table upload";
-            e = hipMemcpy((char *)m.dev + t.offset, t.src, t.bytes, hipMemcpyHostToDevice);
+            e = hipMemcpy(m.dev + t.offset, t.src, t.bytes, hipMemcpyHostToDevice);
         }
-    if (e != hipSuccess) {
-        free_call_scratch(m, r);
+    if (e != hipSuccess) { // (m and r release what they hold)
         (void)hipGetLastError();
         return fail(ctx, code, (std::string(who) + ": " + what).c_str(), e);
     }
-    *mem = m;
-    if (ring) *ring = r;
+    *mem = std::move(m);
+    if (ring) *ring = std::move(r);
     return GG_OK;
 }
 
@@ -1174,7 +1157,7 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
     ctx->no_confidence.assign(n_slots, 0); // layers start as zeros, but only gg_reset_map makes a slot usable
     ctx->fresh.assign(n_slots, 0);
     ctx->fresh_z.assign(n_slots, 0.0f);
-    ctx->fresh_enabled = !(getenv("GG_FRESH_MAPS") && atoi(getenv("GG_FRESH_MAPS")) == 0);
+    ctx->fresh_enabled = env_int("GG_FRESH_MAPS", 1) != 0;
     ctx->lazy_pending.assign(n_slots, 0);
     ctx->lazy_params.assign(n_slots, CloudParams{});
     ctx->slot_own.assign(n_slots, 0);
@@ -1194,19 +1177,19 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
     } while (0)
 
     CREATE_CHK(hipSetDevice(device));
-    CREATE_CHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    CREATE_CHK(hipStreamCreateWithFlags(&ctx->h2d_stream, hipStreamNonBlocking));
-    CREATE_CHK(hipStreamCreateWithFlags(&ctx->d2h_stream, hipStreamNonBlocking));
-    CREATE_CHK(hipStreamCreateWithFlags(&ctx->half_stream, hipStreamNonBlocking));
-    CREATE_CHK(hipEventCreateWithFlags(&ctx->half_fork, hipEventDisableTiming));
-    CREATE_CHK(hipEventCreateWithFlags(&ctx->half_done, hipEventDisableTiming));
-    CREATE_CHK(hipEventCreateWithFlags(&ctx->map_event, hipEventDisableTiming));
-    CREATE_CHK(hipEventCreateWithFlags(&ctx->batch_event, hipEventDisableTiming));
-    CREATE_CHK(hipEventCreateWithFlags(&ctx->gather_event, hipEventDisableTiming));
-    CREATE_CHK(hipEventCreateWithFlags(&ctx->fork_event, hipEventDisableTiming));
-    CREATE_CHK(hipEventCreateWithFlags(&ctx->join_event, hipEventDisableTiming));
-    CREATE_CHK(hipEventCreateWithFlags(&ctx->layers_event, hipEventDisableTiming));
-    if (const char *e = getenv("GG_GRAPH")) ctx->graphs_enabled = atoi(e) != 0; // (1 = one cloud per call replays a captured graph)
+    CREATE_CHK(ctx->stream.create());
+    CREATE_CHK(ctx->h2d_stream.create());
+    CREATE_CHK(ctx->d2h_stream.create());
+    CREATE_CHK(ctx->half_stream.create());
+    CREATE_CHK(ctx->half_fork.create());
+    CREATE_CHK(ctx->half_done.create());
+    CREATE_CHK(ctx->map_event.create());
+    CREATE_CHK(ctx->batch_event.create());
+    CREATE_CHK(ctx->gather_event.create());
+    CREATE_CHK(ctx->fork_event.create());
+    CREATE_CHK(ctx->join_event.create());
+    CREATE_CHK(ctx->layers_event.create());
+    ctx->graphs_enabled = env_int("GG_GRAPH", 0) != 0; // (1 = one cloud per call replays a captured graph)
 
     Arena &a = ctx->arena;
     Geometry &g = a.g;
@@ -1233,22 +1216,21 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
     // number of wavefronts per cloud too -- contexts for big batches take 2048 (k_scan 0.18 -> 0.11 ms per 1024 clouds), small
     // ones 1024 (one cloud: 0.56 instead of 0.60 ms)
     a.PW = g.T <= 1024 ? (n_slots >= PW_BIG_CONTEXT_SLOTS ? 2048 : 1024) : 8192;
-    if (getenv("GG_PW")) a.PW = atoi(getenv("GG_PW")); // (tools, tests: points per wavefront chunk of K1 / scatter / K5)
+    a.PW = env_int("GG_PW", a.PW); // (tools, tests: points per wavefront chunk of K1 / scatter / K5)
     if (a.PW < 64 || a.PW % 64 != 0) {
         gg_destroy(ctx);
         return GG_ERR_INVALID;
     }
-    a.tune_sweep_waves = getenv("GG_SWEEP_WAVES") ? atoi(getenv("GG_SWEEP_WAVES")) : 0;
-    a.tune_sweep_gpw = getenv("GG_SWEEP_GPW") ? atoi(getenv("GG_SWEEP_GPW")) : 0;
-    a.tune_sweep_split = getenv("GG_SWEEP_SPLIT") ? atoi(getenv("GG_SWEEP_SPLIT")) : 0;
-    a.tune_sweep_pair = getenv("GG_SWEEP_PAIR") ? atoi(getenv("GG_SWEEP_PAIR")) : 0;
-    a.tune_sweep_pair_wgs = getenv("GG_SWEEP_PAIR_WGS") ? atoi(getenv("GG_SWEEP_PAIR_WGS")) : 0;
-    a.tune_sweep_pair_waves = getenv("GG_SWEEP_PAIR_WAVES") ? atoi(getenv("GG_SWEEP_PAIR_WAVES")) : 0;
-    a.tune_front = getenv("GG_FRONT") ? atoi(getenv("GG_FRONT")) : 0;
-    a.tune_k2_per_cloud = getenv("GG_K2_PER_CLOUD") ? atoi(getenv("GG_K2_PER_CLOUD")) : 0;
-    a.tune_k2_dense_share = getenv("GG_K2_DENSE_SHARE") ? atoi(getenv("GG_K2_DENSE_SHARE")) : 0;
-    a.k2_skip = getenv("GG_K2_SKIP") ? atoi(getenv("GG_K2_SKIP")) : 0;
-    a.NCH = (int)((max_points + a.PW - 1) / a.PW);
+    a.tune_sweep_waves = env_int("GG_SWEEP_WAVES", 0);
+    a.tune_sweep_gpw = env_int("GG_SWEEP_GPW", 0);
+    a.tune_sweep_split = env_int("GG_SWEEP_SPLIT", 0);
+    a.tune_sweep_pair = env_int("GG_SWEEP_PAIR", 0);
+    a.tune_sweep_pair_wgs = env_int("GG_SWEEP_PAIR_WGS", 0);
+    a.tune_sweep_pair_waves = env_int("GG_SWEEP_PAIR_WAVES", 0);
+    a.tune_front = env_int("GG_FRONT", 0);
+    a.tune_k2_per_cloud = env_int("GG_K2_PER_CLOUD", 0);
+    a.tune_k2_dense_share = env_int("GG_K2_DENSE_SHARE", 0);
+    a.k2_skip = env_int("GG_K2_SKIP", 0);
     make_dev_config(ctx->cfg, a.cfg);
 
     // R1: expectedPoints (src/GroundSegmentation.cpp:40-46) -- host libm atanf, as in the reference
@@ -1276,122 +1258,45 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
         }
     }
 
-    // ---- carve the arena -----------------------------------------------------------------
-    const size_t A = 256;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, A);
-        return o;
-    };
-    const size_t C = (size_t)g.C;
-    const size_t Cpad = align_up(C * 4, A) / 4;
-    const size_t Npad = align_up(max_points * 8, A) / 8;
-    const size_t o_expected = carve(C * 4);
-    const size_t o_ptable = carve(C * 16);
-    const size_t o_trank = carve((size_t)g.T * 2);
-    const size_t o_rtile = carve((size_t)g.T * 2);
-    const size_t o_rcell0 = carve((size_t)g.T * 4);
-    const size_t percall_slot_floats = align_up((size_t)g.T * PERCALL_BLOCK * 4, A) / 4;
-    const size_t o_layers = carve((size_t)n_slots * percall_slot_floats * 4);
-    a.gpl = make_gp_layout(n);
-    // (a slot's written-cell bits -- FRESH maps, gg_internal.h -- live behind its layer: one buffer descriptor reaches both)
-    a.gp_bits_off = (int)align_up((size_t)a.gpl.elems, 16);
-    a.gp_bits_words = (a.gpl.elems / 64 + 2 + 1) & ~1; // (8-byte words; even: k_reset_fresh copies 16 bytes at a time)
-    a.gp2_stride = align_up(((size_t)a.gp_bits_off + (size_t)a.gp_bits_words) * 8, A) / 8;
-    a.gp_bits_stride = a.gp2_stride;
-    const size_t o_gp2 = carve((size_t)n_slots * a.gp2_stride * 8);
-    const size_t o_rec = carve((size_t)n_slots * Npad * 8);
-    const size_t o_sorted = carve((size_t)n_slots * Npad * 8);
-    a.zcell_stride = align_up((Npad + (size_t)32 * g.T + 64) * 4, A) / 4;
-    const size_t o_zcell = carve((size_t)n_slots * a.zcell_stride * 4);
-    a.hist_stride = align_up((size_t)a.NCH * a.hist_pitch * 4, A) / 4;
-    const size_t o_hist = carve((size_t)n_slots * a.hist_stride * 4);
-    a.emit_stride = align_up((size_t)a.NCH * 4 * 4, A) / 4;
-    const size_t o_emit = carve((size_t)n_slots * a.emit_stride * 4);
-    const size_t o_totals = carve((size_t)n_slots * 4 * 4);
-    a.tile_start_stride = align_up((size_t)(g.T + 1) * 4, A) / 4;
-    const size_t o_tstart = carve((size_t)n_slots * a.tile_start_stride * 4);
-    a.tile_live_stride = align_up((size_t)g.T, A);
-    const size_t o_tlive = carve((size_t)n_slots * a.tile_live_stride * 4);
-    a.tile_list_stride = align_up((size_t)g.T * 16, A) / 16;
-    const size_t o_tlist = carve((size_t)n_slots * a.tile_list_stride * 16);
-    const size_t o_tlcnt = carve((size_t)n_slots * 2 * 4);
-    const size_t o_fsync = carve(((size_t)2 * n_slots + 16) * 4);
-    const size_t o_ssync = carve(64);
-    const size_t o_fsync2 = carve(((size_t)2 * n_slots + 16) * 4);
-    const size_t o_ssync2 = carve(64);
-    const size_t o_scansync = carve((size_t)n_slots * SCAN_SYNC_WORDS * 8);
-    const size_t o_scansync2 = carve((size_t)n_slots * SCAN_SYNC_WORDS * 8);
-    a.sweep_xchg_stride = align_up(std::max<size_t>(gg::sweep_xchg_entries(ctx->sweep_params), 1) * 16, A) / 8;
-    const size_t o_xchg = carve((size_t)n_slots * a.sweep_xchg_stride * 8);
-    a.sweep_rec_stride = gg::sweep_pair_rec_floats(ctx->sweep_params);
-    a.sweep_rec_clouds = a.sweep_rec_stride ? std::min(n_slots, SWEEP_PAIR_MAX_CLOUDS) : 0;
-    const size_t o_srec = carve(std::max<size_t>((size_t)a.sweep_rec_clouds * a.sweep_rec_stride * 4, 64));
-    const size_t o_params = carve((size_t)PARAM_RING * n_slots * sizeof(CloudParams));
-    const size_t o_gparams = carve(sizeof(CloudParams));
-    const size_t o_spts = carve(max_points * sizeof(gg_point16));
-    const size_t o_slab = carve(max_points);
-    const size_t o_sidx = carve(max_points * 4);
-    const size_t o_scnt = carve(64);
-    const size_t o_scls = carve(max_points);
-    const size_t o_scell = carve(max_points * 4);
-    size_t o_apts[GG_ASYNC_DEPTH], o_alab[GG_ASYNC_DEPTH], o_aidx[GG_ASYNC_DEPTH], o_acnt[GG_ASYNC_DEPTH];
-    for (int k = 0; k < GG_ASYNC_DEPTH; ++k) {
-        o_apts[k] = carve(max_points * sizeof(gg_point16));
-        // results of one ticket as ONE block -- counts (64 B), then the index (4 n B), then the labels (n B) -- so that they come back
-        // with a single copy; where index and labels start inside it depends on the ticket's n
-        o_acnt[k] = carve(64 + max_points * 5 + 64);
-        o_aidx[k] = o_alab[k] = 0;
+    // ---- the arena: laid out once (arena_layout.h), counted, allocated, assigned ------------
+    std::vector<int> gp_border; // the elements of the cells no sweep visits: ring >= c
+    {
+        const GpLayout L = make_gp_layout(n);
+        for (int col = 0; col < n; ++col)
+            for (int row = 0; row < n; ++row)
+                if (std::max(std::abs(row - L.c), std::abs(col - L.c)) >= L.c) gp_border.push_back(gp_index(L, row, col));
     }
-    const size_t o_scroll = carve(a.gp2_stride * 8); // one layer in its device element order (map scroll) / two planes (images)
-    const size_t o_image = carve(3 * Cpad * 4);
-    const size_t o_bounds = carve(64);
-    const size_t gp_valid_words = ((size_t)a.gpl.elems + 31) / 32;
-    const size_t o_gpvalid = carve(gp_valid_words * 4);
-    std::vector<int> gp_border; // the cells no sweep visits: ring >= c
-    for (int col = 0; col < n; ++col)
-        for (int row = 0; row < n; ++row)
-            if (std::max(std::abs(row - a.gpl.c), std::abs(col - a.gpl.c)) >= a.gpl.c) gp_border.push_back(gp_index(a.gpl, row, col));
-    a.gp_border_n = (int)gp_border.size();
-    const size_t o_gpborder = carve(std::max<size_t>(gp_border.size() * 4, 64));
-    a.gp_fresh_cell = 1 + (a.gpl.VS - 1) * 64; // side 0, group 0, the last sheared position of ring 1: beyond the map's last column
-    const size_t o_dbg = carve(64 * 8); // sweep timing
-    const size_t o_pdbg = carve(2048 * 8); // pair sweep timing
-    const bool k2_timing = getenv("GG_K2_DEBUG") && (atoi(getenv("GG_K2_DEBUG")) == 9 || atoi(getenv("GG_K2_DEBUG")) == 5 || atoi(getenv("GG_K2_DEBUG")) == 6);
-    const size_t o_k2dbg = carve(k2_timing ? (size_t)K2_DBG_WGS * 32 * 8 : 64);
-    const size_t o_slotmaps = carve((size_t)n_slots * sizeof(ExportMap));
-    ctx->arena_bytes = off;
-    CREATE_CHK(hipMalloc(&ctx->d_arena, ctx->arena_bytes));
-    char *base = (char *)ctx->d_arena;
-    CREATE_CHK(hipMemsetAsync(base, 0, ctx->arena_bytes, ctx->stream));
-
-    a.expected = (const float *)(base + o_expected);
-    a.patch_table = (const float4 *)(base + o_ptable);
-    a.tile_rank = (const uint16_t *)(base + o_trank);
-    a.rank_tile = (const uint16_t *)(base + o_rtile);
-    a.rank_cell0 = (const uint32_t *)(base + o_rcell0);
-    a.layers = (float *)(base + o_layers);
-    a.gp2 = (float2 *)(base + o_gp2);
-    a.gp_bits = (unsigned long long *)(base + o_gp2) + a.gp_bits_off;
-    a.slot_layer_stride = percall_slot_floats;
-    a.rec = (uint2 *)(base + o_rec);
-    a.sorted = (uint2 *)(base + o_sorted);
-    a.zcell = (float *)(base + o_zcell);
-    a.point_stride = Npad;
-    a.hist = (uint32_t *)(base + o_hist);
-    a.chunk_emit = (uint32_t *)(base + o_emit);
-    a.totals = (uint32_t *)(base + o_totals);
-    a.tile_start = (uint32_t *)(base + o_tstart);
-    a.tile_live = (uint32_t *)(base + o_tlive);
-    a.tile_list = (uint4 *)(base + o_tlist);
-    a.tile_list_cnt = (uint32_t *)(base + o_tlcnt);
-    a.front_sync = (uint32_t *)(base + o_fsync);
-    a.sweep_sync = (uint32_t *)(base + o_ssync);
-    a.front_sync2 = (uint32_t *)(base + o_fsync2);
-    a.sweep_sync2 = (uint32_t *)(base + o_ssync2);
-    a.scan_sync = (unsigned long long *)(base + o_scansync);
-    a.scan_sync2 = (unsigned long long *)(base + o_scansync2);
+    const int k2_debug = env_int("GG_K2_DEBUG", 0);
+    ArenaShape shape{};
+    shape.g = g;
+    shape.n_slots = n_slots;
+    shape.max_points = max_points;
+    shape.PW = a.PW;
+    shape.hist_pitch = a.hist_pitch;
+    shape.gp_border_n = (int)gp_border.size();
+    shape.k2_timing = k2_debug == 9 || k2_debug == 5 || k2_debug == 6;
+    shape.sweep_timing = getenv("GG_SWEEP_TIMING") != nullptr;
+    shape.pair_timing = getenv("GG_PAIR_TIMING") != nullptr;
+    shape.sweep_xchg_entries = gg::sweep_xchg_entries(ctx->sweep_params);
+    shape.sweep_pair_rec_floats = gg::sweep_pair_rec_floats(ctx->sweep_params);
+    ArenaCounter count;
+    lay_out_arena(count, shape, a, *ctx);
+    ctx->arena_bytes = count.bytes;
+    CREATE_CHK(ctx->d_arena.create(ctx->arena_bytes));
+    CREATE_CHK(hipMemsetAsync(ctx->d_arena, 0, ctx->arena_bytes, ctx->stream));
+    ArenaAssigner assign{static_cast<char *>(ctx->d_arena.get())};
+    lay_out_arena(assign, shape, a, *ctx);
+    a.flags = 0;
+    a.k2_debug = k2_debug;
+    a.k3_debug = env_int("GG_K3_DEBUG", 0);
+    a.k5_debug = env_int("GG_K5_DEBUG", 0);
+    {
+        int row, col;
+        if (gp_cell_of(a.gpl, a.gp_fresh_cell, row, col)) { // (cannot happen: sheared position VS - 1 of ring 1 is column n + 125)
+            gg_destroy(ctx);
+            return GG_ERR_INVALID;
+        }
+    }
     {
         const uint32_t first_epoch[4] = {0u, 0u, 1u, 0u}; // (the exchange region starts zeroed: tag 0 is never current)
         CREATE_CHK(hipMemcpyAsync(a.sweep_sync, first_epoch, sizeof first_epoch, hipMemcpyHostToDevice, ctx->stream));
@@ -1401,56 +1306,21 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
     }
     {
         // one word the kernels can reach and the host can read without a copy: a bounded wait that ran out reports here
-        CREATE_CHK(hipHostMalloc((void **)&ctx->h_dev_error, 64, hipHostMallocMapped));
+        CREATE_CHK(ctx->h_dev_error.create(64, hipHostMallocMapped));
         *ctx->h_dev_error = 0u;
         void *dptr = nullptr;
-        CREATE_CHK(hipHostGetDevicePointer(&dptr, (void *)ctx->h_dev_error, 0));
+        CREATE_CHK(hipHostGetDevicePointer(&dptr, (void *)ctx->h_dev_error.get(), 0));
         a.dev_error = (uint32_t *)dptr;
     }
-    a.sweep_xchg = (unsigned long long *)(base + o_xchg);
-    a.sweep_rec = a.sweep_rec_clouds ? (float *)(base + o_srec) : nullptr;
-    a.pair_dbg = getenv("GG_PAIR_TIMING") ? (unsigned long long *)(base + o_pdbg) : nullptr;
-    a.flags = 0;
-    a.k2_debug = getenv("GG_K2_DEBUG") ? atoi(getenv("GG_K2_DEBUG")) : 0;
-    a.k2_dbg = (unsigned long long *)(base + o_k2dbg);
-    a.k3_debug = getenv("GG_K3_DEBUG") ? atoi(getenv("GG_K3_DEBUG")) : 0;
-    a.k5_debug = getenv("GG_K5_DEBUG") ? atoi(getenv("GG_K5_DEBUG")) : 0;
-    ctx->d_params = (CloudParams *)(base + o_params);
-    ctx->d_gparams = (CloudParams *)(base + o_gparams);
-    ctx->d_stage_pts = (gg_point16 *)(base + o_spts);
-    ctx->d_stage_labels = (uint8_t *)(base + o_slab);
-    ctx->d_stage_index = (int32_t *)(base + o_sidx);
-    ctx->d_stage_counts = (int32_t *)(base + o_scnt);
-    ctx->d_stage_class = (uint8_t *)(base + o_scls);
-    ctx->d_stage_cell = (int32_t *)(base + o_scell);
-    for (int k = 0; k < GG_ASYNC_DEPTH; ++k) {
-        gg_context::AsyncSlot &as = ctx->async_slot[k];
-        as.d_pts = (gg_point16 *)(base + o_apts[k]);
-        as.d_counts = (int32_t *)(base + o_acnt[k]);
-        as.d_index = (int32_t *)(base + o_acnt[k] + 64);
-        as.d_labels = nullptr; // (placed per ticket: behind the n index entries)
-    }
-    ctx->d_scroll_scratch = (float *)(base + o_scroll);
-    ctx->d_image = (float *)(base + o_image);
-    ctx->d_bounds = (float *)(base + o_bounds);
-    a.gp_valid = (const uint32_t *)(base + o_gpvalid);
-    a.gp_border = (const int *)(base + o_gpborder);
-    {
-        int row, col;
-        if (gp_cell_of(a.gpl, a.gp_fresh_cell, row, col)) { // (cannot happen: sheared position VS - 1 of ring 1 is column n + 125)
-            gg_destroy(ctx);
-            return GG_ERR_INVALID;
-        }
-        CREATE_CHK(hipMemcpyAsync(base + o_gpborder, gp_border.data(), gp_border.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        CREATE_CHK(hipStreamSynchronize(ctx->stream)); // (the vectors go out of scope)
-    }
-    if (getenv("GG_SWEEP_TIMING")) {
-        ctx->d_sweep_dbg = (unsigned long long *)(base + o_dbg);
+    CREATE_CHK(hipMemcpyAsync(const_cast<int *>(a.gp_border), gp_border.data(), gp_border.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    CREATE_CHK(hipStreamSynchronize(ctx->stream));
+    if (ctx->d_sweep_dbg) {
         const unsigned long long mode = getenv("GG_SWEEP_DEBUG") ? strtoull(getenv("GG_SWEEP_DEBUG"), nullptr, 0) : 0ull;
-        hipStreamSynchronize(ctx->stream); // (the arena memset above)
-        hipMemcpy(ctx->d_sweep_dbg + 63, &mode, 8, hipMemcpyHostToDevice);
+        CREATE_CHK(hipStreamSynchronize(ctx->stream)); // (the arena memset above)
+        CREATE_CHK(hipMemcpy(ctx->d_sweep_dbg + 63, &mode, 8, hipMemcpyHostToDevice));
     }
 
+    const size_t gp_valid_words = ((size_t)a.gpl.elems + 31) / 32; // one bit per element of the layer
     std::vector<uint32_t> gp_valid(gp_valid_words, 0u);
     for (int col = 0; col < n; ++col)
         for (int row = 0; row < n; ++row) {
@@ -1462,7 +1332,7 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
         // holds a cell is filled whole.  More than half of the lines with cells are only partly cells (the shear), and a partly
         // written line costs the memory a read-modify-write: 1024 maps take 0.60 ms with the exact mask (1.09 GB), 0.41 ms with
         // whole 64-byte sectors, 0.36 ms with whole lines (1.52 GB, 4.3 TB/s).
-        const int group = getenv("GG_FILL_GROUP") ? atoi(getenv("GG_FILL_GROUP")) : 16; // elements; 1 = exact mask (measurement)
+        const int group = env_int("GG_FILL_GROUP", 16); // elements; 1 = exact mask (measurement)
         if (group == 8 || group == 16 || group == 32)
             for (size_t w = 0; w < gp_valid_words; ++w) {
                 uint32_t v = gp_valid[w], o = 0u;
@@ -1473,46 +1343,44 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
                 gp_valid[w] = o;
             }
     }
-    CREATE_CHK(hipMemcpyAsync(base + o_gpvalid, gp_valid.data(), gp_valid_words * 4, hipMemcpyHostToDevice, ctx->stream));
-    CREATE_CHK(hipMemcpyAsync(base + o_expected, ctx->h_expected.data(), C * 4, hipMemcpyHostToDevice, ctx->stream));
-    CREATE_CHK(hipMemcpyAsync(base + o_trank, tile_rank.data(), (size_t)g.T * 2, hipMemcpyHostToDevice, ctx->stream));
-    CREATE_CHK(hipMemcpyAsync(base + o_rtile, rank_tile.data(), (size_t)g.T * 2, hipMemcpyHostToDevice, ctx->stream));
+    CREATE_CHK(hipMemcpyAsync(const_cast<uint32_t *>(a.gp_valid), gp_valid.data(), gp_valid_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    CREATE_CHK(hipMemcpyAsync(const_cast<float *>(a.expected), ctx->h_expected.data(), (size_t)g.C * 4, hipMemcpyHostToDevice, ctx->stream));
+    CREATE_CHK(hipMemcpyAsync(const_cast<uint16_t *>(a.tile_rank), tile_rank.data(), (size_t)g.T * 2, hipMemcpyHostToDevice, ctx->stream));
+    CREATE_CHK(hipMemcpyAsync(const_cast<uint16_t *>(a.rank_tile), rank_tile.data(), (size_t)g.T * 2, hipMemcpyHostToDevice, ctx->stream));
     std::vector<uint32_t> rank_cell0(g.T);
     for (int r = 0; r < g.T; ++r) {
         const int tile = rank_tile[r];
         rank_cell0[r] = (uint32_t)((tile % g.tiles_r) * TILE) | ((uint32_t)((tile / g.tiles_r) * TILE) << 16);
     }
-    CREATE_CHK(hipMemcpyAsync(base + o_rcell0, rank_cell0.data(), (size_t)g.T * 4, hipMemcpyHostToDevice, ctx->stream));
+    CREATE_CHK(hipMemcpyAsync(const_cast<uint32_t *>(a.rank_cell0), rank_cell0.data(), (size_t)g.T * 4, hipMemcpyHostToDevice, ctx->stream));
     // The one-map lists of the single-map getters and setters (extract_planes, insert_planes, gg_insert_cloud): entry s = slot s, NOT fresh.
     // Every such caller runs behind own_stream_waits_for_batches' make_real or behind its own call's sweep, so the layer in memory is the map
     std::vector<ExportMap> slot_maps((size_t)n_slots);
     for (int s = 0; s < n_slots; ++s) slot_maps[(size_t)s] = ExportMap{s, 0, 0.0f, 0};
-    CREATE_CHK(hipMemcpyAsync(base + o_slotmaps, slot_maps.data(), slot_maps.size() * sizeof(ExportMap), hipMemcpyHostToDevice, ctx->stream));
-    ctx->d_slot_maps = (const ExportMap *)(base + o_slotmaps);
+    CREATE_CHK(hipMemcpyAsync(const_cast<ExportMap *>(ctx->d_slot_maps), slot_maps.data(), slot_maps.size() * sizeof(ExportMap), hipMemcpyHostToDevice, ctx->stream));
     CREATE_CHK(hipStreamSynchronize(ctx->stream)); // the host vectors above go out of scope
 
-    CREATE_CHK(hipHostMalloc((void **)&ctx->h_params, sizeof(CloudParams) * PARAM_RING * n_slots, hipHostMallocDefault));
-    CREATE_CHK(hipHostMalloc((void **)&ctx->h_stage_pts, max_points * sizeof(gg_point16), hipHostMallocDefault));
-    CREATE_CHK(hipHostMalloc((void **)&ctx->h_stage_labels, max_points, hipHostMallocDefault));
-    CREATE_CHK(hipHostMalloc((void **)&ctx->h_stage_index, max_points * 4, hipHostMallocDefault));
-    CREATE_CHK(hipHostMalloc((void **)&ctx->h_stage_counts, 64, hipHostMallocDefault));
+    CREATE_CHK(ctx->h_params.create(sizeof(CloudParams) * PARAM_RING * n_slots));
+    CREATE_CHK(ctx->h_stage_pts.create(max_points * sizeof(gg_point16)));
+    CREATE_CHK(ctx->h_stage_labels.create(max_points));
+    CREATE_CHK(ctx->h_stage_index.create(max_points * 4));
+    CREATE_CHK(ctx->h_stage_counts.create(64));
     CREATE_CHK(ctx->ring.create());
     for (int k = 0; k < GG_ASYNC_DEPTH; ++k) {
         gg_context::AsyncSlot &as = ctx->async_slot[k];
-        CREATE_CHK(hipHostMalloc((void **)&as.h_pts, max_points * sizeof(gg_point16), hipHostMallocDefault));
-        CREATE_CHK(hipHostMalloc((void **)&as.h_counts, 64 + max_points * 5 + 64, hipHostMallocDefault)); // (the same block on the host)
+        CREATE_CHK(as.h_pts.create(max_points * sizeof(gg_point16)));
+        CREATE_CHK(as.h_counts.create(64 + max_points * 5 + 64)); // (the same block on the host)
         as.h_index = as.h_counts + 16;
-        as.h_labels = nullptr;
         if (hipHostGetDevicePointer((void **)&as.hd_counts, as.h_counts, 0) != hipSuccess) { // (no device view of pinned memory: the results take the copy)
             as.hd_counts = nullptr;
             (void)hipGetLastError();
         }
-        CREATE_CHK(hipEventCreateWithFlags(&as.uploaded, hipEventDisableTiming));
-        CREATE_CHK(hipEventCreateWithFlags(&as.computed, hipEventDisableTiming));
-        CREATE_CHK(hipEventCreateWithFlags(&as.downloaded, hipEventDisableTiming));
+        CREATE_CHK(as.uploaded.create());
+        CREATE_CHK(as.computed.create());
+        CREATE_CHK(as.downloaded.create());
     }
 
-    ctx->helper.configure((getenv("GG_HOST_THREADS") ? std::max(1, std::min(atoi(getenv("GG_HOST_THREADS")), 16)) : 8) - 1); // (never more than the usable CPUs - 1: host_helper.h)
+    ctx->helper.configure(std::max(1, std::min(env_int("GG_HOST_THREADS", 8), 16)) - 1); // (never more than the usable CPUs - 1: host_helper.h)
     {
         const int rc = rebuild_patch_table(ctx, a.cfg);
         if (rc != GG_OK) {
@@ -1543,52 +1411,10 @@ void gg_destroy(gg_context *ctx)
     if (ctx->h2d_stream) hipStreamSynchronize(ctx->h2d_stream);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     if (ctx->d2h_stream) hipStreamSynchronize(ctx->d2h_stream);
-    for (auto &p : ctx->pending) {
-        if (p.owns_start) hipEventDestroy(p.start);
-        hipEventDestroy(p.stop);
-    }
-    for (hipEvent_t e : ctx->free_single_events) hipEventDestroy(e);
-    ctx->ring.destroy();
-    if (ctx->half_fork) hipEventDestroy(ctx->half_fork);
-    if (ctx->half_done) hipEventDestroy(ctx->half_done);
-    if (ctx->half_stream) hipStreamDestroy(ctx->half_stream);
-    for (int k = 0; k < GG_ASYNC_DEPTH; ++k) {
-        gg_context::AsyncSlot &as = ctx->async_slot[k];
-        if (as.h_pts) hipHostFree(as.h_pts);
-        if (as.h_counts) hipHostFree(as.h_counts); // (index and labels live in the same block)
-        if (as.uploaded) hipEventDestroy(as.uploaded);
-        if (as.computed) hipEventDestroy(as.computed);
-        if (as.downloaded) hipEventDestroy(as.downloaded);
-    }
-    if (ctx->map_event) hipEventDestroy(ctx->map_event);
-    if (ctx->batch_event) hipEventDestroy(ctx->batch_event);
-    if (ctx->gather_event) hipEventDestroy(ctx->gather_event);
-    drop_graphs(ctx);
-    if (ctx->fork_event) hipEventDestroy(ctx->fork_event);
-    if (ctx->join_event) hipEventDestroy(ctx->join_event);
-    if (ctx->layers_event) hipEventDestroy(ctx->layers_event);
     for (auto &r : ctx->registered) hipHostUnregister(r.first);
     ctx->registered.clear();
-    if (ctx->h2d_stream) hipStreamDestroy(ctx->h2d_stream);
-    if (ctx->d2h_stream) hipStreamDestroy(ctx->d2h_stream);
-    if (ctx->h_dev_error) hipHostFree((void *)ctx->h_dev_error);
-    if (ctx->h_params) hipHostFree(ctx->h_params);
-    if (ctx->h_stage_pts) hipHostFree(ctx->h_stage_pts);
-    if (ctx->h_stage_labels) hipHostFree(ctx->h_stage_labels);
-    if (ctx->h_stage_index) hipHostFree(ctx->h_stage_index);
-    if (ctx->h_stage_counts) hipHostFree(ctx->h_stage_counts);
-    if (ctx->d_planes) hipFree(ctx->d_planes);
-    free_call_scratch(ctx->move_mem, ctx->move_ring);
-    free_call_scratch(ctx->export_mem, ctx->export_ring);
-    free_call_scratch(ctx->split_mem);
-    free_call_scratch(ctx->cluster_mem);
-    if (ctx->d_pc2) hipFree(ctx->d_pc2);
-    if (ctx->h_pc2) hipHostFree(ctx->h_pc2);
-    if (ctx->h_planes) hipHostFree(ctx->h_planes);
-    if (ctx->d_arena) hipFree(ctx->d_arena);
-    if (ctx->d_slot_cfg) hipFree(ctx->d_slot_cfg);
-    if (ctx->d_score_block) hipFree(ctx->d_score_block);
-    if (ctx->stream) hipStreamDestroy(ctx->stream);
+    drop_graphs(ctx);
+    release_profile_events(ctx);
     delete ctx;
 }
 
@@ -1668,13 +1494,9 @@ int gg_set_slot_configs(gg_context *ctx, int n, const int32_t *slots, int first_
     if (n == 0) return GG_OK;
     if (const int rc = check_slot_list(ctx, "gg_set_slot_configs", n, slots, first_slot)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_slot_cfg) {
-        void *p = nullptr;
-        if (hipMalloc(&p, sizeof(DevConfig) * (size_t)ctx->n_slots) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, GG_ERR_NOMEM, "gg_set_slot_configs: device table");
-        }
-        ctx->d_slot_cfg = static_cast<DevConfig *>(p);
+    if (!ctx->d_slot_cfg && ctx->d_slot_cfg.create(sizeof(DevConfig) * (size_t)ctx->n_slots) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, GG_ERR_NOMEM, "gg_set_slot_configs: device table");
     }
     std::vector<char> own = ctx->slot_own;
     std::vector<gg_config> cfg = ctx->slot_cfg;
@@ -1723,17 +1545,16 @@ int gg_set_score_labels(gg_context *ctx, int n_ids, const int32_t *ids)
     const size_t masks_off = align_up(scores_off + scores_bytes, 256);
     if (!ctx->d_score_block) {
         const size_t masks_bytes = (size_t)ctx->n_slots * ((ctx->max_points + 3) / 4) + 64;
-        void *p = nullptr;
-        if (hipMalloc(&p, masks_off + masks_bytes) != hipSuccess) {
+        DeviceBlock<uint8_t> block;
+        if (block.create(masks_off + masks_bytes) != hipSuccess) {
             (void)hipGetLastError();
             return fail(ctx, GG_ERR_NOMEM, "gg_set_score_labels: device block");
         }
-        if (hipMemset(p, 0, masks_off) != hipSuccess) { // (every slot off, every counter 0)
-            hipFree(p);
+        if (hipMemset(block, 0, masks_off) != hipSuccess) { // (every slot off, every counter 0)
             return fail(ctx, GG_ERR_HIP, "gg_set_score_labels: hipMemset");
         }
-        ctx->d_score_block = p;
-        uint8_t *base = static_cast<uint8_t *>(p);
+        ctx->d_score_block = std::move(block);
+        uint8_t *base = ctx->d_score_block;
         ctx->score.ring_bin = base;
         ctx->score.slot_on = base + on_off;
         ctx->score.scores = reinterpret_cast<unsigned long long *>(base + scores_off);
@@ -1935,7 +1756,7 @@ int gg_reset_maps(gg_context *ctx, int first_slot, int n, double pos_x, double p
             launch_fill_bytes((uint8_t *)(a.tile_live + (size_t)first * a.tile_live_stride), (size_t)count * a.tile_live_stride * 4, 0xFF, on);
         }
         if (ctx->fresh_enabled) { // the interior stays unwritten: the next batch's sweep rewrites it anyway (make_real() for everybody else)
-            static const bool probe_all = getenv("GG_FRESH_MAPS") && atoi(getenv("GG_FRESH_MAPS")) == 2; // (measurement: every cell written AND marked)
+            static const bool probe_all = env_int("GG_FRESH_MAPS", 1) == 2; // (measurement: every cell written AND marked)
             if (probe_all) launch_fill2_strided(gp2_ptr(a, first), (size_t)a.gpl.elems, a.gp2_stride, count, init[GG_LAYER_GROUND], init[GG_LAYER_GROUNDPATCH], a.gp_valid, on);
             launch_reset_fresh(a, first, count, init[GG_LAYER_GROUND], init[GG_LAYER_GROUNDPATCH], on, probe_all ? 1 : 0);
             for (int s = first; s < first + count; ++s) ctx->fresh[s] = 1, ctx->fresh_z[s] = odom_z;
@@ -2016,11 +1837,11 @@ static int ensure_move_scratch(gg_context *ctx, hipStream_t st)
     if (const int rc = alloc_call_scratch(ctx, "gg_move_maps", st, o_scratch + (size_t)cap * row, ring_bytes, {{o_cells, cells.data(), cells.size() * sizeof(int2)}},
                                           &ctx->move_mem, &ctx->move_ring))
         return rc;
-    char *block = (char *)ctx->move_mem.dev;
+    char *block = ctx->move_mem.dev;
     ctx->d_move_cells = (const int2 *)(block + o_cells);
     ctx->d_move_params = (MoveParams *)(block + o_params);
     ctx->d_move_scratch = (float2 *)(block + o_scratch);
-    ctx->h_move_params = (MoveParams *)ctx->move_mem.pinned;
+    ctx->h_move_params = (MoveParams *)ctx->move_mem.pinned.get();
     ctx->move_cap = cap;
     return GG_OK;
 }
@@ -2149,7 +1970,7 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
                                           {{o_off, off.data(), off.size() * sizeof(uint32_t)}, {o_elem, elem.data(), elem.size() * sizeof(uint32_t)}, {o_cell, cell.data(), cell.size() * sizeof(uint16_t)}},
                                           &ctx->export_mem, &ctx->export_ring))
         return rc;
-    char *block = (char *)ctx->export_mem.dev, *h = (char *)ctx->export_mem.pinned;
+    char *block = ctx->export_mem.dev, *h = ctx->export_mem.pinned;
     ctx->d_export_off = (const uint32_t *)(block + o_off);
     ctx->d_export_elem = (const uint32_t *)(block + o_elem);
     ctx->d_export_cell = (const uint16_t *)(block + o_cell);
@@ -2339,9 +2160,9 @@ static int ensure_split_scratch(gg_context *ctx, const char *who, hipStream_t st
     const size_t o_counts = align_up(ring * sizeof(SplitCloud), 256);
     const size_t n_pairs = ring * (size_t)std::max(ctx->arena.NCH, 1);
     if (const int rc = alloc_call_scratch(ctx, who, st, o_counts + n_pairs * sizeof(uint2), ring * sizeof(SplitCloud), {}, &ctx->split_mem, nullptr)) return rc;
-    ctx->d_split_clouds = (SplitCloud *)ctx->split_mem.dev;
-    ctx->d_split_counts = (uint2 *)((char *)ctx->split_mem.dev + o_counts);
-    ctx->h_split_clouds = (SplitCloud *)ctx->split_mem.pinned;
+    ctx->d_split_clouds = (SplitCloud *)ctx->split_mem.dev.get();
+    ctx->d_split_counts = (uint2 *)(ctx->split_mem.dev + o_counts);
+    ctx->h_split_clouds = (SplitCloud *)ctx->split_mem.pinned.get();
     return GG_OK;
 }
 
@@ -2456,7 +2277,7 @@ static int ensure_cluster_scratch(gg_context *ctx, const char *who, hipStream_t 
     const int chunks = (ctx->arena.g.C + CLUSTER_CHUNK_CELLS - 1) / CLUSTER_CHUNK_CELLS;
     const size_t words = (size_t)PARAM_RING * ctx->n_slots * (size_t)chunks;
     if (const int rc = alloc_call_scratch(ctx, who, st, words * sizeof(uint32_t), 64, {}, &ctx->cluster_mem, nullptr)) return rc;
-    ctx->d_cluster_counts = (uint32_t *)ctx->cluster_mem.dev;
+    ctx->d_cluster_counts = (uint32_t *)ctx->cluster_mem.dev.get();
     ctx->cluster_cell_chunks = chunks;
     return GG_OK;
 }
@@ -2537,36 +2358,55 @@ int gg_get_layer(gg_context *ctx, int slot, int layer, float *dst)
     return GG_OK;
 }
 
-// dst[l] (nullable) receives layer l; the destinations need not be aligned (they may sit inside a serialised message)
+// d_planes / h_planes at their first use: GG_NUM_LAYERS dense planes, `plane_floats` apart, on the device and in pinned host memory
+static size_t plane_floats(const gg_context *ctx) { return align_up((size_t)ctx->arena.g.C * 4, 256) / 4; }
+static int ensure_plane_staging(gg_context *ctx)
+{
+    const size_t bytes = (size_t)GG_NUM_LAYERS * plane_floats(ctx) * sizeof(float);
+    if (!ctx->d_planes) HIPCHK(ctx, ctx->d_planes.create(bytes));
+    if (!ctx->h_planes) HIPCHK(ctx, ctx->h_planes.create(bytes));
+    return GG_OK;
+}
+// Planes that came down into h_planes move on to the caller's, on the context's host threads: plane src[k] of the staging block to dst[k]
+// (which need not be aligned: it may sit inside a serialised message), for k < n_want
+static void copy_staged_planes(gg_context *ctx, void *const dst[], const int src[], int n_want, size_t plane)
+{
+    const size_t C = (size_t)ctx->arena.g.C;
+    if (n_want == 0) return;
+    ctx->helper.split((size_t)n_want * C, [&](size_t lo, size_t hi) {
+        for (size_t k = lo / C; k < (size_t)n_want && k * C < hi; ++k) {
+            const size_t a0 = std::max(lo, k * C) - k * C, a1 = std::min(hi, (k + 1) * C) - k * C;
+            memcpy((char *)dst[k] + a0 * sizeof(float), ctx->h_planes + (size_t)src[k] * plane + a0, (a1 - a0) * sizeof(float));
+        }
+    });
+}
+
+// dst[l] (nullable) receives layer l
 static int get_layers_impl(gg_context *ctx, int slot, void *const dst[GG_NUM_LAYERS])
 {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (const int rc = own_stream_waits_for_batches(ctx)) return rc;
-    const size_t plane = align_up((size_t)ctx->arena.g.C * 4, 256) / 4;
-    if (!ctx->d_planes) HIPCHK(ctx, hipMalloc((void **)&ctx->d_planes, (size_t)GG_NUM_LAYERS * plane * sizeof(float)));
-    if (!ctx->h_planes) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_planes, (size_t)GG_NUM_LAYERS * plane * sizeof(float), hipHostMallocDefault));
+    const size_t plane = plane_floats(ctx);
+    if (const int rc = ensure_plane_staging(ctx)) return rc;
     // The requested planes are extracted side by side, come down in ONE copy into pinned memory (a copy into the caller's
     // pageable matrices is staged by the runtime in small pieces: 0.7 ms for eleven 364 x 364 layers, against 0.15 ms), and the
     // context's host threads move them on to where the caller wants them.
-    int want[GG_NUM_LAYERS], n_want = 0;
+    void *to[GG_NUM_LAYERS];
+    int from[GG_NUM_LAYERS], n_want = 0;
     unsigned want_mask = 0u;
     for (int l = 0; l < GG_NUM_LAYERS; ++l) {
         if (!dst[l]) continue;
         want_mask |= 1u << l;
-        want[n_want++] = l;
+        to[n_want] = dst[l];
+        from[n_want] = n_want; // (plane k = the k-th requested layer)
+        ++n_want;
     }
     if (n_want == 0) return GG_OK;
     if (const int rc = extract_planes(ctx, slot, want_mask, ctx->d_planes, plane, ctx->stream)) return rc; // (plane k = the k-th requested layer)
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_planes, ctx->d_planes, (size_t)n_want * plane * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t C = (size_t)ctx->arena.g.C;
-    ctx->helper.split((size_t)n_want * C, [&](size_t lo, size_t hi) {
-        for (size_t k = lo / C; k < (size_t)n_want && k * C < hi; ++k) {
-            const size_t a0 = std::max(lo, k * C) - k * C, a1 = std::min(hi, (k + 1) * C) - k * C;
-            memcpy((char *)dst[want[k]] + a0 * sizeof(float), ctx->h_planes + k * plane + a0, (a1 - a0) * sizeof(float));
-        }
-    });
+    copy_staged_planes(ctx, to, from, n_want, plane);
     return GG_OK;
 }
 
@@ -2692,6 +2532,37 @@ int gg_get_terrain_image(gg_context *ctx, int slot, float *dst)
     return GG_OK;
 }
 
+// The gg_batch of the single-cloud host entry points: one cloud of n32 packed points at d_points for `slot`.  The caller adds its outputs
+static gg_batch single_cloud_batch(const gg_context *ctx, int slot, const gg_point16 *d_points, const int32_t *n32, const float origin[3], const double *base_z,
+                                   const double *tf)
+{
+    gg_batch b{};
+    b.n_clouds = 1;
+    b.first_slot = slot;
+    b.point_format = GG_POINT16;
+    b.d_points = d_points;
+    b.cloud_stride = ctx->max_points;
+    b.n_points = n32;
+    b.origins = origin;
+    b.base_z = base_z;
+    b.transforms = tf;
+    return b;
+}
+
+// records [lo, hi) of a sensor_msgs/PointCloud2 payload -> the packed records the device reads
+static void unpack_pc2(const uint8_t *data, size_t lo, size_t hi, size_t point_step, size_t off_x, size_t off_y, size_t off_z, size_t off_ring, gg_point16 *dst)
+{
+    for (size_t i = lo; i < hi; ++i) {
+        const uint8_t *p = data + i * point_step;
+        gg_point16 &d = dst[i];
+        memcpy(&d.x, p + off_x, 4);
+        memcpy(&d.y, p + off_y, 4);
+        memcpy(&d.z, p + off_z, 4);
+        memcpy(&d.ring, p + off_ring, 2);
+        d.pad = 0;
+    }
+}
+
 // sensor_msgs/PointCloud2 payload -> the packed records the device reads, in one host pass (the reference goes
 // wire -> 32-byte PCL points first, pcl::fromROSMsg at src/GroundGridNodelet.cpp:120)
 int gg_filter_cloud_pc2(gg_context *ctx, int slot, const uint8_t *data, size_t n, size_t point_step, size_t off_x, size_t off_y,
@@ -2705,27 +2576,10 @@ int gg_filter_cloud_pc2(gg_context *ctx, int slot, const uint8_t *data, size_t n
         return fail(ctx, GG_ERR_INVALID, "field offset outside point_step");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    for (size_t i = 0; i < n; ++i) {
-        const uint8_t *p = data + i * point_step;
-        gg_point16 &d = ctx->h_stage_pts[i];
-        memcpy(&d.x, p + off_x, 4);
-        memcpy(&d.y, p + off_y, 4);
-        memcpy(&d.z, p + off_z, 4);
-        memcpy(&d.ring, p + off_ring, 2);
-        d.pad = 0;
-    }
+    unpack_pc2(data, 0, n, point_step, off_x, off_y, off_z, off_ring, ctx->h_stage_pts); // (serially, one upload: gg_filter_cloud_pc2_out differs)
     if (n) HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage_pts, ctx->h_stage_pts, n * sizeof(gg_point16), hipMemcpyHostToDevice, s));
     const int32_t n32 = (int32_t)n;
-    gg_batch b{};
-    b.n_clouds = 1;
-    b.first_slot = slot;
-    b.point_format = GG_POINT16;
-    b.d_points = ctx->d_stage_pts;
-    b.cloud_stride = ctx->max_points;
-    b.n_points = &n32;
-    b.origins = origin;
-    b.base_z = &base_z;
-    b.transforms = map_from_cloud;
+    gg_batch b = single_cloud_batch(ctx, slot, ctx->d_stage_pts, &n32, origin, &base_z, map_from_cloud);
     b.d_labels = ctx->d_stage_labels;
     b.d_out_index = ctx->d_stage_index;
     b.d_out_counts = ctx->d_stage_counts;
@@ -2752,44 +2606,25 @@ int gg_filter_cloud_pc2_out(gg_context *ctx, int slot, const uint8_t *data, size
     if (ctx->next_ticket != ctx->oldest_ticket) return fail(ctx, GG_ERR_INVALID, "gg_filter_cloud_pc2_out while async tickets are outstanding");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t block = 64 + ctx->max_points * GG_PC2_POINT_STEP;
-    if (!ctx->d_pc2) HIPCHK(ctx, hipMalloc((void **)&ctx->d_pc2, block));
-    if (!ctx->h_pc2) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_pc2, block, hipHostMallocDefault));
+    if (!ctx->d_pc2) HIPCHK(ctx, ctx->d_pc2.create(block));
+    if (!ctx->h_pc2) HIPCHK(ctx, ctx->h_pc2.create(block));
     hipStream_t s = ctx->stream;
     for (int c = 0; c < 2; ++c) { // pack and upload in two pieces, as the 32-byte entry point does
         const size_t lo = n * c / 2, hi = n * (c + 1) / 2;
         if (hi == lo) continue;
-        ctx->helper.split(hi - lo, [&](size_t a0, size_t a1) {
-            for (size_t i = lo + a0; i < lo + a1; ++i) {
-                const uint8_t *p = data + i * point_step;
-                gg_point16 &d = ctx->h_stage_pts[i];
-                memcpy(&d.x, p + off_x, 4);
-                memcpy(&d.y, p + off_y, 4);
-                memcpy(&d.z, p + off_z, 4);
-                memcpy(&d.ring, p + off_ring, 2);
-                d.pad = 0;
-            }
-        });
+        ctx->helper.split(hi - lo, [&](size_t a0, size_t a1) { unpack_pc2(data, lo + a0, lo + a1, point_step, off_x, off_y, off_z, off_ring, ctx->h_stage_pts); });
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage_pts + lo, ctx->h_stage_pts + lo, (hi - lo) * sizeof(gg_point16), hipMemcpyHostToDevice, s));
     }
     const int32_t n32 = (int32_t)n;
-    gg_batch b{};
-    b.n_clouds = 1;
-    b.first_slot = slot;
-    b.point_format = GG_POINT16;
-    b.d_points = ctx->d_stage_pts;
-    b.cloud_stride = ctx->max_points;
-    b.n_points = &n32;
-    b.origins = origin;
-    b.base_z = &base_z;
-    b.transforms = map_from_cloud;
-    b.d_out_counts = reinterpret_cast<int32_t *>(ctx->d_pc2);
+    gg_batch b = single_cloud_batch(ctx, slot, ctx->d_stage_pts, &n32, origin, &base_z, map_from_cloud);
+    b.d_out_counts = reinterpret_cast<int32_t *>(ctx->d_pc2.get());
     b.d_out_pc2 = ctx->d_pc2 + 64;
     const int rc = enqueue_batch(ctx, &b, s);
     if (rc != GG_OK) return rc;
     // counts and records in one copy: the size of the returned cloud is only known on the device, and it is nearly n
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pc2, ctx->d_pc2, 64 + n * GG_PC2_POINT_STEP, hipMemcpyDeviceToHost, s));
     SYNCCHK(ctx, hipStreamSynchronize(s));
-    const size_t got = (size_t)reinterpret_cast<const int32_t *>(ctx->h_pc2)[0];
+    const size_t got = (size_t)reinterpret_cast<const int32_t *>(ctx->h_pc2.get())[0];
     if (out_n) *out_n = got;
     const uint8_t *src = ctx->h_pc2 + 64;
     ctx->helper.split(got * GG_PC2_POINT_STEP, [&](size_t a0, size_t a1) { memcpy(out_data + a0, src + a0, a1 - a0); });
@@ -2861,6 +2696,7 @@ static int enqueue_ticket(gg_context *ctx, int slot, const gg_point32 *cloud, si
     const int set = pipelined ? ctx->next_ticket % GG_ASYNC_DEPTH : 0;
     ctx->slot_of_ticket[ctx->next_ticket % GG_ASYNC_DEPTH] = set;
     gg_context::AsyncSlot &as = ctx->async_slot[set];
+    const ContextBuffers::AsyncSet &dev = ctx->async_set[set]; // (its device side)
 
     static const bool host_timing = getenv("GG_HOST_TIMING") != nullptr; // (tools: where does the host call spend its time)
     const auto t_pack0 = std::chrono::steady_clock::now();
@@ -2871,7 +2707,7 @@ static int enqueue_ticket(gg_context *ctx, int slot, const gg_point32 *cloud, si
         const size_t lo = n * c / pieces, hi = n * (c + 1) / pieces;
         if (hi == lo) continue;
         ctx->helper.split(hi - lo, [&](size_t a0, size_t a1) { pack_points(cloud + lo + a0, as.h_pts + lo + a0, a1 - a0); });
-        HIPCHK(ctx, hipMemcpyAsync(as.d_pts + lo, as.h_pts + lo, (hi - lo) * sizeof(gg_point16), hipMemcpyHostToDevice, pipelined ? ctx->h2d_stream : ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(dev.d_pts + lo, as.h_pts + lo, (hi - lo) * sizeof(gg_point16), hipMemcpyHostToDevice, pipelined ? ctx->h2d_stream : ctx->stream));
     }
     if (host_timing) ctx->host_t[0] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_pack0).count();
     if (pipelined) {
@@ -2880,24 +2716,13 @@ static int enqueue_ticket(gg_context *ctx, int slot, const gg_point32 *cloud, si
     }
 
     const int32_t n32 = (int32_t)n;
-    gg_batch b{};
-    b.n_clouds = 1;
-    b.first_slot = slot;
-    b.point_format = GG_POINT16;
-    b.d_points = as.d_pts;
-    b.cloud_stride = ctx->max_points;
-    b.n_points = &n32;
-    b.origins = origin;
-    b.base_z = &base_z;
-    b.transforms = tf;
-    as.d_labels = reinterpret_cast<uint8_t *>(as.d_index + n); // [counts][index: n][labels: n]
+    gg_batch b = single_cloud_batch(ctx, slot, dev.d_pts, &n32, origin, &base_z, tf);
     as.h_labels = reinterpret_cast<uint8_t *>(as.h_index + n);
     const bool direct = ctx->results_direct != 0 && as.hd_counts != nullptr;
-    int32_t *const res_counts = direct ? as.hd_counts : as.d_counts, *const res_index = direct ? as.hd_counts + 16 : as.d_index;
+    int32_t *const res_counts = direct ? as.hd_counts : dev.d_counts, *const res_index = direct ? as.hd_counts + 16 : dev.d_index;
     b.d_labels = reinterpret_cast<uint8_t *>(res_index); // (+ label_shift = 4 n on the device: the launch's arguments do not depend on n)
     ctx->next_label_shift = (int)(n * 4);
     b.d_out_index = res_index;
-    b.d_out_clouds = nullptr;
     b.d_out_counts = res_counts;
     const int rc = enqueue_batch(ctx, &b, ctx->stream, plan);
     ctx->next_label_shift = 0;
@@ -2911,7 +2736,7 @@ static int enqueue_ticket(gg_context *ctx, int slot, const gg_point32 *cloud, si
             HIPCHK(ctx, hipEventRecord(as.computed, ctx->stream));
             HIPCHK(ctx, hipStreamWaitEvent(down, as.computed, 0));
         }
-        HIPCHK(ctx, hipMemcpyAsync(as.h_counts, as.d_counts, 64 + n * 5, hipMemcpyDeviceToHost, down)); // counts + index + labels: one copy
+        HIPCHK(ctx, hipMemcpyAsync(as.h_counts, dev.d_counts, 64 + n * 5, hipMemcpyDeviceToHost, down)); // counts + index + labels: one copy
         HIPCHK(ctx, hipEventRecord(as.downloaded, down));
     }
     if (plan && (plan->mask & ~EARLY_LAYERS)) { // the layers that are only final now (ground, groundpatch, points) follow the results: the host
@@ -3055,9 +2880,8 @@ int gg_filter_cloud_layers(gg_context *ctx, int slot, const gg_point32 *cloud, s
         return get_layers_impl(ctx, slot, d);
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t C = (size_t)ctx->arena.g.C, plane = align_up(C * 4, 256) / 4;
-    if (!ctx->d_planes) HIPCHK(ctx, hipMalloc((void **)&ctx->d_planes, (size_t)GG_NUM_LAYERS * plane * sizeof(float)));
-    if (!ctx->h_planes) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_planes, (size_t)GG_NUM_LAYERS * plane * sizeof(float), hipHostMallocDefault));
+    const size_t C = (size_t)ctx->arena.g.C, plane = plane_floats(ctx);
+    if (const int rc = ensure_plane_staging(ctx)) return rc;
     LayerPlan plan;
     plan.mask = mask;
     bool staged[GG_NUM_LAYERS] = {};
@@ -3076,16 +2900,14 @@ int gg_filter_cloud_layers(gg_context *ctx, int slot, const gg_point32 *cloud, s
     }
     // planes that came down into the staging block move on to the caller's: the early ones WHILE the device sweeps, the late ones at the end
     auto copy_staged = [&](unsigned group) {
-        int want[GG_NUM_LAYERS], n_want = 0;
-        for (int l = 0; l < GG_NUM_LAYERS; ++l)
-            if (staged[l] && ((group >> l) & 1u)) want[n_want++] = l;
-        if (n_want)
-            ctx->helper.split((size_t)n_want * C, [&](size_t lo, size_t hi) {
-                for (size_t k = lo / C; k < (size_t)n_want && k * C < hi; ++k) {
-                    const size_t a0 = std::max(lo, k * C) - k * C, a1 = std::min(hi, (k + 1) * C) - k * C;
-                    memcpy(layers[want[k]] + a0, ctx->h_planes + (size_t)want[k] * plane + a0, (a1 - a0) * sizeof(float));
-                }
-            });
+        void *to[GG_NUM_LAYERS];
+        int from[GG_NUM_LAYERS], n_want = 0;
+        for (int l = 0; l < GG_NUM_LAYERS; ++l) {
+            if (!staged[l] || !((group >> l) & 1u)) continue;
+            to[n_want] = layers[l];
+            from[n_want++] = l; // (layer l was staged in plane l)
+        }
+        copy_staged_planes(ctx, to, from, n_want, plane);
     };
     if (mask & EARLY_LAYERS) {
         HIPCHK(ctx, hipEventSynchronize(ctx->join_event)); // (the side branch: behind k_reduce, beside k_patch / k_sweep)
