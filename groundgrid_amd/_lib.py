@@ -51,6 +51,7 @@ SYMBOLS = [
     "gg_rasterize_clouds",
     "gg_export_slopes",
     "gg_cluster_clouds",
+    "gg_clearance_clouds",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -149,7 +150,7 @@ class GGSplitSet(C.Structure):
     _fields_ = [("d_points", C.c_void_p), ("d_height", C.c_void_p), ("d_source", C.c_void_p)]
 
 
-# the labelled clouds of a call: the ten leading members of gg_cloud_split, gg_cloud_raster and gg_cloud_clusters
+# the labelled clouds of a call: the ten leading members of gg_cloud_split, gg_cloud_raster, gg_cloud_clusters and gg_cloud_clearance
 _LABELLED_CLOUDS = [
     ("n", C.c_int),
     ("first_slot", C.c_int),
@@ -215,6 +216,28 @@ class GGCloudClusters(C.Structure):
         ("d_n_clusters", C.c_void_p),
         ("d_clusters", C.c_void_p),
         ("max_clusters", C.c_int),
+    ]
+
+
+GG_CLEARANCE_NONE = 0x7FFFFFFF  # d_dist2 of a cell without an obstacle (an empty map, or beyond max_cells)
+
+
+class GGCloudClearance(C.Structure):
+    """gg_cloud_clearance: the obstacle distance field of many maps, in device memory (gg_clearance_clouds)"""
+
+    _fields_ = _LABELLED_CLOUDS + [
+        ("min_points", C.c_int),
+        ("min_height", C.c_float),
+        ("max_height", C.c_float),
+        ("d_seeds", C.c_void_p),
+        ("seed_stride", C.c_size_t),
+        ("max_cells", C.c_int),
+        ("order", C.c_int),
+        ("d_dist2", C.c_void_p),
+        ("plane_stride", C.c_size_t),
+        ("d_nearest", C.c_void_p),
+        ("d_distance", C.c_void_p),
+        ("d_n_occupied", C.c_void_p),
     ]
 
 
@@ -293,6 +316,7 @@ def load():
     L.gg_rasterize_clouds.argtypes = [vp, P(GGCloudRaster), vp]
     L.gg_export_slopes.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
     L.gg_cluster_clouds.argtypes = [vp, P(GGCloudClusters), vp]
+    L.gg_clearance_clouds.argtypes = [vp, P(GGCloudClearance), vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

@@ -277,6 +277,17 @@ class ClusterOutputs:
         return self.clusters[b, :k].cpu().numpy().copy().view(CLUSTER_DTYPE).reshape(k)
 
 
+@dataclass
+class ClearanceOutputs:
+    """what GroundSegmentation.clearance_clouds and clearance_planes return (CUDA torch tensors [B, rows, cols], [B, cols, rows] with
+    order="col"; None where nothing was asked for)"""
+
+    dist2: "object" = None       # torch.int32: the squared distance, in cells, to the nearest occupied cell; _lib.GG_CLEARANCE_NONE: none
+    nearest: "object" = None     # torch.int32: the linear index, in `order`, of that cell; -1: none
+    distance: "object" = None    # torch.float32: sqrt(dist2) * resolution, in metres; +inf: none
+    n_occupied: "object" = None  # torch.int32 [B]: the occupied cells of every map
+
+
 class GroundSegmentation:
     """Mirror of groundgrid::GroundSegmentation (include/groundgrid/GroundSegmentation.h:48-71)."""
 
@@ -653,6 +664,91 @@ class GroundSegmentation:
         stream = self._stream_arg(on_torch_stream, points.device)
         _check(self._L, self._ctx, self._L.gg_cluster_clouds(self._ctx, C.byref(x), stream), "gg_cluster_clouds")
         return res
+
+    def _clearance_call(self, who, x, B, device, max_cells, order, nearest, distance, out, on_torch_stream):
+        """What clearance_clouds and clearance_planes (`who`) share: the outputs of B maps on `device`, the rest of `x`, the call."""
+        import torch
+
+        res = out if out is not None else ClearanceOutputs()
+        plane = (B, self.rows, self.cols) if order == "row" else (B, self.cols, self.rows)
+        want = {"dist2": (plane, torch.int32), "nearest": (plane, torch.int32) if nearest else None,
+                "distance": (plane, torch.float32) if distance else None, "n_occupied": ((B,), torch.int32)}
+        for field, spec in want.items():
+            t = getattr(res, field)
+            if spec is None:
+                if t is not None:
+                    raise ValueError(f"{who}: out.{field} is given but not asked for")
+                continue
+            shape, dtype = spec
+            if t is None:
+                setattr(res, field, torch.empty(shape, dtype=dtype, device=device))
+            elif not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA {dtype} tensor of shape {shape}")
+        x.max_cells = max_cells
+        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.d_dist2, x.plane_stride = res.dist2.data_ptr(), self.rows * self.cols
+        x.d_nearest = res.nearest.data_ptr() if nearest else None
+        x.d_distance = res.distance.data_ptr() if distance else None
+        x.d_n_occupied = res.n_occupied.data_ptr()
+        stream = self._stream_arg(on_torch_stream, device)
+        _check(self._L, self._ctx, self._L.gg_clearance_clouds(self._ctx, C.byref(x), stream), "gg_clearance_clouds")
+        return res
+
+    @staticmethod
+    def _clearance_args(who, max_cells, order):
+        if order not in ("row", "col"):
+            raise ValueError(f"{who}: order is 'row' or 'col'")
+        if int(max_cells) != max_cells or int(max_cells) < 0 or int(max_cells) > 0x7FFFFFFF:
+            raise ValueError(f"{who}: max_cells is an integer >= 0")
+        return int(max_cells)
+
+    def clearance_clouds(self, points, n_points: Sequence[int], *, labels=None, masks=None, transforms=None, slots=None, first_slot: int = 0,
+                         min_points: int = 1, min_height: float = -math.inf, max_height: float = math.inf, max_cells: int = 0,
+                         order: str = "row", nearest: bool = True, distance: bool = True, out: Optional[ClearanceOutputs] = None,
+                         on_torch_stream: bool = True) -> ClearanceOutputs:
+        """The obstacle distance field of many labelled clouds on the device (gg_clearance_clouds, cloud mode): per cell of cloud b's map
+        the exact squared Euclidean distance, in cells, to the nearest occupied cell (dist2, 0 on an occupied cell), the linear index of
+        that cell in `order` (nearest; of several equally near ones the smallest row, then the smallest column) and the distance in metres
+        (distance = sqrt(dist2) * resolution).  A cell is occupied exactly where cluster_clouds with the same points, labels / masks,
+        transforms, slots, min_points, min_height and max_height gives cell_cluster >= 0.  max_cells=R > 0 reports no obstacle beyond R
+        cells.  No obstacle: dist2 = _lib.GG_CLEARANCE_NONE, nearest = -1, distance = +inf.  n_occupied int32 [B] counts the occupied cells.
+        nearest=False / distance=False leave those planes out (None).  `out`: a ClearanceOutputs of an earlier call with the same
+        arguments, whose tensors are reused.  Integer arithmetic only: bit-identical from run to run.  Enqueued on the current torch
+        stream or, with on_torch_stream=False, on the context's own stream; nothing synchronises.  No map changes; fresh maps stay fresh."""
+        who = "clearance_clouds"
+        max_cells = self._clearance_args(who, max_cells, order)
+        if int(min_points) < 1:
+            raise ValueError(f"{who}: min_points < 1")
+        if math.isnan(float(min_height)) or math.isnan(float(max_height)):
+            raise ValueError(f"{who}: min_height or max_height is NaN")
+        self._torch_used = True
+        x = _lib.GGCloudClearance()
+        B, stride, keep = self._labelled_clouds(who, x, points, n_points, labels, masks, transforms, slots, first_slot)
+        x.min_points, x.min_height, x.max_height = int(min_points), float(min_height), float(max_height)
+        return self._clearance_call(who, x, B, points.device, max_cells, order, nearest, distance, out, on_torch_stream)
+
+    def clearance_planes(self, seeds, *, max_cells: int = 0, order: str = "row", nearest: bool = True, distance: bool = True,
+                         out: Optional[ClearanceOutputs] = None, on_torch_stream: bool = True) -> ClearanceOutputs:
+        """The obstacle distance field of occupancy planes the caller holds (gg_clearance_clouds, seed mode): seeds is a contiguous CUDA
+        torch.int32 tensor [B, rows, cols] ([B, cols, rows] with order="col"), B <= n_slots, whose cells are occupied where the word is
+        >= 0 -- ClusterOutputs.cell_cluster as it is, or any plane thresholded into {-1, 0}.  Everything else as clearance_clouds; no map
+        is read.  seeds may not be one of the outputs."""
+        import torch
+
+        who = "clearance_planes"
+        max_cells = self._clearance_args(who, max_cells, order)
+        if not (torch.is_tensor(seeds) and seeds.is_cuda and seeds.dtype == torch.int32 and seeds.dim() == 3 and seeds.is_contiguous()):
+            raise ValueError(f"{who}: seeds must be a contiguous CUDA torch.int32 tensor [B, rows, cols]")
+        B = int(seeds.shape[0])
+        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
+        if tuple(seeds.shape[1:]) != plane:
+            raise ValueError(f"{who}: seeds of shape {tuple(seeds.shape)} do not fit planes of {plane}")
+        if out is not None and out.dist2 is not None and torch.is_tensor(out.dist2) and out.dist2.data_ptr() == seeds.data_ptr():
+            raise ValueError(f"{who}: seeds may not be an output")
+        self._torch_used = True
+        x = _lib.GGCloudClearance()
+        x.n, x.d_seeds, x.seed_stride = B, seeds.data_ptr(), self.rows * self.cols
+        return self._clearance_call(who, x, B, seeds.device, max_cells, order, nearest, distance, out, on_torch_stream)
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:
         """A checkpoint of the named maps: {"planes": export_layers() of all eleven layers [n, 11, cols, rows] (on the device, enqueued on

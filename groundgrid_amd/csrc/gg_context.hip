@@ -2320,6 +2320,62 @@ int gg_cluster_clouds(gg_context *ctx, const gg_cloud_clusters *x, void *stream)
     return map_call_end(ctx, f);
 }
 
+// The obstacle distance field of many maps (k16_clearance.hip).  Cloud mode: the frame of gg_cluster_clouds with the same per-cloud records
+// and the same occupancy launches, on the d_dist2 planes.  Seed mode: a ring entry and the ordering of the export for maps 0 .. n-1, none of
+// which is read.  Nothing is synchronised, no map is filled and no host-side flag changes in either.
+int gg_clearance_clouds(gg_context *ctx, const gg_cloud_clearance *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_clearance_clouds";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_cloud_clearance");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    const bool from_clouds = x->d_points != nullptr;
+    if (from_clouds == (x->d_seeds != nullptr)) return fail(ctx, GG_ERR_INVALID, who, "exactly one of d_points and d_seeds");
+    if (!from_clouds && (x->n_points || x->transforms || x->d_labels || x->d_label_masks || x->slots))
+        return fail(ctx, GG_ERR_INVALID, who, "a cloud member is set together with d_seeds");
+    if (!from_clouds && x->seed_stride < C) return fail(ctx, GG_ERR_INVALID, who, "seed_stride is smaller than rows * cols");
+    if (!x->d_dist2) return fail(ctx, GG_ERR_INVALID, who, "d_dist2 is required");
+    if (x->plane_stride < C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->max_cells < 0) return fail(ctx, GG_ERR_INVALID, who, "max_cells < 0");
+    if (from_clouds && x->min_points < 1) return fail(ctx, GG_ERR_INVALID, who, "min_points < 1");
+    if (from_clouds && (x->min_height != x->min_height || x->max_height != x->max_height)) return fail(ctx, GG_ERR_INVALID, who, "min_height or max_height is NaN");
+    MapCall f;
+    ClearanceArgs ca{};
+    ca.from_clouds = from_clouds;
+    if (from_clouds) {
+        const LabelledClouds in{x->n, x->first_slot, x->slots, x->point_format, x->d_points, x->cloud_stride, x->n_points, x->transforms, x->d_labels, x->d_label_masks};
+        if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &ca.occ.cl)) return rc;
+        ca.occ.min_points = x->min_points;
+        ca.occ.min_height = x->min_height;
+        ca.occ.max_height = x->max_height;
+        ca.occ.order = x->order;
+        ca.occ.planes = reinterpret_cast<uint32_t *>(x->d_dist2);
+        ca.occ.plane_stride = x->plane_stride;
+        ca.occ.cell_chunks = (int)((C + CLUSTER_CHUNK_CELLS - 1) / CLUSTER_CHUNK_CELLS);
+        ca.seeds = x->d_dist2; // (read in place)
+        ca.seed_stride = x->plane_stride;
+    } else {
+        if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc; // (GG_ERR_CAPACITY: n > n_slots)
+        ca.seeds = x->d_seeds;
+        ca.seed_stride = x->seed_stride;
+    }
+    const int cols = ctx->arena.g.cols;
+    const bool bounded = x->max_cells > 0 && x->max_cells < cols; // (max_cells >= cols: no row holds a cell that far)
+    ca.order = x->order;
+    ca.reach = bounded ? x->max_cells : cols;
+    ca.reach2 = (uint32_t)std::min<uint64_t>(x->max_cells > 0 ? (uint64_t)x->max_cells * (uint64_t)x->max_cells : ~0ull, (uint64_t)GG_CLEARANCE_NONE - 1);
+    ca.dist2 = x->d_dist2;
+    ca.nearest = x->d_nearest;
+    ca.distance = x->d_distance;
+    ca.plane_stride = x->plane_stride;
+    ca.n_occupied = x->d_n_occupied;
+    launch_clearance(ctx->arena, ca, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
 int gg_get_map_position(const gg_context *ctx, int slot, double *pos_x, double *pos_y)
 {
     if (!slot_ok(ctx, slot)) return GG_ERR_CAPACITY;

@@ -391,6 +391,24 @@ struct ClusterArgs {
     int cell_chunks;               // ceil(rows * cols / CLUSTER_CHUNK_CELLS)
 };
 
+// gg_clearance_clouds (k16_clearance.hip): what its launches share.  Map i of the call is row i of every buffer.  Cloud mode: `occ` is a
+// ClusterArgs on the d_dist2 planes (launch_cluster_occupancy leaves the occupancy there and the first pass reads it in place: seeds ==
+// dist2, seed_stride == plane_stride); seed mode: `occ` is not looked at
+struct ClearanceArgs {
+    ClusterArgs occ;
+    bool from_clouds;
+    const int32_t *seeds;          // map i's occupancy plane at seeds + i * seed_stride: occupied where the word is >= 0
+    size_t seed_stride;
+    int order;                     // GG_PLANES_*
+    int reach;                     // how far along a row the second pass looks: max_cells, or cols when that is 0 or larger
+    uint32_t reach2;               // a dist2 above this is "no obstacle": max_cells squared, or GG_CLEARANCE_NONE - 1
+    int32_t *dist2;                // the caller's planes, map i's at + i * plane_stride; dist2 is the working memory
+    int32_t *nearest;              // nullable
+    float *distance;               // nullable
+    size_t plane_stride;
+    int32_t *n_occupied;           // [map], nullable
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -435,6 +453,8 @@ void launch_images(const Arena &a, const ImageArgs &x, int n_maps, int variant, 
 void launch_split(const Arena &a, const SplitArgs &x, int n_clouds, hipStream_t s);              // k12_split.hip: k_split_count, then k_split_scatter
 void launch_raster(const Arena &a, const RasterArgs &x, int n_clouds, hipStream_t s);            // k13_raster.hip: k_raster_planes<false>, k_raster_scatter, k_raster_planes<true>
 void launch_cluster(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s);          // k15_cluster.hip: count, seed, merge, flatten, scan, rank, apply, points, finalise
+void launch_cluster_occupancy(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s); // k15_cluster.hip: its first three launches alone: x.planes[L] := occupied ? L : 0xFFFFFFFF
+void launch_clearance(const Arena &a, const ClearanceArgs &x, int n_maps, hipStream_t s);        // k16_clearance.hip: (occupancy,) columns, rows
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

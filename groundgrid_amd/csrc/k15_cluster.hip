@@ -317,13 +317,23 @@ template <bool IDS> static void launch_cluster_points(const Arena &a, const Clus
     });
 }
 
+static bool cluster_band(const ClusterArgs &x) { return !(x.min_height == -__builtin_inff() && x.max_height == __builtin_inff()); }
+
+// THE occupancy of the clouds' obstacle grids, in x.planes: zero, count, seed.  gg_clearance_clouds (k16_clearance.hip) starts from it too:
+// its occupied cells are those whose word is >= 0 as an int32, which is where d_cell_cluster >= 0 at the end of launch_cluster
+void launch_cluster_occupancy(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s)
+{
+    const dim3 cells(x.cell_chunks, n_clouds);
+    hipLaunchKernelGGL((k_cluster_cells<false>), cells, dim3(256), 0, s, a, x);
+    launch_cluster_points<false>(a, x, cluster_band(x), n_clouds, s); // (the count gathers the ground only for a band)
+    hipLaunchKernelGGL((k_cluster_cells<true>), cells, dim3(256), 0, s, a, x);
+}
+
 void launch_cluster(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s)
 {
     const dim3 cells(x.cell_chunks, n_clouds);
-    const bool band = !(x.min_height == -__builtin_inff() && x.max_height == __builtin_inff());
-    hipLaunchKernelGGL((k_cluster_cells<false>), cells, dim3(256), 0, s, a, x);
-    launch_cluster_points<false>(a, x, band, n_clouds, s); // (the count gathers the ground only for a band)
-    hipLaunchKernelGGL((k_cluster_cells<true>), cells, dim3(256), 0, s, a, x);
+    const bool band = cluster_band(x);
+    launch_cluster_occupancy(a, x, n_clouds, s);
     hipLaunchKernelGGL(k_cluster_merge, cells, dim3(256), 0, s, a, x);
     hipLaunchKernelGGL(k_cluster_flatten, cells, dim3(256), 0, s, a, x);
     hipLaunchKernelGGL(k_cluster_scan, dim3(n_clouds), dim3(256), 0, s, a, x);

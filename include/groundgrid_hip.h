@@ -797,6 +797,73 @@ typedef struct gg_cloud_clusters {
 int gg_cluster_clouds(gg_context *ctx, const gg_cloud_clusters *x, void *stream);
 #define GG_HAS_CLUSTER_CLOUDS 1
 
+/* The CLEARANCE of a batch in DEVICE memory: per cell of every map how far the nearest occupied cell is and which one it is -- the exact
+ * Euclidean distance transform of the obstacle grid with its feature transform, what costmap inflation, clearance checks along a path and
+ * "nearest object" look-ups start from, and what a caller otherwise composes from gg_cluster_clouds, a download,
+ * scipy.ndimage.distance_transform_edt per map on the host and an upload.  One call for many maps, in exactly one of two modes:
+ *   cloud mode  d_points != NULL and d_seeds == NULL.  The ten leading members are those of gg_cloud_raster, with the same meaning and the
+ *               same checks; cloud i meets map slots ? slots[i] : first_slot + i.  A cell is occupied exactly where gg_cluster_clouds,
+ *               given the same ten members, min_points, min_height and max_height, writes d_cell_cluster >= 0: participation (label 99 /
+ *               mask code 2, the path's own inside test, !(h < min_height) && !(h > max_height), a NaN h participates, a FRESH map's ground
+ *               is its constant odom_z) and the threshold min_points are its, computed by the same launches.
+ *   seed mode   d_seeds != NULL.  Map i's occupancy is the plane of rows * cols int32 at d_seeds + i * seed_stride, cell (row, col) where
+ *               `order` puts it; a cell is occupied when its word is >= 0: a d_cell_cluster plane of gg_cluster_clouds plugs in as it is,
+ *               and so does any plane the caller thresholds into {-1, 0}.  d_points, n_points, transforms, d_labels, d_label_masks and slots
+ *               must be NULL; point_format, cloud_stride, first_slot, min_points, min_height and max_height are ignored.  No map is read;
+ *               n may not exceed the context's n_slots.  d_seeds may not overlap an output.
+ * For cell (r, c), over the occupied cells (r', c') of the same map, nothing wrapping at the border:
+ *   d_dist2     the minimum of (r - r')^2 + (c - c')^2: an exact integer, 0 on an occupied cell.
+ *   d_nearest   the linear index, in `order` (r' * cols + c' for GG_PLANES_ROWMAJOR, r' + c' * rows for GG_PLANES_COLMAJOR), of the occupied
+ *               cell that attains the minimum; among several the one with the smallest r', then the smallest c'.  The tie rule does not
+ *               depend on `order`.
+ *   d_distance  sqrtf((float)dist2) * res, res the `float` resolution of gg_geometry: IEEE square root, one multiplication, no contraction.
+ *   max_cells   R > 0: a cell whose dist2 > R * R is reported as having no obstacle; every other value is that of R = 0 (unbounded).
+ *   no obstacle (an empty map, or beyond R): d_dist2 = GG_CLEARANCE_NONE, d_nearest = -1, d_distance = +inf (0x7F800000).
+ *   d_n_occupied[i]  the number of occupied cells of map i, whatever max_cells is.
+ *   addressing  map i's plane of rows * cols words at <output> + i * plane_stride, cell (row, col) where `order` puts it.  EVERY cell of
+ *               every given plane of every listed map is written, an empty cloud's (n_points[i] == 0) included; the words between
+ *               rows * cols and plane_stride never are, and an output whose pointer is NULL is not touched.  4-byte alignment.  d_dist2 is
+ *               required: it is the working memory of the call and holds intermediate words while it runs.
+ *   determinism integer arithmetic and one integer atomic add only: bit-identical from run to run and independent of scheduling.
+ * Cloud mode is stateless exactly as gg_rasterize_clouds is: it reads the caller's buffers, the maps' `ground` layer and their positions.
+ * A FRESH map is neither read nor filled, and it and every other fresh map stay fresh; the lazily kept layers stay pending; no layer,
+ * position, configuration, score or liveness flag changes.  `stream` and ordering are those of gg_rasterize_clouds: the call enqueues and
+ * returns, the host arrays may be freed on return, it waits for every earlier map mutation, batch, export and import of the context, and
+ * later writers of these maps on other streams wait for it.  Seed mode takes an entry of the same ring and orders itself the same way, but
+ * reads no map.  The caller's buffers must stay valid and unmodified until `stream` has passed the call.
+ * Argument errors write nothing and change nothing: in cloud mode every error of gg_rasterize_clouds for the ten shared members; and
+ * GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with n > 0: both or neither of d_points and d_seeds, a
+ * cloud member (n_points, transforms, d_labels, d_label_masks, slots) set in seed mode, seed_stride < rows * cols in seed mode, null
+ * d_dist2, plane_stride < rows * cols, an unknown order, max_cells < 0, and in cloud mode min_points < 1 or a NaN min_height or max_height;
+ * GG_ERR_CAPACITY for n > n_slots in seed mode.  n == 0 is GG_OK before anything else is looked at.  The first call of a context may
+ * allocate (GG_ERR_NOMEM) and block; later calls only enqueue.  Capture into a caller's graph is not supported. */
+#define GG_CLEARANCE_NONE 0x7FFFFFFF
+typedef struct gg_cloud_clearance {
+    int n;                         /* clouds (cloud mode) / maps (seed mode) */
+    int first_slot;                /* cloud i meets map first_slot + i when slots == NULL */
+    const int32_t *slots;          /* host [n], nullable, distinct */
+    int point_format;              /* GG_POINT32 / GG_POINT16 */
+    const void *d_points;          /* [n][cloud_stride], as gg_batch.d_points; NULL: seed mode */
+    size_t cloud_stride;           /* points */
+    const int32_t *n_points;       /* host [n] */
+    const double *transforms;      /* host [n][12], nullable, as gg_batch.transforms */
+    const uint8_t *d_labels;       /* [n][cloud_stride] GG_LABEL_*  -- exactly one of these two (cloud mode) */
+    const uint8_t *d_label_masks;  /* [n][(cloud_stride + 3) / 4] 2-bit masks, as gg_batch.d_label_masks */
+    int min_points;                /* >= 1: participating points that make a cell occupied, as gg_cloud_clusters */
+    float min_height, max_height;  /* the height band (not NaN; -INFINITY / +INFINITY: open), as gg_cloud_clusters */
+    const int32_t *d_seeds;        /* [n] planes of rows * cols int32, seed_stride apart: occupied where >= 0; NULL: cloud mode */
+    size_t seed_stride;            /* int32 words, >= rows * cols */
+    int max_cells;                 /* 0: unbounded; R > 0: no obstacle is reported beyond R cells */
+    int order;                     /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR */
+    int32_t *d_dist2;              /* [n] planes of rows * cols int32, plane_stride apart; required: the call's working memory */
+    size_t plane_stride;           /* 32-bit words, >= rows * cols, of all three kinds of plane */
+    int32_t *d_nearest;            /* [n] planes, nullable */
+    float   *d_distance;           /* [n] planes, nullable */
+    int32_t *d_n_occupied;         /* [n], nullable */
+} gg_cloud_clearance;
+int gg_clearance_clouds(gg_context *ctx, const gg_cloud_clearance *x, void *stream);
+#define GG_HAS_CLEARANCE_CLOUDS 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
