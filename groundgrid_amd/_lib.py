@@ -52,6 +52,7 @@ SYMBOLS = [
     "gg_export_slopes",
     "gg_cluster_clouds",
     "gg_clearance_clouds",
+    "gg_visibility_clouds",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -150,7 +151,8 @@ class GGSplitSet(C.Structure):
     _fields_ = [("d_points", C.c_void_p), ("d_height", C.c_void_p), ("d_source", C.c_void_p)]
 
 
-# the labelled clouds of a call: the ten leading members of gg_cloud_split, gg_cloud_raster, gg_cloud_clusters and gg_cloud_clearance
+# the labelled clouds of a call: the ten leading members of gg_cloud_split, gg_cloud_raster, gg_cloud_clusters, gg_cloud_clearance and
+# gg_cloud_visibility
 _LABELLED_CLOUDS = [
     ("n", C.c_int),
     ("first_slot", C.c_int),
@@ -241,6 +243,25 @@ class GGCloudClearance(C.Structure):
     ]
 
 
+GG_CELL_FREE, GG_CELL_UNKNOWN, GG_CELL_OCCUPIED = -1, 0, 1  # the states of a d_state plane (gg_visibility_clouds)
+
+
+class GGCloudVisibility(C.Structure):
+    """gg_cloud_visibility: the free, unknown and occupied cells of many labelled clouds, in device memory (gg_visibility_clouds)"""
+
+    _fields_ = _LABELLED_CLOUDS + [
+        ("min_points", C.c_int),
+        ("min_height", C.c_float),
+        ("max_height", C.c_float),
+        ("origins", C.POINTER(C.c_float)),
+        ("max_cells", C.c_int),
+        ("order", C.c_int),
+        ("d_state", C.c_void_p),
+        ("plane_stride", C.c_size_t),
+        ("d_counts", C.c_void_p),
+    ]
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -317,6 +338,7 @@ def load():
     L.gg_export_slopes.argtypes = [vp, C.c_int, P(C.c_int32), C.c_int, C.c_uint, C.c_int, vp, C.c_size_t, vp]
     L.gg_cluster_clouds.argtypes = [vp, P(GGCloudClusters), vp]
     L.gg_clearance_clouds.argtypes = [vp, P(GGCloudClearance), vp]
+    L.gg_visibility_clouds.argtypes = [vp, P(GGCloudVisibility), vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

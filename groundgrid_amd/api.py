@@ -288,6 +288,14 @@ class ClearanceOutputs:
     n_occupied: "object" = None  # torch.int32 [B]: the occupied cells of every map
 
 
+@dataclass
+class VisibilityOutputs:
+    """what GroundSegmentation.visibility_clouds returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    state: "object" = None   # torch.int32 [B, rows, cols] ([B, cols, rows] with order="col"): _lib.GG_CELL_FREE / _UNKNOWN / _OCCUPIED = -1 / 0 / 1
+    counts: "object" = None  # torch.int32 [B, 3]: the free, unknown and occupied cells of every map
+
+
 class GroundSegmentation:
     """Mirror of groundgrid::GroundSegmentation (include/groundgrid/GroundSegmentation.h:48-71)."""
 
@@ -749,6 +757,61 @@ class GroundSegmentation:
         x = _lib.GGCloudClearance()
         x.n, x.d_seeds, x.seed_stride = B, seeds.data_ptr(), self.rows * self.cols
         return self._clearance_call(who, x, B, seeds.device, max_cells, order, nearest, distance, out, on_torch_stream)
+
+    def visibility_clouds(self, points, n_points: Sequence[int], origins, *, labels=None, masks=None, transforms=None, slots=None,
+                          first_slot: int = 0, min_points: int = 1, min_height: float = -math.inf, max_height: float = math.inf,
+                          max_cells: int = 0, order: str = "row", counts: bool = True, out: Optional[VisibilityOutputs] = None,
+                          on_torch_stream: bool = True) -> VisibilityOutputs:
+        """Where the sensor saw what, for many labelled clouds on the device (gg_visibility_clouds): state int32 [B, rows, cols]
+        (order="row"; [B, cols, rows] with order="col") holds _lib.GG_CELL_OCCUPIED (1) exactly where cluster_clouds with the same points,
+        labels / masks, transforms, slots, min_points, min_height and max_height gives cell_cluster >= 0; else _lib.GG_CELL_FREE (-1) where
+        a ground or non-ground return (label 49 / 99) landed or the integer ray from the sensor cell to the cell of such a return passed;
+        else _lib.GG_CELL_UNKNOWN (0).  origins: [B, 3] float32 (anything np.asarray turns into that), the sensor in the MAP frame as for
+        filter_batch; only x and y are used, and a sensor outside its map or not finite casts no ray.  One ray per distinct cell with a
+        return; an occupied cell does not stop it; max_cells=R > 0 clears at most the first R cells of a ray.  Returns outside the map
+        clear nothing inside it.  counts int32 [B, 3]: the free, unknown and occupied cells of every map (None with counts=False).  A state
+        plane is a seed plane of clearance_planes as it stands (cells >= 0: occupied or never observed).  `out`: a VisibilityOutputs of
+        an earlier call with the same arguments, whose tensors are reused.  Integer arithmetic only: bit-identical from run to run.
+        Enqueued on the current torch stream or, with on_torch_stream=False, on the context's own stream; nothing synchronises.  No map
+        changes; fresh maps stay fresh."""
+        import torch
+
+        who = "visibility_clouds"
+        max_cells = self._clearance_args(who, max_cells, order)
+        if int(min_points) < 1:
+            raise ValueError(f"{who}: min_points < 1")
+        if math.isnan(float(min_height)) or math.isnan(float(max_height)):
+            raise ValueError(f"{who}: min_height or max_height is NaN")
+        try:
+            host_origins = np.ascontiguousarray(np.asarray(origins, dtype=np.float32))
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{who}: origins must be [B, 3] float32: {e}") from None
+        if host_origins.ndim != 2 or host_origins.shape[1] != 3 or not torch.is_tensor(points) or host_origins.shape[0] != points.shape[0]:
+            raise ValueError(f"{who}: origins of shape {host_origins.shape} are not [B, 3]")
+        self._torch_used = True
+        x = _lib.GGCloudVisibility()
+        B, stride, keep = self._labelled_clouds(who, x, points, n_points, labels, masks, transforms, slots, first_slot)
+        res = out if out is not None else VisibilityOutputs()
+        want = {"state": (B, self.rows, self.cols) if order == "row" else (B, self.cols, self.rows), "counts": (B, 3) if counts else None}
+        for field, shape in want.items():
+            t = getattr(res, field)
+            if shape is None:
+                if t is not None:
+                    raise ValueError(f"{who}: out.{field} is given but not asked for")
+                continue
+            if t is None:
+                setattr(res, field, torch.empty(shape, dtype=torch.int32, device=points.device))
+            elif not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {shape}")
+        x.min_points, x.min_height, x.max_height = int(min_points), float(min_height), float(max_height)
+        x.origins = host_origins.ctypes.data_as(C.POINTER(C.c_float))
+        x.max_cells = max_cells
+        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.d_state, x.plane_stride = res.state.data_ptr(), self.rows * self.cols
+        x.d_counts = res.counts.data_ptr() if counts else None
+        stream = self._stream_arg(on_torch_stream, points.device)
+        _check(self._L, self._ctx, self._L.gg_visibility_clouds(self._ctx, C.byref(x), stream), "gg_visibility_clouds")
+        return res
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:
         """A checkpoint of the named maps: {"planes": export_layers() of all eleven layers [n, 11, cols, rows] (on the device, enqueued on

@@ -2176,6 +2176,7 @@ struct LabelledClouds {
     const int32_t *n_points;
     const double *transforms;
     const uint8_t *d_labels, *d_label_masks;
+    const float *origins = nullptr; // gg_visibility_clouds alone: host [n][3], the sensor in the map frame
 };
 
 // Their frame, the export's: the arguments are checked before anything is touched (in.n > 0), then the call's ring entry is taken, `f->st`
@@ -2211,6 +2212,8 @@ static int labelled_clouds_begin(gg_context *ctx, const char *who, const Labelle
         c.fresh_z = f->hm[i].fresh_z;
         c.has_tf = in.transforms ? 1 : 0;
         c.io_index = i;
+        c.ox = in.origins ? in.origins[(size_t)3 * i] : 0.f;
+        c.oy = in.origins ? in.origins[(size_t)3 * i + 1] : 0.f;
         c.pos_x = ctx->pos_x[c.slot];
         c.pos_y = ctx->pos_y[c.slot];
         for (int k = 0; k < 12; ++k) c.tf[k] = in.transforms ? in.transforms[(size_t)12 * i + k] : 0.0;
@@ -2373,6 +2376,46 @@ int gg_clearance_clouds(gg_context *ctx, const gg_cloud_clearance *x, void *stre
     ca.plane_stride = x->plane_stride;
     ca.n_occupied = x->d_n_occupied;
     launch_clearance(ctx->arena, ca, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
+// The free, unknown and occupied cells of many labelled clouds (k17_visibility.hip), in the frame of gg_cluster_clouds with the same per-cloud
+// records (plus the sensor) and the same occupancy launches, on the d_state planes.  Nothing is synchronised, no map is filled and no
+// host-side flag changes.
+int gg_visibility_clouds(gg_context *ctx, const gg_cloud_visibility *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_visibility_clouds";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_cloud_visibility");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    if (!x->origins || !x->d_state) return fail(ctx, GG_ERR_INVALID, who, "origins and d_state are required");
+    if (x->plane_stride < C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->max_cells < 0) return fail(ctx, GG_ERR_INVALID, who, "max_cells < 0");
+    if (x->min_points < 1) return fail(ctx, GG_ERR_INVALID, who, "min_points < 1");
+    if (x->min_height != x->min_height || x->max_height != x->max_height) return fail(ctx, GG_ERR_INVALID, who, "min_height or max_height is NaN");
+    // one bit per cell in a work-group's LDS, and 2 n n + n < 2^24 along a ray (k17_visibility.hip): both hold up to a side of 1143
+    if (C > VISIBILITY_MAX_CELLS) return fail(ctx, GG_ERR_GEOMETRY, who, "the map has more cells than a work-group's local memory has bits");
+    MapCall f;
+    VisibilityArgs va{};
+    const LabelledClouds in{x->n, x->first_slot, x->slots, x->point_format, x->d_points, x->cloud_stride, x->n_points, x->transforms, x->d_labels, x->d_label_masks, x->origins};
+    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &va.occ.cl)) return rc;
+    va.occ.min_points = x->min_points;
+    va.occ.min_height = x->min_height;
+    va.occ.max_height = x->max_height;
+    va.occ.order = x->order;
+    va.occ.planes = reinterpret_cast<uint32_t *>(x->d_state);
+    va.occ.plane_stride = x->plane_stride;
+    va.occ.cell_chunks = (int)((C + CLUSTER_CHUNK_CELLS - 1) / CLUSTER_CHUNK_CELLS);
+    va.order = x->order;
+    va.max_cells = x->max_cells;
+    va.state = va.occ.planes;
+    va.plane_stride = x->plane_stride;
+    va.counts = x->d_counts;
+    va.bitmap_words = (int)((C + 31) / 32);
+    launch_visibility(ctx->arena, va, x->n, f.st);
     return map_call_end(ctx, f);
 }
 

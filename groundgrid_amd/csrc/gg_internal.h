@@ -338,6 +338,7 @@ struct SplitCloud {
     float fresh_z;
     int has_tf;      // the points are in the sensor frame: p_map = transform_point(tf, p) first
     int io_index;    // the cloud's row of the caller's buffers and of the call's chunk counters: its position in gg_cloud_split
+    float ox, oy;    // gg_visibility_clouds: the sensor in the map frame (zero in every other call)
     double pos_x, pos_y; // the map's position when the call was made
     double tf[12];
 };
@@ -409,6 +410,20 @@ struct ClearanceArgs {
     int32_t *n_occupied;           // [map], nullable
 };
 
+// gg_visibility_clouds (k17_visibility.hip): what its launches share.  `occ` is a ClusterArgs on the d_state planes (launch_cluster_occupancy
+// leaves the occupancy there); the per-cloud records are gg_split_clouds' with the sensor in (ox, oy)
+constexpr size_t VISIBILITY_LDS_MAX = 160 * 1024 - 256;              // bytes of the crossed-cell bitmap one work-group may hold
+constexpr size_t VISIBILITY_MAX_CELLS = VISIBILITY_LDS_MAX * 8;      // ... so rows * cols may not exceed this (a side of 1143)
+struct VisibilityArgs {
+    ClusterArgs occ;
+    int order;                     // GG_PLANES_*
+    int max_cells;                 // 0: unbounded; R > 0: a ray crosses at most its first R cells
+    uint32_t *state;               // the caller's d_state as 32-bit words, cloud i's plane at state + i * plane_stride; the working memory
+    size_t plane_stride;
+    int32_t *counts;               // [cloud][3] free, unknown, occupied; nullable
+    int bitmap_words;              // ceil(rows * cols / 32): 32-bit words of dynamic LDS of the trace launch
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -455,6 +470,7 @@ void launch_raster(const Arena &a, const RasterArgs &x, int n_clouds, hipStream_
 void launch_cluster(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s);          // k15_cluster.hip: count, seed, merge, flatten, scan, rank, apply, points, finalise
 void launch_cluster_occupancy(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s); // k15_cluster.hip: its first three launches alone: x.planes[L] := occupied ? L : 0xFFFFFFFF
 void launch_clearance(const Arena &a, const ClearanceArgs &x, int n_maps, hipStream_t s);        // k16_clearance.hip: (occupancy,) columns, rows
+void launch_visibility(const Arena &a, const VisibilityArgs &x, int n_clouds, hipStream_t s);    // k17_visibility.hip: occupancy, hits, trace, states
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

@@ -864,6 +864,75 @@ typedef struct gg_cloud_clearance {
 int gg_clearance_clouds(gg_context *ctx, const gg_cloud_clearance *x, void *stream);
 #define GG_HAS_CLEARANCE_CLOUDS 1
 
+/* The VISIBILITY of a batch in DEVICE memory: per cell of every map whether the sensor saw it free, saw an obstacle in it, or never saw it
+ * -- the third state a clearance field lacks (gg_clearance_clouds gives a cell behind a wall as much clearance as one a hundred beams
+ * crossed), what costmap_2d's obstacle layer clears by ray tracing, what exploration takes its frontiers from, and what a caller otherwise
+ * composes from a download of the clouds and a ray walk per point on the host.  One call for many clouds.  The ten leading members are
+ * those of gg_cloud_raster, with the same meaning and the same checks; cloud i meets map slots ? slots[i] : first_slot + i.
+ *   occupied    exactly where gg_cluster_clouds, given the same ten members, min_points, min_height and max_height, writes
+ *               d_cell_cluster >= 0: participation (label 99 / mask code 2, the path's own inside test, !(h < min_height) &&
+ *               !(h > max_height), a NaN h participates, a FRESH map's ground is its constant odom_z) and the threshold min_points are
+ *               its, computed by the same launches, as gg_clearance_clouds does in cloud mode.
+ *   hit         a cell in which at least one point p < n_points[i] lands whose label is 49 or 99 (mask code 1 or 2); the cell is that of
+ *               the path's inside test, on the map-frame point when `transforms` is given.  A point outside the map and any other label
+ *               byte contribute nothing, neither a hit nor a ray: RETURNS BEYOND THE MAP'S EDGE CLEAR NOTHING INSIDE IT.
+ *   sensor cell (r0, c0), the cell of ((double)origins[i][0], (double)origins[i][1]) by the same inside test and index arithmetic under
+ *               the map's current position.  When the origin lies outside the map or is not finite, cloud i casts no ray; its hits and
+ *               its occupancy still count.
+ *   ray         of a hit cell (r1, c1): with dr = r1 - r0, dc = c1 - c0 and n = max(|dr|, |dc|), for k = 0 .. n-1 -- and only k < R when
+ *               max_cells = R > 0 -- the cell
+ *                   (r0 + sgn(dr) * ((2 k |dr| + n) / (2 n)), c0 + sgn(dc) * ((2 k |dc| + n) / (2 n)))     (integer division)
+ *               is CROSSED: k d / n rounded to the nearest integer, halves away from zero.  The sensor cell is crossed, the end cell is
+ *               not; consecutive cells are 8-neighbours; the eight octants mirror each other exactly; n = 0 crosses nothing.  One ray per
+ *               distinct hit cell: the ray depends on (sensor cell, end cell) alone.  The implementation relies on 2 n n + n < 2^24 (every
+ *               term is then exact in a float as well) and on one bit per cell fitting a work-group's local memory: rows * cols <=
+ *               1 308 672 (a side of 1143); a context with a larger map gets GG_ERR_GEOMETRY from this call.
+ *   state       GG_CELL_OCCUPIED where occupied; else GG_CELL_FREE where hit or crossed; else GG_CELL_UNKNOWN.  A ray is not stopped by
+ *               an occupied cell on its way: the return behind it was measured.
+ *   d_counts[i] the number of cells of map i in each state, in the order free, unknown, occupied; they sum to rows * cols.
+ *   values      FREE < 0 <= UNKNOWN < OCCUPIED: a state plane is a seed plane of gg_clearance_clouds as it stands (cells >= 0, "occupied or
+ *               never observed", are its seeds), which gives the conservative clearance.
+ *   addressing  cloud i's plane of rows * cols int32 at d_state + i * plane_stride, cell (row, col) where `order` puts it.  EVERY cell of
+ *               every listed plane is written, an empty cloud's included (all GG_CELL_UNKNOWN, counts {0, rows * cols, 0}); the words
+ *               between rows * cols and plane_stride never are, and d_counts is not touched when NULL.  4-byte alignment.  d_state is the
+ *               working memory of the call and holds intermediate words while it runs.
+ *   determinism integer arithmetic and integer atomics (add, and) only: bit-identical from run to run and independent of scheduling.
+ * The call is stateless exactly as gg_rasterize_clouds is: it reads the caller's buffers, the maps' `ground` layer and their positions, and
+ * no record a batch left behind.  A FRESH map is neither read nor filled, and it and every other fresh map stay fresh.  None of the nine
+ * per-call layers is read (the three lazily kept ones stay pending), and no layer, position, configuration, score or liveness flag changes.
+ * `stream` and ordering are those of gg_rasterize_clouds: the call enqueues and returns, the host arrays (origins included) may be freed on
+ * return, it waits for every earlier map mutation, batch, export and import of the context (both halves under GG_FLAG_CONCURRENT_HALVES),
+ * and later writers of these maps on other streams wait for it; it takes an entry of the same ring of parameter entries.  The caller's
+ * buffers must stay valid and unmodified until `stream` has passed the call.
+ * Argument errors write nothing and change nothing: every error of gg_rasterize_clouds for the ten shared members, and GG_ERR_INVALID for
+ * null ctx (before the device is touched), null x, n < 0; and with n > 0: null origins or d_state, plane_stride < rows * cols, an unknown
+ * order, max_cells < 0, min_points < 1, a NaN min_height or max_height; GG_ERR_GEOMETRY for a map of more cells than stated above.
+ * n == 0 is GG_OK before anything else is looked at.  The first call of a context may allocate (GG_ERR_NOMEM) and block; later calls only
+ * enqueue.  Capture into a caller's graph is not supported. */
+enum { GG_CELL_FREE = -1, GG_CELL_UNKNOWN = 0, GG_CELL_OCCUPIED = 1 };
+typedef struct gg_cloud_visibility {
+    int n;                         /* clouds */
+    int first_slot;                /* cloud i meets map first_slot + i when slots == NULL */
+    const int32_t *slots;          /* host [n], nullable, distinct */
+    int point_format;              /* GG_POINT32 / GG_POINT16 */
+    const void *d_points;          /* [n][cloud_stride], as gg_batch.d_points */
+    size_t cloud_stride;           /* points */
+    const int32_t *n_points;       /* host [n] */
+    const double *transforms;      /* host [n][12], nullable, as gg_batch.transforms */
+    const uint8_t *d_labels;       /* [n][cloud_stride] GG_LABEL_*  -- exactly one of these two */
+    const uint8_t *d_label_masks;  /* [n][(cloud_stride + 3) / 4] 2-bit masks, as gg_batch.d_label_masks */
+    int min_points;                /* >= 1: participating points that make a cell occupied, as gg_cloud_clusters */
+    float min_height, max_height;  /* the height band (not NaN; -INFINITY / +INFINITY: open), as gg_cloud_clusters */
+    const float *origins;          /* host [n][3], required: the sensor in the MAP frame, as gg_batch.origins; only x, y are used */
+    int max_cells;                 /* 0: unbounded; R > 0: a ray clears at most its first R cells */
+    int order;                     /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR */
+    int32_t *d_state;              /* [n] planes of rows * cols int32, plane_stride apart; required: the call's working memory */
+    size_t plane_stride;           /* int32 words, >= rows * cols */
+    int32_t *d_counts;             /* [n][3]: free, unknown, occupied cells of map i; nullable */
+} gg_cloud_visibility;
+int gg_visibility_clouds(gg_context *ctx, const gg_cloud_visibility *x, void *stream);
+#define GG_HAS_VISIBILITY_CLOUDS 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
