@@ -53,6 +53,7 @@ SYMBOLS = [
     "gg_cluster_clouds",
     "gg_clearance_clouds",
     "gg_visibility_clouds",
+    "gg_fuse_states",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -262,6 +263,37 @@ class GGCloudVisibility(C.Structure):
     ]
 
 
+class GGStateFusion(C.Structure):
+    """gg_state_fusion: the evidence, fused state and frontier planes of many maps carried from scan to scan (gg_fuse_states)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("d_state", C.c_void_p),
+        ("state_stride", C.c_size_t),
+        ("d_evidence_in", C.c_void_p),
+        ("shifts", C.POINTER(C.c_int32)),
+        ("hit", C.c_int),
+        ("miss", C.c_int),
+        ("decay", C.c_int),
+        ("e_min", C.c_int),
+        ("e_max", C.c_int),
+        ("free_threshold", C.c_int),
+        ("occ_threshold", C.c_int),
+        ("order", C.c_int),
+        ("d_evidence_out", C.c_void_p),
+        ("plane_stride", C.c_size_t),
+        ("d_fused", C.c_void_p),
+        ("d_frontier", C.c_void_p),
+        ("d_counts", C.c_void_p),
+    ]
+
+
+GG_FUSE_LIMIT = (1 << 30) - 1  # the largest hit, miss, decay, -e_min and e_max of gg_fuse_states
+# the cells a work-group of k18_fuse.hip owns, along the contiguous direction of `order` and across it (gg_internal.h FUSE_TILE_X / _Y):
+# where the tests of the frontier put their tile seams
+GG_FUSE_TILE = (62, 26)
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -339,6 +371,7 @@ def load():
     L.gg_cluster_clouds.argtypes = [vp, P(GGCloudClusters), vp]
     L.gg_clearance_clouds.argtypes = [vp, P(GGCloudClearance), vp]
     L.gg_visibility_clouds.argtypes = [vp, P(GGCloudVisibility), vp]
+    L.gg_fuse_states.argtypes = [vp, P(GGStateFusion), vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

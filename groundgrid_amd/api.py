@@ -296,6 +296,16 @@ class VisibilityOutputs:
     counts: "object" = None  # torch.int32 [B, 3]: the free, unknown and occupied cells of every map
 
 
+@dataclass
+class FusionOutputs:
+    """what GroundSegmentation.fuse_states returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    evidence: "object" = None  # torch.int32 [B, rows, cols] ([B, cols, rows] with order="col"): the evidence to hand to the next call
+    state: "object" = None     # torch.int32, same shape: _lib.GG_CELL_FREE / _UNKNOWN / _OCCUPIED = -1 / 0 / 1 by the two thresholds
+    frontier: "object" = None  # torch.int32, same shape: 0 on a free cell with an unknown neighbour, -1 elsewhere
+    counts: "object" = None    # torch.int32 [B, 4]: the free, unknown, occupied and frontier cells of every map
+
+
 class GroundSegmentation:
     """Mirror of groundgrid::GroundSegmentation (include/groundgrid/GroundSegmentation.h:48-71)."""
 
@@ -811,6 +821,97 @@ class GroundSegmentation:
         x.d_counts = res.counts.data_ptr() if counts else None
         stream = self._stream_arg(on_torch_stream, points.device)
         _check(self._L, self._ctx, self._L.gg_visibility_clouds(self._ctx, C.byref(x), stream), "gg_visibility_clouds")
+        return res
+
+    def fuse_states(self, states, evidence=None, *, shifts=None, hit: int = 4, miss: int = 1, decay: int = 0, e_min: int = -16,
+                    e_max: int = 32, free_threshold: int = -2, occ_threshold: int = 4, order: str = "row", fused: bool = True,
+                    frontier: bool = True, counts: bool = True, out: Optional[FusionOutputs] = None,
+                    on_torch_stream: bool = False) -> FusionOutputs:
+        """The occupancy grid that persists across scans (gg_fuse_states).  states: a contiguous CUDA torch.int32 tensor [B, rows, cols]
+        ([B, cols, rows] with order="col"), B <= n_slots, this scan's observation -- VisibilityOutputs.state as it is: > 0 occupied, < 0
+        free, 0 not observed.  evidence: FusionOutputs.evidence of the previous call (same shape), or None for no prior.  shifts: what
+        move_maps returned for the move between the two scans, [B, 2] (anything np.asarray turns into int32 of that shape), or None for
+        no move; a cell the move exposed starts without evidence.  Per cell, in integers: the prior is clamped to [e_min, e_max] and moves
+        `decay` towards 0; an occupied observation adds `hit`, a free one subtracts `miss`; the clamped sum is the new evidence.  state is
+        OCCUPIED from occ_threshold up, FREE from free_threshold down, UNKNOWN between; frontier is 0 on a FREE cell with an UNKNOWN one
+        among its eight neighbours and -1 elsewhere; counts int32 [B, 4]: free, unknown, occupied, frontier cells.  The defaults are a
+        policy of this layer alone (the C call has none): one hit marks a cell, two misses free an unknown one, and a cell hit once is
+        unknown again after one miss.
+        state and frontier are seed planes of clearance_planes as they stand.  fused=False / frontier=False / counts=False leave those
+        out (None).  `out`: a FusionOutputs of an earlier call with the same arguments, whose tensors are reused; it may not hold
+        `evidence` or `states` -- no update in place is defined, alternate between two FusionOutputs.  Integer arithmetic only:
+        bit-identical from run to run.  Enqueued on the context's own stream or, with on_torch_stream=True, on the current torch stream;
+        nothing synchronises.  No map is read or changed."""
+        import torch
+
+        who = "fuse_states"
+        if order not in ("row", "col"):
+            raise ValueError(f"{who}: order is 'row' or 'col'")
+        par = {"hit": hit, "miss": miss, "decay": decay, "e_min": e_min, "e_max": e_max, "free_threshold": free_threshold, "occ_threshold": occ_threshold}
+        for name, v in par.items():
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{who}: {name} is an integer")
+        lim = _lib.GG_FUSE_LIMIT
+        if not (0 <= hit <= lim and 0 <= miss <= lim and 0 <= decay <= lim):
+            raise ValueError(f"{who}: hit, miss and decay lie in [0, 2^30 - 1]")
+        if not (-lim <= e_min <= 0 <= e_max <= lim):
+            raise ValueError(f"{who}: -(2^30 - 1) <= e_min <= 0 <= e_max <= 2^30 - 1")
+        if not (e_min <= free_threshold <= -1 and 1 <= occ_threshold <= e_max):
+            raise ValueError(f"{who}: e_min <= free_threshold <= -1 and 1 <= occ_threshold <= e_max")
+        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
+
+        def is_planes(t):
+            return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 3 and t.is_contiguous() and tuple(t.shape[1:]) == plane
+
+        if not is_planes(states):
+            raise ValueError(f"{who}: states must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
+        B = int(states.shape[0])
+        if evidence is not None and not (is_planes(evidence) and evidence.shape[0] == B and evidence.device == states.device):
+            raise ValueError(f"{who}: evidence must be a contiguous CUDA torch.int32 tensor of the shape and device of states")
+        host_shifts = None
+        if shifts is not None:
+            try:
+                given = np.asarray(shifts)
+                host_shifts = np.ascontiguousarray(given.astype(np.int32))
+                exact = given.shape == host_shifts.shape and np.array_equal(given, host_shifts)
+            except (TypeError, ValueError, OverflowError) as e:
+                raise ValueError(f"{who}: shifts must be [B, 2] int32: {e}") from None
+            if host_shifts.shape != (B, 2) or not exact:
+                raise ValueError(f"{who}: shifts of shape {host_shifts.shape} are not [B, 2] int32")
+        res = out if out is not None else FusionOutputs()
+        shape = (B,) + plane
+        want = {"evidence": shape, "state": shape if fused else None, "frontier": shape if frontier else None, "counts": (B, 4) if counts else None}
+        inputs = [t.data_ptr() for t in (states, evidence) if t is not None]
+        for field, sh in want.items():
+            t = getattr(res, field)
+            if sh is None:
+                if t is not None:
+                    raise ValueError(f"{who}: out.{field} is given but not asked for")
+                continue
+            if t is None:
+                continue
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == sh and t.is_contiguous() and t.device == states.device):
+                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
+            if t.data_ptr() in inputs:
+                raise ValueError(f"{who}: out.{field} is an input of the call: no update in place is defined")
+        for field, sh in want.items():
+            if sh is not None and getattr(res, field) is None:
+                setattr(res, field, torch.empty(sh, dtype=torch.int32, device=states.device))
+        self._torch_used = True
+        x = _lib.GGStateFusion()
+        x.n, x.d_state, x.state_stride = B, states.data_ptr(), self.rows * self.cols
+        x.d_evidence_in = evidence.data_ptr() if evidence is not None else None
+        if host_shifts is not None:
+            x.shifts = host_shifts.ctypes.data_as(C.POINTER(C.c_int32))
+        x.hit, x.miss, x.decay, x.e_min, x.e_max = int(hit), int(miss), int(decay), int(e_min), int(e_max)
+        x.free_threshold, x.occ_threshold = int(free_threshold), int(occ_threshold)
+        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.d_evidence_out, x.plane_stride = res.evidence.data_ptr(), self.rows * self.cols
+        x.d_fused = res.state.data_ptr() if fused else None
+        x.d_frontier = res.frontier.data_ptr() if frontier else None
+        x.d_counts = res.counts.data_ptr() if counts else None
+        stream = self._stream_arg(on_torch_stream, states.device)
+        _check(self._L, self._ctx, self._L.gg_fuse_states(self._ctx, C.byref(x), stream), "gg_fuse_states")
         return res
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:

@@ -222,6 +222,7 @@ struct gg_context : ContextBuffers {
     const uint16_t *d_export_cell = nullptr;
     ExportMap *d_export_maps = nullptr, *h_export_maps = nullptr;
     CloudParams *d_export_lazy = nullptr, *h_export_lazy = nullptr;
+    int2 *d_export_shifts = nullptr, *h_export_shifts = nullptr; // gg_fuse_states: the per-map index shifts of a call, [PARAM_RING][n_slots]
     ParamRing export_ring;
     int slopes_variant = 0; // tuning "slopes_variant": 0 = k_slopes_tiled, 1 = k_slopes_gather (the A/B of tools/bench_slopes.py)
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
@@ -1966,7 +1967,10 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     // (gg_export_images: the partial bounds of either variant's bounds launch, per ring entry)
     const int parts_cap = std::max(image_parts(a.g, 0), image_parts(a.g, 1));
     const size_t o_partials = align_up(o_lazy + ring * sizeof(CloudParams), 256);
-    if (const int rc = alloc_call_scratch(ctx, who, st, o_partials + ring * GG_NUM_LAYERS * (size_t)parts_cap * 2 * sizeof(float), h_lazy + ring * sizeof(CloudParams),
+    // (gg_fuse_states: the index shifts of its maps, per ring entry)
+    const size_t o_shifts = align_up(o_partials + ring * GG_NUM_LAYERS * (size_t)parts_cap * 2 * sizeof(float), 256);
+    const size_t h_shifts = align_up(h_lazy + ring * sizeof(CloudParams), 256);
+    if (const int rc = alloc_call_scratch(ctx, who, st, o_shifts + ring * sizeof(int2), h_shifts + ring * sizeof(int2),
                                           {{o_off, off.data(), off.size() * sizeof(uint32_t)}, {o_elem, elem.data(), elem.size() * sizeof(uint32_t)}, {o_cell, cell.data(), cell.size() * sizeof(uint16_t)}},
                                           &ctx->export_mem, &ctx->export_ring))
         return rc;
@@ -1980,6 +1984,8 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     ctx->image_parts_cap = parts_cap;
     ctx->h_export_maps = (ExportMap *)h;
     ctx->h_export_lazy = (CloudParams *)(h + h_lazy);
+    ctx->d_export_shifts = (int2 *)(block + o_shifts);
+    ctx->h_export_shifts = (int2 *)(h + h_shifts);
     return GG_OK;
 }
 
@@ -2416,6 +2422,86 @@ int gg_visibility_clouds(gg_context *ctx, const gg_cloud_visibility *x, void *st
     va.counts = x->d_counts;
     va.bitmap_words = (int)((C + 31) / 32);
     launch_visibility(ctx->arena, va, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
+// The evidence planes of many maps carried from one scan to the next (k18_fuse.hip): a ring entry and the ordering of the export for maps
+// 0 .. n-1, none of which is read, as the seed mode of gg_clearance_clouds; the per-map shifts travel in the ring entry.  Nothing is
+// synchronised, no map is filled and no host-side flag changes.
+int gg_fuse_states(gg_context *ctx, const gg_state_fusion *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_fuse_states";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_state_fusion");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    const int rows = ctx->arena.g.rows, cols = ctx->arena.g.cols;
+    constexpr int LIMIT = (1 << 30) - 1; // of every increment and bound: P -+ decay and D +- hit / miss stay inside an int32
+    if (!x->d_state || !x->d_evidence_out) return fail(ctx, GG_ERR_INVALID, who, "d_state and d_evidence_out are required");
+    if (x->state_stride < C) return fail(ctx, GG_ERR_INVALID, who, "state_stride is smaller than rows * cols");
+    if (x->plane_stride < C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->hit < 0 || x->hit > LIMIT || x->miss < 0 || x->miss > LIMIT || x->decay < 0 || x->decay > LIMIT)
+        return fail(ctx, GG_ERR_INVALID, who, "hit, miss and decay lie in [0, 2^30 - 1]");
+    if (x->e_min > 0 || x->e_min < -LIMIT || x->e_max < 0 || x->e_max > LIMIT) return fail(ctx, GG_ERR_INVALID, who, "-(2^30 - 1) <= e_min <= 0 <= e_max <= 2^30 - 1");
+    if (x->free_threshold > -1 || x->free_threshold < x->e_min) return fail(ctx, GG_ERR_INVALID, who, "e_min <= free_threshold <= -1");
+    if (x->occ_threshold < 1 || x->occ_threshold > x->e_max) return fail(ctx, GG_ERR_INVALID, who, "1 <= occ_threshold <= e_max");
+    if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
+    // no output may share a byte with an input or another output: the scroll reads d_evidence_in at shifted cells and the frontier reads
+    // neighbours, so no update in place is defined.  The ranges run from a buffer's first word to the last cell of its last plane
+    struct Range {
+        const char *name, *lo, *hi;
+        bool out;
+    };
+    const auto planes = [&](const char *name, const void *p, size_t stride, bool out) {
+        return Range{name, (const char *)p, (const char *)p + ((size_t)(x->n - 1) * stride + C) * sizeof(int32_t), out};
+    };
+    const Range ranges[6] = {planes("d_state", x->d_state, x->state_stride, false),
+                             planes("d_evidence_in", x->d_evidence_in, x->plane_stride, false),
+                             planes("d_evidence_out", x->d_evidence_out, x->plane_stride, true),
+                             planes("d_fused", x->d_fused, x->plane_stride, true),
+                             planes("d_frontier", x->d_frontier, x->plane_stride, true),
+                             Range{"d_counts", (const char *)x->d_counts, (const char *)x->d_counts + (size_t)x->n * 4 * sizeof(int32_t), true}};
+    for (int i = 0; i < 6; ++i)
+        for (int j = i + 1; j < 6; ++j) {
+            const Range &p = ranges[i], &q = ranges[j];
+            if (!p.lo || !q.lo || !(p.out || q.out)) continue;
+            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
+                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
+        }
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    const bool row_major = x->order == GG_PLANES_ROWMAJOR;
+    FuseArgs fa{};
+    if (x->shifts) { // (rows, cols) -> (along a line, across lines), clamped: from |s| = side on no prior lies inside the map
+        int2 *hs = ctx->h_export_shifts + (size_t)f.g * ctx->n_slots, *ds = ctx->d_export_shifts + (size_t)f.g * ctx->n_slots;
+        for (int i = 0; i < x->n; ++i) {
+            const int s0 = std::min(std::max(x->shifts[2 * (size_t)i], -rows), rows), s1 = std::min(std::max(x->shifts[2 * (size_t)i + 1], -cols), cols);
+            hs[i] = row_major ? make_int2(s1, s0) : make_int2(s0, s1);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(int2) * x->n, hipMemcpyHostToDevice, f.st));
+        fa.shifts = ds;
+    }
+    fa.state = x->d_state;
+    fa.state_stride = x->state_stride;
+    fa.evidence_in = x->d_evidence_in;
+    fa.hit = x->hit;
+    fa.miss = x->miss;
+    fa.decay = x->decay;
+    fa.e_min = x->e_min;
+    fa.e_max = x->e_max;
+    fa.free_threshold = x->free_threshold;
+    fa.occ_threshold = x->occ_threshold;
+    fa.nx = row_major ? cols : rows;
+    fa.ny = row_major ? rows : cols;
+    fa.tiles_x = (fa.nx + FUSE_TILE_X - 1) / FUSE_TILE_X;
+    fa.evidence_out = x->d_evidence_out;
+    fa.fused = x->d_fused;
+    fa.frontier = x->d_frontier;
+    fa.plane_stride = x->plane_stride;
+    fa.counts = x->d_counts;
+    launch_fuse(fa, x->n, f.st);
     return map_call_end(ctx, f);
 }
 

@@ -424,6 +424,24 @@ struct VisibilityArgs {
     int bitmap_words;              // ceil(rows * cols / 32): 32-bit words of dynamic LDS of the trace launch
 };
 
+// gg_fuse_states (k18_fuse.hip): what its one launch takes.  Map i of the call is row i of every buffer.  A plane is `ny` lines of `nx`
+// contiguous words: (nx, ny) = (cols, rows) row-major, (rows, cols) column-major, and a map's shift arrives as (along x, along y), clamped to
+// [-nx, nx] x [-ny, ny].  A work-group owns FUSE_TILE_X x FUSE_TILE_Y cells (_lib.py mirrors the two for the tests of the tile seams)
+constexpr int FUSE_TILE_X = 62; // cells along a line: a wavefront minus the one-cell halo on either side
+constexpr int FUSE_TILE_Y = 26; // lines
+struct FuseArgs {
+    const int32_t *state;          // map i's observation plane at state + i * state_stride
+    size_t state_stride;
+    const int32_t *evidence_in;    // nullable: every prior is 0
+    const int2 *shifts;            // device [map] (the call's ring entry); null: all (0, 0)
+    int hit, miss, decay, e_min, e_max, free_threshold, occ_threshold;
+    int nx, ny, tiles_x;           // tiles_x = ceil(nx / FUSE_TILE_X)
+    int32_t *evidence_out;         // map i's planes at + i * plane_stride
+    int32_t *fused, *frontier;     // nullable
+    size_t plane_stride;
+    int32_t *counts;               // [map][4] free, unknown, occupied, frontier; nullable
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -471,6 +489,7 @@ void launch_cluster(const Arena &a, const ClusterArgs &x, int n_clouds, hipStrea
 void launch_cluster_occupancy(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s); // k15_cluster.hip: its first three launches alone: x.planes[L] := occupied ? L : 0xFFFFFFFF
 void launch_clearance(const Arena &a, const ClearanceArgs &x, int n_maps, hipStream_t s);        // k16_clearance.hip: (occupancy,) columns, rows
 void launch_visibility(const Arena &a, const VisibilityArgs &x, int n_clouds, hipStream_t s);    // k17_visibility.hip: occupancy, hits, trace, states
+void launch_fuse(const FuseArgs &x, int n_maps, hipStream_t s);                                  // k18_fuse.hip: (counts := 0,) k_fuse_states
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

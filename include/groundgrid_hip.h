@@ -933,6 +933,72 @@ typedef struct gg_cloud_visibility {
 int gg_visibility_clouds(gg_context *ctx, const gg_cloud_visibility *x, void *stream);
 #define GG_HAS_VISIBILITY_CLOUDS 1
 
+/* The occupancy grid that PERSISTS ACROSS SCANS, in DEVICE memory: gg_visibility_clouds describes one scan -- most far cells of a rotating
+ * LiDAR are GG_CELL_UNKNOWN in any single one, and an obstacle that drops out of one scan is gone from that scan's plane -- while a costmap
+ * accumulates.  gg_fuse_states carries one int32 of EVIDENCE per cell of many maps from scan to scan: it scrolls the previous evidence by
+ * the index shift gg_move_maps returned, lets it decay towards 0, adds this scan's observation, clamps, and writes the new evidence, the
+ * three-valued state it gives, the exploration frontier and the counts, in one launch.  What a caller otherwise composes per frame from a
+ * shifted copy into a zeroed buffer, a where, a clamp, two thresholds and an eight-neighbour pooling pass -- with the sign of the shift to
+ * get right.  Map i of the call is row i of every buffer and of `shifts`; with (s0, s1) = (shifts[2 i], shifts[2 i + 1]) (both 0 when
+ * `shifts` is NULL), for cell (r, c), all in 32-bit integers:
+ *   prior        (r', c') = (r + s0, c + s1), nothing wraps.  P = 0 when r' lies outside [0, rows) or c' outside [0, cols) -- so for every
+ *                cell when |s0| >= rows or |s1| >= cols -- or when d_evidence_in is NULL; otherwise P = clamp(in[r', c'], e_min, e_max), `in`
+ *                being map i's plane of d_evidence_in.  This is the rule of gg_move_maps for the map's own layers, new(r, c) = exposed ?
+ *                fill : old(r + s0, c + s1): a cell that gg_move_maps fills as newly exposed starts here without evidence.  THE SHIFT IS THE
+ *                ONE gg_move_maps RETURNED FOR THE MOVE BETWEEN THE TWO OBSERVATIONS: between the scan d_evidence_in was fused from and
+ *                the scan of d_state; of several moves in between, the sum of their shifts.
+ *   decay        D = P > 0 ? max(P - decay, 0) : min(P + decay, 0).
+ *   observation  with s = map i's d_state[r, c]:  E = clamp(D + (s > 0 ? hit : s < 0 ? -miss : 0), e_min, e_max).  A d_state plane of
+ *                gg_visibility_clouds fits as it stands (GG_CELL_OCCUPIED > 0, GG_CELL_FREE < 0, GG_CELL_UNKNOWN = 0 "not observed"); any
+ *                other positive or negative word counts by its sign alone.  d_evidence_out[r, c] = E.
+ *   fused state  F = GG_CELL_OCCUPIED if E >= occ_threshold, else GG_CELL_FREE if E <= free_threshold, else GG_CELL_UNKNOWN.
+ *                d_fused[r, c] = F.
+ *   frontier     d_frontier[r, c] = 0 where F == GG_CELL_FREE and at least one of the up to eight neighbours (r + a, c + b), a, b in
+ *                {-1, 0, 1}, inside the map has F == GG_CELL_UNKNOWN; -1 everywhere else.  Cells beyond the border are no neighbours.
+ *   d_counts[i]  the number of cells of map i with F free, unknown, occupied (they sum to rows * cols), then the number of zeros of its
+ *                frontier plane.  The frontier is counted whether or not d_frontier is given.
+ *   limits       0 <= hit, miss, decay <= 2^30 - 1;  -(2^30 - 1) <= e_min <= 0 <= e_max <= 2^30 - 1;  e_min <= free_threshold <= -1;
+ *                1 <= occ_threshold <= e_max: every sum above then stays inside an int32.  The C ABI has no defaults.
+ *   values       a fused plane is a seed plane of gg_clearance_clouds as it stands (cells >= 0: occupied or never observed: the
+ *                conservative clearance), and so is a frontier plane (the distance to the nearest frontier cell, and which cell it is).
+ *   addressing   map i's plane of rows * cols int32 at d_state + i * state_stride, and at d_evidence_in / d_evidence_out / d_fused /
+ *                d_frontier + i * plane_stride; cell (row, col) where `order` puts it, the same order for every plane of the call.  EVERY
+ *                cell of every given output plane of every map is written; the words between rows * cols and a stride never are, and a
+ *                NULL output is not touched.  4-byte alignment.
+ *   no overlap   no output may share a byte with an input or with another output: the prior is read at shifted cells and the frontier from
+ *                neighbours, so NO UPDATE IN PLACE IS DEFINED -- the caller alternates between two evidence buffers.  The call compares
+ *                the address ranges, each from a buffer's first word to the last cell of its last plane (planes of two buffers interleaved
+ *                in each other's slack count as overlapping), and answers GG_ERR_INVALID.  d_state and d_evidence_in may overlap each other.
+ *   determinism  integer arithmetic and integer atomic adds only: bit-identical from run to run and independent of scheduling.
+ * The contract is that of gg_clearance_clouds in seed mode: NO MAP IS READ OR CHANGED -- no layer, position, freshness, configuration, score
+ * or liveness flag, and the lazily kept layers stay pending; the evidence lives in the caller's buffers, not in the context.  n <= n_slots
+ * (GG_ERR_CAPACITY): the call takes an entry of the same ring of parameter entries (the shifts travel in it) and orders itself on `stream`
+ * exactly as that call does; it enqueues and returns, and `shifts` may be freed on return.  The caller's device buffers must stay valid and
+ * unmodified until `stream` has passed the call.
+ * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
+ * n > 0: null d_state or d_evidence_out, state_stride or plane_stride < rows * cols, an unknown order, a parameter outside the limits above,
+ * overlapping buffers; GG_ERR_CAPACITY for n > n_slots.  n == 0 is GG_OK before anything else is looked at.  The first many-map call of a
+ * context may allocate (GG_ERR_NOMEM) and block; later calls only enqueue.  Capture into a caller's graph is not supported. */
+typedef struct gg_state_fusion {
+    int n;                          /* maps */
+    const int32_t *d_state;         /* [n] observation planes, state_stride apart: > 0 occupied, < 0 free, 0 not observed
+                                       (a d_state plane of gg_visibility_clouds as it stands); required */
+    size_t state_stride;            /* int32 words, >= rows * cols */
+    const int32_t *d_evidence_in;   /* [n] evidence planes of the previous call, plane_stride apart; NULL: every prior is 0 */
+    const int32_t *shifts;          /* host [n][2] index shifts (rows, cols) as gg_move_maps returns them; NULL: all (0, 0) */
+    int hit, miss, decay;           /* >= 0 */
+    int e_min, e_max;               /* e_min <= 0 <= e_max */
+    int free_threshold, occ_threshold; /* free_threshold <= -1, occ_threshold >= 1 */
+    int order;                      /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR, of every plane of the call */
+    int32_t *d_evidence_out;        /* [n] planes, plane_stride apart; required */
+    size_t plane_stride;            /* int32 words, >= rows * cols: evidence in/out, fused, frontier */
+    int32_t *d_fused;               /* [n] planes GG_CELL_*; nullable */
+    int32_t *d_frontier;            /* [n] planes: 0 on a frontier cell, -1 elsewhere; nullable */
+    int32_t *d_counts;              /* [n][4]: free, unknown, occupied, frontier cells; nullable */
+} gg_state_fusion;
+int gg_fuse_states(gg_context *ctx, const gg_state_fusion *x, void *stream);
+#define GG_HAS_FUSE_STATES 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
