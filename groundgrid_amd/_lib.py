@@ -54,6 +54,7 @@ SYMBOLS = [
     "gg_clearance_clouds",
     "gg_visibility_clouds",
     "gg_fuse_states",
+    "gg_route_planes",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -294,6 +295,41 @@ GG_FUSE_LIMIT = (1 << 30) - 1  # the largest hit, miss, decay, -e_min and e_max 
 GG_FUSE_TILE = (62, 26)
 
 
+class GGPlaneRoutes(C.Structure):
+    """gg_plane_routes: the cost-to-go, next-cell and path outputs of many maps over caller-given goal, blocked and cost planes (gg_route_planes)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("d_blocked", C.c_void_p),
+        ("blocked_stride", C.c_size_t),
+        ("d_cost", C.c_void_p),
+        ("cost_stride", C.c_size_t),
+        ("d_goals", C.c_void_p),
+        ("goal_stride", C.c_size_t),
+        ("connectivity", C.c_int),
+        ("straight", C.c_int),
+        ("diagonal", C.c_int),
+        ("cost_max", C.c_int),
+        ("max_cost", C.c_int),
+        ("order", C.c_int),
+        ("d_dist", C.c_void_p),
+        ("plane_stride", C.c_size_t),
+        ("d_next", C.c_void_p),
+        ("d_counts", C.c_void_p),
+        ("starts", C.POINTER(C.c_int32)),
+        ("d_paths", C.c_void_p),
+        ("max_path", C.c_int),
+        ("d_path_len", C.c_void_p),
+    ]
+
+
+GG_ROUTE_NONE = 0x7FFFFFFF  # d_dist of a cell no admissible path leads from (gg_route_planes)
+GG_HAS_ROUTE_PLANES = 1
+GG_ROUTE_LIMIT = (1 << 31) - 2  # the largest max(straight, diagonal) * cost_max * rows * cols of gg_route_planes
+# the side of the tiles a work-group of k19_route.hip relaxes a map by (gg_internal.h ROUTE_TILE): where the tests put their tile seams
+GG_ROUTE_TILE = 64
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -372,6 +408,7 @@ def load():
     L.gg_clearance_clouds.argtypes = [vp, P(GGCloudClearance), vp]
     L.gg_visibility_clouds.argtypes = [vp, P(GGCloudVisibility), vp]
     L.gg_fuse_states.argtypes = [vp, P(GGStateFusion), vp]
+    L.gg_route_planes.argtypes = [vp, P(GGPlaneRoutes), vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

@@ -306,6 +306,35 @@ class FusionOutputs:
     counts: "object" = None    # torch.int32 [B, 4]: the free, unknown, occupied and frontier cells of every map
 
 
+@dataclass
+class RouteOutputs:
+    """what GroundSegmentation.route_planes returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    dist: "object" = None      # torch.int32 [B, rows, cols] ([B, cols, rows] with order="col"): the cost to the nearest goal, _lib.GG_ROUTE_NONE where none is reached
+    next: "object" = None      # torch.int32, same shape: the linear index (in `order`) of the next cell of the cheapest path; own index on a goal, -1 unreached
+    counts: "object" = None    # torch.int32 [B, 3]: the goals, the reached cells (goals included) and the unblocked cells of every map
+    paths: "object" = None     # torch.int32 [B, max_path]: the cells of the path from starts[i]; the words from path_len[i] on are never written
+    path_len: "object" = None  # torch.int32 [B]: the cells of the whole path, also beyond max_path; 0: no start, or an unreached one
+
+
+def goal_planes(cells, rows: int, cols: int, order: str = "row", device=None):
+    """A goal plane per map for GroundSegmentation.route_planes from a list of goal cells, for "route from the robot cell": cells[i] is the
+    list of (row, col) goals of map i (an empty list: no goal).  Returns torch.int32 [B, rows, cols] ([B, cols, rows] with order="col"): 0 on
+    a goal, -1 elsewhere -- the words of a d_frontier plane."""
+    import torch
+
+    if order not in ("row", "col"):
+        raise ValueError("goal_planes: order is 'row' or 'col'")
+    plane = (rows, cols) if order == "row" else (cols, rows)
+    host = torch.full((len(cells),) + plane, -1, dtype=torch.int32)
+    for i, goals in enumerate(cells):
+        for r, c in goals:
+            if not (0 <= int(r) < rows and 0 <= int(c) < cols):
+                raise ValueError(f"goal_planes: map {i}: cell {(r, c)} lies outside the map")
+            host[(i, int(r), int(c)) if order == "row" else (i, int(c), int(r))] = 0
+    return host.to(device) if device is not None else host
+
+
 class GroundSegmentation:
     """Mirror of groundgrid::GroundSegmentation (include/groundgrid/GroundSegmentation.h:48-71)."""
 
@@ -912,6 +941,113 @@ class GroundSegmentation:
         x.d_counts = res.counts.data_ptr() if counts else None
         stream = self._stream_arg(on_torch_stream, states.device)
         _check(self._L, self._ctx, self._L.gg_fuse_states(self._ctx, C.byref(x), stream), "gg_fuse_states")
+        return res
+
+    def route_planes(self, goals, blocked=None, cost=None, *, connectivity: int = 8, straight: int = 5, diagonal: int = 7, cost_max: int = 252,
+                     max_cost: int = 0, order: str = "row", next: bool = True, counts: bool = True, starts=None, max_path: int = 0,
+                     out: Optional[RouteOutputs] = None, on_torch_stream: bool = False) -> RouteOutputs:
+        """The navigation function of many maps (gg_route_planes): per cell the exact cost of the cheapest admissible path to the nearest goal
+        cell, and the next cell on it.  goals: a contiguous CUDA torch.int32 tensor [B, rows, cols] ([B, cols, rows] with order="col"),
+        B <= n_slots: a goal where the word is >= 0 and the cell is not blocked -- FusionOutputs.frontier as it is, or goal_planes() of a list
+        of cells.  blocked: same shape or None: blocked where the word is >= 0 -- FusionOutputs.state as it is (occupied or never observed).
+        cost: same shape or None: a step INTO a cell costs straight (diagonal) * min(max(word, 1), cost_max); None: 1 everywhere.  A diagonal
+        step also needs both side cells unblocked.  dist is _lib.GG_ROUTE_NONE where no path leads to a goal, or where it costs more than
+        max_cost > 0.  next: own index on a goal, -1 on an unreached cell, else the first neighbour, in the order N, W, E, S, NW, NE, SW, SE of
+        (row, col), that attains the minimum.  counts int32 [B, 3]: goals, reached, unblocked cells.
+        starts: [B] linear cell indices in `order` (anything np.asarray turns into int32), -1 for no start: with max_path >= 1, paths
+        [B, max_path] holds start, next(start), ... up to the goal and path_len [B] the length of the whole path (0: unreached); the words of
+        paths from path_len on keep what they held (they are -1 in a tensor this call allocates).
+        The limit max(straight, diagonal) * cost_max * rows * cols <= 2^31 - 2 keeps every sum inside an int32.  The defaults (5, 7, 252) are
+        a policy of this layer alone (the C call has none).  next=False / counts=False leave those out (None).  `out`: a RouteOutputs of an
+        earlier call with the same arguments, whose tensors are reused; it may not hold an input.  Integer arithmetic only: bit-identical
+        from run to run.  Enqueued on the context's own stream or, with on_torch_stream=True, on the current torch stream; nothing
+        synchronises.  No map is read or changed."""
+        import torch
+
+        who = "route_planes"
+        if order not in ("row", "col"):
+            raise ValueError(f"{who}: order is 'row' or 'col'")
+        par = {"connectivity": connectivity, "straight": straight, "diagonal": diagonal, "cost_max": cost_max, "max_cost": max_cost, "max_path": max_path}
+        for name, v in par.items():
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{who}: {name} is an integer")
+        if connectivity not in (4, 8):
+            raise ValueError(f"{who}: connectivity is 4 or 8")
+        if not (1 <= straight <= 65535 and (connectivity == 4 or 1 <= diagonal <= 65535)):
+            raise ValueError(f"{who}: straight and diagonal lie in [1, 65535]")
+        if cost_max < 1:
+            raise ValueError(f"{who}: cost_max >= 1")
+        if not 0 <= max_cost <= _lib.GG_ROUTE_NONE:
+            raise ValueError(f"{who}: max_cost lies in [0, 2^31 - 1]")
+        if max_path < 0 or (starts is None and max_path != 0):
+            raise ValueError(f"{who}: max_path is >= 1 with starts and 0 without")
+        if max(straight, diagonal if connectivity == 8 else 0) * cost_max * self.rows * self.cols > _lib.GG_ROUTE_LIMIT:
+            raise ValueError(f"{who}: max(straight, diagonal) * cost_max * rows * cols exceeds 2^31 - 2")
+        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
+
+        def is_planes(t):
+            return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 3 and t.is_contiguous() and tuple(t.shape[1:]) == plane
+
+        if not is_planes(goals):
+            raise ValueError(f"{who}: goals must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
+        B = int(goals.shape[0])
+        for name, t in (("blocked", blocked), ("cost", cost)):
+            if t is not None and not (is_planes(t) and t.shape[0] == B and t.device == goals.device):
+                raise ValueError(f"{who}: {name} must be a contiguous CUDA torch.int32 tensor of the shape and device of goals")
+        host_starts = None
+        if starts is not None:
+            try:
+                given = np.asarray(starts)
+                host_starts = np.ascontiguousarray(given.astype(np.int32))
+                exact = given.shape == host_starts.shape and np.array_equal(given, host_starts)
+            except (TypeError, ValueError, OverflowError) as e:
+                raise ValueError(f"{who}: starts must be [B] int32: {e}") from None
+            if host_starts.shape != (B,) or not exact:
+                raise ValueError(f"{who}: starts of shape {host_starts.shape} are not [B] int32")
+            if ((host_starts < -1) | (host_starts >= self.rows * self.cols)).any():
+                raise ValueError(f"{who}: a start lies outside [-1, rows * cols)")
+            if max_path < 1:
+                raise ValueError(f"{who}: starts needs max_path >= 1")
+        res = out if out is not None else RouteOutputs()
+        shape = (B,) + plane
+        with_paths = host_starts is not None
+        want = {"dist": shape, "next": shape if next else None, "counts": (B, 3) if counts else None,
+                "paths": (B, max_path) if with_paths else None, "path_len": (B,) if with_paths else None}
+        inputs = [t.data_ptr() for t in (goals, blocked, cost) if t is not None]
+        for field, sh in want.items():
+            t = getattr(res, field)
+            if sh is None:
+                if t is not None:
+                    raise ValueError(f"{who}: out.{field} is given but not asked for")
+                continue
+            if t is None:
+                continue
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == sh and t.is_contiguous() and t.device == goals.device):
+                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
+            if t.data_ptr() in inputs:
+                raise ValueError(f"{who}: out.{field} is an input of the call: no update in place is defined")
+        for field, sh in want.items():
+            if sh is not None and getattr(res, field) is None:
+                if field == "paths":  # (the call leaves the words behind a path alone)
+                    setattr(res, field, torch.full(sh, -1, dtype=torch.int32, device=goals.device))
+                else:
+                    setattr(res, field, torch.empty(sh, dtype=torch.int32, device=goals.device))
+        self._torch_used = True
+        x = _lib.GGPlaneRoutes()
+        cells = self.rows * self.cols
+        x.n, x.d_goals, x.goal_stride = B, goals.data_ptr(), cells
+        x.d_blocked, x.blocked_stride = (blocked.data_ptr(), cells) if blocked is not None else (None, 0)
+        x.d_cost, x.cost_stride = (cost.data_ptr(), cells) if cost is not None else (None, 0)
+        x.connectivity, x.straight, x.diagonal, x.cost_max, x.max_cost = int(connectivity), int(straight), int(diagonal), int(cost_max), int(max_cost)
+        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.d_dist, x.plane_stride = res.dist.data_ptr(), cells
+        x.d_next = res.next.data_ptr() if next else None
+        x.d_counts = res.counts.data_ptr() if counts else None
+        if with_paths:
+            x.starts = host_starts.ctypes.data_as(C.POINTER(C.c_int32))
+            x.d_paths, x.max_path, x.d_path_len = res.paths.data_ptr(), int(max_path), res.path_len.data_ptr()
+        stream = self._stream_arg(on_torch_stream, goals.device)
+        _check(self._L, self._ctx, self._L.gg_route_planes(self._ctx, C.byref(x), stream), "gg_route_planes")
         return res
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:

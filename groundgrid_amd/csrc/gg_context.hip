@@ -223,6 +223,7 @@ struct gg_context : ContextBuffers {
     ExportMap *d_export_maps = nullptr, *h_export_maps = nullptr;
     CloudParams *d_export_lazy = nullptr, *h_export_lazy = nullptr;
     int2 *d_export_shifts = nullptr, *h_export_shifts = nullptr; // gg_fuse_states: the per-map index shifts of a call, [PARAM_RING][n_slots]
+    int32_t *d_export_starts = nullptr, *h_export_starts = nullptr; // gg_route_planes: the per-map start cells of a call, [PARAM_RING][n_slots]
     ParamRing export_ring;
     int slopes_variant = 0; // tuning "slopes_variant": 0 = k_slopes_tiled, 1 = k_slopes_gather (the A/B of tools/bench_slopes.py)
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
@@ -1970,7 +1971,10 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     // (gg_fuse_states: the index shifts of its maps, per ring entry)
     const size_t o_shifts = align_up(o_partials + ring * GG_NUM_LAYERS * (size_t)parts_cap * 2 * sizeof(float), 256);
     const size_t h_shifts = align_up(h_lazy + ring * sizeof(CloudParams), 256);
-    if (const int rc = alloc_call_scratch(ctx, who, st, o_shifts + ring * sizeof(int2), h_shifts + ring * sizeof(int2),
+    // (gg_route_planes: the start cells of its maps, per ring entry)
+    const size_t o_starts = align_up(o_shifts + ring * sizeof(int2), 256);
+    const size_t h_starts = align_up(h_shifts + ring * sizeof(int2), 256);
+    if (const int rc = alloc_call_scratch(ctx, who, st, o_starts + ring * sizeof(int32_t), h_starts + ring * sizeof(int32_t),
                                           {{o_off, off.data(), off.size() * sizeof(uint32_t)}, {o_elem, elem.data(), elem.size() * sizeof(uint32_t)}, {o_cell, cell.data(), cell.size() * sizeof(uint16_t)}},
                                           &ctx->export_mem, &ctx->export_ring))
         return rc;
@@ -1986,6 +1990,8 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     ctx->h_export_lazy = (CloudParams *)(h + h_lazy);
     ctx->d_export_shifts = (int2 *)(block + o_shifts);
     ctx->h_export_shifts = (int2 *)(h + h_shifts);
+    ctx->d_export_starts = (int32_t *)(block + o_starts);
+    ctx->h_export_starts = (int32_t *)(h + h_starts);
     return GG_OK;
 }
 
@@ -2502,6 +2508,107 @@ int gg_fuse_states(gg_context *ctx, const gg_state_fusion *x, void *stream)
     fa.plane_stride = x->plane_stride;
     fa.counts = x->d_counts;
     launch_fuse(fa, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
+// The cost-to-go fields and paths of many maps (k19_route.hip): a ring entry and the ordering of the export for maps 0 .. n-1, none of which
+// is read, as gg_fuse_states; the per-map start cells travel in the ring entry.  Nothing is synchronised, no map is filled and no host-side
+// flag changes.
+int gg_route_planes(gg_context *ctx, const gg_plane_routes *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_route_planes";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_plane_routes");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    const int rows = ctx->arena.g.rows, cols = ctx->arena.g.cols;
+    if (!x->d_goals || !x->d_dist) return fail(ctx, GG_ERR_INVALID, who, "d_goals and d_dist are required");
+    if (x->d_blocked && x->blocked_stride < C) return fail(ctx, GG_ERR_INVALID, who, "blocked_stride is smaller than rows * cols");
+    if (x->d_cost && x->cost_stride < C) return fail(ctx, GG_ERR_INVALID, who, "cost_stride is smaller than rows * cols");
+    if (x->goal_stride < C) return fail(ctx, GG_ERR_INVALID, who, "goal_stride is smaller than rows * cols");
+    if (x->plane_stride < C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->connectivity != 4 && x->connectivity != 8) return fail(ctx, GG_ERR_INVALID, who, "connectivity is 4 or 8");
+    const bool diagonals = x->connectivity == 8;
+    if (x->straight < 1 || x->straight > 65535 || (diagonals && (x->diagonal < 1 || x->diagonal > 65535)))
+        return fail(ctx, GG_ERR_INVALID, who, "straight and diagonal lie in [1, 65535]");
+    if (x->cost_max < 1) return fail(ctx, GG_ERR_INVALID, who, "cost_max < 1");
+    if (x->max_cost < 0) return fail(ctx, GG_ERR_INVALID, who, "max_cost < 0");
+    // every true D fits an int32 and the unsigned sum of a stored word and one step cannot wrap (k19_route.hip relies on it).  The product of
+    // the first two factors is < 2^47, so the test by division is exact and nothing here overflows
+    const uint64_t step_max = (uint64_t)std::max(x->straight, diagonals ? x->diagonal : 0) * (uint64_t)x->cost_max;
+    if (step_max > (uint64_t)GG_ROUTE_NONE - 1 || step_max > ((uint64_t)GG_ROUTE_NONE - 1) / (uint64_t)C)
+        return fail(ctx, GG_ERR_INVALID, who, "max(straight, diagonal) * cost_max * rows * cols exceeds 2^31 - 2");
+    if (x->starts) {
+        if (!x->d_paths || !x->d_path_len || x->max_path < 1) return fail(ctx, GG_ERR_INVALID, who, "starts needs d_paths, d_path_len and max_path >= 1");
+        if (x->n <= ctx->n_slots) // (beyond that the call is refused below, and starts[] is the caller's to size by n)
+            for (int i = 0; i < x->n; ++i)
+                if (x->starts[i] < -1 || (int64_t)x->starts[i] >= (int64_t)C) return fail(ctx, GG_ERR_INVALID, who, "a start lies outside [-1, rows * cols)");
+    }
+    if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
+    const bool row_major = x->order == GG_PLANES_ROWMAJOR;
+    RouteArgs ra{};
+    ra.nx = row_major ? cols : rows;
+    ra.ny = row_major ? rows : cols;
+    ra.tiles_x = (ra.nx + ROUTE_TILE - 1) / ROUTE_TILE;
+    ra.tiles_y = (ra.ny + ROUTE_TILE - 1) / ROUTE_TILE;
+    if ((int64_t)ra.tiles_x * ra.tiles_y > ROUTE_MAX_TILES) return fail(ctx, GG_ERR_GEOMETRY, who, "the map has more than 4096 tiles of 64 x 64 cells");
+    // no output may share a byte with an input or another output, by the ranges of gg_fuse_states: from a buffer's first word to the last
+    // cell of its last plane
+    struct Range {
+        const char *name, *lo, *hi;
+        bool out;
+    };
+    const auto planes = [&](const char *name, const void *p, size_t stride, bool out) {
+        return Range{name, (const char *)p, (const char *)p + ((size_t)(x->n - 1) * stride + C) * sizeof(int32_t), out};
+    };
+    const auto rows_of = [&](const char *name, const void *p, size_t words) {
+        return Range{name, (const char *)p, (const char *)p + (size_t)x->n * words * sizeof(int32_t), true};
+    };
+    const Range ranges[8] = {planes("d_blocked", x->d_blocked, x->blocked_stride, false),
+                             planes("d_cost", x->d_cost, x->cost_stride, false),
+                             planes("d_goals", x->d_goals, x->goal_stride, false),
+                             planes("d_dist", x->d_dist, x->plane_stride, true),
+                             planes("d_next", x->d_next, x->plane_stride, true),
+                             rows_of("d_counts", x->d_counts, 3),
+                             rows_of("d_paths", x->starts ? x->d_paths : nullptr, x->starts ? (size_t)x->max_path : 0),
+                             rows_of("d_path_len", x->starts ? x->d_path_len : nullptr, 1)};
+    for (int i = 0; i < 8; ++i)
+        for (int j = i + 1; j < 8; ++j) {
+            const Range &p = ranges[i], &q = ranges[j];
+            if (!p.lo || !q.lo || !(p.out || q.out)) continue;
+            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
+                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
+        }
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    if (x->starts) {
+        int32_t *hs = ctx->h_export_starts + (size_t)f.g * ctx->n_slots, *ds = ctx->d_export_starts + (size_t)f.g * ctx->n_slots;
+        std::copy(x->starts, x->starts + x->n, hs);
+        HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(int32_t) * x->n, hipMemcpyHostToDevice, f.st));
+        ra.starts = ds;
+        ra.paths = x->d_paths;
+        ra.max_path = x->max_path;
+        ra.path_len = x->d_path_len;
+    }
+    ra.blocked = x->d_blocked;
+    ra.blocked_stride = x->blocked_stride;
+    ra.cost = x->d_cost;
+    ra.cost_stride = x->cost_stride;
+    ra.goals = x->d_goals;
+    ra.goal_stride = x->goal_stride;
+    ra.row_major = row_major;
+    ra.diagonals = diagonals;
+    ra.straight = (uint32_t)x->straight;
+    ra.diagonal = diagonals ? (uint32_t)x->diagonal : 0u;
+    ra.cost_max = x->cost_max;
+    ra.reach = x->max_cost > 0 ? (uint32_t)x->max_cost : (uint32_t)GG_ROUTE_NONE - 1u;
+    ra.dist = x->d_dist;
+    ra.next = x->d_next;
+    ra.plane_stride = x->plane_stride;
+    ra.counts = x->d_counts;
+    launch_route(ra, x->n, f.st);
     return map_call_end(ctx, f);
 }
 

@@ -442,6 +442,33 @@ struct FuseArgs {
     int32_t *counts;               // [map][4] free, unknown, occupied, frontier; nullable
 };
 
+// gg_route_planes (k19_route.hip): what its launches share.  Map i of the call is row i of every buffer.  A plane is `ny` lines of `nx`
+// contiguous words: (nx, ny) = (cols, rows) row-major, (rows, cols) column-major.  One work-group relaxes a map tile by tile, ROUTE_TILE x
+// ROUTE_TILE cells at a time (_lib.py mirrors it for the tests of the tile seams), with one byte per tile in LDS
+constexpr int ROUTE_TILE = 64;
+constexpr int ROUTE_MAX_TILES = 4096; // tiles of a map (a side of 4096): more is GG_ERR_GEOMETRY
+struct RouteArgs {
+    const int32_t *blocked;        // map i's plane at blocked + i * blocked_stride: blocked where the word is >= 0; nullable
+    size_t blocked_stride;
+    const int32_t *cost;           // ... at cost + i * cost_stride: w = min(max(word, 1), cost_max); nullable: w = 1
+    size_t cost_stride;
+    const int32_t *goals;          // ... at goals + i * goal_stride: a goal where the word is >= 0 and the cell is not blocked
+    size_t goal_stride;
+    int nx, ny, tiles_x, tiles_y;  // tiles_x = ceil(nx / ROUTE_TILE), tiles_y = ceil(ny / ROUTE_TILE)
+    bool row_major;                // a line is a row: what the direction order of d_next, in (row, col) terms, needs to know
+    bool diagonals;                // connectivity 8
+    uint32_t straight, diagonal;   // step weights
+    int cost_max;
+    uint32_t reach;                // a tentative D above this is not stored: max_cost, or GG_ROUTE_NONE - 1
+    int32_t *dist, *next;          // map i's planes at + i * plane_stride; dist is the working memory, next is nullable
+    size_t plane_stride;
+    int32_t *counts;               // [map][3] goals, reached, unblocked; nullable
+    const int32_t *starts;         // device [map] (the call's ring entry): linear index of the start cell or -1; null: no paths
+    int32_t *paths;                // [map][max_path]
+    int max_path;
+    int32_t *path_len;             // [map]
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -490,6 +517,7 @@ void launch_cluster_occupancy(const Arena &a, const ClusterArgs &x, int n_clouds
 void launch_clearance(const Arena &a, const ClearanceArgs &x, int n_maps, hipStream_t s);        // k16_clearance.hip: (occupancy,) columns, rows
 void launch_visibility(const Arena &a, const VisibilityArgs &x, int n_clouds, hipStream_t s);    // k17_visibility.hip: occupancy, hits, trace, states
 void launch_fuse(const FuseArgs &x, int n_maps, hipStream_t s);                                  // k18_fuse.hip: (counts := 0,) k_fuse_states
+void launch_route(const RouteArgs &x, int n_maps, hipStream_t s);                                // k19_route.hip: relax, (counts := 0, next,) (paths)
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

@@ -999,6 +999,89 @@ typedef struct gg_state_fusion {
 int gg_fuse_states(gg_context *ctx, const gg_state_fusion *x, void *stream);
 #define GG_HAS_FUSE_STATES 1
 
+/* The NAVIGATION FUNCTION of many maps, in DEVICE memory: gg_fuse_states ends with a persistent three-valued grid and an exploration frontier
+ * per map, and gg_clearance_clouds with a frontier plane as seeds gives the distance to the nearest frontier THROUGH walls.  gg_route_planes
+ * gives the distance AROUND them: per cell the exact cost D of the cheapest admissible 4- or 8-connected path to the nearest goal cell over a
+ * caller-given cost plane, the next cell on that path, three counts per map and, from one start cell per map, the cell list of the path.  What
+ * a caller otherwise gets per map and per frame from a download of three planes, a graph, Dijkstra on the host and an upload.  The goal set (a
+ * d_frontier plane) and the blocked set (a d_fused plane) are read as they stand.  Map i of the call is row i of every buffer and of `starts`.
+ * Everything is 32-bit integer; nothing wraps at the border; all of the following is per map:
+ *   blocked      cell q is BLOCKED where map i's d_blocked word is >= 0 (no cell when d_blocked is NULL).
+ *   weight       w(q) = min(max(word of d_cost, 1), cost_max); 1 everywhere when d_cost is NULL.
+ *   goal         a cell whose d_goals word is >= 0 and that is not blocked.  A blocked goal is no goal.
+ *   step         from q = (r, c) to p = (r + a, c + b): the straight steps (a, b) in {(-1,0), (0,-1), (0,+1), (+1,0)} always, the four
+ *                diagonals with connectivity 8.  ADMISSIBLE when p lies inside the map and neither p nor q is blocked, and for a diagonal
+ *                when (r + a, c) and (r, c + b) are both inside and unblocked as well: no corner cutting.  It costs s * w(p): s = `straight`
+ *                or `diagonal`, w of the cell ENTERED.
+ *   D            0 on a goal; elsewhere the minimum, over all finite chains of admissible steps from q to a goal, of the sum of the step
+ *                costs; GG_ROUTE_NONE where there is no such chain (a blocked cell, a pocket, a map without goals).  Equivalently D is the
+ *                unique solution of D(q) = min over admissible p of D(p) + s * w(p) with D = 0 on the goals, which makes it independent of
+ *                how it is computed.  d_dist[q] = D(q).
+ *   limits       1 <= straight, diagonal <= 65535; 1 <= cost_max; max(straight, diagonal) * cost_max * rows * cols <= 2^31 - 2, `diagonal`
+ *                counted with connectivity 8 only.  Every true D then fits an int32, every word the call stores while it works is
+ *                <= 2^31 - 1 and one step costs <= 2^31 - 2, so the UNSIGNED sum of a stored word and a step cannot wrap: the kernel relies
+ *                on that.  The C ABI has no defaults.
+ *   max_cost     R > 0: a cell with D > R gets d_dist = GG_ROUTE_NONE and d_next = -1 and is not counted as reached; every other word is
+ *                that of R = 0 (a prefix of a cheapest path is cheaper, so the bounded field is consistent).  0: unbounded.
+ *   d_next       a goal's own linear index; -1 on an unreached cell; otherwise the linear index, in `order`, of the FIRST p in the direction
+ *                order (-1,0), (0,-1), (0,+1), (+1,0), (-1,-1), (-1,+1), (+1,-1), (+1,+1) whose step is admissible and attains D(q) =
+ *                D(p) + s * w(p).  Directions are in (row, col) terms: the tie rule does not depend on `order`.  Following d_next lowers D
+ *                by at least 1 per step: every chain ends on a goal and has no cycle.
+ *   d_counts[i]  the number of goals, of reached cells (goals included; under max_cost), and of unblocked cells.
+ *   paths        with `starts`, map i's path is starts[i], next(starts[i]), ... up to and including the goal.  d_path_len[i] is the number
+ *                of cells of the whole path, also when that exceeds max_path; d_paths[i][k] is written for k < min(len, max_path) and the
+ *                other words of the row never are.  d_path_len[i] = 0 and the row is untouched when starts[i] is -1 or an unreached cell
+ *                (blocked cells and cells beyond max_cost included).  A start on a goal gives len 1.  starts[i] is a linear index in
+ *                `order`.  d_next need not be given for the paths.
+ *   values       a d_fused or d_frontier plane of gg_fuse_states, a d_state plane of gg_visibility_clouds and a d_cell_cluster plane of
+ *                gg_cluster_clouds fit d_blocked and d_goals as they stand.
+ *   addressing   map i's plane of rows * cols int32 at d_blocked + i * blocked_stride, d_cost + i * cost_stride, d_goals + i * goal_stride
+ *                and d_dist / d_next + i * plane_stride; cell (row, col) where `order` puts it, the same order for every plane of the call.
+ *                EVERY cell of every given output plane of every map is written; the words between rows * cols and a stride never are,
+ *                and a NULL output is not touched.  d_dist is the call's working memory.  4-byte alignment.
+ *   no overlap   no output may share a byte with an input or with another output; the call compares the address ranges as gg_fuse_states
+ *                does and answers GG_ERR_INVALID.  The inputs may overlap each other.
+ *   determinism  integer arithmetic only; D is a unique fixed point and d_next and the paths are functions of D: bit-identical from run to
+ *                run and independent of scheduling.
+ * The contract is that of gg_clearance_clouds in seed mode and of gg_fuse_states: NO MAP IS READ OR CHANGED -- no layer, position, freshness,
+ * configuration, score or liveness flag, and the lazily kept layers stay pending.  n <= n_slots (GG_ERR_CAPACITY): the call takes an entry
+ * of the same ring of parameter entries (the starts travel in it) and orders itself on `stream` as those calls do; it enqueues and returns
+ * with no synchronisation, and `starts` may be freed on return.  The caller's device buffers must stay valid and unmodified until `stream`
+ * has passed the call.  One work-group computes one map's D, so many maps fill the device and a single map runs on one compute unit.
+ * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
+ * n > 0: null d_goals or d_dist, a stride < rows * cols for a given plane, an unknown order, connectivity not 4 or 8, a parameter outside
+ * the limits above, max_cost < 0, `starts` given without d_paths, d_path_len or max_path >= 1, a starts[i] < -1 or >= rows * cols,
+ * overlapping buffers; GG_ERR_CAPACITY for n > n_slots; GG_ERR_GEOMETRY for a map of more than 4096 tiles of 64 x 64 cells.  n == 0 is
+ * GG_OK before anything else is looked at.  The first many-map call of a context may allocate (GG_ERR_NOMEM) and block; later calls only
+ * enqueue.  Capture into a caller's graph is not supported. */
+#define GG_ROUTE_NONE 0x7FFFFFFF
+typedef struct gg_plane_routes {
+    int n;                        /* maps */
+    const int32_t *d_blocked;     /* [n] planes, blocked_stride apart: a cell is BLOCKED where the word is >= 0 (a d_fused plane of
+                                     gg_fuse_states, a d_state plane, a d_cell_cluster plane as they stand); NULL: nothing is blocked */
+    size_t blocked_stride;
+    const int32_t *d_cost;        /* [n] planes, cost_stride apart: w = min(max(word, 1), cost_max); NULL: w = 1 everywhere */
+    size_t cost_stride;
+    const int32_t *d_goals;       /* [n] planes, goal_stride apart: a GOAL where the word is >= 0 and the cell is not blocked
+                                     (a d_frontier plane of gg_fuse_states as it stands); required */
+    size_t goal_stride;
+    int connectivity;             /* 4 or 8 */
+    int straight, diagonal;       /* step weights, e.g. 5 and 7; diagonal is ignored with connectivity 4 */
+    int cost_max;                 /* >= 1 */
+    int max_cost;                 /* 0: unbounded; R > 0: a cell whose D > R is reported as unreached */
+    int order;                    /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR, of every plane of the call */
+    int32_t *d_dist;              /* [n] planes, plane_stride apart; required: the call's working memory */
+    size_t plane_stride;          /* d_dist and d_next */
+    int32_t *d_next;              /* [n] planes; nullable */
+    int32_t *d_counts;            /* [n][3]: goals, reached cells (goals included), unblocked cells; nullable */
+    const int32_t *starts;        /* host [n]: linear index in `order` of map i's start cell, or -1; nullable */
+    int32_t *d_paths;             /* [n][max_path]; required when starts is given */
+    int max_path;                 /* >= 1 when starts is given */
+    int32_t *d_path_len;          /* [n]; required when starts is given */
+} gg_plane_routes;
+int gg_route_planes(gg_context *ctx, const gg_plane_routes *x, void *stream);
+#define GG_HAS_ROUTE_PLANES 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
