@@ -55,6 +55,7 @@ SYMBOLS = [
     "gg_visibility_clouds",
     "gg_fuse_states",
     "gg_route_planes",
+    "gg_match_planes",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -330,6 +331,40 @@ GG_ROUTE_LIMIT = (1 << 31) - 2  # the largest max(straight, diagonal) * cost_max
 GG_ROUTE_TILE = 64
 
 
+class GGPlaneMatches(C.Structure):
+    """gg_plane_matches: the best alignment (yaw candidate, translation) of many scan planes to their field planes (gg_match_planes)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("d_scan", C.c_void_p),
+        ("scan_stride", C.c_size_t),
+        ("d_field", C.c_void_p),
+        ("field_stride", C.c_size_t),
+        ("field_max", C.c_int),
+        ("shifts", C.POINTER(C.c_int32)),
+        ("pivots", C.POINTER(C.c_int32)),
+        ("rotations", C.POINTER(C.c_int32)),
+        ("n_rotations", C.c_int),
+        ("window", C.c_int),
+        ("order", C.c_int),
+        ("d_best", C.c_void_p),
+        ("d_scores", C.c_void_p),
+        ("score_stride", C.c_size_t),
+    ]
+
+
+GG_HAS_MATCH_PLANES = 1
+GG_MATCH_MAX_WINDOW = 32      # the largest `window` of gg_match_planes
+GG_MATCH_MAX_ROTATIONS = 64   # ... and the most yaw candidates
+GG_MATCH_UNIT = 16384         # 1.0 of a rotation pair (Q14)
+GG_MATCH_LIMIT = (1 << 31) - 1  # the largest field_max * rows * cols
+GG_MATCH_MAX_SIDE = 32768     # more rows or cols is GG_ERR_GEOMETRY
+# the cells of the scan plane a work-group of k20_match.hip looks at between two barriers, and the entries of its list (MATCH_CHUNK,
+# MATCH_LIST): where the tests put their chunk seams and how many scan cells fill the list
+GG_MATCH_CHUNK = 1024
+GG_MATCH_LIST = 2048
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -409,6 +444,7 @@ def load():
     L.gg_visibility_clouds.argtypes = [vp, P(GGCloudVisibility), vp]
     L.gg_fuse_states.argtypes = [vp, P(GGStateFusion), vp]
     L.gg_route_planes.argtypes = [vp, P(GGPlaneRoutes), vp]
+    L.gg_match_planes.argtypes = [vp, P(GGPlaneMatches), vp]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

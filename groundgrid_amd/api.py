@@ -317,6 +317,25 @@ class RouteOutputs:
     path_len: "object" = None  # torch.int32 [B]: the cells of the whole path, also beyond max_path; 0: no start, or an unreached one
 
 
+@dataclass
+class MatchOutputs:
+    """what GroundSegmentation.match_planes returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    best: "object" = None    # torch.int32 [B, 6]: k*, dy*, dx*, S*, the scan cells of the map, the candidates whose score equals S*
+    scores: "object" = None  # torch.int32 [B, K, 2 W + 1, 2 W + 1]: S(k, dy, dx) at [k, dy + W, dx + W]
+
+
+def rotation_table(angles_rad):
+    """The yaw candidates of GroundSegmentation.match_planes from angles in radians: int32 [K, 2], row k = (cq, sq) = (16384 cos, 16384 sin)
+    of angles_rad[k], each rounded half away from zero, computed in float64.  A positive angle turns the row axis towards the column axis:
+    (dr, dc) = (1, 0) goes to (cos, sin).  List the prior yaw (0.0) first: among equal scores the earlier candidate wins."""
+    a = np.atleast_1d(np.asarray(angles_rad, dtype=np.float64))
+    if a.ndim != 1 or not np.isfinite(a).all():
+        raise ValueError("rotation_table: angles_rad is a list of finite angles")
+    v = np.stack([np.cos(a), np.sin(a)], axis=1) * float(_lib.GG_MATCH_UNIT)
+    return (np.sign(v) * np.floor(np.abs(v) + 0.5)).astype(np.int32)
+
+
 def goal_planes(cells, rows: int, cols: int, order: str = "row", device=None):
     """A goal plane per map for GroundSegmentation.route_planes from a list of goal cells, for "route from the robot cell": cells[i] is the
     list of (row, col) goals of map i (an empty list: no goal).  Returns torch.int32 [B, rows, cols] ([B, cols, rows] with order="col"): 0 on
@@ -1048,6 +1067,109 @@ class GroundSegmentation:
             x.d_paths, x.max_path, x.d_path_len = res.paths.data_ptr(), int(max_path), res.path_len.data_ptr()
         stream = self._stream_arg(on_torch_stream, goals.device)
         _check(self._L, self._ctx, self._L.gg_route_planes(self._ctx, C.byref(x), stream), "gg_route_planes")
+        return res
+
+    def match_planes(self, scan, field, *, shifts=None, pivots=None, rotations=None, window: int = 8, field_max: int = 32, order: str = "row",
+                     scores: bool = False, out: Optional[MatchOutputs] = None, on_torch_stream: bool = False) -> MatchOutputs:
+        """Correlative scan-to-map matching of many maps (gg_match_planes): which yaw candidate and which translation of a window lay this
+        scan's occupied cells best over the accumulated grid.  scan: a contiguous CUDA torch.int32 tensor [B, rows, cols] ([B, cols, rows]
+        with order="col"), B <= n_slots: a scan cell where the word is > 0 -- VisibilityOutputs.state or FusionOutputs.state as it is.
+        field: same shape: a cell's reward is min(max(word, 0), field_max), 0 outside the map -- FusionOutputs.evidence of the previous
+        call as it is.  shifts: the prior shift per map, [B, 2] with the meaning it has in fuse_states (scan cell (r, c) lies over field
+        cell (r + s0, c + s1)), or None for no move.  pivots: the centre of rotation per map, [B, 2] (row, col) inside the map, or None for
+        (rows // 2, cols // 2).  rotations: rotation_table(angles), int32 [K, 2] with 1 <= K <= 64 and |word| <= 16384, or None for the
+        identity alone.  window: W in [0, 32]: the translations (dy, dx) in [-W, W]^2.
+        best int32 [B, 6]: k*, dy*, dx*, the best score S*, the scan cells of the map, and how many candidates attain S*; among equal
+        scores the smallest dy^2 + dx^2 wins, then the smallest k, dy, dx.  With k* the identity, shifts[i] + (dy*, dx*) is the corrected
+        shift to hand to fuse_states; another k* is a yaw correction for the next cloud-to-map transform.  scores=True adds the volumes,
+        int32 [B, K, 2 W + 1, 2 W + 1].  The limit field_max * rows * cols <= 2^31 - 1 keeps every score inside an int32; the default
+        field_max is the default e_max of fuse_states, a policy of this layer alone (the C call has none).  `out`: a MatchOutputs of an
+        earlier call with the same arguments, whose tensors are reused; it may not hold an input.  Integer sums only: bit-identical from
+        run to run.  Enqueued on the context's own stream or, with on_torch_stream=True, on the current torch stream; nothing
+        synchronises.  No map is read or changed."""
+        import torch
+
+        who = "match_planes"
+        if order not in ("row", "col"):
+            raise ValueError(f"{who}: order is 'row' or 'col'")
+        for name, v in {"window": window, "field_max": field_max}.items():
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{who}: {name} is an integer")
+        if not 0 <= window <= _lib.GG_MATCH_MAX_WINDOW:
+            raise ValueError(f"{who}: window lies in [0, {_lib.GG_MATCH_MAX_WINDOW}]")
+        if field_max < 1 or field_max * self.rows * self.cols > _lib.GG_MATCH_LIMIT:
+            raise ValueError(f"{who}: field_max >= 1 and field_max * rows * cols <= 2^31 - 1")
+        if self.rows > _lib.GG_MATCH_MAX_SIDE or self.cols > _lib.GG_MATCH_MAX_SIDE:
+            raise ValueError(f"{who}: the map has more than {_lib.GG_MATCH_MAX_SIDE} rows or columns")
+
+        def int32_rows(name, given, shape_text, ok):
+            try:
+                given = np.asarray(given)
+                host = np.ascontiguousarray(given.astype(np.int32))
+                exact = given.shape == host.shape and np.array_equal(given, host)
+            except (TypeError, ValueError, OverflowError) as e:
+                raise ValueError(f"{who}: {name} must be {shape_text} int32: {e}") from None
+            if not ok(host.shape) or not exact:
+                raise ValueError(f"{who}: {name} of shape {host.shape} are not {shape_text} int32")
+            return host
+
+        host_rotations = None
+        if rotations is not None:
+            host_rotations = int32_rows("rotations", rotations, "[K, 2]", lambda s: len(s) == 2 and s[1] == 2)
+            if not 1 <= host_rotations.shape[0] <= _lib.GG_MATCH_MAX_ROTATIONS:
+                raise ValueError(f"{who}: rotations holds 1 to {_lib.GG_MATCH_MAX_ROTATIONS} candidates")
+            if (np.abs(host_rotations.astype(np.int64)) > _lib.GG_MATCH_UNIT).any():
+                raise ValueError(f"{who}: a word of rotations lies outside [-{_lib.GG_MATCH_UNIT}, {_lib.GG_MATCH_UNIT}]")
+        K = host_rotations.shape[0] if host_rotations is not None else 1
+        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
+
+        def is_planes(t):
+            return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 3 and t.is_contiguous() and tuple(t.shape[1:]) == plane
+
+        if not is_planes(scan):
+            raise ValueError(f"{who}: scan must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
+        B = int(scan.shape[0])
+        if not (is_planes(field) and field.shape[0] == B and field.device == scan.device):
+            raise ValueError(f"{who}: field must be a contiguous CUDA torch.int32 tensor of the shape and device of scan")
+        host_shifts = int32_rows("shifts", shifts, "[B, 2]", lambda s: s == (B, 2)) if shifts is not None else None
+        host_pivots = int32_rows("pivots", pivots, "[B, 2]", lambda s: s == (B, 2)) if pivots is not None else None
+        if host_pivots is not None and ((host_pivots < 0) | (host_pivots >= np.array([self.rows, self.cols]))).any():
+            raise ValueError(f"{who}: a pivot lies outside the map")
+        res = out if out is not None else MatchOutputs()
+        D = 2 * int(window) + 1
+        want = {"best": (B, 6), "scores": (B, K, D, D) if scores else None}
+        inputs = [scan.data_ptr(), field.data_ptr()]
+        for name, sh in want.items():
+            t = getattr(res, name)
+            if sh is None:
+                if t is not None:
+                    raise ValueError(f"{who}: out.{name} is given but not asked for")
+                continue
+            if t is None:
+                continue
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == sh and t.is_contiguous() and t.device == scan.device):
+                raise ValueError(f"{who}: out.{name} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
+            if t.data_ptr() in inputs:
+                raise ValueError(f"{who}: out.{name} is an input of the call")
+        for name, sh in want.items():
+            if sh is not None and getattr(res, name) is None:
+                setattr(res, name, torch.empty(sh, dtype=torch.int32, device=scan.device))
+        self._torch_used = True
+        x = _lib.GGPlaneMatches()
+        cells = self.rows * self.cols
+        x.n, x.d_scan, x.scan_stride, x.d_field, x.field_stride = B, scan.data_ptr(), cells, field.data_ptr(), cells
+        x.field_max, x.window = int(field_max), int(window)
+        if host_shifts is not None:
+            x.shifts = host_shifts.ctypes.data_as(C.POINTER(C.c_int32))
+        if host_pivots is not None:
+            x.pivots = host_pivots.ctypes.data_as(C.POINTER(C.c_int32))
+        if host_rotations is not None:
+            x.rotations, x.n_rotations = host_rotations.ctypes.data_as(C.POINTER(C.c_int32)), K
+        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.d_best = res.best.data_ptr()
+        x.d_scores, x.score_stride = (res.scores.data_ptr(), K * D * D) if scores else (None, 0)
+        stream = self._stream_arg(on_torch_stream, scan.device)
+        _check(self._L, self._ctx, self._L.gg_match_planes(self._ctx, C.byref(x), stream), "gg_match_planes")
         return res
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:

@@ -224,6 +224,9 @@ struct gg_context : ContextBuffers {
     CloudParams *d_export_lazy = nullptr, *h_export_lazy = nullptr;
     int2 *d_export_shifts = nullptr, *h_export_shifts = nullptr; // gg_fuse_states: the per-map index shifts of a call, [PARAM_RING][n_slots]
     int32_t *d_export_starts = nullptr, *h_export_starts = nullptr; // gg_route_planes: the per-map start cells of a call, [PARAM_RING][n_slots]
+    int2 *d_export_pivots = nullptr, *h_export_pivots = nullptr; // gg_match_planes: the per-map pivots of a call, [PARAM_RING][n_slots] (its shifts: d_export_shifts)
+    int2 *d_export_rotations = nullptr, *h_export_rotations = nullptr; // ... the rotation table of a call, [PARAM_RING][MATCH_MAX_ROTATIONS]
+    MatchPartial *d_match_partials = nullptr; // ... what its two launches hand over, [PARAM_RING][n_slots][MATCH_MAX_ROTATIONS], device only
     ParamRing export_ring;
     int slopes_variant = 0; // tuning "slopes_variant": 0 = k_slopes_tiled, 1 = k_slopes_gather (the A/B of tools/bench_slopes.py)
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
@@ -1974,7 +1977,14 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     // (gg_route_planes: the start cells of its maps, per ring entry)
     const size_t o_starts = align_up(o_shifts + ring * sizeof(int2), 256);
     const size_t h_starts = align_up(h_shifts + ring * sizeof(int2), 256);
-    if (const int rc = alloc_call_scratch(ctx, who, st, o_starts + ring * sizeof(int32_t), h_starts + ring * sizeof(int32_t),
+    // (gg_match_planes: the pivots of its maps and its rotation table, per ring entry, and the partial results between its two launches)
+    const size_t o_pivots = align_up(o_starts + ring * sizeof(int32_t), 256);
+    const size_t h_pivots = align_up(h_starts + ring * sizeof(int32_t), 256);
+    const size_t o_rotations = align_up(o_pivots + ring * sizeof(int2), 256);
+    const size_t h_rotations = align_up(h_pivots + ring * sizeof(int2), 256);
+    const size_t rotations_bytes = (size_t)PARAM_RING * MATCH_MAX_ROTATIONS * sizeof(int2);
+    const size_t o_match = align_up(o_rotations + rotations_bytes, 256);
+    if (const int rc = alloc_call_scratch(ctx, who, st, o_match + ring * MATCH_MAX_ROTATIONS * sizeof(MatchPartial), h_rotations + rotations_bytes,
                                           {{o_off, off.data(), off.size() * sizeof(uint32_t)}, {o_elem, elem.data(), elem.size() * sizeof(uint32_t)}, {o_cell, cell.data(), cell.size() * sizeof(uint16_t)}},
                                           &ctx->export_mem, &ctx->export_ring))
         return rc;
@@ -1992,6 +2002,11 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     ctx->h_export_shifts = (int2 *)(h + h_shifts);
     ctx->d_export_starts = (int32_t *)(block + o_starts);
     ctx->h_export_starts = (int32_t *)(h + h_starts);
+    ctx->d_export_pivots = (int2 *)(block + o_pivots);
+    ctx->h_export_pivots = (int2 *)(h + h_pivots);
+    ctx->d_export_rotations = (int2 *)(block + o_rotations);
+    ctx->h_export_rotations = (int2 *)(h + h_rotations);
+    ctx->d_match_partials = (MatchPartial *)(block + o_match);
     return GG_OK;
 }
 
@@ -2609,6 +2624,100 @@ int gg_route_planes(gg_context *ctx, const gg_plane_routes *x, void *stream)
     ra.plane_stride = x->plane_stride;
     ra.counts = x->d_counts;
     launch_route(ra, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
+// The best alignment of many scans to their grids (k20_match.hip): a ring entry and the ordering of the export for maps 0 .. n-1, none of
+// which is read, as gg_route_planes; the per-map shifts and pivots and the rotation table travel in the ring entry, and so do the partial
+// results between the two launches.  Nothing is synchronised, no map is filled and no host-side flag changes.
+int gg_match_planes(gg_context *ctx, const gg_plane_matches *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_match_planes";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_plane_matches");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    const int rows = ctx->arena.g.rows, cols = ctx->arena.g.cols;
+    if (!x->d_scan || !x->d_field || !x->d_best) return fail(ctx, GG_ERR_INVALID, who, "d_scan, d_field and d_best are required");
+    if (x->scan_stride < C) return fail(ctx, GG_ERR_INVALID, who, "scan_stride is smaller than rows * cols");
+    if (x->field_stride < C) return fail(ctx, GG_ERR_INVALID, who, "field_stride is smaller than rows * cols");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->window < 0 || x->window > MATCH_MAX_WINDOW) return fail(ctx, GG_ERR_INVALID, who, "window lies in [0, 32]");
+    if (x->rotations ? (x->n_rotations < 1 || x->n_rotations > MATCH_MAX_ROTATIONS) : x->n_rotations != 0)
+        return fail(ctx, GG_ERR_INVALID, who, "n_rotations lies in [1, 64] with rotations and is 0 without");
+    for (int k = 0; k < 2 * x->n_rotations; ++k)
+        if (x->rotations[k] < -GG_MATCH_UNIT || x->rotations[k] > GG_MATCH_UNIT) return fail(ctx, GG_ERR_INVALID, who, "a rotation word lies outside [-16384, 16384]");
+    // every score fits an int32: at most rows * cols scan cells of at most field_max each (the test by division is exact)
+    if (x->field_max < 1 || (uint64_t)x->field_max > (uint64_t)INT32_MAX / (uint64_t)C) return fail(ctx, GG_ERR_INVALID, who, "field_max < 1 or field_max * rows * cols exceeds 2^31 - 1");
+    // cq dr - sq dc and sq dr + cq dc stay inside an int32 (k20_match.hip relies on it)
+    if (rows > 32768 || cols > 32768) return fail(ctx, GG_ERR_GEOMETRY, who, "the map has more than 32768 rows or columns");
+    const int K = x->rotations ? x->n_rotations : 1, D = 2 * x->window + 1;
+    const size_t volume = (size_t)K * D * D;
+    if (x->d_scores && x->score_stride < volume) return fail(ctx, GG_ERR_INVALID, who, "score_stride is smaller than n_rotations * (2 * window + 1)^2");
+    if (x->pivots && x->n <= ctx->n_slots) // (beyond that the call is refused below, and pivots[] is the caller's to size by n)
+        for (int i = 0; i < x->n; ++i) {
+            const int32_t pr = x->pivots[2 * (size_t)i], pc = x->pivots[2 * (size_t)i + 1];
+            if (pr < 0 || pr >= rows || pc < 0 || pc >= cols) return fail(ctx, GG_ERR_INVALID, who, "a pivot lies outside the map");
+        }
+    if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
+    // no output may share a byte with an input or the other output, by the ranges of gg_route_planes: from a buffer's first word to the
+    // last cell of its last plane, or the last word of its last volume
+    struct Range {
+        const char *name, *lo, *hi;
+        bool out;
+    };
+    const auto planes = [&](const char *name, const void *p, size_t stride, size_t words, bool out) {
+        return Range{name, (const char *)p, (const char *)p + ((size_t)(x->n - 1) * stride + words) * sizeof(int32_t), out};
+    };
+    const Range ranges[4] = {planes("d_scan", x->d_scan, x->scan_stride, C, false), planes("d_field", x->d_field, x->field_stride, C, false),
+                             planes("d_best", x->d_best, 6, 6, true), planes("d_scores", x->d_scores, x->score_stride, volume, true)};
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j) {
+            const Range &p = ranges[i], &q = ranges[j];
+            if (!p.lo || !q.lo || !(p.out || q.out)) continue;
+            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
+                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
+        }
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    MatchArgs ma{};
+    const size_t entry = (size_t)f.g * ctx->n_slots;
+    if (x->shifts) { // clamped as gg_fuse_states clamps them: from |s| = side on no cell lies inside the map
+        int2 *hs = ctx->h_export_shifts + entry, *ds = ctx->d_export_shifts + entry;
+        for (int i = 0; i < x->n; ++i)
+            hs[i] = make_int2(std::min(std::max(x->shifts[2 * (size_t)i], -rows), rows), std::min(std::max(x->shifts[2 * (size_t)i + 1], -cols), cols));
+        HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(int2) * x->n, hipMemcpyHostToDevice, f.st));
+        ma.shifts = ds;
+    }
+    if (x->pivots) {
+        int2 *hp = ctx->h_export_pivots + entry, *dp = ctx->d_export_pivots + entry;
+        for (int i = 0; i < x->n; ++i) hp[i] = make_int2(x->pivots[2 * (size_t)i], x->pivots[2 * (size_t)i + 1]);
+        HIPCHK(ctx, hipMemcpyAsync(dp, hp, sizeof(int2) * x->n, hipMemcpyHostToDevice, f.st));
+        ma.pivots = dp;
+    }
+    if (x->rotations) {
+        int2 *hr = ctx->h_export_rotations + (size_t)f.g * MATCH_MAX_ROTATIONS, *dr = ctx->d_export_rotations + (size_t)f.g * MATCH_MAX_ROTATIONS;
+        for (int k = 0; k < K; ++k) hr[k] = make_int2(x->rotations[2 * (size_t)k], x->rotations[2 * (size_t)k + 1]);
+        HIPCHK(ctx, hipMemcpyAsync(dr, hr, sizeof(int2) * K, hipMemcpyHostToDevice, f.st));
+        ma.rotations = dr;
+    }
+    const bool row_major = x->order == GG_PLANES_ROWMAJOR;
+    ma.scan = x->d_scan;
+    ma.scan_stride = x->scan_stride;
+    ma.field = x->d_field;
+    ma.field_stride = x->field_stride;
+    ma.field_max = x->field_max;
+    ma.n_rotations = K;
+    ma.window = x->window;
+    ma.nx = row_major ? cols : rows;
+    ma.ny = row_major ? rows : cols;
+    ma.row_major = row_major;
+    ma.partials = ctx->d_match_partials + entry * MATCH_MAX_ROTATIONS;
+    ma.best = x->d_best;
+    ma.scores = x->d_scores;
+    ma.score_stride = x->score_stride;
+    launch_match(ma, x->n, f.st);
     return map_call_end(ctx, f);
 }
 

@@ -469,6 +469,35 @@ struct RouteArgs {
     int32_t *path_len;             // [map]
 };
 
+// gg_match_planes (k20_match.hip): what its two launches share.  Map i of the call is row i of every buffer.  A plane is `ny` lines of `nx`
+// contiguous words: (nx, ny) = (cols, rows) row-major, (rows, cols) column-major.  The rotation, the tie rule and the score volume are in
+// (row, col) terms, so the kernel is told the order; shifts and pivots arrive as (row, col), the shifts clamped to [-rows, rows] x [-cols, cols]
+constexpr int MATCH_MAX_WINDOW = 32;
+constexpr int MATCH_MAX_ROTATIONS = 64;
+struct MatchPartial {              // what the work-group of (map, k) leaves for k_match_best
+    unsigned long long key;        // S << 32 | ~rank of the best candidate of this k (k20_match.hip match_rank)
+    uint32_t ties;                 // candidates of this k whose score equals that S
+    uint32_t cells;                // scan cells of the map (the same for every k)
+};
+struct MatchArgs {
+    const int32_t *scan;           // map i's plane at scan + i * scan_stride: a scan cell where the word is > 0
+    size_t scan_stride;
+    const int32_t *field;          // ... at field + i * field_stride: f = min(max(word, 0), field_max)
+    size_t field_stride;
+    int field_max;
+    const int2 *shifts;            // device [map] (row, col), clamped (the call's ring entry); null: all (0, 0)
+    const int2 *pivots;            // device [map] (row, col); null: (rows / 2, cols / 2)
+    const int2 *rotations;         // device [K] (cq, sq) in Q14; null: K == 1, (16384, 0)
+    int n_rotations;               // K
+    int window;                    // W
+    int nx, ny;
+    bool row_major;
+    MatchPartial *partials;        // device [map][K] (the call's ring entry)
+    int32_t *best;                 // [map][6]
+    int32_t *scores;               // map i's volume at scores + i * score_stride; nullable
+    size_t score_stride;
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -518,6 +547,7 @@ void launch_clearance(const Arena &a, const ClearanceArgs &x, int n_maps, hipStr
 void launch_visibility(const Arena &a, const VisibilityArgs &x, int n_clouds, hipStream_t s);    // k17_visibility.hip: occupancy, hits, trace, states
 void launch_fuse(const FuseArgs &x, int n_maps, hipStream_t s);                                  // k18_fuse.hip: (counts := 0,) k_fuse_states
 void launch_route(const RouteArgs &x, int n_maps, hipStream_t s);                                // k19_route.hip: relax, (counts := 0, next,) (paths)
+void launch_match(const MatchArgs &x, int n_maps, hipStream_t s);                                // k20_match.hip: k_match_scores, k_match_best
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

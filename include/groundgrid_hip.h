@@ -1082,6 +1082,80 @@ typedef struct gg_plane_routes {
 int gg_route_planes(gg_context *ctx, const gg_plane_routes *x, void *stream);
 #define GG_HAS_ROUTE_PLANES 1
 
+/* CORRELATIVE SCAN-TO-MAP MATCHING of many maps, in DEVICE memory: everything persistent in the chain above is placed by odometry the caller
+ * hands in and nobody checks -- the map's own layers through gg_move_maps, the evidence of gg_fuse_states through the index shifts that
+ * call returns -- and a shift that is one cell off smears every wall of the fused grid.  gg_match_planes scores this scan's occupied cells
+ * against the accumulated grid over a window of translations and a few yaw candidates, and returns the best candidate and how ambiguous it
+ * is.  What a caller otherwise composes per map from nonzero (which synchronises), a rotation, a scatter and a padded correlation per yaw.
+ * Both inputs are planes of earlier calls as they stand.  Map i of the call is row i of every buffer and of `shifts` and `pivots`.
+ * Everything is 32-bit integer; nothing wraps at the border; all of the following is per map:
+ *   scan cell    cell (r, c) where map i's d_scan word is > 0 (a d_state plane of gg_visibility_clouds, a d_fused plane of gg_fuse_states:
+ *                the occupied cells alone).
+ *   reward       f(r, c) = min(max(word of d_field, 0), field_max) inside the map, 0 for any cell outside it (a d_evidence_out plane of
+ *                gg_fuse_states as it stands: positive evidence means occupied; or a likelihood composed from a clearance plane).
+ *   prior shift  (s0, s1) = (shifts[2 i], shifts[2 i + 1]), both 0 when `shifts` is NULL, WITH THE MEANING IT HAS IN gg_fuse_states: scan
+ *                cell (r, c) lies over field cell (r + s0, c + s1).  Clamped to [-rows, rows] x [-cols, cols] as there.
+ *   pivot        (pr, pc) = (pivots[2 i], pivots[2 i + 1]), a cell inside the map, (rows / 2, cols / 2) when `pivots` is NULL: the centre
+ *                of rotation, the sensor's cell.
+ *   rotation k   the pair (cq, sq) = (rotations[2 k], rotations[2 k + 1]) in Q14 (16384 = 1.0), shared by all maps, |cq|, |sq| <= 16384,
+ *                1 <= n_rotations = K <= 64; NULL with n_rotations == 0 is the single candidate (16384, 0).  The pair is used as given: no
+ *                unit length is asked for.  With dr = r - pr, dc = c - pc:  a = cq dr - sq dc,  b = sq dr + cq dc,  r' = pr + rnd(a),
+ *                c' = pc + rnd(b), rnd(v) = (|v| + 8192) >> 14 with the sign of v: round half away from zero, the convention of
+ *                gg_visibility_clouds.  rows, cols <= 32768 (GG_ERR_GEOMETRY), so a and b fit an int32.  The formula is in (row, col)
+ *                terms and does not depend on `order`.  Two scan cells that land on the same (r', c') both count.
+ *   score        S(k, dy, dx) = the sum over the scan cells of f(r' + s0 + dy, c' + s1 + dx), for every k and every translation (dy, dx) in
+ *                [-W, W] x [-W, W] in (row, col) terms, W = `window`, 0 <= W <= 32.
+ *   limits       field_max >= 1 and field_max * rows * cols <= 2^31 - 1: every score fits an int32.  The C ABI has no defaults.
+ *   d_best[i]    six words: k*, dy*, dx*, S*, the number of scan cells of the map, and the number of candidates (k, dy, dx) whose score
+ *                equals S*.  (k*, dy*, dx*) attains the maximum S*; among the maximisers it has the smallest dy^2 + dx^2, then the
+ *                smallest k, then the smallest dy, then the smallest dx: a caller who lists the prior yaw first gets "no correction" on a
+ *                featureless scene.  A map without scan cells gives (0, 0, 0, 0, 0, K (2 W + 1)^2).
+ *   d_scores     nullable: map i's volume of K (2 W + 1)^2 words at d_scores + i * score_stride, S(k, dy, dx) at word
+ *                (k (2 W + 1) + dy + W) (2 W + 1) + dx + W.  Every word of a given volume is written; the words between the volume and
+ *                the stride never are.
+ *   use          with k* the identity, (s0 + dy*, s1 + dx*) IS THE CORRECTED SHIFT TO PASS TO gg_fuse_states for this scan.  A k* that is
+ *                not the identity is a yaw correction for the caller's next cloud-to-map transform; no call rotates planes.  The sixth
+ *                word against K (2 W + 1)^2, and S* against field_max times the fifth, say how much to trust either.
+ *   addressing   map i's plane of rows * cols int32 at d_scan + i * scan_stride and d_field + i * field_stride; cell (row, col) where
+ *                `order` puts it, the same order for both planes.  4-byte alignment.
+ *   no overlap   no output may share a byte with an input or with the other output; the call compares the address ranges as
+ *                gg_route_planes does (a plane buffer from its first word to the last cell of its last plane, d_scores to the last word
+ *                of its last volume) and answers GG_ERR_INVALID.  The two inputs may overlap each other.
+ *   determinism  integer sums only: bit-identical from run to run and independent of scheduling.
+ * The contract is that of gg_fuse_states: NO MAP IS READ OR CHANGED -- no layer, position, freshness, configuration, score or liveness flag,
+ * and the lazily kept layers stay pending.  n <= n_slots (GG_ERR_CAPACITY): the call takes an entry of the same ring of parameter entries
+ * (the shifts, the pivots and the rotation table travel in it) and orders itself on `stream` as those calls do; it enqueues and returns with
+ * no synchronisation, and the host arrays may be freed on return.  The caller's device buffers must stay valid and unmodified until
+ * `stream` has passed the call.
+ * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
+ * n > 0: null d_scan, d_field or d_best, scan_stride or field_stride < rows * cols, score_stride < K (2 W + 1)^2 with d_scores given, an
+ * unknown order, window outside [0, 32], field_max < 1 or beyond the limit, n_rotations outside [1, 64] with `rotations` given or != 0
+ * without, a rotation word beyond +-16384, a pivot outside the map, overlapping buffers; GG_ERR_GEOMETRY for rows or cols > 32768;
+ * GG_ERR_CAPACITY for n > n_slots.  n == 0 is GG_OK before anything else is looked at.  The first many-map call of a context may allocate
+ * (GG_ERR_NOMEM) and block; later calls only enqueue.  Capture into a caller's graph is not supported. */
+#define GG_MATCH_MAX_WINDOW 32
+#define GG_MATCH_MAX_ROTATIONS 64
+#define GG_MATCH_UNIT 16384
+typedef struct gg_plane_matches {
+    int n;                        /* maps */
+    const int32_t *d_scan;        /* [n] planes, scan_stride apart: a SCAN CELL where the word is > 0; required */
+    size_t scan_stride;           /* int32 words, >= rows * cols */
+    const int32_t *d_field;       /* [n] planes, field_stride apart: the reward min(max(word, 0), field_max); required */
+    size_t field_stride;          /* int32 words, >= rows * cols */
+    int field_max;                /* >= 1, field_max * rows * cols <= 2^31 - 1 */
+    const int32_t *shifts;        /* host [n][2] prior shifts (rows, cols), as gg_state_fusion.shifts; NULL: all (0, 0) */
+    const int32_t *pivots;        /* host [n][2] (row, col) inside the map; NULL: (rows / 2, cols / 2) for every map */
+    const int32_t *rotations;     /* host [n_rotations][2] (cq, sq) in Q14; NULL with n_rotations == 0: the one candidate (16384, 0) */
+    int n_rotations;              /* K, 1 .. 64 */
+    int window;                   /* W, 0 .. 32 */
+    int order;                    /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR, of both planes */
+    int32_t *d_best;              /* [n][6]: k*, dy*, dx*, S*, scan cells, candidates that attain S*; required */
+    int32_t *d_scores;            /* [n] volumes of K (2 W + 1)^2 int32, score_stride apart; nullable */
+    size_t score_stride;          /* int32 words, >= K (2 W + 1)^2 when d_scores is given */
+} gg_plane_matches;
+int gg_match_planes(gg_context *ctx, const gg_plane_matches *x, void *stream);
+#define GG_HAS_MATCH_PLANES 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
