@@ -13,16 +13,30 @@ Three parts, none of which needs a GPU to import:
                                library's own cross-stream ordering is what makes them right.
 
 A result is a dict name -> array / scalar / bytes; first_diff() compares bit for bit (NaN == NaN, -0.0 != 0.0).
+
+The many-map device calls that read or write map state (NEW_KINDS: gg_import_layers, gg_export_images, gg_export_slopes, gg_split_clouds,
+gg_rasterize_clouds, gg_cluster_clouds, gg_clearance_clouds in cloud mode, gg_visibility_clouds) are inserted into that list by a second
+generator stream (_Ins), so that make_sequence(seed, shape, device_calls=False) stays the list it was.  A cloud call takes its points and
+labels from an earlier filter_batch of the sequence (chained: that batch's device buffers, named by the batch's index) or from seeded
+data that belong to no batch (foreign).  The model derives what they return from the slot's OracleMap as it stands and the references
+of tests/cloud_refs.py, slopes_ref.py, cluster_ref.py, clearance_ref.py and visibility_ref.py; the driver hands them sentinel-filled
+destinations with slack words and padded strides, and compares at the next checkpoint, untouched words included.
+The three plane calls (gg_fuse_states, gg_route_planes, gg_match_planes) stay out: they read and write no map state, so the order of
+the calls around them cannot change their result, and test_the_chain_from_a_drive covers their chain.
 """
 from __future__ import annotations
 
+import contextlib
+import hashlib
 import importlib.util
+import json
 import os
 
 import numpy as np
 
 from groundgrid_amd import kitti
 from oracle import oracle
+from tests import clearance_ref, cloud_refs, slopes_ref
 
 LAYERS = list(oracle.LAYERS)
 PER_CALL = [k for k in LAYERS if k not in ("ground", "groundpatch")]
@@ -67,9 +81,23 @@ MUTATING = ["reset_maps", "map_reset", "move_maps", "map_move", "set_position", 
             "set_score_labels", "set_scoring", "reset_scores"]
 OBSERVING = ["get_layer", "get_layers", "export_layers", "scores", "point_classes", "slot_config", "get_position", "image_u8", "terrain_image",
              "gridmap_message", "synchronize", "batch_fence", "set_flags", "checkpoint"]
-KINDS = MUTATING + OBSERVING   # (set_flags changes no observable -- every layer reads as the reference's at all times -- so it is not "mutating")
+OLD_KINDS = MUTATING + OBSERVING   # (set_flags changes no observable -- every layer reads as the reference's at all times -- so it is not "mutating")
+# the many-map device calls that read or write map state: drawn from a generator stream of their own and inserted into the list of the
+# kinds above (make_sequence), so that a committed seed keeps every op it had
+LAYER_READERS = ["export_images", "export_slopes"]
+CLOUD_KINDS = ["split_clouds", "rasterize_clouds", "cluster_clouds", "clearance_clouds", "visibility_clouds"]
+NEW_READERS = LAYER_READERS + CLOUD_KINDS
+NEW_KINDS = ["import_layers"] + NEW_READERS
+MUTATING = MUTATING + ["import_layers"]
+OBSERVING = OBSERVING + NEW_READERS
+KINDS = MUTATING + OBSERVING
 GLOBAL_KINDS = {"set_config", "set_conventions", "set_score_labels", "set_flags", "synchronize", "batch_fence", "checkpoint"}
-DEVICE_KINDS = {"reset_maps", "move_maps", "filter_batch", "export_layers", "batch_fence"}   # enqueue and return (on a caller stream)
+DEVICE_KINDS = {"reset_maps", "move_maps", "filter_batch", "export_layers", "batch_fence"} | set(NEW_KINDS)   # enqueue and return (on a caller stream)
+MUTATING_DEVICE_KINDS = {"reset_maps", "move_maps", "filter_batch", "import_layers"}
+PARAM_RING = 4   # (gg_context.hip: the entries of the ring of parameter blocks the many-map calls share)
+SLOPE_CHANNELS = ["grad_x", "grad_y", "tangent", "normal_z", "step", "min_confidence"]
+RASTER_CHANNELS = ["nonground_count", "nonground_max_height", "nonground_min_height", "ground_count", "ground_max_height", "ground_min_height"]
+SENTINEL = 0x7FC12345   # what the driver fills every destination with (a NaN no kernel produces); bytes: 0xA5
 
 PREDICATES = ["fresh", "no-confidence", "lazy-owed", "own-config", "scoring", "partly-live"]
 
@@ -264,7 +292,7 @@ def first_diff(want, got):
 def _pair_table():
     """every (predicate or None, op kind) the coverage table asks for, in one fixed shuffled order, dealt to the committed sequences in
     proportion to their step counts"""
-    pairs = [(p, k) for p in PREDICATES + [None] for k in KINDS if allowed(p, k)]
+    pairs = [(p, k) for p in PREDICATES + [None] for k in OLD_KINDS if allowed(p, k)]
     order = np.random.default_rng(20260101).permutation(len(pairs))
     pairs = [pairs[i] for i in order]
     deal = []
@@ -693,7 +721,7 @@ class _Gen:
             if step < len(pairs):
                 pred, kind = pairs[step]
             else:
-                pred, kind = None, KINDS[int(self.rng.integers(0, len(KINDS)))]
+                pred, kind = None, OLD_KINDS[int(self.rng.integers(0, len(OLD_KINDS)))]
             if kind == "checkpoint":
                 kind = "synchronize"
             slot = self.slot()
@@ -706,10 +734,367 @@ class _Gen:
         return self.ops
 
 
-def make_sequence(seed, shape):
+def _new_pairs(shape, seed):
+    """the (predicate or None, new kind) pairs the inserter of (shape, seed) tries to bring about: every kind with no predicate in every
+    sequence, every other pair in two of the six committed ones"""
+    pairs = [(p, k) for p in PREDICATES for k in NEW_KINDS if allowed(p, k)]
+    pairs = [pairs[i] for i in np.random.default_rng(20261019).permutation(len(pairs))]
+    q = 2 * list(SHAPES).index(shape) + int(seed) % SEEDS_PER_SHAPE
+    total = len(SHAPES) * SEEDS_PER_SHAPE
+    return [(None, k) for k in NEW_KINDS] + [pair for t, pair in enumerate(pairs) if q in (t % total, (t + 3) % total)]
+
+
+class _Ins:
+    """Inserts ops of NEW_KINDS into the list `old` of the other kinds, which stays a subsequence with every dict as it was.  A generator
+    stream of its own; like _Gen it knows the header's preconditions and nothing of the library.  Four sources of insertions:
+      anchors   next to a mutating device op (or an export, for the import) of the old list, on ANOTHER stream and on one of its maps: the
+                reader behind it (read after write) or in front of it (write after read); a cloud call behind a batch takes that batch's
+                cloud and label buffers (chained)
+      pairs     _new_pairs, wherever a slot happens to satisfy the predicate; what is left at the end is brought about there
+      ring      once, more than PARAM_RING new ops in a row on two streams
+      tail      short scripts in front of the last checkpoint, one per promise of the import and of the readers (MUTANTS)
+    An import is not inserted where it would take a predicate from an old op that is the last of its (predicate, kind) cell."""
+
+    GP = {"ground", "groundpatch"}
+
+    def __init__(self, seed, shape, old):
+        self.shape, self.sh, self.seed, self.old = shape, SHAPES[shape], int(seed), old
+        self.rng = np.random.default_rng([int(seed), list(SHAPES).index(shape), 20261019])
+        self.n = self.sh["n_slots"]
+        self.out = []
+        self.pos = [(0.0, 0.0)] * self.n
+        self.alive = []                   # [(index in out, op)]: batches with a label output since the last checkpoint
+        self.pred = Predicates(self.n)    # over the list as it grows
+        self.cursor = {}
+        self.next_seed = 500000 + 1000 * self.seed
+        self.labels_set = False
+        self.flags = dict(minimal=False, eager=False, halves=False)
+        self.pending = _new_pairs(shape, seed)
+        # the old list's own coverage: per op the touched slots for which each predicate holds when the op arrives, and the cell counts
+        p = Predicates(self.n)
+        self.touch, self.held, self.cells = [], [], {}
+        for op in old:
+            t = touched(op, self.n) if op["op"] in OLD_KINDS else []
+            h = {q: {s for s in t if p.state[q][s]} for q in ("fresh", "no-confidence", "lazy-owed")}
+            for q, hs in h.items():
+                if hs:
+                    self.cells[(q, op["op"])] = self.cells.get((q, op["op"]), 0) + 1
+            self.touch.append(set(t))
+            self.held.append(h)
+            p.apply(op)
+
+    # -- pieces
+    def r(self, lo, hi):
+        return round(float(self.rng.uniform(lo, hi)), 3)
+
+    def seed_of(self):
+        self.next_seed += 1
+        return self.next_seed
+
+    def next_of(self, names, attr):
+        k = self.cursor.get(attr, 0)
+        self.cursor[attr] = k + 1
+        return names[k % len(names)]
+
+    def other_stream(self, stream):
+        while True:
+            s = self.next_of(["s1", "s2", "default", "s2", "s1", "ctx", "default"], "stream")
+            if s != stream:
+                return s
+
+    def slots(self, count, must):
+        pick = [int(v) for v in self.rng.permutation(self.n)[: min(count, self.n)]]
+        if must not in pick:
+            pick[int(self.rng.integers(0, len(pick)))] = must
+        return pick
+
+    def push(self, op):
+        k = op["op"]
+        if k == "reset_maps":
+            for s in range(op["first"], op["first"] + op["n"]):
+                self.pos[s] = tuple(op["pos"])
+        elif k in ("map_reset", "set_position"):
+            self.pos[op["slot"]] = tuple(op["pos"])
+        elif k == "move_maps":
+            for s, o in zip(op["slots"], op["odoms"]):
+                self.pos[s] = tuple(o)
+        elif k == "map_move":
+            self.pos[op["slot"]] = tuple(op["odom"])
+        elif k == "set_score_labels":
+            self.labels_set = True
+        elif k == "set_flags":
+            self.flags = dict(minimal=op["minimal"], eager=op["eager"], halves=op["halves"])
+        elif k == "checkpoint":
+            self.alive = []
+        elif k == "filter_batch" and ("labels" in op["outputs"] or "masks" in op["outputs"]):
+            self.alive.append((len(self.out), op))
+        self.out.append(op)
+        self.pred.apply(op)
+        if k in NEW_KINDS:   # a pair that this op happens to meet is no longer looked for
+            sl = touched(op, self.n)
+            self.pending = [(p, kk) for p, kk in self.pending if not (kk == k and (p is None or self._held_before(p, sl)))]
+
+    def _held_before(self, p, slots):
+        return any(self._before[p][s] for s in slots)
+
+    def emit(self, op):
+        self._before = {p: list(v) for p, v in self.pred.state.items()} if op["op"] in NEW_KINDS else None
+        self.push(op)
+
+    # -- the import's safety rule
+    def import_ok(self, j, slots, names):
+        ends = (["fresh", "no-confidence"] if set(names) & self.GP else []) + (["lazy-owed"] if set(names) & set(PER_CALL) else [])
+        gone, lost = [], {}
+        for s in slots:
+            for p in ends:
+                for i in range(j, len(self.old)):
+                    if s not in self.touch[i]:
+                        continue
+                    if s not in self.held[i][p]:
+                        break
+                    gone.append((i, p, s))
+        left = {}
+        for i, p, s in gone:
+            left.setdefault((i, p), set(self.held[i][p])).discard(s)
+        for (i, p), rest in left.items():
+            if not rest:
+                cell = (p, self.old[i]["op"])
+                lost[cell] = lost.get(cell, 0) + 1
+        if any(self.cells[cell] - k < 1 for cell, k in lost.items()):
+            return False
+        for (i, p), rest in left.items():
+            self.held[i][p] = rest
+        for cell, k in lost.items():
+            self.cells[cell] -= k
+        return True
+
+    # -- the new ops
+    def layer_names(self, must_gp=None):
+        names = [k for k in LAYERS if self.rng.random() < 0.3]
+        if must_gp is True and not set(names) & self.GP:
+            names.append(str(self.rng.choice(["ground", "groundpatch"])))
+        return [k for k in LAYERS if k in names] or ["ground"]
+
+    def mk_import_layers(self, slot, stream, j, names=None, slots=None, fill=None):
+        names = names or self.layer_names()
+        slots = slots or self.slots(int(self.rng.integers(1, 4)), slot)
+        if j is not None and not self.import_ok(j, slots, names):
+            slots = [slot]
+            if not self.import_ok(j, slots, names):
+                return None
+        return dict(op="import_layers", slots=slots, names=names, row_major=bool(self.rng.random() < 0.5), pad=self.next_of([0, 5, 0, 64], "import pad"),
+                    fills=[dict(seed=self.seed_of(), kind=fill or str(self.rng.choice(["integer", "fractional", "confident"]))) for _ in slots], stream=stream)
+
+    def mk_export_images(self, slot, stream, names=None, terrain=None):
+        names = [k for k in LAYERS if self.rng.random() < 0.25] if names is None else names
+        terrain = bool(self.rng.random() < 0.5 or not names) if terrain is None else terrain
+        return dict(op="export_images", slots=self.slots(int(self.rng.integers(1, 4)), slot), names=names, terrain=terrain, chw=bool(self.rng.random() < 0.5),
+                    pad=self.next_of([0, 3, 0, 32], "image pad"), bounds=bool(self.rng.random() < 0.8), stream=stream)
+
+    def mk_export_slopes(self, slot, stream):
+        return dict(op="export_slopes", slots=self.slots(int(self.rng.integers(1, 4)), slot),
+                    channels=[k for k in SLOPE_CHANNELS if self.rng.random() < 0.5] or ["step"], row_major=bool(self.rng.random() < 0.5),
+                    pad=self.next_of([0, 1, 0, 33], "slopes pad"), stream=stream)
+
+    def source(self, slot, batch=None, foreign=None, cloud_kind=None):
+        """(slots, source, masks): chained to an alive batch that holds `slot` (to `batch` = (index, op) where given), else foreign"""
+        have = [b for b in self.alive if slot in b[1]["slots"]]
+        if batch is None and have and foreign is not True and (foreign is False or self.rng.random() < 0.7):
+            batch = have[-1]
+        if batch is not None:
+            at, bop = batch
+            row, B = bop["slots"].index(slot), len(bop["slots"])
+            cnt = int(self.rng.integers(1, min(3, B) + 1))
+            row0 = int(np.clip(row - int(self.rng.integers(0, cnt)), 0, B - cnt))
+            both = "labels" in bop["outputs"] and "masks" in bop["outputs"]
+            masks = bool(self.rng.random() < 0.5) if both else "masks" in bop["outputs"]
+            return bop["slots"][row0: row0 + cnt], dict(mode="chained", batch=at, row0=row0), masks
+        slots = self.slots(int(self.rng.integers(1, 4)), slot)
+        tf = bool(self.rng.random() < 0.4)
+        masks = bool(self.rng.random() < 0.5)
+        clouds, tfs = [], []
+        for s in slots:
+            u = self.rng.random()
+            ck = cloud_kind or ("empty" if u < 0.05 else "outside" if u < 0.2 else "nanz" if u < 0.3 and not tf else "scene")
+            cx, cy = (0.0, 0.0) if tf else self.pos[s]
+            clouds.append(dict(seed=self.seed_of(), n=int(self.rng.integers(20, min(300, self.sh["stride"]))), kind=ck, cx=cx, cy=cy))
+            th = float(self.rng.uniform(-0.6, 0.6))
+            q = np.array([self.r(-0.01, 0.01), self.r(-0.01, 0.01), np.sin(th / 2), np.cos(th / 2)])
+            tfs.append([self.pos[s][0], self.pos[s][1], self.r(-0.05, 0.05)] + [float(v) for v in q / np.linalg.norm(q)])
+        longest = max(c["n"] for c in clouds)
+        stride = min(self.sh["stride"], longest + int(self.rng.choice([0, 1, 7, 30])))
+        if masks:
+            stride = min(self.sh["stride"], 4 * ((stride + 3) // 4))
+        return slots, dict(mode="foreign", clouds=clouds, labels=dict(seed=self.seed_of()), fmt=int(self.rng.choice([16, 32])), tfs=tfs if tf else None,
+                           stride=stride), masks
+
+    def mk_cloud(self, kind, slot, stream, **src):
+        slots, source, masks = self.source(slot, **src)
+        op = dict(op=kind, slots=slots, source=source, masks=masks, stream=stream)
+        pad = self.next_of([0, 2, 0, 40], "cloud pad")
+        band = dict(min_points=int(self.rng.choice([1, 1, 2])), min_height=None if self.rng.random() < 0.5 else self.r(-0.3, 0.2),
+                    max_height=None if self.rng.random() < 0.5 else self.r(0.4, 2.5))
+        if kind == "split_clouds":
+            fields = ["points", "height", "source"]
+            want = {s: ([f for f in fields if self.rng.random() < 0.8] or ["height"]) for s in ("ground", "nonground") if self.rng.random() < 0.85}
+            op.update(want=want or {"nonground": fields})
+        elif kind == "rasterize_clouds":
+            op.update(channels=[k for k in RASTER_CHANNELS if self.rng.random() < 0.5] or ["nonground_count"], row_major=bool(self.rng.random() < 0.5), pad=pad)
+        elif kind == "cluster_clouds":
+            op.update(band, connectivity=int(self.rng.choice([4, 8])), row_major=bool(self.rng.random() < 0.5), pad=pad,
+                      max_clusters=int(self.rng.choice([0, 3, 64])), point_clusters=bool(self.rng.random() < 0.7))
+        elif kind == "clearance_clouds":
+            op.update(band, max_cells=int(self.rng.choice([0, 0, 5, 20])), row_major=bool(self.rng.random() < 0.5), pad=pad,
+                      nearest=bool(self.rng.random() < 0.7) and self.shape != "latency", distance=bool(self.rng.random() < 0.7))
+        elif kind == "visibility_clouds":
+            org = [[self.pos[s][0] + self.r(-0.5, 0.5), self.pos[s][1] + self.r(-0.5, 0.5), self.r(-0.05, 0.05)] for s in slots]
+            if self.rng.random() < 0.15:
+                org[0][0] += 3.0 * self.sh["length"]   # (a sensor outside its map casts no ray)
+            op.update(band, max_cells=int(self.rng.choice([0, 0, 7, 40])), row_major=bool(self.rng.random() < 0.5), pad=pad, origins=org,
+                      counts=bool(self.rng.random() < 0.7))
+        return op
+
+    def mk(self, kind, slot, stream, j=None, **kw):
+        if kind == "import_layers":
+            return self.mk_import_layers(slot, stream, j, **kw)
+        if kind == "export_images":
+            return self.mk_export_images(slot, stream, **kw)
+        if kind == "export_slopes":
+            return self.mk_export_slopes(slot, stream)
+        return self.mk_cloud(kind, slot, stream, **kw)
+
+    def put(self, kind, slot, stream, j=None, **kw):
+        op = self.mk(kind, slot, stream, j, **kw)
+        if op is not None:
+            self.emit(op)
+        return op is not None
+
+    # -- where
+    @staticmethod
+    def guarded(op):
+        """tests/test_sequences_cpu.py looks at what stands right behind a batch of more than 256 clouds: nothing goes there"""
+        return op["op"] == "batch_fence" or (op["op"] == "filter_batch" and len(op["slots"]) > 256) or op["op"] == "tunings"
+
+    def anchors(self, j):
+        """the old op in front of this place and the one behind it"""
+        prev, nxt = self.old[j - 1], self.old[j]
+        for anchor, after in ((prev, True), (nxt, False)):
+            k = anchor["op"]
+            if k not in ("filter_batch", "move_maps", "reset_maps", "export_layers") or self.rng.random() >= (0.55 if k == "export_layers" else 0.3):
+                continue
+            kind = "import_layers" if k == "export_layers" else self.next_of(NEW_READERS + ["import_layers"] + NEW_READERS, "after" if after else "before")
+            t = touched(anchor, self.n)
+            slot = t[int(self.rng.integers(0, len(t)))]
+            kw = {}
+            if kind in CLOUD_KINDS and after and k == "filter_batch" and self.alive and self.alive[-1][1] is anchor:
+                kw = dict(batch=self.alive[-1])   # (the labels this batch is still writing, read from another stream)
+            self.put(kind, slot, self.other_stream(anchor["stream"]), j, **kw)
+
+    def pairs(self, j):
+        done = 0
+        for pred, kind in list(self.pending):
+            if done == 2:
+                break
+            if pred is None:
+                if self.rng.random() >= 0.05:
+                    continue
+                ok = list(range(self.n))
+            else:
+                ok = [s for s in range(self.n) if self.pred.state[pred][s]]
+            if ok:
+                done += self.put(kind, ok[int(self.rng.integers(0, len(ok)))], self.next_of(MAP_STREAMS, "pair stream"), j)
+
+    def ring(self):
+        """seven new ops of five kinds in a row on two caller streams: every entry of the shared ring is taken again by another kind"""
+        s = self.alive[-1][1]["slots"][0] if self.alive else int(self.rng.integers(0, self.n))
+        a, b = [("s1", "s2"), ("default", "s2")][self.seed % 2]
+        for kind, st in (("split_clouds", a), ("export_slopes", b), ("rasterize_clouds", a), ("export_images", b), ("cluster_clouds", b),
+                         ("visibility_clouds", a), ("clearance_clouds", b)):
+            self.put(kind, s, st)
+
+    # -- the tail: old kinds as scaffolding, then the call the script is about
+    def establish(self, pred, s):
+        if pred in ("fresh", "no-confidence"):
+            self.push(dict(op="reset_maps", first=s, n=1, odom_z=self.r(-1.9, -1.5), pos=[self.r(-30, 30), self.r(-30, 30)], persistent=False, stream="s1"))
+        elif pred == "lazy-owed":
+            self.batch(s, "s2")
+        elif pred == "own-config":
+            self.push(dict(op="set_slot_configs", slots=[s], cfgs=[int(self.rng.integers(1, len(CONFIGS)))]))
+        elif pred == "scoring":
+            if not self.labels_set:
+                self.push(dict(op="set_score_labels", ids=LABEL_LISTS[0]))
+            self.push(dict(op="set_scoring", slots=[s], enable=True))
+        elif pred == "partly-live":
+            self.push(dict(op="set_layer", slot=s, layer="points", fill=dict(seed=self.seed_of(), kind="integer")))
+
+    def batch(self, s, stream, count=2):
+        if self.flags["eager"]:
+            self.push(dict(op="set_flags", **dict(self.flags, eager=False)))
+        sl = self.slots(count, s)
+        lo, hi = self.sh["pts"]
+        clouds = [dict(seed=self.seed_of(), n=int(self.rng.integers(lo, hi)), kind="scene", cx=self.pos[t][0], cy=self.pos[t][1]) for t in sl]
+        self.push(dict(op="filter_batch", slots=sl, clouds=clouds, origins=[[self.pos[t][0], self.pos[t][1], 0.0] for t in sl], base_z=[BASE_Z for _ in sl],
+                       tfs=None, fmt=16, outputs=["labels", "counts", "masks"], stream=stream))
+
+    def tail(self):
+        for pred, kind in list(self.pending):
+            s = int(self.rng.integers(0, self.n))
+            if pred is not None:
+                self.establish(pred, s)
+            self.put(kind, s, self.next_of(MAP_STREAMS, "pair stream"))
+        s = int(self.rng.integers(0, self.n))
+        # a fresh map becomes real by the import alone, and its confidence counts for the next cloud's outlier walk
+        self.push(dict(op="set_slot_configs", slots=[s], cfgs=None))
+        self.push(dict(op="set_config", cfg=5))
+        self.establish("fresh", s)
+        self.put("import_layers", s, "s2", names=["ground", "groundpatch"], slots=[s], fill="confident")
+        self.put("export_slopes", s, "s1")
+        self.batch(s, "default")
+        self.push(dict(op="get_layers", slot=s, names=None))
+        # the three lazily kept layers are computed before an import makes the nine dense, and before their images are taken
+        self.batch(s, "s1")
+        self.put("import_layers", s, "s2", names=["m2"], slots=[s])
+        self.push(dict(op="get_layers", slot=s, names=list(LAZY3)))
+        self.batch(s, "s2")
+        self.put("export_images", s, "s1", names=["groundCandidates", "planeDist"], terrain=False)
+        # a cloud call sees the map where the last move left it, position and terrain
+        th = 0.2
+        self.push(dict(op="move_maps", slots=[s], odoms=[[round(self.pos[s][0] + 5 * self.sh["res"], 3), round(self.pos[s][1] - 3 * self.sh["res"], 3)]],
+                       poses=[[0.3, 0.2, 1.5, 0.0, 0.0, float(np.sin(th / 2)), float(np.cos(th / 2))]], stream="s1"))
+        self.put("split_clouds", s, "s2", foreign=False)
+        self.put("rasterize_clouds", s, "default", foreign=True, cloud_kind="scene")
+        self.push(dict(op="set_position", slot=s, pos=[round(self.pos[s][0] + 1.0, 3), round(self.pos[s][1] + 0.7, 3)]))
+        self.put("cluster_clouds", s, "s1", foreign=True, cloud_kind="scene")
+        # a fresh map reads as the constant odom_z, whatever lay there before
+        self.push(dict(op="reset_maps", first=s, n=1, odom_z=self.r(-1.9, -1.5), pos=list(self.pos[s]), persistent=bool(self.seed % 2), stream="s2"))
+        self.put("split_clouds", s, "s1", foreign=True, cloud_kind="scene")
+        self.put("export_images", s, "default", names=["ground"], terrain=True)
+        self.put("visibility_clouds", s, "s2", foreign=True, cloud_kind="scene")
+        # labels that belong to no batch select points outside the map
+        self.put("split_clouds", s, "s1", foreign=True, cloud_kind="outside")
+
+    def run(self):
+        n = len(self.old)
+        ring_at = None
+        for j, op in enumerate(self.old):
+            if j == n - 1:
+                self.tail()
+            elif j >= 2 and not self.guarded(self.old[j - 1]) and not self.guarded(op):
+                self.anchors(j)
+                self.pairs(j)
+                if ring_at is None and j > n // 3 and self.old[j - 1]["op"] == "filter_batch" and self.alive:
+                    ring_at = j
+                    self.ring()
+            self.push(op)
+        return self.out
+
+
+def make_sequence(seed, shape, device_calls=True):
     """The op list of (seed, shape): deterministic, JSON-serialisable.  The first record ("tunings") fixes the launch tunings of the
-    context for the whole sequence."""
-    return _Gen(seed, shape).run()
+    context for the whole sequence.  device_calls=False: without the ops of NEW_KINDS (and the few ops of other kinds that the last
+    scripts put in front of theirs) -- the list as it was before those calls were added, and a subsequence of the full one."""
+    old = _Gen(seed, shape).run()
+    return _Ins(seed, shape, old).run() if device_calls else old
 
 
 def touched(op, n_slots):
@@ -741,7 +1126,7 @@ class Predicates:
       scoring        set_scoring switched it on
       partly-live    since its last cloud a per-call layer was set, or read whole"""
 
-    KEEP_FRESH = {"export_layers", "scores", "set_position", "get_position", "slot_config", "set_slot_configs", "set_scoring", "reset_scores"}
+    KEEP_FRESH = {"export_layers", "scores", "set_position", "get_position", "slot_config", "set_slot_configs", "set_scoring", "reset_scores"} | set(NEW_READERS)
 
     def __init__(self, n_slots):
         self.n = n_slots
@@ -761,7 +1146,7 @@ class Predicates:
             return
         reads3 = (k in ("get_layer", "image_u8", "set_layer") and op["layer"] in LAZY3) or \
                  (k in ("get_layers",) and (op["names"] is None or set(op["names"]) & set(LAZY3))) or \
-                 (k == "export_layers" and set(op["names"]) & set(LAZY3)) or \
+                 (k in ("export_layers", "export_images") and set(op["names"]) & set(LAZY3)) or \
                  (k == "gridmap_message" and (op["layers"] is None or set(op["layers"]) & set(LAZY3))) or \
                  (k == "filter_layers")
         for i, s in enumerate(touched(op, self.n)):
@@ -777,6 +1162,12 @@ class Predicates:
                 st["fresh"][s] = st["no-confidence"][s] = True
                 if not op.get("persistent", False):
                     st["lazy-owed"][s] = st["partly-live"][s] = False
+                continue
+            if k == "import_layers":   # (the header's import paragraph: what gg_set_layer of every named layer would leave)
+                if set(op["names"]) & {"ground", "groundpatch"}:
+                    st["fresh"][s] = st["no-confidence"][s] = False
+                if set(op["names"]) & set(PER_CALL):
+                    st["lazy-owed"][s], st["partly-live"][s] = False, True
                 continue
             if k not in self.KEEP_FRESH:
                 st["fresh"][s] = False
@@ -818,7 +1209,18 @@ MUTANTS = [
     "nonscoring_slot_feeds_counters",
     "eigen_convention_not_applied_to_stage",
     "position_not_updated_for_next_batch",
+    # -- the many-map calls (one slip per promise of their header paragraphs)
+    "import_leaves_fresh_map_fresh",            # ground / groundpatch imported into a fresh map: it goes on reading as the reset's constants
+    "import_groundpatch_keeps_no_confidence",   # ... the next cloud still skips the outlier walk
+    "import_drops_lazy_layers",                 # an import of a per-call layer marks all nine dense without computing the three owed ones first
+    "import_slots_as_first_plus_i",
+    "cloud_reader_position_before_last_move",   # a cloud call computes cells under the position from before the last set_position / move
+    "cloud_reader_ground_before_last_scroll",   # ... reads `ground` as it stood before the last move scrolled it
+    "fresh_map_read_as_before_reset",           # a reader of a fresh map gets the terrain from before the reset, not the constant odom_z
+    "images_read_lazy_layer_uncomputed",        # export_images of one of the three lazily kept layers while it is owed: the stale plane
+    "foreign_point_outside_gets_finite_height",  # a selected point outside the map (labels that belong to no batch): 0.0 instead of the quiet NaN
 ]
+LAZY_MUTANTS = {"import_drops_lazy_layers", "images_read_lazy_layer_uncomputed"}   # (they need what the three layers held before the cloud)
 
 
 class _Slot:
@@ -835,6 +1237,9 @@ class _Slot:
         self.stale_gp = None      # (mutant) (ground, groundpatch) from before a reset the library "forgot"
         self.unconfident = False  # (mutant) the library believes no cell is confident
         self.stale_pos = None     # (mutant) the position from before move_maps
+        self.prev_pos = None      # (mutant) the position from before the last set_position / move
+        self.prev_ground = None   # (mutant) `ground` from before the last move's scroll, while nothing has written the layer since
+        self.stale_ground = None  # (mutant) `ground` from before the last reset_maps
 
 
 class ContextModel:
@@ -849,6 +1254,9 @@ class ContextModel:
         self.ids = None
         self.flags = dict(minimal=False, eager=False, halves=False)
         self._clouds = {}
+        self.pred = Predicates(self.n)   # (mutants: which slots are fresh as the header has it)
+        self.batches = {}                # op index of a filter_batch -> per row (map-frame cloud, label bytes), until the next checkpoint
+        self.at = -1                     # index of the op being applied
 
     # -- helpers
     def cloud(self, spec):
@@ -873,13 +1281,14 @@ class ContextModel:
     def _filter(self, s, cloud, origin, base_z, lazy, scoring_launch=False):
         sl = self.slots[s]
         m = self.mutant
-        if m and m.startswith("lazy_layers_stale"):
+        if m and (m.startswith("lazy_layers_stale") or m in LAZY_MUTANTS):
             sl.prev3 = {k: sl.ref.layer(k).copy() for k in LAZY3} if lazy else None
         sl.lazy = lazy
         cfg = self.config_of(s)
-        if m == "outlier_walk_skipped_after_set_groundpatch" and sl.unconfident:
+        if m in ("outlier_walk_skipped_after_set_groundpatch", "import_groundpatch_keeps_no_confidence") and sl.unconfident:
             cfg.min_outlier_detection_ground_confidence = 1e30
         sl.unconfident = False
+        sl.prev_ground = None
         pos = None
         if sl.stale_pos is not None:
             pos = tuple(sl.ref._m.contents.position)
@@ -932,6 +1341,7 @@ class ContextModel:
             sl.ref.reset_state(pos=(float(pos[0]), float(pos[1])), odom_z=float(np.float32(odom_z)))
             sl.last, sl.lazy = None, False
         sl.unconfident = True
+        sl.prev_pos = sl.prev_ground = None
         if m == "counters_zeroed_by_reset":
             sl.counts[...] = 0
             sl.clouds = 0
@@ -942,7 +1352,12 @@ class ContextModel:
         sl, m = self.slots[s], self.mutant
         keep = {k: sl.ref.layer(k).copy() for k in PER_CALL}
         before = tuple(sl.ref._m.contents.position)
+        if m == "cloud_reader_ground_before_last_scroll":
+            sl.prev_ground = sl.ref.layer("ground").copy()
         moved, shift = sl.ref.update(float(odom[0]), float(odom[1]), pose, "kdl")
+        if shift == (0, 0):
+            sl.prev_ground = None
+        sl.prev_pos = before
         for k in PER_CALL:
             sl.ref.set_layer(k, keep[k])
         if m == "counters_zeroed_by_move" and shift != (0, 0):
@@ -966,21 +1381,29 @@ class ContextModel:
         return out
 
     # -- ops
-    def apply(self, op):
-        """what the library must return for `op` (None: nothing to compare)"""
+    def apply(self, op, index=None):
+        """what the library must return for `op` (None: nothing to compare); `index`: where the op stands in its list (default: one
+        behind the op applied last) -- a cloud op in chained mode names its batch by that"""
         k = op["op"]
         m = self.mutant
+        self.at = self.at + 1 if index is None else index
+        if k == "checkpoint":
+            self.batches.clear()   # (the driver lets go of the batches' device buffers there)
         if k in ("tunings", "synchronize", "batch_fence", "checkpoint"):
             return None
-        return getattr(self, "do_" + k)(op, m)
+        res = getattr(self, "do_" + k)(op, m)
+        self.pred.apply(op)
+        return res
 
     def run(self, ops):
-        return [self.apply(op) for op in ops]
+        return [self.apply(op, i) for i, op in enumerate(ops)]
 
     def do_reset_maps(self, op, m):
         for s in range(op["first"], op["first"] + op["n"]):
             sl = self.slots[s]
             old = (sl.ref.layer("ground").copy(), sl.ref.layer("groundpatch").copy()) if m == "fresh_reset_ignored_before_small_batch" else None
+            if m == "fresh_map_read_as_before_reset":
+                sl.stale_ground = sl.ref.layer("ground").copy()
             self._reset(s, op["pos"], op["odom_z"], op["persistent"])
             sl.stale_gp = old
             if m == "own_config_lost_by_reset_maps":
@@ -1012,6 +1435,7 @@ class ContextModel:
 
     def do_set_position(self, op, m):
         p = self.slots[op["slot"]].ref._m.contents.position
+        self.slots[op["slot"]].prev_pos = (p[0], p[1])
         p[0], p[1] = float(op["pos"][0]), float(op["pos"][1])
 
     def do_set_layer(self, op, m):
@@ -1025,6 +1449,8 @@ class ContextModel:
             sl.lazy = False
         if op["layer"] == "groundpatch" and m != "outlier_walk_skipped_after_set_groundpatch":
             sl.unconfident = False
+        if op["layer"] == "ground":
+            sl.prev_ground = None
         sl.ref.set_layer(op["layer"], make_layer(op["fill"], op["layer"], self.rows))
 
     def do_filter_batch(self, op, m):
@@ -1034,6 +1460,7 @@ class ContextModel:
         lazy = not self.flags["eager"]
         launch_scores = any(self.slots[s].scoring for s in slots)
         res = {k: [] for k in op["outputs"]}
+        rows = self.batches[self.at] = []
         for b, s in enumerate(slots):
             sl = self.slots[s]
             if sl.stale_gp is not None and len(slots) <= 16:
@@ -1041,7 +1468,9 @@ class ContextModel:
                 sl.ref.set_layer("groundpatch", sl.stale_gp[1])
             sl.stale_gp = None
             item = dict(cloud=op["clouds"][b], tf=op["tfs"][b] if op["tfs"] else None)
-            r = self._filter(s, self.map_cloud(item), op["origins"][b], op["base_z"][b], lazy, launch_scores)
+            in_map = self.map_cloud(item)
+            r = self._filter(s, in_map, op["origins"][b], op["base_z"][b], lazy, launch_scores)
+            rows.append((in_map, r["label"].copy()))
             emitted = r["index"] >= 0
             k = len(r["out_points"])
             for name in op["outputs"]:
@@ -1104,6 +1533,7 @@ class ContextModel:
         s = op["slot"]
         sl = self.slots[s]
         self._touch(s)
+        sl.prev_ground = None
         sl.ref.cfg = self.config_of(s)
         oracle.set_eigen_reduction(0 if m == "eigen_convention_not_applied_to_stage" else self.eigen)
         try:
@@ -1236,6 +1666,211 @@ class ContextModel:
         return {"message": _gridmap_bytes(ref.rows, ref.cols, ref.resolution, ref.length, pos, [(k, ref.layer(k)) for k in names], tuple(op["stamp"]),
                                           seq=op["seq"])}
 
+    # -- the many-map calls (include/groundgrid_hip.h: gg_import_layers, gg_export_images, gg_export_slopes, gg_split_clouds, ...)
+    def do_import_layers(self, op, m):
+        """what gg_set_layer of every named layer of every listed map would leave"""
+        slots = list(op["slots"])
+        if m == "import_slots_as_first_plus_i":
+            slots = list(range(len(slots)))
+        names = list(op["names"])
+        for i, s in enumerate(slots):
+            sl = self.slots[s]
+            self._touch(s)
+            skip = set()
+            if m == "import_leaves_fresh_map_fresh" and self.pred.state["fresh"][s]:
+                skip = {"ground", "groundpatch"}
+            if m == "import_drops_lazy_layers" and sl.lazy and sl.prev3 and set(names) & set(PER_CALL):
+                for k in LAZY3:
+                    sl.ref.set_layer(k, sl.prev3[k])
+            if set(names) & set(PER_CALL):
+                sl.lazy = False
+            if "groundpatch" in names and m != "import_groundpatch_keeps_no_confidence":
+                sl.unconfident = False
+            if "ground" in names:
+                sl.prev_ground = None
+            for k in names:
+                if k not in skip:
+                    sl.ref.set_layer(k, make_layer(op["fills"][i], k, self.rows))
+        return {"fresh maps as the header says": 1}
+
+    @contextlib.contextmanager
+    def _as_read(self, s, cloud_reader):
+        """(mutants) the slot as a wrong library would see it while a reader runs: put back afterwards"""
+        sl, m = self.slots[s], self.mutant
+        p = sl.ref._m.contents.position
+        pos = ground = None
+        if cloud_reader and m == "cloud_reader_position_before_last_move" and sl.prev_pos is not None:
+            pos, (p[0], p[1]) = (p[0], p[1]), sl.prev_pos
+        stale = None
+        if cloud_reader and m == "cloud_reader_ground_before_last_scroll" and sl.prev_ground is not None:
+            stale = sl.prev_ground
+        if m == "fresh_map_read_as_before_reset" and sl.stale_ground is not None and self.pred.state["fresh"][s]:
+            stale = sl.stale_ground
+        if stale is not None:
+            ground = sl.ref.layer("ground").copy()
+            sl.ref.set_layer("ground", stale)
+        try:
+            yield sl.ref
+        finally:
+            if pos is not None:
+                p[0], p[1] = pos
+            if ground is not None:
+                sl.ref.set_layer("ground", ground)
+
+    def do_export_images(self, op, m):
+        out = {"fresh maps kept": 1, "nothing else written": 1}
+        for i, s in enumerate(op["slots"]):
+            sl = self.slots[s]
+            with self._as_read(s, False) as ref:
+                for k in op["names"]:
+                    L = ref.layer(k)
+                    if m == "images_read_lazy_layer_uncomputed" and sl.lazy and sl.prev3 and k in LAZY3:
+                        L = sl.prev3[k]
+                    if np.isfinite(L).any():
+                        img, lo, hi = image_u8_reference(L)
+                    else:
+                        img, lo, hi = np.zeros(L.shape, np.uint8), np.float32(np.inf), np.float32(-np.inf)
+                    out[f"map {i} (slot {s}) image {k}"] = np.ascontiguousarray(img)
+                    if op["bounds"]:
+                        out[f"map {i} (slot {s}) bounds {k}"] = np.array([lo, hi], dtype=np.float32)
+                if op["terrain"]:
+                    for key, v in terrain_reference(ref.layer("ground"), ref.layer("pointsRaw")).items():
+                        out[f"map {i} (slot {s}) terrain {key}"] = v
+            if set(op["names"]) & set(LAZY3):
+                sl.lazy = False
+        return out
+
+    def do_export_slopes(self, op, m):
+        out = {"fresh maps kept": 1, "lazy maps kept": 1, "nothing else written": 1}
+        for i, s in enumerate(op["slots"]):
+            with self._as_read(s, False) as ref:
+                planes = _memo(("slopes", _digest(ref.layer("ground")), _digest(ref.layer("groundpatch")), self.shape),
+                               lambda: slopes_ref.slopes_reference(ref.layer("ground"), ref.layer("groundpatch"), np.float32(self.sh["res"])))
+            for k in op["channels"]:
+                out[f"map {i} (slot {s}) {k}"] = planes[SLOPE_CHANNELS.index(k)]
+        return out
+
+    def _labelled(self, op):
+        """per listed cloud (slot, the points in the map frame, one label byte per point), or None: a chained op whose batch is not there
+        (a list with ops deleted)"""
+        src = op["source"]
+        if src["mode"] == "chained":
+            rows = self.batches.get(src["batch"])
+            if rows is None or len(rows) < src["row0"] + len(op["slots"]):
+                return None
+            return [(s,) + rows[src["row0"] + i] for i, s in enumerate(op["slots"])]
+        out = []
+        for i, s in enumerate(op["slots"]):
+            c = self.map_cloud(dict(cloud=src["clouds"][i], tf=src["tfs"][i] if src["tfs"] else None))
+            out.append((s, c, foreign_labels(src["labels"], i, len(c))))
+        return out
+
+    def _cloud_call(self, op, m, expect):
+        clouds = self._labelled(op)
+        if clouds is None:
+            return {"undefined": 1}
+        out = {"fresh maps kept": 1, "lazy maps kept": 1, "nothing else written": 1}
+        params = json.dumps({k: v for k, v in op.items() if k not in ("slots", "source", "stream", "origins")}, sort_keys=True)
+        for i, (s, cloud, labels) in enumerate(clouds):
+            with self._as_read(s, True) as ref:
+                key = (params, json.dumps(op["origins"][i]) if "origins" in op else "", self.shape, tuple(ref._m.contents.position),
+                       _digest(ref.layer("ground")), _digest(cloud), _digest(labels))
+                res = _memo(key, lambda: expect(i, ref, cloud, labels))
+            if m == "foreign_point_outside_gets_finite_height" and op["source"]["mode"] == "foreign":
+                res = {k: (np.where(np.isnan(v), np.float32(0.0), v) if k.endswith("height") else v) for k, v in res.items()}
+            for k, v in res.items():
+                out[f"cloud {i} (slot {s}) {k}"] = v
+        return out
+
+    def do_split_clouds(self, op, m):
+        def expect(i, ref, cloud, labels):
+            res = {}
+            sets = cloud_refs.expected_sets(ref, cloud, labels)
+            for name in cloud_refs.SETS:
+                idx, recs, h = sets[name]
+                res[f"{name} count"] = np.int32(len(idx))
+                for field in op["want"].get(name, []):
+                    res[f"{name} {field}"] = {"points": np.frombuffer(recs.tobytes(), dtype=np.uint32).reshape(-1, 4), "height": h, "source": idx}[field]
+            return res
+
+        return self._cloud_call(op, m, expect)
+
+    def do_rasterize_clouds(self, op, m):
+        def expect(i, ref, cloud, labels):
+            planes = cloud_refs.expected_planes(ref, cloud, labels)
+            return {k: planes[RASTER_CHANNELS.index(k)] for k in op["channels"]}
+
+        return self._cloud_call(op, m, expect)
+
+    @staticmethod
+    def _band(op):
+        return (-np.inf if op["min_height"] is None else op["min_height"]), (np.inf if op["max_height"] is None else op["max_height"])
+
+    def do_cluster_clouds(self, op, m):
+        def expect(i, ref, cloud, labels):
+            lo, hi = self._band(op)
+            plane, K, table, ids = cloud_refs.expected_clusters(ref, cloud, labels, op["min_points"], lo, hi, op["connectivity"],
+                                                                "row" if op["row_major"] else "col")
+            res = {"cell ids": plane, "clusters": np.int32(K)}
+            if op["max_clusters"]:
+                res["table"] = table[: min(K, op["max_clusters"])]
+            if op["point_clusters"]:
+                res["point ids"] = ids
+            return res
+
+        return self._cloud_call(op, m, expect)
+
+    def do_clearance_clouds(self, op, m):
+        def expect(i, ref, cloud, labels):
+            lo, hi = self._band(op)
+            occupied = cloud_refs.occupied_cells(ref, cloud, labels, op["min_points"], lo, hi)
+            if op["nearest"]:
+                dist2, nearest, distance, count = clearance_ref.expected_clearance(occupied, op["max_cells"], "row" if op["row_major"] else "col", self.sh["res"])
+            else:
+                dist2, distance, count = cloud_refs.expected_clearance_fast(occupied, op["max_cells"], self.sh["res"])
+            res = {"dist2": dist2, "occupied cells": np.int32(count)}
+            if op["nearest"]:
+                res["nearest"] = nearest
+            if op["distance"]:
+                res["distance bits"] = distance
+            return res
+
+        return self._cloud_call(op, m, expect)
+
+    def do_visibility_clouds(self, op, m):
+        def expect(i, ref, cloud, labels):
+            lo, hi = self._band(op)
+            state, counts = cloud_refs.expected_visibility(ref, cloud, labels, op["origins"][i][:2], op["min_points"], lo, hi, op["max_cells"], "row")
+            res = {"state": state}
+            if op["counts"]:
+                res["counts"] = counts
+            return res
+
+        return self._cloud_call(op, m, expect)
+
+
+_MEMO = {}
+
+
+def _digest(a):
+    return hashlib.blake2b(np.ascontiguousarray(a).tobytes(), digest_size=16).digest()
+
+
+def _memo(key, compute):
+    """the expectation of a reader is a pure function of the planes, the position, the points, the labels and the op's data: the tests run
+    the model many times (once per mutant) over mostly the same states"""
+    if key not in _MEMO:
+        if len(_MEMO) > 4000:
+            _MEMO.clear()
+        _MEMO[key] = compute()
+    return _MEMO[key]
+
+
+def foreign_labels(spec, i, n):
+    """the label bytes of cloud i of a foreign source: {"seed"}; ground, non-ground and bytes that select nothing"""
+    rng = np.random.default_rng([int(spec["seed"]), i, 79])
+    return rng.choice(np.array([49, 99, 99, 49, 0, 7, 98, 255], dtype=np.uint8), n)
+
 
 # ---------------------------------------------------------------------------------------------------------------- the driver
 
@@ -1282,6 +1917,8 @@ class Driver:
         self.keep = []             # device tensors that must outlive the enqueued work
         self._clouds = {}
         self.planes = {}
+        self.batches = {}          # op index of a filter_batch -> its device buffers, until the next checkpoint (chained cloud calls)
+        self.at = -1
 
     def cloud(self, spec):
         return cached_cloud(spec, self.shape)
@@ -1313,6 +1950,7 @@ class Driver:
         from groundgrid_amd import api
 
         for i, op in enumerate(ops):
+            self.at = i
             try:
                 got = getattr(self, "do_" + op["op"])(op)
             except api.GroundGridError as e:
@@ -1341,6 +1979,7 @@ class Driver:
         self.check_device()
         self.flush(force=True)
         self.keep.clear()
+        self.batches.clear()
 
     def do_synchronize(self, op):
         self.seg.synchronize()
@@ -1415,6 +2054,7 @@ class Driver:
             self.used.add(op["stream"])
         self.keep.append((staged, pts, out))
         n = [len(c) for c in clouds]
+        self.batches[self.at] = (pts, out, n, tfs)
 
         def collect():
             res = {}
@@ -1601,6 +2241,388 @@ class Driver:
 
     def do_gridmap_message(self, op):
         return {"message": self.seg.map(op["slot"]).gridmap_message(layers=op["layers"], seq=op["seq"], stamp=tuple(op["stamp"]))}
+
+    # -- the many-map calls: sentinel-filled destinations with SLACK words behind them, everything compared on bits at the next checkpoint
+    SLACK = 5
+
+    def _stream_arg(self, name):
+        return self.seg._stream_arg(name != "ctx", handle=self.handle(name))
+
+    def _dev(self):
+        return self.torch.device("cuda", self.seg.device)
+
+    def _words(self, count):
+        return self.torch.full((count + self.SLACK,), SENTINEL, dtype=self.torch.int32, device=self._dev())
+
+    def _upload(self, host):
+        staged = self.torch.from_numpy(np.ascontiguousarray(host)).pin_memory()   # (pinned: enqueued, the host does not wait)
+        dev = staged.to(self._dev(), non_blocking=True)
+        self.keep.append((staged, dev))
+        return dev
+
+    def _marks(self):
+        return self.fresh_count(), self.seg.debug_set_tuning("lazy_count", 0)
+
+    def _enqueue(self, op, call):
+        """the C call on the op's stream; returns what the host-side marks did: (fresh maps before, after, lazy maps before, after)"""
+        from groundgrid_amd import api
+
+        if op["stream"] == "ctx":   # the context's own stream is no torch stream: the inputs and the fills have to be there first
+            self.torch.cuda.current_stream(self.seg.device).synchronize()
+        else:
+            self.used.add(op["stream"])
+        before = self._marks()
+        api._check(self.seg._L, self.seg._ctx, call(self._stream_arg(op["stream"])), "gg_" + op["op"])
+        after = self._marks()
+        return before[0], after[0], before[1], after[1]
+
+    def _planes(self, a, n, K, stride, row_major):
+        """the n * K planes of a downloaded destination as [rows, cols] arrays, and whether every other word still holds the sentinel"""
+        rows, cols = self.seg.rows, self.seg.cols
+        cells = rows * cols
+        body = a[: n * K * stride].reshape(n * K, stride)
+        clean = bool(np.all(body[:, cells:].view(np.uint32) == SENTINEL) and np.all(a[n * K * stride:].view(np.uint32) == SENTINEL))
+        planes = [p[:cells].reshape(rows, cols) if row_major else p[:cells].reshape((rows, cols), order="F") for p in body]
+        return planes, clean
+
+    def do_import_layers(self, op):
+        torch, rows, cols = self.torch, self.seg.rows, self.seg.cols
+        n, K, stride = len(op["slots"]), len(op["names"]), rows * cols + int(op["pad"])
+        host = np.full(n * K * stride + self.SLACK, SENTINEL, dtype=np.uint32).view(np.float32)
+        for i in range(n):
+            for k, name in enumerate(op["names"]):
+                plane = make_layer(op["fills"][i], name, rows)
+                host[(i * K + k) * stride: (i * K + k) * stride + rows * cols] = plane.ravel(order="C" if op["row_major"] else "F")
+        own = op["stream"] == "ctx"
+        with self.on(op["stream"]):
+            src = self._upload(host)
+            if own:
+                torch.cuda.current_stream(self.seg.device).synchronize()
+            else:
+                self.used.add(op["stream"])
+            f0 = self.fresh_count()
+            self.seg.import_layers(src[: n * K * stride], op["names"], slots=op["slots"], row_major=op["row_major"], stream=self.handle(op["stream"]),
+                                   own_stream=own, plane_stride=stride)
+            f1 = self.fresh_count()
+        # (a fresh map whose mask names neither ground nor groundpatch, and every map that is not listed, stays fresh)
+        return {"fresh maps as the header says": int(f1 == f0 if not set(op["names"]) & {"ground", "groundpatch"} else f0 - n <= f1 <= f0)}
+
+    def do_export_slopes(self, op):
+        rows, cols = self.seg.rows, self.seg.cols
+        n, K, stride = len(op["slots"]), len(op["channels"]), rows * cols + int(op["pad"])
+        own = op["stream"] == "ctx"
+        with self.on(op["stream"]):
+            dst = self._words(n * K * stride)
+            if own:
+                self.torch.cuda.current_stream(self.seg.device).synchronize()
+            else:
+                self.used.add(op["stream"])
+            before = self._marks()
+            self.seg.export_slopes(op["channels"], slots=op["slots"], out=dst[: n * K * stride].view(self.torch.float32), row_major=op["row_major"],
+                                   stream=self.handle(op["stream"]), own_stream=own, plane_stride=stride)
+            after = self._marks()
+        self.keep.append(dst)
+
+        def collect():
+            planes, clean = self._planes(dst.cpu().numpy(), n, K, stride, op["row_major"])
+            res = {"fresh maps kept": int(before[0] == after[0]), "lazy maps kept": int(before[1] == after[1]), "nothing else written": int(clean)}
+            for i, s in enumerate(op["slots"]):
+                for k, name in enumerate(op["channels"]):
+                    res[f"map {i} (slot {s}) {name}"] = planes[i * K + k].view(np.float32)
+            return res
+
+        return collect
+
+    def do_export_images(self, op):
+        import ctypes as C
+
+        from groundgrid_amd import _lib
+
+        torch, rows, cols = self.torch, self.seg.rows, self.seg.cols
+        cells, n, K, pad = rows * cols, len(op["slots"]), len(op["names"]), int(op["pad"])
+        with self.on(op["stream"]):
+            images = torch.full((n * K * (cells + pad) + self.SLACK,), 0xA5, dtype=torch.uint8, device=self._dev()) if K else None
+            bounds = self._words(n * K * 2) if K and op["bounds"] else None
+            terrain = self._words(n * (3 * cells + pad)) if op["terrain"] else None
+            x = _lib.GGImageExport()
+            sl = (C.c_int32 * n)(*op["slots"])
+            x.n, x.first_slot, x.slots = n, 0, sl
+            x.layer_mask = sum(1 << LAYERS.index(k) for k in op["names"])
+            x.d_images, x.image_stride = (images.data_ptr() if K else None), cells + pad
+            x.d_bounds = bounds.data_ptr() if bounds is not None else None
+            x.d_terrain, x.terrain_stride = (terrain.data_ptr() if op["terrain"] else None), 3 * cells + pad
+            x.terrain_layout = _lib.GG_TERRAIN_CHW if op["chw"] else _lib.GG_TERRAIN_HWC
+            marks = self._enqueue(op, lambda st: self.seg._L.gg_export_images(self.seg._ctx, C.byref(x), st))
+        self.keep.append((images, bounds, terrain))
+
+        def collect():
+            res = {"fresh maps kept": int(marks[0] == marks[1])}
+            clean = True
+            if K:
+                a = images.cpu().numpy()
+                body = a[: n * K * (cells + pad)].reshape(n * K, cells + pad)
+                clean &= bool(np.all(body[:, cells:] == 0xA5) and np.all(a[n * K * (cells + pad):] == 0xA5))
+                if bounds is not None:
+                    b = bounds.cpu().numpy()
+                    clean &= bool(np.all(b[n * K * 2:].view(np.uint32) == SENTINEL))
+            if op["terrain"]:
+                t = terrain.cpu().numpy()
+                tb = t[: n * (3 * cells + pad)].reshape(n, 3 * cells + pad)
+                clean &= bool(np.all(tb[:, 3 * cells:].view(np.uint32) == SENTINEL) and np.all(t[n * (3 * cells + pad):].view(np.uint32) == SENTINEL))
+            for i, s in enumerate(op["slots"]):
+                for k, name in enumerate(op["names"]):
+                    res[f"map {i} (slot {s}) image {name}"] = body[i * K + k, :cells].reshape(rows, cols)
+                    if bounds is not None:
+                        res[f"map {i} (slot {s}) bounds {name}"] = b[(i * K + k) * 2: (i * K + k) * 2 + 2].view(np.float32)
+                if op["terrain"]:
+                    img = tb[i, : 3 * cells].view(np.float32)
+                    ch = img.reshape(3, rows, cols) if op["chw"] else np.moveaxis(img.reshape(rows, cols, 3), 2, 0)
+                    res[f"map {i} (slot {s}) terrain ground"], res[f"map {i} (slot {s}) terrain raw"] = ch[0], ch[2]
+                    res[f"map {i} (slot {s}) terrain visited"] = ch[1][1:-1, 1:-1]
+            res["nothing else written"] = int(clean)
+            return res
+
+        return collect
+
+    def _cloud_source(self, op, x):
+        """the ten leading members of a gg_cloud_* structure `x`; returns (n_points per cloud, cloud_stride, what has to stay referenced
+        until the C call has returned)"""
+        import ctypes as C
+
+        from groundgrid_amd import _lib, api
+
+        src, n = op["source"], len(op["slots"])
+        if src["mode"] == "chained":   # the batch's own device buffers, wherever that batch stands in its stream
+            pts, out, n_pts, tfs = self.batches[src["batch"]]
+            rec, stride, row0 = int(pts.shape[2]), int(pts.shape[1]), src["row0"]
+            d_points = pts.data_ptr() + row0 * stride * rec
+            n_pts = n_pts[row0: row0 + n]
+            tfs = None if tfs is None else tfs[row0: row0 + n]
+            labels = None if op["masks"] else out.labels.data_ptr() + row0 * stride
+            masks = out.label_masks.data_ptr() + row0 * (stride // 4) if op["masks"] else None
+        else:
+            rec, stride = src["fmt"], src["stride"]
+            clouds = [self.cloud(c) for c in src["clouds"]]
+            n_pts = [len(c) for c in clouds]
+            raw = np.zeros((n, stride, rec), dtype=np.uint8)
+            lab = np.full((n, stride), 99, dtype=np.uint8)   # (behind a cloud's end: non-ground points at the origin, for a kernel that reads too far)
+            for i, c in enumerate(clouds):
+                raw[i, : len(c)] = np.frombuffer((api.pack16(c) if rec == 16 else c).tobytes(), dtype=np.uint8).reshape(-1, rec)
+                lab[i, : len(c)] = foreign_labels(src["labels"], i, len(c))
+            if op["masks"]:
+                code = np.where(lab == 49, 1, np.where(lab == 99, 2, 0)).astype(np.uint8).reshape(n, stride // 4, 4)
+                lab = (code[:, :, 0] | (code[:, :, 1] << 2) | (code[:, :, 2] << 4) | (code[:, :, 3] << 6)).astype(np.uint8)
+            d_points = self._upload(raw).data_ptr()
+            given = self._upload(lab).data_ptr()
+            labels, masks = (None, given) if op["masks"] else (given, None)
+            tfs = None if not src["tfs"] else np.stack([api.transform_from_pose(p, "kdl") for p in src["tfs"]])
+        keep = [(C.c_int32 * n)(*op["slots"]), (C.c_int32 * n)(*[int(v) for v in n_pts])]
+        x.n, x.first_slot, x.slots, x.point_format = n, 0, keep[0], _lib.GG_POINT16 if rec == 16 else _lib.GG_POINT32
+        x.d_points, x.cloud_stride, x.n_points = d_points, stride, keep[1]
+        if tfs is not None:
+            keep.append(np.ascontiguousarray(np.asarray(tfs, dtype=np.float64).reshape(n, 12)))
+            x.transforms = keep[-1].ctypes.data_as(C.POINTER(C.c_double))
+        x.d_labels, x.d_label_masks = labels, masks
+        return n_pts, stride, keep
+
+    @staticmethod
+    def _marks_kept(marks):
+        return {"fresh maps kept": int(marks[0] == marks[1]), "lazy maps kept": int(marks[2] == marks[3])}
+
+    def do_split_clouds(self, op):
+        import ctypes as C
+
+        from groundgrid_amd import _lib
+
+        n = len(op["slots"])
+        words = {"points": 4, "height": 1, "source": 1}
+        with self.on(op["stream"]):
+            x = _lib.GGCloudSplit()
+            n_pts, stride, keep = self._cloud_source(op, x)
+            bufs = {(s, f): self._words(n * stride * words[f]) for s, fields in op["want"].items() for f in fields}
+            counts = self._words(n * 2)
+            for (s, f), t in bufs.items():
+                setattr(getattr(x, s), "d_" + f, t.data_ptr())
+            x.d_counts = counts.data_ptr()
+            marks = self._enqueue(op, lambda st: self.seg._L.gg_split_clouds(self.seg._ctx, C.byref(x), st))
+        self.keep.append((bufs, counts))
+
+        def collect():
+            res = self._marks_kept(marks)
+            c = counts.cpu().numpy()
+            clean = bool(np.all(c[n * 2:] == SENTINEL))
+            host = {key: t.cpu().numpy() for key, t in bufs.items()}
+            for i, s in enumerate(op["slots"]):
+                for col, name in enumerate(("ground", "nonground")):
+                    m = int(c[2 * i + col])
+                    res[f"cloud {i} (slot {s}) {name} count"] = np.int32(m)
+                    m = min(max(m, 0), stride)
+                    for f in op["want"].get(name, []):
+                        w = words[f]
+                        row = host[(name, f)][i * stride * w: (i + 1) * stride * w]
+                        clean &= bool(np.all(row[m * w:] == SENTINEL))
+                        got = row[: m * w]
+                        res[f"cloud {i} (slot {s}) {name} {f}"] = got.view(np.uint32).reshape(-1, 4) if f == "points" else got.view(np.float32) if f == "height" else got
+            for key, a in host.items():
+                clean &= bool(np.all(a[n * stride * words[key[1]]:] == SENTINEL))
+            res["nothing else written"] = int(clean)
+            return res
+
+        return collect
+
+    def do_rasterize_clouds(self, op):
+        import ctypes as C
+
+        from groundgrid_amd import _lib
+
+        n, K, pstride = len(op["slots"]), len(op["channels"]), self.seg.rows * self.seg.cols + int(op["pad"])
+        with self.on(op["stream"]):
+            x = _lib.GGCloudRaster()
+            n_pts, stride, keep = self._cloud_source(op, x)
+            dst = self._words(n * K * pstride)
+            x.channel_mask = sum(1 << RASTER_CHANNELS.index(k) for k in op["channels"])
+            x.order = _lib.GG_PLANES_ROWMAJOR if op["row_major"] else _lib.GG_PLANES_COLMAJOR
+            x.d_dst, x.plane_stride = dst.data_ptr(), pstride
+            marks = self._enqueue(op, lambda st: self.seg._L.gg_rasterize_clouds(self.seg._ctx, C.byref(x), st))
+        self.keep.append(dst)
+
+        def collect():
+            res = self._marks_kept(marks)
+            planes, clean = self._planes(dst.cpu().numpy(), n, K, pstride, op["row_major"])
+            for i, s in enumerate(op["slots"]):
+                for k, name in enumerate(op["channels"]):
+                    res[f"cloud {i} (slot {s}) {name}"] = planes[i * K + k].view(np.uint32)
+            res["nothing else written"] = int(clean)
+            return res
+
+        return collect
+
+    @staticmethod
+    def _set_band(x, op):
+        x.min_points = op["min_points"]
+        x.min_height = -np.inf if op["min_height"] is None else op["min_height"]
+        x.max_height = np.inf if op["max_height"] is None else op["max_height"]
+
+    def do_cluster_clouds(self, op):
+        import ctypes as C
+
+        from groundgrid_amd import _lib
+
+        n, pstride, cap = len(op["slots"]), self.seg.rows * self.seg.cols + int(op["pad"]), op["max_clusters"]
+        with self.on(op["stream"]):
+            x = _lib.GGCloudClusters()
+            n_pts, stride, keep = self._cloud_source(op, x)
+            self._set_band(x, op)
+            planes, count = self._words(n * pstride), self._words(n)
+            table = self._words(n * cap * 8) if cap else None
+            ids = self._words(n * stride) if op["point_clusters"] else None
+            x.connectivity, x.order = op["connectivity"], _lib.GG_PLANES_ROWMAJOR if op["row_major"] else _lib.GG_PLANES_COLMAJOR
+            x.d_cell_cluster, x.plane_stride, x.d_n_clusters = planes.data_ptr(), pstride, count.data_ptr()
+            x.d_point_cluster = ids.data_ptr() if ids is not None else None
+            x.d_clusters, x.max_clusters = (table.data_ptr() if cap else None), cap
+            marks = self._enqueue(op, lambda st: self.seg._L.gg_cluster_clouds(self.seg._ctx, C.byref(x), st))
+        self.keep.append((planes, count, table, ids))
+
+        def collect():
+            res = self._marks_kept(marks)
+            cells, clean = self._planes(planes.cpu().numpy(), n, 1, pstride, op["row_major"])
+            c = count.cpu().numpy()
+            clean &= bool(np.all(c[n:] == SENTINEL))
+            t = table.cpu().numpy() if cap else None
+            p = ids.cpu().numpy() if ids is not None else None
+            for i, s in enumerate(op["slots"]):
+                res[f"cloud {i} (slot {s}) cell ids"] = cells[i]
+                res[f"cloud {i} (slot {s}) clusters"] = np.int32(c[i])
+                if cap:
+                    m = min(max(int(c[i]), 0), cap)
+                    rec = t[i * cap * 8: (i + 1) * cap * 8]
+                    res[f"cloud {i} (slot {s}) table"] = rec[: m * 8].view(np.uint32).reshape(-1, 8)
+                    clean &= bool(np.all(rec[m * 8:] == SENTINEL))
+                if p is not None:
+                    row = p[i * stride: (i + 1) * stride]
+                    res[f"cloud {i} (slot {s}) point ids"] = row[: n_pts[i]]
+                    clean &= bool(np.all(row[n_pts[i]:] == SENTINEL))
+            if cap:
+                clean &= bool(np.all(t[n * cap * 8:] == SENTINEL))
+            if p is not None:
+                clean &= bool(np.all(p[n * stride:] == SENTINEL))
+            res["nothing else written"] = int(clean)
+            return res
+
+        return collect
+
+    def do_clearance_clouds(self, op):
+        import ctypes as C
+
+        from groundgrid_amd import _lib
+
+        n, pstride = len(op["slots"]), self.seg.rows * self.seg.cols + int(op["pad"])
+        with self.on(op["stream"]):
+            x = _lib.GGCloudClearance()
+            n_pts, stride, keep = self._cloud_source(op, x)
+            self._set_band(x, op)
+            dist2, count = self._words(n * pstride), self._words(n)
+            nearest = self._words(n * pstride) if op["nearest"] else None
+            distance = self._words(n * pstride) if op["distance"] else None
+            x.max_cells, x.order = op["max_cells"], _lib.GG_PLANES_ROWMAJOR if op["row_major"] else _lib.GG_PLANES_COLMAJOR
+            x.d_dist2, x.plane_stride, x.d_n_occupied = dist2.data_ptr(), pstride, count.data_ptr()
+            x.d_nearest = nearest.data_ptr() if nearest is not None else None
+            x.d_distance = distance.data_ptr() if distance is not None else None
+            marks = self._enqueue(op, lambda st: self.seg._L.gg_clearance_clouds(self.seg._ctx, C.byref(x), st))
+        self.keep.append((dist2, count, nearest, distance))
+
+        def collect():
+            res = self._marks_kept(marks)
+            c = count.cpu().numpy()
+            clean = bool(np.all(c[n:] == SENTINEL))
+            got = {}
+            for name, t in (("dist2", dist2), ("nearest", nearest), ("distance bits", distance)):
+                if t is not None:
+                    got[name], ok = self._planes(t.cpu().numpy(), n, 1, pstride, op["row_major"])
+                    clean &= ok
+            for i, s in enumerate(op["slots"]):
+                for name, planes in got.items():
+                    res[f"cloud {i} (slot {s}) {name}"] = planes[i].view(np.uint32) if name == "distance bits" else planes[i]
+                res[f"cloud {i} (slot {s}) occupied cells"] = np.int32(c[i])
+            res["nothing else written"] = int(clean)
+            return res
+
+        return collect
+
+    def do_visibility_clouds(self, op):
+        import ctypes as C
+
+        from groundgrid_amd import _lib
+
+        n, pstride = len(op["slots"]), self.seg.rows * self.seg.cols + int(op["pad"])
+        with self.on(op["stream"]):
+            x = _lib.GGCloudVisibility()
+            n_pts, stride, keep = self._cloud_source(op, x)
+            self._set_band(x, op)
+            state = self._words(n * pstride)
+            counts = self._words(n * 3) if op["counts"] else None
+            origins = np.ascontiguousarray(np.asarray(op["origins"], dtype=np.float32).reshape(n, 3))
+            x.origins = origins.ctypes.data_as(C.POINTER(C.c_float))
+            x.max_cells, x.order = op["max_cells"], _lib.GG_PLANES_ROWMAJOR if op["row_major"] else _lib.GG_PLANES_COLMAJOR
+            x.d_state, x.plane_stride = state.data_ptr(), pstride
+            x.d_counts = counts.data_ptr() if counts is not None else None
+            marks = self._enqueue(op, lambda st: self.seg._L.gg_visibility_clouds(self.seg._ctx, C.byref(x), st))
+        self.keep.append((state, counts))
+
+        def collect():
+            res = self._marks_kept(marks)
+            planes, clean = self._planes(state.cpu().numpy(), n, 1, pstride, op["row_major"])
+            c = counts.cpu().numpy() if counts is not None else None
+            for i, s in enumerate(op["slots"]):
+                res[f"cloud {i} (slot {s}) state"] = planes[i]
+                if c is not None:
+                    res[f"cloud {i} (slot {s}) counts"] = c[3 * i: 3 * i + 3]
+            if c is not None:
+                clean &= bool(np.all(c[3 * n:] == SENTINEL))
+            res["nothing else written"] = int(clean)
+            return res
+
+        return collect
 
     def state(self, s, with_scores):
         """what ContextModel.state(s) describes, read through the getters"""

@@ -17,57 +17,19 @@ if ROOT not in sys.path:
 from groundgrid_amd import _lib, api, kitti, synth  # noqa: E402
 from groundgrid_amd._lib import LAYERS  # noqa: E402
 from oracle import oracle  # noqa: E402
+from tests.cloud_refs import QUIET_NAN, expected_planes, floats_of, keys_of  # noqa: E402
 from tests.test_export_layers_gpu import SENTINEL, batch_points, fresh_count, same_bits, stride_of, warm_maps  # noqa: E402
 from tests.test_split_clouds_gpu import GEOMETRY, PARAM_RING, lazy_count, masks_of, points_tensor, transform_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 INVALID, CAPACITY = -1, -5
-QUIET_NAN = 0x7FC00000
 ALL = (1 << _lib.GG_NUM_RASTER_CHANNELS) - 1
 ROW, COL = _lib.GG_PLANES_ROWMAJOR, _lib.GG_PLANES_COLMAJOR
 SIGNED_SENTINEL = SENTINEL - (1 << 32) if SENTINEL >= (1 << 31) else SENTINEL
 
 
 # ---------------------------------------------------------------- helpers
-
-def keys_of(h):
-    """the order-preserving uint32 key of non-NaN float32 values: IEEE totalOrder as unsigned order"""
-    b = np.ascontiguousarray(h, dtype=np.float32).view(np.uint32)
-    return b ^ np.where(b >> 31, np.uint32(0xFFFFFFFF), np.uint32(0x80000000)).astype(np.uint32)
-
-
-def floats_of(keys):
-    return np.where(keys >> 31, keys ^ np.uint32(0x80000000), ~keys).astype(np.uint32)
-
-
-def expected_planes(ref, cloud_map, labels, ground=None):
-    """uint32 [6, rows, cols]: the bits of the six channels of one cloud in GG_RASTER_* order, from the oracle: ref's position and `ground`
-    layer as they stand (or the constant `ground` of a fresh map), cloud_map the points in the map frame, labels one byte per point"""
-    rows, cols = ref.rows, ref.cols
-    layer = ref.layer("ground")
-    out = np.empty((6, rows * cols), dtype=np.uint32)
-    for s, code in enumerate((99, 49)):
-        idx = np.nonzero(labels[: len(cloud_map)] == code)[0]
-        cells, hs = [], []
-        for p in idx:
-            inside, r, c = ref.get_index(float(cloud_map["x"][p]), float(cloud_map["y"][p]))
-            if inside and 0 <= r < rows and 0 <= c < cols:
-                cells.append(r * cols + c)
-                with np.errstate(invalid="ignore", over="ignore"):
-                    hs.append(np.float32(cloud_map["z"][p]) - (layer[r, c] if ground is None else np.float32(ground)))
-        cells, hs = np.array(cells, dtype=np.int64), np.array(hs, dtype=np.float32)
-        count = np.zeros(rows * cols, dtype=np.uint32)
-        np.add.at(count, cells, 1)
-        ok = ~np.isnan(hs)
-        hi, lo = np.zeros(rows * cols, dtype=np.uint32), np.full(rows * cols, 0xFFFFFFFF, dtype=np.uint32)
-        np.maximum.at(hi, cells[ok], keys_of(hs[ok]))
-        np.minimum.at(lo, cells[ok], keys_of(hs[ok]))
-        out[3 * s] = count.astype(np.float32).view(np.uint32)
-        out[3 * s + 1] = np.where(hi == 0, np.uint32(QUIET_NAN), floats_of(hi))
-        out[3 * s + 2] = np.where(lo == 0xFFFFFFFF, np.uint32(QUIET_NAN), floats_of(lo))
-    return out.reshape(6, rows, cols)
-
 
 def channels_of(mask):
     return [ch for ch in range(6) if (mask >> ch) & 1]

@@ -1,9 +1,13 @@
 """The sequence harness of tests/seq_model.py without a GPU: the generator is deterministic, the committed seeds cover what they have to
-cover, few ops are inert, and the model tells every deliberate bookkeeping slip (seq_model.MUTANTS) from the truth.
+cover, few ops are inert, and the model tells every deliberate bookkeeping slip (seq_model.MUTANTS) from the truth.  For the many-map
+device calls (seq_model.NEW_KINDS): the committed seeds keep every op they had before those were inserted, every call occurs in every
+shape, follows and precedes a writer of its map on another stream with no host synchronisation between them, one run of them is longer
+than the ring they share, and every cloud call occurs chained to a batch (also on another stream than the batch) and foreign.
 
 `python -m tests.test_sequences_cpu` prints the coverage table and the mutant table of DESIGN.md.
 """
 import functools
+import hashlib
 import json
 import os
 import sys
@@ -33,7 +37,7 @@ def truth(shape, seed):
     inside = []
     results = []
     for i, op in enumerate(sequence(shape, seed)):
-        results.append(model.apply(op))
+        results.append(model.apply(op, i))
         for s in (sm.touched(op, model.n) if op["op"] in sm.FILTERS else []):
             inside.append((i, int((model.slots[s].last[0] != sm.oracle.OUTSIDE).sum())))
     return results, [model.state(s) for s in range(model.n)], inside
@@ -53,7 +57,9 @@ def distinguishes(shape, seed, mutant=None, drop=None):
     for i, op in enumerate(sequence(shape, seed)):
         if op["op"] == drop:
             continue
-        d = differs(results[i], model.apply(op))
+        if drop == "filter_batch" and op.get("source", {}).get("mode") == "chained":
+            continue   # (a cloud call on the buffers of a batch that is gone: nothing to say about it)
+        d = differs(results[i], model.apply(op, i))
         if d:
             return f"op {i} ({op['op']}): {d}"
     for s in range(model.n):
@@ -155,6 +161,114 @@ def test_every_gpu_sequence_has_device_ops_in_a_row_on_two_streams():
         assert best >= 3, (shape, seed, best)
 
 
+# ---------------------------------------------------------------------------------------------------------------- the many-map device calls
+
+# length and sha256 (first 32 hex digits, of json.dumps(ops, sort_keys=True)) of every committed list as it was before the ops of
+# sm.NEW_KINDS were inserted
+BEFORE_THE_DEVICE_CALLS = {
+    ("latency", 0): (132, "969a6780750e76b3576de63fdf7a51c3"),
+    ("latency", 1): (134, "fb94a7f1493e139c4348704e93e630ae"),
+    ("fleet", 0): (272, "d6ca014acda7a922a93bd2de08f91c41"),
+    ("fleet", 1): (261, "6cac62b3a85789751fb477ec3701776a"),
+    ("server", 0): (131, "b9ea3904a2ffdd3e4c33be63d35b75c9"),
+    ("server", 1): (132, "72074d3428f0b1a7e553aa8666d13c11"),
+}
+
+
+def test_the_committed_seeds_keep_every_op_they_had():
+    """make_sequence(.., device_calls=False) is the list from before the device calls were added, dict for dict, and a subsequence of the
+    full list: the same dicts in the same order"""
+    for shape, seed in CASES:
+        old = sm.make_sequence(seed, shape, device_calls=False)
+        assert (len(old), hashlib.sha256(json.dumps(old, sort_keys=True).encode()).hexdigest()[:32]) == BEFORE_THE_DEVICE_CALLS[(shape, seed)], (shape, seed)
+        assert not any(op["op"] in sm.NEW_KINDS for op in old)
+        rest = iter(sequence(shape, seed))
+        for i, op in enumerate(old):
+            assert any(op == other for other in rest), (shape, seed, i, "is missing from the full list, or out of order")
+
+
+def test_every_device_call_occurs_in_every_shape():
+    for shape in sm.SHAPES:
+        seen = {op["op"] for seed in SEEDS[shape] for op in sequence(shape, seed)}
+        assert set(sm.NEW_KINDS) <= seen, (shape, set(sm.NEW_KINDS) - seen)
+
+
+def ordered_pairs(ops):
+    """{(kind of the earlier op, kind of the later op)} over the pairs of device ops that name a common map, run on two different streams
+    and have no host-synchronising op between them (in the style of consecutive_device_ops of tests/test_sequences_gpu.py)"""
+    pairs, run = set(), []
+    for op in ops:
+        if op["op"] not in sm.DEVICE_KINDS:
+            run = []
+            continue
+        if "stream" in op and op["op"] != "batch_fence":
+            slots = set(sm.touched(op, 0))   # (every device op with a stream names its maps)
+            for kind, stream, other in run:
+                if stream != op["stream"] and slots & other:
+                    pairs.add((kind, op["op"]))
+            run.append((op["op"], op["stream"], slots))
+    return pairs
+
+
+@functools.lru_cache(maxsize=None)
+def all_ordered_pairs():
+    return frozenset(p for shape, seed in CASES for p in ordered_pairs(sequence(shape, seed)))
+
+
+@pytest.mark.parametrize("reader", sm.NEW_READERS)
+def test_every_reader_follows_and_precedes_a_writer_of_its_map_on_another_stream(reader):
+    pairs = all_ordered_pairs()
+    assert any((w, reader) in pairs for w in sm.MUTATING_DEVICE_KINDS), f"no read after write for {reader}"
+    assert any((reader, w) in pairs for w in sm.MUTATING_DEVICE_KINDS), f"no write after read for {reader}"
+
+
+def test_the_import_follows_and_precedes_batches_and_exports_of_its_map_on_another_stream():
+    pairs = all_ordered_pairs()
+    for other in ("filter_batch", "export_layers"):
+        assert (other, "import_layers") in pairs and ("import_layers", other) in pairs, other
+
+
+def longest_run_of_device_calls(ops):
+    """the longest run of ops of sm.NEW_KINDS with nothing between them: (length, kinds, streams)"""
+    best, run = (0, set(), set()), []
+    for op in ops + [{"op": "checkpoint"}]:
+        if op["op"] in sm.NEW_KINDS:
+            run.append(op)
+            continue
+        if len(run) > best[0]:
+            best = (len(run), {o["op"] for o in run}, {o["stream"] for o in run})
+        run = []
+    return best
+
+
+def test_one_run_of_device_calls_takes_every_entry_of_the_shared_ring_again():
+    runs = [longest_run_of_device_calls(sequence(shape, seed)) for shape, seed in CASES]
+    assert any(n > sm.PARAM_RING and len(kinds) >= 3 and len(streams) >= 2 for n, kinds, streams in runs), runs
+
+
+@pytest.mark.parametrize("kind", sm.CLOUD_KINDS)
+def test_every_cloud_call_occurs_chained_and_foreign(kind):
+    modes, across = set(), 0
+    for shape, seed in CASES:
+        ops = sequence(shape, seed)
+        for at, op in enumerate(ops):
+            if op["op"] == kind:
+                src = op["source"]
+                modes.add(src["mode"])
+                if src["mode"] == "chained":
+                    batch = ops[src["batch"]]
+                    assert batch["op"] == "filter_batch" and batch["slots"][src["row0"]: src["row0"] + len(op["slots"])] == op["slots"]
+                    assert ("masks" if op["masks"] else "labels") in batch["outputs"]
+                    assert not any(o["op"] == "checkpoint" for o in ops[src["batch"]: at]), "the batch's buffers are gone"
+                    across += batch["stream"] != op["stream"]
+                else:   # the header's preconditions
+                    assert len(set(op["slots"])) == len(op["slots"]) == len(src["clouds"])
+                    assert all((0 if c["kind"] == "empty" else c["n"]) <= src["stride"] <= sm.SHAPES[shape]["stride"] for c in src["clouds"])
+                    assert not op["masks"] or src["stride"] % 4 == 0
+    assert modes == {"chained", "foreign"}, (kind, modes)
+    assert across >= 1, f"{kind} never reads the labels of a batch on another stream"
+
+
 # ---------------------------------------------------------------------------------------------------------------- inertness caps
 
 def test_at_most_a_tenth_of_the_filter_ops_have_no_point_inside_the_map():
@@ -229,6 +343,15 @@ def tables():
     for k in sm.MUTATING:
         shape, seed, d = first_kill(drop=k) or ("-", "-", "NOT NOTICED")
         rows.append(f"| {k} | {shape} seed {seed}: {d[:90]} |")
+    pairs = all_ordered_pairs()
+    rows += ["", "| device call | follows, on another stream, a ... of its map | is followed by | chained / foreign |", "|---|---|---|---|"]
+    others = sorted(sm.MUTATING_DEVICE_KINDS | {"export_layers"})
+    for k in sm.NEW_KINDS:
+        modes = [op["source"]["mode"] for shape, seed in CASES for op in sequence(shape, seed) if op["op"] == k and "source" in op]
+        rows.append(f"| {k} | " + ", ".join(o for o in others if (o, k) in pairs and o != k) + " | " + ", ".join(o for o in others if (k, o) in pairs and o != k)
+                    + " | " + (f"{modes.count('chained')} / {modes.count('foreign')}" if modes else "n/a") + " |")
+    n, kinds, streams = max((longest_run_of_device_calls(sequence(shape, seed)) for shape, seed in CASES), key=lambda r: r[0])
+    rows += ["", f"longest run of device calls: {n} ops of {len(kinds)} kinds on {len(streams)} streams (the shared ring has {sm.PARAM_RING} entries)"]
     return "\n".join(rows)
 
 

@@ -16,15 +16,13 @@ if ROOT not in sys.path:
 from groundgrid_amd import _lib, api, kitti, synth  # noqa: E402
 from groundgrid_amd._lib import LAYERS  # noqa: E402
 from oracle import oracle  # noqa: E402
+from tests.cloud_refs import CODE, QUIET_NAN, SETS, expected_sets  # noqa: E402
 from tests.test_export_layers_gpu import SENTINEL, batch_points, fresh_count, same_bits, stride_of, warm_maps  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 INVALID, CAPACITY = -1, -5
-QUIET_NAN = 0x7FC00000
-SETS = ("ground", "nonground")
 FIELDS = ("points", "height", "source")
-CODE = {"ground": 49, "nonground": 99}
 PARAM_RING = 4  # (gg_context.hip: entries of a call's parameter ring)
 GEOMETRY = {79: (26.0, 0.33), 364: (120.0, 0.33)}
 SIGNED_SENTINEL = SENTINEL - (1 << 32) if SENTINEL >= (1 << 31) else SENTINEL
@@ -95,24 +93,6 @@ def raw_split(seg, n, slots, first_slot, fmt, points, stride, n_points, out, lab
     x.d_counts = (out.counts.data_ptr() if counts == "out" else counts) or None
     h = stream if stream is not None else torch.cuda.current_stream().cuda_stream
     return seg._L.gg_split_clouds(seg._ctx, C.byref(x), None if own else C.c_void_p(h if h else _lib.GG_STREAM_DEFAULT))
-
-
-def expected_sets(ref, cloud_map, labels, ground=None):
-    """{set: (source indices, packed records, heights)} of one cloud from the oracle: ref's position and `ground` layer as they stand (or the
-    constant `ground` of a fresh map), cloud_map the points in the map frame, labels one byte per point of it"""
-    layer = ref.layer("ground")
-    out = {}
-    for s in SETS:
-        idx = np.nonzero(labels[: len(cloud_map)] == CODE[s])[0].astype(np.int32)
-        h = np.empty(len(idx), dtype=np.float32)
-        for k, p in enumerate(idx):
-            inside, r, c = ref.get_index(float(cloud_map["x"][p]), float(cloud_map["y"][p]))
-            if inside and 0 <= r < ref.rows and 0 <= c < ref.cols:
-                h[k] = np.float32(cloud_map["z"][p]) - (layer[r, c] if ground is None else np.float32(ground))
-            else:
-                h[k : k + 1].view(np.uint32)[0] = QUIET_NAN
-        out[s] = (idx, api.pack16(cloud_map[idx]), h)
-    return out
 
 
 def check_cloud(host, counts, i, stride, want, tag, given=None):
