@@ -56,6 +56,8 @@ SYMBOLS = [
     "gg_fuse_states",
     "gg_route_planes",
     "gg_match_planes",
+    "gg_footprint_planes",
+    "gg_footprint_spans",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -365,6 +367,35 @@ GG_MATCH_CHUNK = 1024
 GG_MATCH_LIST = 2048
 
 
+class GGPlaneFootprints(C.Structure):
+    """gg_plane_footprints: which headings of a footprint fit at every cell of many blocked planes (gg_footprint_planes)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("d_blocked", C.c_void_p),
+        ("blocked_stride", C.c_size_t),
+        ("spans", C.POINTER(C.c_int32)),
+        ("n_headings", C.c_int),
+        ("radius", C.c_int),
+        ("min_fit", C.c_int),
+        ("outside_free", C.c_int),
+        ("order", C.c_int),
+        ("d_mask", C.c_void_p),
+        ("mask_stride", C.c_size_t),
+        ("d_fit", C.c_void_p),
+        ("fit_stride", C.c_size_t),
+        ("d_counts", C.c_void_p),
+    ]
+
+
+GG_HAS_FOOTPRINT_PLANES = 1
+GG_FOOTPRINT_MAX_HEADINGS = 32  # the most headings of gg_footprint_planes
+GG_FOOTPRINT_MAX_RADIUS = 32    # ... and its largest radius
+GG_FOOTPRINT_RECT_LIMIT = 1 << 30  # the largest |word| of the rectangle of gg_footprint_spans
+# the side of a work-group's tile in k21_footprint.hip (FOOTPRINT_TILE): where the tests put their seams
+GG_FOOTPRINT_TILE = 64
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -445,6 +476,8 @@ def load():
     L.gg_fuse_states.argtypes = [vp, P(GGStateFusion), vp]
     L.gg_route_planes.argtypes = [vp, P(GGPlaneRoutes), vp]
     L.gg_match_planes.argtypes = [vp, P(GGPlaneMatches), vp]
+    L.gg_footprint_planes.argtypes = [vp, P(GGPlaneFootprints), vp]
+    L.gg_footprint_spans.argtypes = [P(C.c_int32), C.c_int, P(C.c_int32), C.c_int, P(C.c_int32), P(C.c_int)]
     L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

@@ -336,6 +336,65 @@ def rotation_table(angles_rad):
     return (np.sign(v) * np.floor(np.abs(v) + 0.5)).astype(np.int32)
 
 
+@dataclass
+class FootprintOutputs:
+    """what GroundSegmentation.footprint_planes returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    mask: "object" = None    # torch.int32 [B, rows, cols]: bit k set iff heading k fits at the cell (the uint32 word of gg_footprint_planes, same bits)
+    fit: "object" = None     # torch.int32 [B, rows, cols]: -1 where at least min_fit headings fit, else the number that fit
+    counts: "object" = None  # torch.int32 [B, 3]: cells where all K headings fit, where at least min_fit fit, where none fits
+
+
+def footprint_spans(rotations, ahead, behind, left, right, *, pad=0.7072, radius=None):
+    """The span table of a rectangular vehicle for GroundSegmentation.footprint_planes (gg_footprint_spans): int32 [K, 2 R + 1, 2], row
+    a + R of heading k = (lo, hi), the cells (a, lo .. hi) of the footprint, (1, 0) for an empty row.  rotations: rotation_table(angles),
+    int32 [K, 2] with 1 <= K <= 32: the forward axis of heading k is (cq, sq) in (row, col).  The rectangle reaches `ahead` cells along the
+    forward axis from the reference cell and `behind` cells against it, `left` cells along the axis a quarter turn from forward (the turn
+    that takes the row axis to the column axis) and `right` cells against that; all four >= 0 give a rectangle that holds the reference
+    cell, negative values move it off.  A cell belongs to the footprint when its centre lies in the rectangle grown by `pad` cells on
+    every side; the default, just over half a cell diagonal, catches every cell the rectangle touches (a choice of this layer alone:
+    the C call takes the padded rectangle).  Lengths become units of 1/16384 cell, rounded half away from zero as rotation_table
+    rounds.  radius=None takes the smallest radius that holds every heading; ValueError when that exceeds 32 or the radius given."""
+    who = "footprint_spans"
+    try:
+        given = np.asarray(rotations)
+        rot = np.ascontiguousarray(given.astype(np.int32))
+        exact = given.shape == rot.shape and np.array_equal(given, rot)
+    except (TypeError, ValueError, OverflowError) as e:
+        raise ValueError(f"{who}: rotations must be [K, 2] int32: {e}") from None
+    if rot.ndim != 2 or rot.shape[1] != 2 or not exact or not 1 <= rot.shape[0] <= _lib.GG_FOOTPRINT_MAX_HEADINGS:
+        raise ValueError(f"{who}: rotations are [K, 2] int32 with 1 <= K <= {_lib.GG_FOOTPRINT_MAX_HEADINGS}")
+    lengths = [float(v) for v in (ahead, behind, left, right, pad)]
+    if not all(math.isfinite(v) for v in lengths):
+        raise ValueError(f"{who}: ahead, behind, left, right and pad are finite lengths in cells")
+    ahead, behind, left, right, pad = lengths
+
+    def q14(v):
+        m = math.floor(abs(v) * float(_lib.GG_MATCH_UNIT) + 0.5)
+        return -m if v < 0 else m
+
+    rect = [q14(-(behind + pad)), q14(ahead + pad), q14(-(right + pad)), q14(left + pad)]
+    if any(abs(v) > _lib.GG_FOOTPRINT_RECT_LIMIT for v in rect) or rect[0] > rect[1] or rect[2] > rect[3]:
+        raise ValueError(f"{who}: the padded rectangle {rect} (1/16384 cell) is empty or reaches beyond 2^30")
+    if radius is not None and (isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= _lib.GG_FOOTPRINT_MAX_RADIUS):
+        raise ValueError(f"{who}: radius is an integer in [0, {_lib.GG_FOOTPRINT_MAX_RADIUS}] or None")
+    L = _lib.load()
+    K = rot.shape[0]
+    c_rot, c_rect, needed = rot.ctypes.data_as(C.POINTER(C.c_int32)), (C.c_int32 * 4)(*rect), C.c_int(0)
+    rc = L.gg_footprint_spans(c_rot, K, c_rect, 0, None, C.byref(needed))
+    if rc != _lib.GG_OK:
+        raise GroundGridError(f"gg_footprint_spans: {_lib.STATUS.get(rc, rc)}")
+    R = max(needed.value, 0) if radius is None else int(radius)
+    if needed.value > R or R > _lib.GG_FOOTPRINT_MAX_RADIUS:
+        raise ValueError(f"{who}: the footprint needs radius {needed.value}{' or more' if needed.value > _lib.GG_FOOTPRINT_MAX_RADIUS else ''}, "
+                         f"beyond {'the largest radius' if radius is None else 'the radius given,'} {min(R, _lib.GG_FOOTPRINT_MAX_RADIUS) if radius is None else R}")
+    spans = np.zeros((K, 2 * R + 1, 2), dtype=np.int32)
+    rc = L.gg_footprint_spans(c_rot, K, c_rect, R, spans.ctypes.data_as(C.POINTER(C.c_int32)), None)
+    if rc != _lib.GG_OK:
+        raise GroundGridError(f"gg_footprint_spans: {_lib.STATUS.get(rc, rc)}")
+    return spans
+
+
 def goal_planes(cells, rows: int, cols: int, order: str = "row", device=None):
     """A goal plane per map for GroundSegmentation.route_planes from a list of goal cells, for "route from the robot cell": cells[i] is the
     list of (row, col) goals of map i (an empty list: no goal).  Returns torch.int32 [B, rows, cols] ([B, cols, rows] with order="col"): 0 on
@@ -1170,6 +1229,83 @@ class GroundSegmentation:
         x.d_scores, x.score_stride = (res.scores.data_ptr(), K * D * D) if scores else (None, 0)
         stream = self._stream_arg(on_torch_stream, scan.device)
         _check(self._L, self._ctx, self._L.gg_match_planes(self._ctx, C.byref(x), stream), "gg_match_planes")
+        return res
+
+    def footprint_planes(self, blocked, spans, *, min_fit: Optional[int] = None, outside_free: bool = False, order: str = "row", mask: bool = True,
+                         fit: bool = True, counts: bool = True, out: Optional[FootprintOutputs] = None, on_torch_stream: bool = False) -> FootprintOutputs:
+        """Which headings of a vehicle footprint fit at every cell of many maps (gg_footprint_planes).  blocked: a contiguous CUDA
+        torch.int32 tensor [B, rows, cols] ([B, cols, rows] with order="col"), B <= n_slots: a cell is blocked where the word is >= 0 --
+        FusionOutputs.state, VisibilityOutputs.state or ClusterOutputs.cell_cluster as it is, the convention of route_planes.  spans:
+        footprint_spans(...), int32 [K, 2 R + 1, 2] with 1 <= K <= 32 and 0 <= R <= 32, shared by all maps: row a + R of heading k is
+        (lo, hi), the cells (a, lo .. hi) of the footprint in (row, col) offsets from the reference cell, lo > hi an empty row; every
+        heading must be column-convex.  Heading k fits at (r, c) iff no cell (r + a, c + b) of its footprint is blocked; a cell outside
+        the map is blocked, or free with outside_free=True.
+        mask int32 [B, rows, cols]: bit k set iff heading k fits (the uint32 word of the C call, same bits).  fit int32: -1 where at
+        least min_fit headings fit, else their number -- a `blocked` plane of route_planes and a seed plane of clearance_planes as it is;
+        min_fit=None means K ("fits at every heading", the conservative plane), min_fit=1 "fits at some heading", the exact projection
+        of the configuration space.  counts int32 [B, 3]: cells where all K fit, where at least min_fit fit, where none fits.  At least
+        one of the three must be asked for.  `out`: a FootprintOutputs of an earlier call with the same arguments, whose tensors are
+        reused; it may not hold the input.  Bit operations and integer sums only: bit-identical from run to run.  Enqueued on the
+        context's own stream or, with on_torch_stream=True, on the current torch stream; nothing synchronises.  No map is read or
+        changed."""
+        import torch
+
+        who = "footprint_planes"
+        if order not in ("row", "col"):
+            raise ValueError(f"{who}: order is 'row' or 'col'")
+        if not isinstance(outside_free, (bool, np.bool_)):
+            raise ValueError(f"{who}: outside_free is True or False")
+        try:
+            given = np.asarray(spans)
+            host_spans = np.ascontiguousarray(given.astype(np.int32))
+            exact = given.shape == host_spans.shape and np.array_equal(given, host_spans)
+        except (TypeError, ValueError, OverflowError) as e:
+            raise ValueError(f"{who}: spans must be [K, 2 R + 1, 2] int32: {e}") from None
+        if host_spans.ndim != 3 or host_spans.shape[2] != 2 or host_spans.shape[1] % 2 != 1 or not exact:
+            raise ValueError(f"{who}: spans of shape {host_spans.shape} are not [K, 2 R + 1, 2] int32")
+        K, R = int(host_spans.shape[0]), int(host_spans.shape[1]) // 2
+        if not 1 <= K <= _lib.GG_FOOTPRINT_MAX_HEADINGS or R > _lib.GG_FOOTPRINT_MAX_RADIUS:
+            raise ValueError(f"{who}: spans hold 1 to {_lib.GG_FOOTPRINT_MAX_HEADINGS} headings of radius 0 to {_lib.GG_FOOTPRINT_MAX_RADIUS}")
+        if min_fit is None:
+            min_fit = K
+        if isinstance(min_fit, bool) or not isinstance(min_fit, (int, np.integer)) or not 1 <= min_fit <= K:
+            raise ValueError(f"{who}: min_fit is an integer in [1, {K}] or None")
+        if not (mask or fit or counts):
+            raise ValueError(f"{who}: at least one of mask, fit and counts must be asked for")
+        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
+        if not (torch.is_tensor(blocked) and blocked.is_cuda and blocked.dtype == torch.int32 and blocked.dim() == 3 and blocked.is_contiguous()
+                and tuple(blocked.shape[1:]) == plane):
+            raise ValueError(f"{who}: blocked must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
+        B = int(blocked.shape[0])
+        res = out if out is not None else FootprintOutputs()
+        want = {"mask": (B,) + plane if mask else None, "fit": (B,) + plane if fit else None, "counts": (B, 3) if counts else None}
+        for name, sh in want.items():
+            t = getattr(res, name)
+            if sh is None:
+                if t is not None:
+                    raise ValueError(f"{who}: out.{name} is given but not asked for")
+                continue
+            if t is None:
+                continue
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == sh and t.is_contiguous() and t.device == blocked.device):
+                raise ValueError(f"{who}: out.{name} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
+            if t.data_ptr() == blocked.data_ptr():
+                raise ValueError(f"{who}: out.{name} is the input of the call")
+        for name, sh in want.items():
+            if sh is not None and getattr(res, name) is None:
+                setattr(res, name, torch.empty(sh, dtype=torch.int32, device=blocked.device))
+        self._torch_used = True
+        x = _lib.GGPlaneFootprints()
+        cells = self.rows * self.cols
+        x.n, x.d_blocked, x.blocked_stride = B, blocked.data_ptr(), cells
+        x.spans, x.n_headings, x.radius = host_spans.ctypes.data_as(C.POINTER(C.c_int32)), K, R
+        x.min_fit, x.outside_free = int(min_fit), int(bool(outside_free))
+        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.d_mask, x.mask_stride = (res.mask.data_ptr(), cells) if mask else (None, 0)
+        x.d_fit, x.fit_stride = (res.fit.data_ptr(), cells) if fit else (None, 0)
+        x.d_counts = res.counts.data_ptr() if counts else None
+        stream = self._stream_arg(on_torch_stream, blocked.device)
+        _check(self._L, self._ctx, self._L.gg_footprint_planes(self._ctx, C.byref(x), stream), "gg_footprint_planes")
         return res
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:

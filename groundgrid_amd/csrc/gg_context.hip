@@ -227,6 +227,7 @@ struct gg_context : ContextBuffers {
     int2 *d_export_pivots = nullptr, *h_export_pivots = nullptr; // gg_match_planes: the per-map pivots of a call, [PARAM_RING][n_slots] (its shifts: d_export_shifts)
     int2 *d_export_rotations = nullptr, *h_export_rotations = nullptr; // ... the rotation table of a call, [PARAM_RING][MATCH_MAX_ROTATIONS]
     MatchPartial *d_match_partials = nullptr; // ... what its two launches hand over, [PARAM_RING][n_slots][MATCH_MAX_ROTATIONS], device only
+    uint32_t *d_export_footprint = nullptr, *h_export_footprint = nullptr; // gg_footprint_planes: the packed span table of a call, [PARAM_RING][FOOTPRINT_TABLE]
     ParamRing export_ring;
     int slopes_variant = 0; // tuning "slopes_variant": 0 = k_slopes_tiled, 1 = k_slopes_gather (the A/B of tools/bench_slopes.py)
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
@@ -1984,7 +1985,11 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     const size_t h_rotations = align_up(h_pivots + ring * sizeof(int2), 256);
     const size_t rotations_bytes = (size_t)PARAM_RING * MATCH_MAX_ROTATIONS * sizeof(int2);
     const size_t o_match = align_up(o_rotations + rotations_bytes, 256);
-    if (const int rc = alloc_call_scratch(ctx, who, st, o_match + ring * MATCH_MAX_ROTATIONS * sizeof(MatchPartial), h_rotations + rotations_bytes,
+    // (gg_footprint_planes: its packed span table, per ring entry)
+    const size_t o_footprint = align_up(o_match + ring * MATCH_MAX_ROTATIONS * sizeof(MatchPartial), 256);
+    const size_t h_footprint = align_up(h_rotations + rotations_bytes, 256);
+    const size_t footprint_bytes = (size_t)PARAM_RING * FOOTPRINT_TABLE * sizeof(uint32_t);
+    if (const int rc = alloc_call_scratch(ctx, who, st, o_footprint + footprint_bytes, h_footprint + footprint_bytes,
                                           {{o_off, off.data(), off.size() * sizeof(uint32_t)}, {o_elem, elem.data(), elem.size() * sizeof(uint32_t)}, {o_cell, cell.data(), cell.size() * sizeof(uint16_t)}},
                                           &ctx->export_mem, &ctx->export_ring))
         return rc;
@@ -2007,6 +2012,8 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     ctx->d_export_rotations = (int2 *)(block + o_rotations);
     ctx->h_export_rotations = (int2 *)(h + h_rotations);
     ctx->d_match_partials = (MatchPartial *)(block + o_match);
+    ctx->d_export_footprint = (uint32_t *)(block + o_footprint);
+    ctx->h_export_footprint = (uint32_t *)(h + h_footprint);
     return GG_OK;
 }
 
@@ -2718,6 +2725,139 @@ int gg_match_planes(gg_context *ctx, const gg_plane_matches *x, void *stream)
     ma.scores = x->d_scores;
     ma.score_stride = x->score_stride;
     launch_match(ma, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
+// The span table of a rectangle for gg_footprint_planes: host integer arithmetic only, no context
+int gg_footprint_spans(const int32_t *rotations, int n_rotations, const int32_t rect[4], int radius, int32_t *spans, int *needed)
+{
+    constexpr int BOX = FOOTPRINT_MAX_RADIUS + 1; // the test is evaluated on [-33, 33]^2
+    if (!rotations || !rect) return GG_ERR_INVALID;
+    if (n_rotations < 1 || n_rotations > FOOTPRINT_MAX_HEADINGS) return GG_ERR_INVALID;
+    for (int k = 0; k < 2 * n_rotations; ++k)
+        if (rotations[k] < -GG_MATCH_UNIT || rotations[k] > GG_MATCH_UNIT) return GG_ERR_INVALID;
+    for (int k = 0; k < 4; ++k)
+        if (rect[k] < -(1 << 30) || rect[k] > (1 << 30)) return GG_ERR_INVALID;
+    if (rect[0] > rect[1] || rect[2] > rect[3]) return GG_ERR_INVALID;
+    if (spans && (radius < 0 || radius > FOOTPRINT_MAX_RADIUS)) return GG_ERR_INVALID;
+    std::vector<int32_t> lo((size_t)n_rotations * (2 * BOX + 1)), hi(lo.size()); // (min b, max b) of row a of heading k; (1, 0): empty
+    int need = -1;
+    for (int k = 0; k < n_rotations; ++k) {
+        const int32_t cq = rotations[2 * k], sq = rotations[2 * k + 1];
+        for (int a = -BOX; a <= BOX; ++a) {
+            int32_t first = 1, last = 0;
+            for (int b = -BOX; b <= BOX; ++b) {
+                const int32_t u = cq * a + sq * b, v = -sq * a + cq * b;
+                if (u < rect[0] || u > rect[1] || v < rect[2] || v > rect[3]) continue;
+                if (first > last) first = b;
+                last = b;
+                need = std::max(need, std::max(std::abs(a), std::abs(b)));
+            }
+            lo[(size_t)k * (2 * BOX + 1) + a + BOX] = first;
+            hi[(size_t)k * (2 * BOX + 1) + a + BOX] = last;
+        }
+    }
+    if (needed) *needed = need;
+    if (!spans) return GG_OK;
+    if (need > radius) return GG_ERR_INVALID;
+    const int D = 2 * radius + 1;
+    for (int k = 0; k < n_rotations; ++k)
+        for (int a = -radius; a <= radius; ++a) {
+            spans[((size_t)k * D + a + radius) * 2] = lo[(size_t)k * (2 * BOX + 1) + a + BOX];
+            spans[((size_t)k * D + a + radius) * 2 + 1] = hi[(size_t)k * (2 * BOX + 1) + a + BOX];
+        }
+    return GG_OK;
+}
+
+// Which headings a footprint fits, per cell (k21_footprint.hip): a ring entry and the ordering of the export for maps 0 .. n-1, none of which
+// is read, as gg_route_planes and gg_match_planes; the span table travels in the ring entry, per line offset of the plane (transposed for
+// column-major planes: column-convexity makes that exact) and packed (footprint_pack).  Nothing is synchronised, no map is filled and no
+// host-side flag changes.
+int gg_footprint_planes(gg_context *ctx, const gg_plane_footprints *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_footprint_planes";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_plane_footprints");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    const int rows = ctx->arena.g.rows, cols = ctx->arena.g.cols;
+    if (!x->d_blocked) return fail(ctx, GG_ERR_INVALID, who, "d_blocked is required");
+    if (!x->spans) return fail(ctx, GG_ERR_INVALID, who, "spans is required");
+    if (!x->d_mask && !x->d_fit && !x->d_counts) return fail(ctx, GG_ERR_INVALID, who, "at least one of d_mask, d_fit and d_counts must be given");
+    if (x->blocked_stride < C) return fail(ctx, GG_ERR_INVALID, who, "blocked_stride is smaller than rows * cols");
+    if (x->d_mask && x->mask_stride < C) return fail(ctx, GG_ERR_INVALID, who, "mask_stride is smaller than rows * cols");
+    if (x->d_fit && x->fit_stride < C) return fail(ctx, GG_ERR_INVALID, who, "fit_stride is smaller than rows * cols");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->n_headings < 1 || x->n_headings > FOOTPRINT_MAX_HEADINGS) return fail(ctx, GG_ERR_INVALID, who, "n_headings lies in [1, 32]");
+    if (x->radius < 0 || x->radius > FOOTPRINT_MAX_RADIUS) return fail(ctx, GG_ERR_INVALID, who, "radius lies in [0, 32]");
+    if (x->min_fit < 1 || x->min_fit > x->n_headings) return fail(ctx, GG_ERR_INVALID, who, "min_fit lies in [1, n_headings]");
+    if (x->outside_free != 0 && x->outside_free != 1) return fail(ctx, GG_ERR_INVALID, who, "outside_free is 0 or 1");
+    const int K = x->n_headings, R = x->radius, D = 2 * R + 1;
+    // the rows as given, the columns they make (the transposed table), and column-convexity: the rows that hold column b are consecutive
+    std::vector<int32_t> across((size_t)K * D * 2);
+    for (int k = 0; k < K; ++k) {
+        const int32_t *sp = x->spans + (size_t)k * D * 2;
+        int32_t *tr = across.data() + (size_t)k * D * 2;
+        for (int b = 0; b < D; ++b) tr[2 * b] = 1, tr[2 * b + 1] = 0;
+        for (int a = -R; a <= R; ++a) {
+            const int32_t lo = sp[2 * (a + R)], hi = sp[2 * (a + R) + 1];
+            if (lo > hi) continue;
+            if (lo < -R || hi > R) return fail(ctx, GG_ERR_INVALID, who, "a span reaches beyond the radius");
+            for (int b = lo; b <= hi; ++b) {
+                int32_t *t = tr + 2 * (b + R);
+                if (t[0] > t[1]) t[0] = t[1] = a;
+                else if (t[1] == a - 1) t[1] = a;
+                else return fail(ctx, GG_ERR_INVALID, who, "a heading of the span table is not column-convex");
+            }
+        }
+    }
+    if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
+    // no output may share a byte with the input or another output, by the ranges of gg_route_planes
+    struct Range {
+        const char *name, *lo, *hi;
+    };
+    const auto planes = [&](const char *name, const void *p, size_t stride, size_t words) {
+        return Range{name, (const char *)p, (const char *)p + ((size_t)(x->n - 1) * stride + words) * sizeof(int32_t)};
+    };
+    const Range ranges[4] = {planes("d_blocked", x->d_blocked, x->blocked_stride, C), planes("d_mask", x->d_mask, x->mask_stride, C),
+                             planes("d_fit", x->d_fit, x->fit_stride, C), planes("d_counts", x->d_counts, 3, 3)};
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j) {
+            const Range &p = ranges[i], &q = ranges[j];
+            if (!p.lo || !q.lo) continue;
+            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
+                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
+        }
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    const bool row_major = x->order == GG_PLANES_ROWMAJOR;
+    uint32_t *ht = ctx->h_export_footprint + (size_t)f.g * FOOTPRINT_TABLE, *dt = ctx->d_export_footprint + (size_t)f.g * FOOTPRINT_TABLE;
+    const int32_t *per_line = row_major ? x->spans : across.data();
+    int n_levels = 1;
+    for (int e = 0; e < K * D; ++e) {
+        ht[e] = footprint_pack(per_line[2 * e], per_line[2 * e + 1]);
+        if (ht[e] != FOOTPRINT_EMPTY) n_levels = std::max(n_levels, (int)(ht[e] >> 16) + 1);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(dt, ht, sizeof(uint32_t) * K * D, hipMemcpyHostToDevice, f.st));
+    FootprintArgs fa{};
+    fa.blocked = x->d_blocked;
+    fa.blocked_stride = x->blocked_stride;
+    fa.table = dt;
+    fa.n_headings = K;
+    fa.radius = R;
+    fa.n_levels = n_levels;
+    fa.min_fit = x->min_fit;
+    fa.outside_free = x->outside_free;
+    fa.nx = row_major ? cols : rows;
+    fa.ny = row_major ? rows : cols;
+    fa.tiles_x = (fa.nx + FOOTPRINT_TILE - 1) / FOOTPRINT_TILE;
+    fa.mask = x->d_mask;
+    fa.mask_stride = x->mask_stride;
+    fa.fit = x->d_fit;
+    fa.fit_stride = x->fit_stride;
+    fa.counts = x->d_counts;
+    launch_footprint(fa, x->n, f.st);
     return map_call_end(ctx, f);
 }
 

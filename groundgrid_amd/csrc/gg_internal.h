@@ -498,6 +498,45 @@ struct MatchArgs {
     size_t score_stride;
 };
 
+// gg_footprint_planes (k21_footprint.hip).  Map i of the call is row i of every buffer.  A plane is `ny` lines of `nx` contiguous words: (nx, ny) =
+// (cols, rows) row-major, (rows, cols) column-major.  The kernel knows lines and positions along a line alone: the entry point hands it the
+// span table per LINE offset (the caller's table row-major, its transpose column-major), every row already turned into the two shifts and the
+// erosion level the kernel needs (footprint_pack)
+constexpr int FOOTPRINT_MAX_HEADINGS = 32;
+constexpr int FOOTPRINT_MAX_RADIUS = 32;
+constexpr int FOOTPRINT_TILE = 64; // cells along a line, and lines, of a work-group's tile (_lib.py mirrors it for the tests' seams)
+constexpr int FOOTPRINT_TABLE = FOOTPRINT_MAX_HEADINGS * (2 * FOOTPRINT_MAX_RADIUS + 1); // words of one call's table
+constexpr uint32_t FOOTPRINT_EMPTY = 0xFFFFFFFFu; // an empty row
+// a row (lo, hi) of width w = hi - lo + 1 with p = 2^level the largest power of two <= w: "the w cells from x + lo on are free" is bit
+// x + lo and bit x + lo + w - p of the line's erosion by p.  Bit 0 of a line's 128-bit word is position x0 - 32: s1 = lo + 32, s2 = s1 + w - p,
+// both in [0, 64]
+inline uint32_t footprint_pack(int lo, int hi)
+{
+    if (lo > hi) return FOOTPRINT_EMPTY;
+    const int w = hi - lo + 1;
+    int level = 0;
+    while ((2 << level) <= w) ++level;
+    const int s1 = lo + FOOTPRINT_MAX_RADIUS, s2 = s1 + w - (1 << level);
+    return (uint32_t)s1 | (uint32_t)s2 << 8 | (uint32_t)level << 16;
+}
+struct FootprintArgs {
+    const int32_t *blocked;        // map i's plane at blocked + i * blocked_stride: blocked where the word is >= 0
+    size_t blocked_stride;
+    const uint32_t *table;         // device [K][2 R + 1] packed rows per line offset (the call's ring entry)
+    int n_headings;                // K
+    int radius;                    // R
+    int n_levels;                  // erosion levels the table uses: 1 + the largest level of a row (1 when every row is empty)
+    int min_fit;
+    int outside_free;
+    int nx, ny;
+    int tiles_x;                   // tiles along a line
+    uint32_t *mask;                // nullable; map i's plane at mask + i * mask_stride
+    size_t mask_stride;
+    int32_t *fit;                  // nullable; ... at fit + i * fit_stride
+    size_t fit_stride;
+    int32_t *counts;               // nullable; [map][3]
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -548,6 +587,7 @@ void launch_visibility(const Arena &a, const VisibilityArgs &x, int n_clouds, hi
 void launch_fuse(const FuseArgs &x, int n_maps, hipStream_t s);                                  // k18_fuse.hip: (counts := 0,) k_fuse_states
 void launch_route(const RouteArgs &x, int n_maps, hipStream_t s);                                // k19_route.hip: relax, (counts := 0, next,) (paths)
 void launch_match(const MatchArgs &x, int n_maps, hipStream_t s);                                // k20_match.hip: k_match_scores, k_match_best
+void launch_footprint(const FootprintArgs &x, int n_maps, hipStream_t s);                        // k21_footprint.hip: (counts := 0,) k_footprint_planes
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

@@ -1156,6 +1156,89 @@ typedef struct gg_plane_matches {
 int gg_match_planes(gg_context *ctx, const gg_plane_matches *x, void *stream);
 #define GG_HAS_MATCH_PLANES 1
 
+/* WHICH HEADINGS A VEHICLE FOOTPRINT FITS, per cell, for many maps in DEVICE memory: gg_route_planes blocks single cells, and the only size a
+ * caller can give the robot there is one radius of inflation -- the circumscribed radius of a car closes every lane it fits through, the
+ * inscribed one opens gaps it can only enter sideways.  gg_footprint_planes is the oriented-footprint test of a lattice planner: for every
+ * cell and each of K headings, does the footprint placed at that cell with that heading touch a blocked cell?  What a caller otherwise
+ * composes per map from K dense correlations with kernels of up to 65 x 65.  The input is a plane of an earlier call as it stands.  Map i of
+ * the call is row i of every buffer.  Everything is 32-bit integer and in (row, col) terms whatever `order` is; all of the following is
+ * per map:
+ *   blocked      cell q is blocked where map i's d_blocked word is >= 0, as in gg_route_planes (a d_fused or d_state plane, a
+ *                d_cell_cluster plane, a d_fit plane of this call as they stand).  Required.
+ *   outside      a cell outside the map counts as blocked when outside_free == 0 and as free when outside_free == 1; no other value.
+ *   footprint    K = n_headings (1 .. 32) headings and a radius R (0 .. 32) come with a HOST table spans[K][2 R + 1][2] of int32, shared by
+ *                all maps of the call: row a + R of heading k holds (lo, hi), and the cells of heading k are
+ *                F_k = {(a, b): -R <= a <= R, lo(k, a) <= b <= hi(k, a)}.  lo > hi is an empty row; a non-empty row needs
+ *                -R <= lo <= hi <= R.  F_k must also be column-convex: for every b the rows a with (a, b) in F_k are consecutive
+ *                (GG_ERR_INVALID otherwise; gg_footprint_spans makes such tables).  An empty F_k is allowed and fits everywhere.
+ *   fits         heading k fits at (r, c) iff no cell (r + a, c + b) with (a, b) in F_k is blocked, the outside rule applied: the
+ *                footprint is laid over the map, not reflected.
+ *   d_mask       uint32 planes, nullable: bit k of the word of (r, c) is set iff heading k fits there; bits K .. 31 are zero.
+ *   d_fit        int32 planes, nullable: with p = the number of headings that fit at the cell, the word is -1 where p >= min_fit and p
+ *                (0 <= p < min_fit) elsewhere; 1 <= min_fit <= K.  A d_blocked plane of gg_route_planes and a seed plane of
+ *                gg_clearance_clouds (d_seeds) as it stands.  min_fit == 1 is the exact projection of the configuration space ("fits at some
+ *                heading"), min_fit == K the conservative one ("fits at every heading").
+ *   d_counts     nullable: three words per map, d_counts[3 i + 0 .. 2]: the number of cells with p == K, with p >= min_fit, with p == 0.
+ *   At least one of d_mask, d_fit and d_counts must be given.
+ *   addressing   map i's plane of rows * cols words at d_blocked + i * blocked_stride, d_mask + i * mask_stride and d_fit + i * fit_stride;
+ *                cell (row, col) where `order` puts it, the same order for all planes; strides >= rows * cols.  4-byte alignment.  Every
+ *                cell of every given plane is written; the words between rows * cols and a stride never are.
+ *   no overlap   no output may share a byte with the input or with another output; the call compares the address ranges as
+ *                gg_route_planes does (a plane buffer from its first word to the last cell of its last plane, d_counts its 3 n words) and
+ *                answers GG_ERR_INVALID.
+ *   determinism  bit operations and integer sums only: bit-identical from run to run and independent of scheduling.
+ * The contract is that of gg_route_planes and gg_match_planes: NO MAP IS READ OR CHANGED -- no layer, position, freshness, configuration,
+ * score or liveness flag, and the lazily kept layers stay pending.  n <= n_slots (GG_ERR_CAPACITY): the call takes an entry of the same
+ * ring of parameter entries (the span table travels in it) and orders itself on `stream` as those calls do; it enqueues and returns with
+ * no synchronisation, and the host table may be freed on return.  The caller's device buffers must stay valid and unmodified until
+ * `stream` has passed the call.
+ * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
+ * n > 0: null d_blocked, null spans, no output at all, a stride < rows * cols, an unknown order, n_headings outside [1, 32], radius outside
+ * [0, 32], min_fit outside [1, n_headings], outside_free not 0 or 1, a non-empty row with lo < -R or hi > R, a heading that is not
+ * column-convex, overlapping buffers; GG_ERR_CAPACITY for n > n_slots.  n == 0 is GG_OK before anything else is looked at.  The first
+ * many-map call of a context may allocate (GG_ERR_NOMEM) and block; later calls only enqueue.  Capture into a caller's graph is not
+ * supported. */
+#define GG_FOOTPRINT_MAX_HEADINGS 32
+#define GG_FOOTPRINT_MAX_RADIUS 32
+typedef struct gg_plane_footprints {
+    int n;                        /* maps */
+    const int32_t *d_blocked;     /* [n] planes, blocked_stride apart: BLOCKED where the word is >= 0; required */
+    size_t blocked_stride;        /* int32 words, >= rows * cols */
+    const int32_t *spans;         /* host [n_headings][2 radius + 1][2]: (lo, hi) of row a + radius; lo > hi: an empty row; required */
+    int n_headings;               /* K, 1 .. 32 */
+    int radius;                   /* R, 0 .. 32 */
+    int min_fit;                  /* 1 .. K: d_fit is -1 where at least this many headings fit */
+    int outside_free;             /* 0: cells outside the map are blocked, 1: they are free */
+    int order;                    /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR, of all planes */
+    uint32_t *d_mask;             /* [n] planes, mask_stride apart: bit k set iff heading k fits; nullable */
+    size_t mask_stride;           /* words, >= rows * cols when d_mask is given */
+    int32_t *d_fit;               /* [n] planes, fit_stride apart: -1 where p >= min_fit, else p; nullable */
+    size_t fit_stride;            /* words, >= rows * cols when d_fit is given */
+    int32_t *d_counts;            /* [n][3]: cells with p == K, with p >= min_fit, with p == 0; nullable */
+} gg_plane_footprints;
+int gg_footprint_planes(gg_context *ctx, const gg_plane_footprints *x, void *stream);
+
+/* The span table of a RECTANGLE for gg_footprint_planes.  Host arithmetic only: no context, no device call.
+ *   rotations    the Q14 table of gg_match_planes (GG_MATCH_UNIT = 1.0), [n_rotations][2], 1 <= n_rotations <= 32, |word| <= 16384: the
+ *                forward axis of heading k is (cq, sq) = (rotations[2 k], rotations[2 k + 1]) in (row, col), used as given (no unit
+ *                length is asked for).
+ *   rect         (u_lo, u_hi, v_lo, v_hi) in units of 1/16384 cell, |word| <= 2^30, u_lo <= u_hi, v_lo <= v_hi: the extent along the
+ *                forward axis and along the axis a quarter turn from it (the turn that takes the row axis to the column axis).
+ *   membership   with u = cq a + sq b and v = -sq a + cq b (both fit an int32 for |a|, |b| <= 33), offset (a, b) belongs to heading k iff
+ *                u_lo <= u <= u_hi and v_lo <= v <= v_hi.  This tests the centre of the cell: a caller who wants every cell the rectangle
+ *                touches pads the rectangle.  Both conditions are intervals in b for a fixed a and in a for a fixed b, so every heading
+ *                is row- and column-convex whatever the pair.
+ *   needed       the test is evaluated on the box [-33, 33]^2.  *needed (nullable) receives the largest max(|a|, |b|) of a member cell
+ *                over all headings, -1 when there is none; 33 means the footprint cannot be represented.
+ *   spans        NULL: a pure query; `radius` is not looked at and the answer is GG_OK.  Otherwise 0 <= radius <= 32, and with
+ *                needed <= radius the table [n_rotations][2 radius + 1][2] is written, row a + radius of heading k = (min b, max b) of
+ *                its members, an empty row as (1, 0); with needed > radius the answer is GG_ERR_INVALID and `spans` is left untouched
+ *                (*needed is written either way).
+ * GG_ERR_INVALID also for null rotations or rect, n_rotations outside [1, 32], a rotation word beyond +-16384, a rect word beyond +-2^30,
+ * lo > hi, and radius outside [0, 32] with `spans` given. */
+int gg_footprint_spans(const int32_t *rotations, int n_rotations, const int32_t rect[4], int radius, int32_t *spans, int *needed);
+#define GG_HAS_FOOTPRINT_PLANES 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
