@@ -58,6 +58,8 @@ SYMBOLS = [
     "gg_match_planes",
     "gg_footprint_planes",
     "gg_footprint_spans",
+    "gg_route_headings",
+    "gg_heading_moves",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -396,6 +398,56 @@ GG_FOOTPRINT_RECT_LIMIT = 1 << 30  # the largest |word| of the rectangle of gg_f
 GG_FOOTPRINT_TILE = 64
 
 
+class GGHeadingRoutes(C.Structure):
+    """gg_heading_routes: the cost-to-go over cells and headings, the moves and the paths of many maps over a heading mask (gg_route_headings)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("d_mask", C.c_void_p),
+        ("mask_stride", C.c_size_t),
+        ("d_cost", C.c_void_p),
+        ("cost_stride", C.c_size_t),
+        ("d_goals", C.c_void_p),
+        ("goal_stride", C.c_size_t),
+        ("goal_headings", C.c_uint32),
+        ("n_headings", C.c_int),
+        ("moves", C.POINTER(C.c_int32)),
+        ("cost_max", C.c_int),
+        ("max_cost", C.c_int),
+        ("order", C.c_int),
+        ("d_dist", C.c_void_p),
+        ("dist_stride", C.c_size_t),
+        ("plane_stride", C.c_size_t),
+        ("d_next", C.c_void_p),
+        ("next_stride", C.c_size_t),
+        ("next_plane_stride", C.c_size_t),
+        ("d_best", C.c_void_p),
+        ("best_stride", C.c_size_t),
+        ("d_best_heading", C.c_void_p),
+        ("best_heading_stride", C.c_size_t),
+        ("d_counts", C.c_void_p),
+        ("starts", C.POINTER(C.c_int32)),
+        ("d_paths", C.c_void_p),
+        ("path_stride", C.c_size_t),
+        ("max_len", C.c_int),
+        ("d_path_len", C.c_void_p),
+    ]
+
+
+GG_HAS_ROUTE_HEADINGS = 1
+GG_HEADINGS_MAX = 32         # the most headings of gg_route_headings
+GG_HEADINGS_MAX_MOVES = 8    # ... moves per heading
+GG_HEADINGS_MAX_STEP = 3     # ... cells a move spans along either axis
+GG_HEADINGS_MAX_COST = 32767  # ... and the largest cost s of a move
+GG_HEADINGS_AT_GOAL = 8      # d_next of a goal state
+GG_HEADINGS_LIMIT = (1 << 31) - 2  # the largest max s * cost_max * rows * cols * n_headings
+
+
+def headings_tile(n_headings):
+    """the side of the tiles a work-group of k22_headings.hip relaxes a map by (gg_internal.h headings_tile): where the tests put their seams"""
+    return 32 if n_headings <= 16 else 16
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -478,7 +530,9 @@ def load():
     L.gg_match_planes.argtypes = [vp, P(GGPlaneMatches), vp]
     L.gg_footprint_planes.argtypes = [vp, P(GGPlaneFootprints), vp]
     L.gg_footprint_spans.argtypes = [P(C.c_int32), C.c_int, P(C.c_int32), C.c_int, P(C.c_int32), P(C.c_int)]
-    L.gg_get_map_position.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_double)]
+    L.gg_route_headings.argtypes = [vp, P(GGHeadingRoutes), vp]
+    L.gg_heading_moves.argtypes = [P(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int32)]
+    L.gg_get_map_position.argtypes =[vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_expected_points.argtypes = [vp, vp]

@@ -395,6 +395,52 @@ def footprint_spans(rotations, ahead, behind, left, right, *, pad=0.7072, radius
     return spans
 
 
+@dataclass
+class HeadingOutputs:
+    """what GroundSegmentation.route_headings returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    dist: "object" = None          # torch.int32 [B, K, rows, cols] ([B, K, cols, rows] with order="col"): the cost to a goal state, _lib.GG_ROUTE_NONE where none is reached
+    next: "object" = None          # torch.int32, same shape: the slot of the move to take; _lib.GG_HEADINGS_AT_GOAL on a goal state, -1 unreached
+    best: "object" = None          # torch.int32 [B, rows, cols]: the least dist over the headings of a cell
+    best_heading: "object" = None  # torch.int32 [B, rows, cols]: the smallest heading that attains it, -1 where none is reached
+    counts: "object" = None        # torch.int32 [B, 3]: the goal states, the reached states (goal states included) and the admissible states of every map
+    paths: "object" = None         # torch.int32 [B, max_len, 2]: the (cell, heading) pairs of the path from starts[i]; the pairs from path_len[i] on are never written
+    path_len: "object" = None      # torch.int32 [B]: the states of the whole path, also beyond max_len; 0: no start, or an unreached one
+
+
+def heading_moves(rotations, *, step: int = 1, unit: int = 10, turn: int = 0, reverse_pct: int = 0, spin: int = 0):
+    """The move table of a car-like vehicle for GroundSegmentation.route_headings (gg_heading_moves): int32 [K, 8, 4], entry m of heading
+    k = (da, db, k2, s): from (k, (r, c)) to (k2, (r + da, c + db)) at cost s times the clamped cost of the cell entered; s == 0 marks an
+    absent entry.  rotations: rotation_table(angles), int32 [K, 2] with 1 <= K <= 32: the forward axis of heading k is (cq, sq) in
+    (row, col).  With d_k = `step` (1 .. 3) cells along that axis, rounded half away from zero per component, and s_k = max(1,
+    floor(unit * |d_k|)) (unit in 1 .. 1024): slot 0 goes d_k ahead and keeps the heading, slots 1 and 2 go d_k ahead and end one
+    heading to the left (k + 1) and to the right (k - 1) at s_k + turn; slots 3 .. 5 are the same three backwards (-d_k) at
+    ceil(cost * reverse_pct / 100), absent with reverse_pct == 0 (otherwise >= 100); slots 6 and 7 turn in place by one heading at `spin`,
+    absent with spin == 0 or K == 1.  ValueError for a value outside its range or a cost above 32767.  The defaults are a policy of this
+    layer alone (the C call has none)."""
+    who = "heading_moves"
+    try:
+        given = np.asarray(rotations)
+        rot = np.ascontiguousarray(given.astype(np.int32))
+        exact = given.shape == rot.shape and np.array_equal(given, rot)
+    except (TypeError, ValueError, OverflowError) as e:
+        raise ValueError(f"{who}: rotations must be [K, 2] int32: {e}") from None
+    if rot.ndim != 2 or rot.shape[1] != 2 or not exact or not 1 <= rot.shape[0] <= _lib.GG_HEADINGS_MAX:
+        raise ValueError(f"{who}: rotations are [K, 2] int32 with 1 <= K <= {_lib.GG_HEADINGS_MAX}")
+    par = {"step": step, "unit": unit, "turn": turn, "reverse_pct": reverse_pct, "spin": spin}
+    for name, v in par.items():
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError(f"{who}: {name} is an int32")
+    K = rot.shape[0]
+    moves = np.zeros((K, _lib.GG_HEADINGS_MAX_MOVES, 4), dtype=np.int32)
+    rc = _lib.load().gg_heading_moves(rot.ctypes.data_as(C.POINTER(C.c_int32)), K, int(step), int(unit), int(turn), int(reverse_pct), int(spin),
+                                      moves.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != _lib.GG_OK:
+        raise ValueError(f"{who}: step in [1, 3], unit in [1, 1024], turn >= 0, reverse_pct 0 or >= 100, spin >= 0, |rotation word| <= {_lib.GG_MATCH_UNIT} "
+                         f"and every cost <= {_lib.GG_HEADINGS_MAX_COST}: gg_heading_moves answered {_lib.STATUS.get(rc, rc)}")
+    return moves
+
+
 def goal_planes(cells, rows: int, cols: int, order: str = "row", device=None):
     """A goal plane per map for GroundSegmentation.route_planes from a list of goal cells, for "route from the robot cell": cells[i] is the
     list of (row, col) goals of map i (an empty list: no goal).  Returns torch.int32 [B, rows, cols] ([B, cols, rows] with order="col"): 0 on
@@ -1306,6 +1352,141 @@ class GroundSegmentation:
         x.d_counts = res.counts.data_ptr() if counts else None
         stream = self._stream_arg(on_torch_stream, blocked.device)
         _check(self._L, self._ctx, self._L.gg_footprint_planes(self._ctx, C.byref(x), stream), "gg_footprint_planes")
+        return res
+
+    def route_headings(self, mask, goals, moves, cost=None, *, goal_headings: int = 0xFFFFFFFF, cost_max: int = 252, max_cost: int = 0,
+                       order: str = "row", next: bool = True, best: bool = True, counts: bool = True, starts=None, max_len: int = 0,
+                       out: Optional[HeadingOutputs] = None, on_torch_stream: bool = False) -> HeadingOutputs:
+        """The navigation function of a state lattice over cells and headings of many maps (gg_route_headings): per cell and heading the
+        exact cost of the cheapest chain of moves to a goal state, every state on it one the heading mask admits.  mask: a contiguous CUDA
+        torch.int32 tensor [B, rows, cols] ([B, cols, rows] with order="col"), B <= n_slots: state (k, cell) is admissible where bit k is
+        set -- FootprintOutputs.mask as it is.  goals: same shape: a goal cell where the word is >= 0 -- FusionOutputs.frontier as it is, or
+        goal_planes(); heading k of a goal cell is a goal state where bit k of goal_headings is set and the state is admissible.  moves:
+        heading_moves(...), int32 [K, 8, 4] with 1 <= K <= 32, shared by all maps: entry m of heading k = (da, db, k2, s) leads from
+        (k, (r, c)) to (k2, (r + da, c + db)) at s * min(max(cost word, 1), cost_max) of the cell entered (cost None: 1 everywhere);
+        s == 0 marks an absent entry.  The cells between the ends of a move longer than one cell are not looked at: pad the footprint.
+        dist [B, K, rows, cols] is _lib.GG_ROUTE_NONE on an inadmissible state, where no chain leads to a goal, or where it costs more
+        than max_cost > 0.  next: the smallest slot whose move attains dist, _lib.GG_HEADINGS_AT_GOAL on a goal state, -1 unreached.
+        best / best_heading [B, rows, cols]: the least dist over the headings and the smallest heading that attains it (-1: none).
+        counts int32 [B, 3]: goal, reached and admissible states.
+        starts: [B, 2] (linear cell index in `order` or -1, heading): with max_len >= 1, paths [B, max_len, 2] holds the (cell, heading)
+        pairs from the start state to the goal state and path_len [B] the length of the whole path (0: unreached); the pairs from path_len
+        on keep what they held (-1 in a tensor this call allocates).
+        The limit max s * cost_max * rows * cols * K <= 2^31 - 2 keeps every sum inside an int32.  next=False / best=False / counts=False
+        leave those out (None).  `out`: a HeadingOutputs of an earlier call with the same arguments, whose tensors are reused; it may not
+        hold an input.  Integer arithmetic only: bit-identical from run to run.  Enqueued on the context's own stream or, with
+        on_torch_stream=True, on the current torch stream; nothing synchronises.  No map is read or changed."""
+        import torch
+
+        who = "route_headings"
+        if order not in ("row", "col"):
+            raise ValueError(f"{who}: order is 'row' or 'col'")
+        par = {"goal_headings": goal_headings, "cost_max": cost_max, "max_cost": max_cost, "max_len": max_len}
+        for name, v in par.items():
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{who}: {name} is an integer")
+        if not 0 <= goal_headings <= 0xFFFFFFFF:
+            raise ValueError(f"{who}: goal_headings is a uint32 mask")
+        if not 1 <= cost_max <= _lib.GG_ROUTE_NONE:
+            raise ValueError(f"{who}: cost_max >= 1")
+        if not 0 <= max_cost <= _lib.GG_ROUTE_NONE:
+            raise ValueError(f"{who}: max_cost lies in [0, 2^31 - 1]")
+        if max_len < 0 or max_len > _lib.GG_ROUTE_NONE or (starts is None and max_len != 0):
+            raise ValueError(f"{who}: max_len is >= 1 with starts and 0 without")
+        try:
+            given = np.asarray(moves)
+            host_moves = np.ascontiguousarray(given.astype(np.int32))
+            exact = given.shape == host_moves.shape and np.array_equal(given, host_moves)
+        except (TypeError, ValueError, OverflowError) as e:
+            raise ValueError(f"{who}: moves must be [K, 8, 4] int32: {e}") from None
+        if host_moves.ndim != 3 or host_moves.shape[1:] != (_lib.GG_HEADINGS_MAX_MOVES, 4) or not exact or not 1 <= host_moves.shape[0] <= _lib.GG_HEADINGS_MAX:
+            raise ValueError(f"{who}: moves of shape {host_moves.shape} are not [K, 8, 4] int32 with 1 <= K <= {_lib.GG_HEADINGS_MAX}")
+        K = int(host_moves.shape[0])
+        present = host_moves[:, :, 3] != 0
+        s = host_moves[:, :, 3][present]
+        if ((s < 1) | (s > _lib.GG_HEADINGS_MAX_COST)).any():
+            raise ValueError(f"{who}: a move's cost lies outside [1, {_lib.GG_HEADINGS_MAX_COST}]")
+        if (np.abs(host_moves[:, :, :2][present]) > _lib.GG_HEADINGS_MAX_STEP).any():
+            raise ValueError(f"{who}: a move is longer than {_lib.GG_HEADINGS_MAX_STEP} cells")
+        k2 = host_moves[:, :, 2]
+        if ((k2 < 0) | (k2 >= K))[present].any():
+            raise ValueError(f"{who}: a move's heading lies outside [0, K)")
+        own = (host_moves[:, :, 0] == 0) & (host_moves[:, :, 1] == 0) & (k2 == np.arange(K)[:, None])
+        if (own & present).any():
+            raise ValueError(f"{who}: a move leads to its own state")
+        if (int(s.max()) if s.size else 0) * cost_max * self.rows * self.cols * K > _lib.GG_HEADINGS_LIMIT:
+            raise ValueError(f"{who}: max s * cost_max * rows * cols * K exceeds 2^31 - 2")
+        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
+
+        def is_planes(t):
+            return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 3 and t.is_contiguous() and tuple(t.shape[1:]) == plane
+
+        if not is_planes(mask):
+            raise ValueError(f"{who}: mask must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
+        B = int(mask.shape[0])
+        for name, t in (("goals", goals), ("cost", cost)):
+            if (t is not None or name == "goals") and not (is_planes(t) and t.shape[0] == B and t.device == mask.device):
+                raise ValueError(f"{who}: {name} must be a contiguous CUDA torch.int32 tensor of the shape and device of mask")
+        host_starts = None
+        if starts is not None:
+            try:
+                given = np.asarray(starts)
+                host_starts = np.ascontiguousarray(given.astype(np.int32))
+                exact = given.shape == host_starts.shape and np.array_equal(given, host_starts)
+            except (TypeError, ValueError, OverflowError) as e:
+                raise ValueError(f"{who}: starts must be [B, 2] int32: {e}") from None
+            if host_starts.shape != (B, 2) or not exact:
+                raise ValueError(f"{who}: starts of shape {host_starts.shape} are not [B, 2] int32")
+            cell, heading = host_starts[:, 0], host_starts[:, 1]
+            if ((cell < -1) | (cell >= self.rows * self.cols)).any():
+                raise ValueError(f"{who}: a start cell lies outside [-1, rows * cols)")
+            if ((cell >= 0) & ((heading < 0) | (heading >= K))).any():
+                raise ValueError(f"{who}: a start heading lies outside [0, K)")
+            if max_len < 1:
+                raise ValueError(f"{who}: starts needs max_len >= 1")
+        res = out if out is not None else HeadingOutputs()
+        with_paths = host_starts is not None
+        want = {"dist": (B, K) + plane, "next": (B, K) + plane if next else None, "best": (B,) + plane if best else None,
+                "best_heading": (B,) + plane if best else None, "counts": (B, 3) if counts else None,
+                "paths": (B, max_len, 2) if with_paths else None, "path_len": (B,) if with_paths else None}
+        inputs = [t.data_ptr() for t in (mask, goals, cost) if t is not None]
+        for field, sh in want.items():
+            t = getattr(res, field)
+            if sh is None:
+                if t is not None:
+                    raise ValueError(f"{who}: out.{field} is given but not asked for")
+                continue
+            if t is None:
+                continue
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == sh and t.is_contiguous() and t.device == mask.device):
+                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
+            if t.data_ptr() in inputs:
+                raise ValueError(f"{who}: out.{field} is an input of the call: no update in place is defined")
+        for field, sh in want.items():
+            if sh is not None and getattr(res, field) is None:
+                if field == "paths":  # (the call leaves the pairs behind a path alone)
+                    setattr(res, field, torch.full(sh, -1, dtype=torch.int32, device=mask.device))
+                else:
+                    setattr(res, field, torch.empty(sh, dtype=torch.int32, device=mask.device))
+        self._torch_used = True
+        x = _lib.GGHeadingRoutes()
+        cells = self.rows * self.cols
+        x.n, x.d_mask, x.mask_stride, x.d_goals, x.goal_stride = B, mask.data_ptr(), cells, goals.data_ptr(), cells
+        x.d_cost, x.cost_stride = (cost.data_ptr(), cells) if cost is not None else (None, 0)
+        x.goal_headings, x.n_headings, x.moves = int(goal_headings), K, host_moves.ctypes.data_as(C.POINTER(C.c_int32))
+        x.cost_max, x.max_cost = int(cost_max), int(max_cost)
+        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.d_dist, x.dist_stride, x.plane_stride = res.dist.data_ptr(), K * cells, cells
+        if next:
+            x.d_next, x.next_stride, x.next_plane_stride = res.next.data_ptr(), K * cells, cells
+        if best:
+            x.d_best, x.best_stride, x.d_best_heading, x.best_heading_stride = res.best.data_ptr(), cells, res.best_heading.data_ptr(), cells
+        x.d_counts = res.counts.data_ptr() if counts else None
+        if with_paths:
+            x.starts = host_starts.ctypes.data_as(C.POINTER(C.c_int32))
+            x.d_paths, x.path_stride, x.max_len, x.d_path_len = res.paths.data_ptr(), 2 * int(max_len), int(max_len), res.path_len.data_ptr()
+        stream = self._stream_arg(on_torch_stream, mask.device)
+        _check(self._L, self._ctx, self._L.gg_route_headings(self._ctx, C.byref(x), stream), "gg_route_headings")
         return res
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:

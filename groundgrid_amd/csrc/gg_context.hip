@@ -228,6 +228,8 @@ struct gg_context : ContextBuffers {
     int2 *d_export_rotations = nullptr, *h_export_rotations = nullptr; // ... the rotation table of a call, [PARAM_RING][MATCH_MAX_ROTATIONS]
     MatchPartial *d_match_partials = nullptr; // ... what its two launches hand over, [PARAM_RING][n_slots][MATCH_MAX_ROTATIONS], device only
     uint32_t *d_export_footprint = nullptr, *h_export_footprint = nullptr; // gg_footprint_planes: the packed span table of a call, [PARAM_RING][FOOTPRINT_TABLE]
+    uint32_t *d_export_moves = nullptr, *h_export_moves = nullptr; // gg_route_headings: the packed move table of a call, [PARAM_RING][HEADINGS_TABLE]
+    int2 *d_export_poses = nullptr, *h_export_poses = nullptr; // gg_route_headings: the per-map start (cell, heading) of a call, [PARAM_RING][n_slots]
     ParamRing export_ring;
     int slopes_variant = 0; // tuning "slopes_variant": 0 = k_slopes_tiled, 1 = k_slopes_gather (the A/B of tools/bench_slopes.py)
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
@@ -1989,7 +1991,13 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     const size_t o_footprint = align_up(o_match + ring * MATCH_MAX_ROTATIONS * sizeof(MatchPartial), 256);
     const size_t h_footprint = align_up(h_rotations + rotations_bytes, 256);
     const size_t footprint_bytes = (size_t)PARAM_RING * FOOTPRINT_TABLE * sizeof(uint32_t);
-    if (const int rc = alloc_call_scratch(ctx, who, st, o_footprint + footprint_bytes, h_footprint + footprint_bytes,
+    // (gg_route_headings: its packed move table and the start poses of its maps, per ring entry)
+    const size_t o_moves = align_up(o_footprint + footprint_bytes, 256);
+    const size_t h_moves = align_up(h_footprint + footprint_bytes, 256);
+    const size_t moves_bytes = (size_t)PARAM_RING * HEADINGS_TABLE * sizeof(uint32_t);
+    const size_t o_poses = align_up(o_moves + moves_bytes, 256);
+    const size_t h_poses = align_up(h_moves + moves_bytes, 256);
+    if (const int rc = alloc_call_scratch(ctx, who, st, o_poses + ring * sizeof(int2), h_poses + ring * sizeof(int2),
                                           {{o_off, off.data(), off.size() * sizeof(uint32_t)}, {o_elem, elem.data(), elem.size() * sizeof(uint32_t)}, {o_cell, cell.data(), cell.size() * sizeof(uint16_t)}},
                                           &ctx->export_mem, &ctx->export_ring))
         return rc;
@@ -2014,6 +2022,10 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     ctx->d_match_partials = (MatchPartial *)(block + o_match);
     ctx->d_export_footprint = (uint32_t *)(block + o_footprint);
     ctx->h_export_footprint = (uint32_t *)(h + h_footprint);
+    ctx->d_export_moves = (uint32_t *)(block + o_moves);
+    ctx->h_export_moves = (uint32_t *)(h + h_moves);
+    ctx->d_export_poses = (int2 *)(block + o_poses);
+    ctx->h_export_poses = (int2 *)(h + h_poses);
     return GG_OK;
 }
 
@@ -2858,6 +2870,204 @@ int gg_footprint_planes(gg_context *ctx, const gg_plane_footprints *x, void *str
     fa.fit_stride = x->fit_stride;
     fa.counts = x->d_counts;
     launch_footprint(fa, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
+// The move table of a car-like vehicle for gg_route_headings: host integer arithmetic only, no context
+int gg_heading_moves(const int32_t *rotations, int n_rotations, int step, int unit, int turn, int reverse_pct, int spin, int32_t *moves)
+{
+    if (!rotations || !moves) return GG_ERR_INVALID;
+    if (n_rotations < 1 || n_rotations > HEADINGS_MAX) return GG_ERR_INVALID;
+    for (int k = 0; k < 2 * n_rotations; ++k)
+        if (rotations[k] < -GG_MATCH_UNIT || rotations[k] > GG_MATCH_UNIT) return GG_ERR_INVALID;
+    if (step < 1 || step > HEADINGS_MAX_STEP || unit < 1 || unit > 1024 || turn < 0 || spin < 0) return GG_ERR_INVALID;
+    if (reverse_pct != 0 && reverse_pct < 100) return GG_ERR_INVALID;
+    const int K = n_rotations;
+    const auto rha = [](int32_t v) { return v < 0 ? -((-v + GG_MATCH_UNIT / 2) >> 14) : (v + GG_MATCH_UNIT / 2) >> 14; };
+    std::vector<int32_t> table((size_t)K * HEADINGS_MAX_MOVES * 4, 0);
+    bool fits = true;
+    const auto put = [&](int k, int m, int da, int db, int k2, int64_t s) {
+        int32_t *e = table.data() + ((size_t)k * HEADINGS_MAX_MOVES + m) * 4;
+        if (s > HEADINGS_MAX_COST) fits = false;
+        e[0] = da, e[1] = db, e[2] = k2, e[3] = (int32_t)std::min<int64_t>(s, HEADINGS_MAX_COST);
+    };
+    for (int k = 0; k < K; ++k) {
+        const int da = rha(step * rotations[2 * k]), db = rha(step * rotations[2 * k + 1]);
+        const int left = (k + 1) % K, right = (k + K - 1) % K;
+        if (da != 0 || db != 0) {
+            const int64_t sq = (int64_t)unit * unit * (da * da + db * db); // <= 2^20 * 18
+            int64_t root = (int64_t)std::sqrt((double)sq);
+            while (root * root > sq) --root;
+            while ((root + 1) * (root + 1) <= sq) ++root;
+            const int64_t s = std::max<int64_t>(1, root), st = s + turn;
+            put(k, 0, da, db, k, s);
+            put(k, 1, da, db, left, st);
+            put(k, 2, da, db, right, st);
+            if (reverse_pct) {
+                const auto back = [&](int64_t c) { return (c * reverse_pct + 99) / 100; };
+                put(k, 3, -da, -db, k, back(s));
+                put(k, 4, -da, -db, left, back(st));
+                put(k, 5, -da, -db, right, back(st));
+            }
+        }
+        if (spin && K > 1) {
+            put(k, 6, 0, 0, left, spin);
+            put(k, 7, 0, 0, right, spin);
+        }
+    }
+    if (!fits) return GG_ERR_INVALID;
+    std::copy(table.begin(), table.end(), moves);
+    return GG_OK;
+}
+
+// The cost-to-go over cells and headings of many maps (k22_headings.hip): a ring entry and the ordering of the export for maps 0 .. n-1, none
+// of which is read, as gg_route_planes and gg_footprint_planes; the move table travels in the ring entry in (line, position) offsets (da and
+// db swapped for column-major planes) and packed (headings_pack), and so do the start poses.  Nothing is synchronised, no map is filled and
+// no host-side flag changes.
+int gg_route_headings(gg_context *ctx, const gg_heading_routes *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_route_headings";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_heading_routes");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    const int rows = ctx->arena.g.rows, cols = ctx->arena.g.cols;
+    if (!x->d_mask || !x->d_goals || !x->d_dist) return fail(ctx, GG_ERR_INVALID, who, "d_mask, d_goals and d_dist are required");
+    if (!x->moves) return fail(ctx, GG_ERR_INVALID, who, "moves is required");
+    if (x->n_headings < 1 || x->n_headings > HEADINGS_MAX) return fail(ctx, GG_ERR_INVALID, who, "n_headings lies in [1, 32]");
+    const int K = x->n_headings;
+    if (x->mask_stride < C) return fail(ctx, GG_ERR_INVALID, who, "mask_stride is smaller than rows * cols");
+    if (x->d_cost && x->cost_stride < C) return fail(ctx, GG_ERR_INVALID, who, "cost_stride is smaller than rows * cols");
+    if (x->goal_stride < C) return fail(ctx, GG_ERR_INVALID, who, "goal_stride is smaller than rows * cols");
+    if (x->plane_stride < C || x->dist_stride / (size_t)K < x->plane_stride) return fail(ctx, GG_ERR_INVALID, who, "plane_stride >= rows * cols and dist_stride >= n_headings * plane_stride");
+    if (x->d_next && (x->next_plane_stride < C || x->next_stride / (size_t)K < x->next_plane_stride))
+        return fail(ctx, GG_ERR_INVALID, who, "next_plane_stride >= rows * cols and next_stride >= n_headings * next_plane_stride");
+    if (x->d_best && x->best_stride < C) return fail(ctx, GG_ERR_INVALID, who, "best_stride is smaller than rows * cols");
+    if (x->d_best_heading && x->best_heading_stride < C) return fail(ctx, GG_ERR_INVALID, who, "best_heading_stride is smaller than rows * cols");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->cost_max < 1) return fail(ctx, GG_ERR_INVALID, who, "cost_max < 1");
+    if (x->max_cost < 0) return fail(ctx, GG_ERR_INVALID, who, "max_cost < 0");
+    int s_max = 0;
+    for (int k = 0; k < K; ++k)
+        for (int m = 0; m < HEADINGS_MAX_MOVES; ++m) {
+            const int32_t *e = x->moves + ((size_t)k * HEADINGS_MAX_MOVES + m) * 4;
+            if (e[3] == 0) continue; // an absent entry: its other words are not looked at
+            if (e[3] < 1 || e[3] > HEADINGS_MAX_COST) return fail(ctx, GG_ERR_INVALID, who, "a move's cost lies outside [1, 32767]");
+            if (std::abs(e[0]) > HEADINGS_MAX_STEP || std::abs(e[1]) > HEADINGS_MAX_STEP) return fail(ctx, GG_ERR_INVALID, who, "a move is longer than 3 cells");
+            if (e[2] < 0 || e[2] >= K) return fail(ctx, GG_ERR_INVALID, who, "a move's heading lies outside [0, n_headings)");
+            if (e[0] == 0 && e[1] == 0 && e[2] == k) return fail(ctx, GG_ERR_INVALID, who, "a move leads to its own state");
+            s_max = std::max(s_max, e[3]);
+        }
+    // every true D fits an int32 and the unsigned sum of a stored word and one move cannot wrap (k22_headings.hip relies on it).  The product
+    // of the first two factors is < 2^46, so the test by division is exact and nothing here overflows
+    const uint64_t step_max = (uint64_t)s_max * (uint64_t)x->cost_max, states = (uint64_t)C * (uint64_t)K;
+    if (step_max > (uint64_t)GG_ROUTE_NONE - 1 || step_max > ((uint64_t)GG_ROUTE_NONE - 1) / states)
+        return fail(ctx, GG_ERR_INVALID, who, "max s * cost_max * rows * cols * n_headings exceeds 2^31 - 2");
+    if (x->starts) {
+        if (!x->d_paths || !x->d_path_len || x->max_len < 1) return fail(ctx, GG_ERR_INVALID, who, "starts needs d_paths, d_path_len and max_len >= 1");
+        if (x->path_stride / 2 < (size_t)x->max_len) return fail(ctx, GG_ERR_INVALID, who, "path_stride is smaller than 2 * max_len");
+        if (x->n <= ctx->n_slots) // (beyond that the call is refused below, and starts[] is the caller's to size by n)
+            for (int i = 0; i < x->n; ++i) {
+                const int32_t cell = x->starts[2 * i], heading = x->starts[2 * i + 1];
+                if (cell < -1 || (int64_t)cell >= (int64_t)C) return fail(ctx, GG_ERR_INVALID, who, "a start cell lies outside [-1, rows * cols)");
+                if (cell >= 0 && (heading < 0 || heading >= K)) return fail(ctx, GG_ERR_INVALID, who, "a start heading lies outside [0, n_headings)");
+            }
+    }
+    if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
+    const bool row_major = x->order == GG_PLANES_ROWMAJOR;
+    HeadingsArgs ha{};
+    ha.nx = row_major ? cols : rows;
+    ha.ny = row_major ? rows : cols;
+    ha.tile = headings_tile(K);
+    ha.tiles_x = (ha.nx + ha.tile - 1) / ha.tile;
+    ha.tiles_y = (ha.ny + ha.tile - 1) / ha.tile;
+    if ((int64_t)ha.tiles_x * ha.tiles_y > HEADINGS_MAX_TILES) return fail(ctx, GG_ERR_GEOMETRY, who, "the map has more than 4096 tiles");
+    // no output may share a byte with an input or another output, by the ranges of gg_route_planes: from a buffer's first word to the last
+    // cell of its last plane
+    struct Range {
+        const char *name, *lo, *hi;
+        bool out;
+    };
+    const auto span = [&](const char *name, const void *p, size_t words, bool out) { return Range{name, (const char *)p, (const char *)p + words * sizeof(int32_t), out}; };
+    const size_t last = (size_t)(x->n - 1);
+    const Range ranges[10] = {span("d_mask", x->d_mask, last * x->mask_stride + C, false),
+                              span("d_cost", x->d_cost, last * x->cost_stride + C, false),
+                              span("d_goals", x->d_goals, last * x->goal_stride + C, false),
+                              span("d_dist", x->d_dist, last * x->dist_stride + (size_t)(K - 1) * x->plane_stride + C, true),
+                              span("d_next", x->d_next, last * x->next_stride + (size_t)(K - 1) * x->next_plane_stride + C, true),
+                              span("d_best", x->d_best, last * x->best_stride + C, true),
+                              span("d_best_heading", x->d_best_heading, last * x->best_heading_stride + C, true),
+                              span("d_counts", x->d_counts, (size_t)x->n * 3, true),
+                              span("d_paths", x->starts ? x->d_paths : nullptr, x->starts ? last * x->path_stride + 2 * (size_t)x->max_len : 0, true),
+                              span("d_path_len", x->starts ? x->d_path_len : nullptr, (size_t)x->n, true)};
+    for (int i = 0; i < 10; ++i)
+        for (int j = i + 1; j < 10; ++j) {
+            const Range &p = ranges[i], &q = ranges[j];
+            if (!p.lo || !q.lo || !(p.out || q.out)) continue;
+            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
+                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
+        }
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    uint32_t *ht = ctx->h_export_moves + (size_t)f.g * HEADINGS_TABLE, *dt = ctx->d_export_moves + (size_t)f.g * HEADINGS_TABLE;
+    for (int k = 0; k < K; ++k) {
+        // the heading's first translating move decides how a slot walks the tile for it: along the axis the move is longer in, against the move
+        int first_line = 0, first_pos = 0;
+        uint8_t walk = 0;
+        for (int m = 0; m < HEADINGS_MAX_MOVES; ++m) {
+            const int32_t *e = x->moves + ((size_t)k * HEADINGS_MAX_MOVES + m) * 4;
+            const int d_line = row_major ? e[0] : e[1], d_pos = row_major ? e[1] : e[0];
+            ht[k * HEADINGS_MAX_MOVES + m] = e[3] == 0 ? 0u : headings_pack(d_line, d_pos, e[2], e[3]);
+            if (e[3] == 0 || (d_line == 0 && d_pos == 0)) continue;
+            const bool positions = std::abs(d_pos) > std::abs(d_line);
+            if (first_line == 0 && first_pos == 0) {
+                first_line = d_line, first_pos = d_pos;
+                walk = (positions ? HEADINGS_WALK_POSITIONS : 0) | ((positions ? d_pos : d_line) > 0 ? HEADINGS_WALK_BACK : 0);
+                continue;
+            }
+            const bool first_positions = (walk & HEADINGS_WALK_POSITIONS) != 0;
+            if (positions != first_positions) walk |= HEADINGS_WALK_ALT_AXIS;
+            if ((first_positions ? d_pos * first_pos : d_line * first_line) < 0) walk |= HEADINGS_WALK_ALT_DIR;
+        }
+        ha.walk[k] = walk;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(dt, ht, sizeof(uint32_t) * K * HEADINGS_MAX_MOVES, hipMemcpyHostToDevice, f.st));
+    if (x->starts) {
+        int2 *hs = ctx->h_export_poses + (size_t)f.g * ctx->n_slots, *ds = ctx->d_export_poses + (size_t)f.g * ctx->n_slots;
+        for (int i = 0; i < x->n; ++i) hs[i] = make_int2(x->starts[2 * i], x->starts[2 * i] >= 0 ? x->starts[2 * i + 1] : 0);
+        HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(int2) * x->n, hipMemcpyHostToDevice, f.st));
+        ha.starts = ds;
+        ha.paths = x->d_paths;
+        ha.path_stride = x->path_stride;
+        ha.max_len = x->max_len;
+        ha.path_len = x->d_path_len;
+    }
+    ha.mask = x->d_mask;
+    ha.mask_stride = x->mask_stride;
+    ha.cost = x->d_cost;
+    ha.cost_stride = x->cost_stride;
+    ha.goals = x->d_goals;
+    ha.goal_stride = x->goal_stride;
+    ha.goal_headings = x->goal_headings;
+    ha.n_headings = K;
+    ha.table = dt;
+    ha.cost_max = x->cost_max;
+    ha.reach = x->max_cost > 0 ? (uint32_t)x->max_cost : (uint32_t)GG_ROUTE_NONE - 1u;
+    ha.max_rounds = (int)std::min<uint64_t>(states, (uint64_t)GG_ROUTE_NONE - 1);
+    ha.max_sweeps = K * ha.tile * ha.tile;
+    ha.dist = x->d_dist;
+    ha.dist_stride = x->dist_stride;
+    ha.plane_stride = x->plane_stride;
+    ha.next = x->d_next;
+    ha.next_stride = x->next_stride;
+    ha.next_plane_stride = x->next_plane_stride;
+    ha.best = x->d_best;
+    ha.best_stride = x->best_stride;
+    ha.best_heading = x->d_best_heading;
+    ha.best_heading_stride = x->best_heading_stride;
+    ha.counts = x->d_counts;
+    launch_headings(ha, x->n, f.st);
     return map_call_end(ctx, f);
 }
 

@@ -537,6 +537,58 @@ struct FootprintArgs {
     int32_t *counts;               // nullable; [map][3]
 };
 
+// gg_route_headings (k22_headings.hip).  Map i of the call is row i of every buffer.  A plane is `ny` lines of `nx` contiguous words: (nx, ny) =
+// (cols, rows) row-major, (rows, cols) column-major.  The kernel knows lines and positions along a line alone: the entry point hands it the
+// move table in (line, position) offsets (the caller's (da, db) row-major, swapped column-major), one packed word per move (headings_pack),
+// and per heading how a wavefront best walks a tile for that heading's moves (headings_walk).  One work-group relaxes a map tile by tile;
+// the tile side depends on the number of headings (headings_tile; _lib.py mirrors it for the tests of the tile seams)
+constexpr int HEADINGS_MAX = 32;       // headings
+constexpr int HEADINGS_MAX_MOVES = 8;  // moves per heading
+constexpr int HEADINGS_MAX_STEP = 3;   // cells a move spans along either axis: the halo of a tile
+constexpr int HEADINGS_MAX_COST = 32767;
+constexpr int HEADINGS_AT_GOAL = 8;    // d_next of a goal state
+constexpr int HEADINGS_TABLE = HEADINGS_MAX * HEADINGS_MAX_MOVES; // packed words of one call's table
+constexpr int HEADINGS_MAX_TILES = 4096; // tiles of a map: more is GG_ERR_GEOMETRY
+constexpr int HEADINGS_THREADS = 512;  // of the relaxing work-group
+inline int headings_tile(int n_headings) { return n_headings <= 16 ? 32 : 16; }
+// bits 0-2: line offset + 3, 3-5: position offset + 3, 6-10: k2, 11-25: s; an absent move is the word 0 (s == 0)
+inline uint32_t headings_pack(int d_line, int d_pos, int k2, int s)
+{
+    return s == 0 ? 0u : (uint32_t)(d_line + HEADINGS_MAX_STEP) | (uint32_t)(d_pos + HEADINGS_MAX_STEP) << 3 | (uint32_t)k2 << 6 | (uint32_t)s << 11;
+}
+// how the slots of k_headings_relax walk a tile for heading k: bit 0: a lane per LINE, stepping along the positions (else a lane per position,
+// stepping over the lines); bit 1: from the last step to the first; bit 2: turn the direction round every other sweep; bit 3: swap the axis
+// every other pair of sweeps
+enum : uint8_t { HEADINGS_WALK_POSITIONS = 1, HEADINGS_WALK_BACK = 2, HEADINGS_WALK_ALT_DIR = 4, HEADINGS_WALK_ALT_AXIS = 8 };
+struct HeadingsArgs {
+    const uint32_t *mask;          // map i's plane at mask + i * mask_stride: state (k, q) is admissible where bit k of q's word is set
+    size_t mask_stride;
+    const int32_t *cost;           // ... at cost + i * cost_stride: w = min(max(word, 1), cost_max); nullable: w = 1
+    size_t cost_stride;
+    const int32_t *goals;          // ... at goals + i * goal_stride: a goal cell where the word is >= 0
+    size_t goal_stride;
+    uint32_t goal_headings;        // bit k: heading k of a goal cell is a goal state
+    int n_headings;                // K
+    const uint32_t *table;         // device [K][8] packed moves (the call's ring entry)
+    uint8_t walk[HEADINGS_MAX];    // HEADINGS_WALK_* per heading
+    int nx, ny, tile, tiles_x, tiles_y;
+    int cost_max;
+    uint32_t reach;                // a tentative D above this is not stored: max_cost, or GG_ROUTE_NONE - 1
+    int max_rounds, max_sweeps;    // min(K * rows * cols, 2^31 - 2) and K * tile * tile: the bounds of the two loops of k_headings_relax
+    int32_t *dist;                 // plane k of map i at dist + i * dist_stride + k * plane_stride: the working memory
+    size_t dist_stride, plane_stride;
+    int32_t *next;                 // nullable; ... at next + i * next_stride + k * next_plane_stride
+    size_t next_stride, next_plane_stride;
+    int32_t *best, *best_heading;  // nullable; map i's plane at + i * best_stride / best_heading_stride
+    size_t best_stride, best_heading_stride;
+    int32_t *counts;               // [map][3] goal, reached, admissible states; nullable
+    const int2 *starts;            // device [map] (the call's ring entry): (linear index of the start cell or -1, heading); null: no paths
+    int32_t *paths;                // map i's row of (cell, heading) pairs at paths + i * path_stride
+    size_t path_stride;
+    int max_len;                   // pairs of a row
+    int32_t *path_len;             // [map]
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -588,6 +640,7 @@ void launch_fuse(const FuseArgs &x, int n_maps, hipStream_t s);                 
 void launch_route(const RouteArgs &x, int n_maps, hipStream_t s);                                // k19_route.hip: relax, (counts := 0, next,) (paths)
 void launch_match(const MatchArgs &x, int n_maps, hipStream_t s);                                // k20_match.hip: k_match_scores, k_match_best
 void launch_footprint(const FootprintArgs &x, int n_maps, hipStream_t s);                        // k21_footprint.hip: (counts := 0,) k_footprint_planes
+void launch_headings(const HeadingsArgs &x, int n_maps, hipStream_t s);                          // k22_headings.hip: relax, (counts := 0, next,) (paths)
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

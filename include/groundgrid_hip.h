@@ -1239,6 +1239,139 @@ int gg_footprint_planes(gg_context *ctx, const gg_plane_footprints *x, void *str
 int gg_footprint_spans(const int32_t *rotations, int n_rotations, const int32_t rect[4], int radius, int32_t *spans, int *needed);
 #define GG_HAS_FOOTPRINT_PLANES 1
 
+/* The NAVIGATION FUNCTION OF A STATE LATTICE, SE(2) on the grid, for many maps in DEVICE memory: gg_route_planes routes a point without a
+ * heading, and gg_footprint_planes says at which headings a vehicle fits at a cell; the only way from one to the other is the d_fit
+ * projection, which throws the headings away -- it does not know that a car cannot turn on the spot, has to back out of a dead end, or needs
+ * room to swing round a corner.  gg_route_headings reads the heading mask: for every cell and every one of K headings it gives the exact cost D
+ * of the cheapest chain of motion primitives ("moves") to a goal state, every state on the chain one the mask admits; the move to take, the
+ * best heading per cell, three counts per map and, from one start pose per map, the path.  What a caller otherwise gets per map and per frame
+ * from a download of the mask, a graph of (cell, heading) nodes, Dijkstra on the host and an upload.  Map i of the call is row i of every
+ * buffer and of `starts`.  Everything is 32-bit integer and in (row, col) terms whatever `order` is; all of the following is per map:
+ *   states       K = n_headings (1 .. 32).  A state is (k, q), heading k at cell q.  It is ADMISSIBLE where q lies inside the map and bit k of
+ *                map i's d_mask word of q is set (a d_mask plane of gg_footprint_planes as it stands).  Bits K .. 31 are ignored.  Required.
+ *   weight       w(q) = min(max(word of d_cost, 1), cost_max); 1 everywhere when d_cost is NULL: exactly as in gg_route_planes.
+ *   moves        a HOST table moves[K][GG_HEADINGS_MAX_MOVES = 8][4] of int32, shared by all maps of the call: entry m of heading k is
+ *                (da, db, k2, s).  s == 0 is an absent entry, whose other words are not looked at.  Otherwise 1 <= s <= 32767,
+ *                |da|, |db| <= GG_HEADINGS_MAX_STEP = 3, 0 <= k2 < K, and not (da, db, k2) == (0, 0, k).  Turns in place (da = db = 0 with
+ *                k2 != k) are allowed.  The move leads from (k, (r, c)) to (k2, (r + da, c + db)); it is admissible when both states are;
+ *                it costs s * w of the cell ENTERED, (r + da, c + db), as in gg_route_planes.  The cells BETWEEN the two ends of a move
+ *                longer than one cell are NOT looked at: the footprint table of gg_footprint_planes is where a caller covers them (a
+ *                footprint padded by the length of the longest move sweeps every cell the vehicle passes over).  gg_heading_moves makes
+ *                the table of a car-like vehicle.
+ *   goals        (k, q) is a GOAL STATE when it is admissible, map i's d_goals word of q is >= 0 (a d_frontier plane of gg_fuse_states or
+ *                a goal plane as for gg_route_planes, as it stands; required) and bit k of goal_headings is set.  0xFFFFFFFF means "any
+ *                heading"; a goal_headings with none of its low K bits set means no goal state at all, which is legal.
+ *   D            0 on a goal state; elsewhere the minimum, over all finite chains of admissible moves from (k, q) to a goal state, of the
+ *                sum of the move costs; GG_ROUTE_NONE on an inadmissible state and where there is no such chain.  Equivalently D is the
+ *                solution of D(k, q) = min over the admissible moves m of (k, q) of D(k2_m, q + d_m) + s_m * w(q + d_m) with D = 0 on the goal
+ *                states and GG_ROUTE_NONE where the minimum is over nothing reached.  The solution is UNIQUE because every move costs at
+ *                least 1: two solutions that differ would differ at a state of smallest value among those where they differ, whose
+ *                minimising successor has a smaller value and so is equal in both -- a contradiction; hence D does not depend on how it
+ *                is computed.
+ *   limits       1 <= cost_max; max s (over the present moves) * cost_max * rows * cols * K <= 2^31 - 2, compared in 64 bits
+ *                (GG_ERR_INVALID beyond).  A chain without a repeated state has fewer than rows * cols * K moves, so every true D fits an
+ *                int32, every word the call stores while it works is <= 2^31 - 1 and one move costs <= 2^31 - 2: the UNSIGNED sum of a
+ *                stored word and a move cannot wrap, which the kernel relies on.  The C ABI has no defaults.
+ *   max_cost     R > 0: a state with D > R is reported as unreached (d_dist = GG_ROUTE_NONE, d_next = -1, not counted as reached, not a
+ *                candidate of d_best); every other word is that of R = 0.  0: unbounded.
+ *   d_dist       required, int32: K planes per map, plane k of map i at d_dist + i * dist_stride + k * plane_stride, plane_stride >=
+ *                rows * cols and dist_stride >= K * plane_stride; cell (row, col) where `order` puts it.  d_dist[k][q] = D(k, q).  It is
+ *                the call's working memory.
+ *   d_next       nullable, int32, the same addressing with next_stride and next_plane_stride of its own: GG_HEADINGS_AT_GOAL (= 8) on a
+ *                goal state, -1 where D is GG_ROUTE_NONE, otherwise the SMALLEST m whose admissible move attains the minimum.  Following
+ *                it lowers D by at least 1 per move: every chain ends on a goal state and has no cycle.
+ *   d_best, d_best_heading   nullable, one plane per map each at + i * best_stride / best_heading_stride: the minimum over k of D(k, q) and
+ *                the SMALLEST k that attains it; GG_ROUTE_NONE and -1 where no heading of the cell is reached.  The plane a caller draws
+ *                and compares with gg_route_planes'.
+ *   d_counts[i]  nullable, three words per map: the number of goal states, of reached states (goal states included; under max_cost), and
+ *                of admissible states.
+ *   paths        with `starts`, a host array [n][2] of (cell, heading), cell a linear index in `order` or -1 for no start (the heading is
+ *                then not looked at): map i's path is the start state, the state its d_next move leads to, ... up to and including the
+ *                goal state.  d_paths holds rows of (cell, heading) pairs, path_stride words apart (>= 2 * max_len), at most max_len pairs
+ *                each; d_path_len[i] is the number of states of the whole path, also when that exceeds max_len.  Pair j of row i is
+ *                written for j < min(len, max_len) and the other words of the row never are.  The cell numbering, the unreached start
+ *                (len 0, row untouched), the absent start and the truncation are exactly those of gg_route_planes' paths.  d_next need not
+ *                be given for the paths.
+ *   addressing   map i's plane of rows * cols words at d_mask + i * mask_stride, d_cost + i * cost_stride, d_goals + i * goal_stride; the
+ *                same order for every plane of the call.  EVERY word of every given output plane inside rows * cols is written, of every
+ *                map and heading; the words between rows * cols and a stride never are, and a NULL output is not touched.  4-byte
+ *                alignment.
+ *   no overlap   no output may share a byte with an input or with another output; the call compares the address ranges as
+ *                gg_route_planes does (a buffer from its first word to the last cell of its last plane) and answers GG_ERR_INVALID.  The
+ *                inputs may overlap each other.
+ *   determinism  integer arithmetic only; D is a unique fixed point and d_next, d_best and the paths are functions of D: bit-identical
+ *                from run to run and independent of scheduling.
+ * The contract is that of gg_route_planes and gg_footprint_planes: NO MAP IS READ OR CHANGED -- no layer, position, freshness,
+ * configuration, score or liveness flag, and the lazily kept layers stay pending.  n <= n_slots (GG_ERR_CAPACITY): the call takes an entry
+ * of the same ring of parameter entries (the move table and the starts travel in it) and orders itself on `stream` as those calls do; it
+ * enqueues and returns with no synchronisation, and the host arrays may be freed on return.  The caller's device buffers must stay valid
+ * and unmodified until `stream` has passed the call.  One work-group computes one map's D, so many maps fill the device and a single map
+ * runs on one compute unit.
+ * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
+ * n > 0: null d_mask, d_goals, d_dist or moves, n_headings outside [1, 32], a stride smaller than stated above for a given buffer, an
+ * unknown order, cost_max < 1, max_cost < 0, a present move with s outside [1, 32767], |da| or |db| > 3, k2 outside [0, K) or (0, 0, k), a
+ * product beyond the limit, `starts` given without d_paths, d_path_len, max_len >= 1 or path_stride >= 2 * max_len, a start cell < -1 or
+ * >= rows * cols, a start heading outside [0, K) with a start cell >= 0, overlapping buffers; GG_ERR_CAPACITY for n > n_slots;
+ * GG_ERR_GEOMETRY for a map of more than 4096 tiles (of 32 x 32 cells up to 16 headings, of 16 x 16 above).  n == 0 is GG_OK before anything
+ * else is looked at.  The first many-map call of a context may allocate (GG_ERR_NOMEM) and block; later calls only enqueue.  Capture into a
+ * caller's graph is not supported. */
+#define GG_HEADINGS_MAX 32
+#define GG_HEADINGS_MAX_MOVES 8
+#define GG_HEADINGS_MAX_STEP 3
+#define GG_HEADINGS_MAX_COST 32767
+#define GG_HEADINGS_AT_GOAL 8
+typedef struct gg_heading_routes {
+    int n;                        /* maps */
+    const uint32_t *d_mask;       /* [n] planes, mask_stride apart: state (k, q) is admissible where bit k is set (a d_mask plane of
+                                     gg_footprint_planes as it stands); required */
+    size_t mask_stride;           /* words, >= rows * cols */
+    const int32_t *d_cost;        /* [n] planes, cost_stride apart: w = min(max(word, 1), cost_max); NULL: w = 1 everywhere */
+    size_t cost_stride;
+    const int32_t *d_goals;       /* [n] planes, goal_stride apart: a goal cell where the word is >= 0; required */
+    size_t goal_stride;
+    uint32_t goal_headings;       /* bit k: heading k of a goal cell is a goal state; 0xFFFFFFFF: any heading */
+    int n_headings;               /* K, 1 .. 32 */
+    const int32_t *moves;         /* host [K][8][4]: (da, db, k2, s), s == 0 an absent entry; required */
+    int cost_max;                 /* >= 1 */
+    int max_cost;                 /* 0: unbounded; R > 0: a state whose D > R is reported as unreached */
+    int order;                    /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR, of every plane of the call */
+    int32_t *d_dist;              /* [n][K] planes; required: the call's working memory */
+    size_t dist_stride;           /* between maps, >= K * plane_stride */
+    size_t plane_stride;          /* between the headings of a map, >= rows * cols */
+    int32_t *d_next;              /* [n][K] planes; nullable */
+    size_t next_stride;           /* >= K * next_plane_stride when d_next is given */
+    size_t next_plane_stride;     /* >= rows * cols when d_next is given */
+    int32_t *d_best;              /* [n] planes, best_stride apart: min over k of D; nullable */
+    size_t best_stride;
+    int32_t *d_best_heading;      /* [n] planes, best_heading_stride apart: the smallest k that attains it, -1: none; nullable */
+    size_t best_heading_stride;
+    int32_t *d_counts;            /* [n][3]: goal states, reached states (goal states included), admissible states; nullable */
+    const int32_t *starts;        /* host [n][2]: (linear index in `order` of the start cell or -1, heading); nullable */
+    int32_t *d_paths;             /* [n] rows of (cell, heading) pairs, path_stride words apart; required when starts is given */
+    size_t path_stride;           /* words, >= 2 * max_len */
+    int max_len;                  /* pairs of a row, >= 1 when starts is given */
+    int32_t *d_path_len;          /* [n]; required when starts is given */
+} gg_heading_routes;
+int gg_route_headings(gg_context *ctx, const gg_heading_routes *x, void *stream);
+
+/* The move table of a CAR-LIKE vehicle for gg_route_headings.  Host arithmetic only: no context, no device call.
+ *   rotations    the Q14 table of gg_match_planes / gg_footprint_spans, [n_rotations][2], 1 <= n_rotations = K <= 32, |word| <= 16384: the
+ *                forward axis of heading k is (cq, sq) in (row, col), used as given.
+ *   step         L in 1 .. 3: the length of a translating move in cells.  d_k = (rha(L * cq), rha(L * sq)) with rha(v) = (|v| + 8192) >> 14
+ *                with the sign of v: L * cq / 16384 rounded half away from zero, the convention of gg_match_planes.
+ *   unit         U in 1 .. 1024: the cost of one cell of travel.  s_k = max(1, floor(sqrt(U * U * (da^2 + db^2)))), an exact integer root.
+ *   turn         >= 0, added to a move that changes the heading by one.
+ *   reverse_pct  0: no reverse moves; otherwise >= 100: a reverse move costs ceil(cost * reverse_pct / 100) of its forward twin.
+ *   spin         >= 0: the cost of a turn in place by one heading; 0: none.
+ *   moves        [K][8][4] is written, heading k:  slot 0 (d_k, k, s_k);  1 (d_k, (k + 1) mod K, s_k + turn);  2 (d_k, (k - 1) mod K,
+ *                s_k + turn);  3 .. 5 the same three with -d_k and the reverse cost, absent with reverse_pct == 0;  6 and 7
+ *                (0, 0, (k + 1) mod K, spin) and (0, 0, (k - 1) mod K, spin), absent with spin == 0 or K == 1.  A heading with d_k == (0, 0)
+ *                gets no translating moves.  An absent entry is four zeros.
+ * GG_ERR_INVALID, with `moves` untouched, for null rotations or moves, a range violation above, a rotation word beyond +-16384, and a cost
+ * above 32767. */
+int gg_heading_moves(const int32_t *rotations, int n_rotations, int step, int unit, int turn, int reverse_pct, int spin, int32_t *moves);
+#define GG_HAS_ROUTE_HEADINGS 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
