@@ -60,6 +60,7 @@ SYMBOLS = [
     "gg_footprint_spans",
     "gg_route_headings",
     "gg_heading_moves",
+    "gg_track_clusters",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -448,6 +449,51 @@ def headings_tile(n_headings):
     return 32 if n_headings <= 16 else 16
 
 
+class GGTrack(C.Structure):
+    """gg_track: record k of a map describes cluster k of this scan (gg_track_clusters)"""
+
+    _fields_ = [
+        ("track_id", C.c_int32),
+        ("age", C.c_int32),
+        ("prev", C.c_int32),
+        ("overlap", C.c_int32),
+        ("still", C.c_int32),
+        ("cells", C.c_int32),
+        ("sum_row", C.c_int32),
+        ("sum_col", C.c_int32),
+    ]
+
+
+class GGClusterTracks(C.Structure):
+    """gg_cluster_tracks: this scan's clusters of many maps associated with the last scan's (gg_track_clusters)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("d_cells", C.c_void_p),
+        ("cells_stride", C.c_size_t),
+        ("d_cells_prev", C.c_void_p),
+        ("prev_stride", C.c_size_t),
+        ("d_tracks_in", C.c_void_p),
+        ("d_heads_in", C.c_void_p),
+        ("shifts", C.POINTER(C.c_int32)),
+        ("max_clusters", C.c_int),
+        ("gate", C.c_int),
+        ("order", C.c_int),
+        ("d_tracks_out", C.c_void_p),
+        ("d_heads_out", C.c_void_p),
+        ("d_cell_track", C.c_void_p),
+        ("track_stride", C.c_size_t),
+    ]
+
+
+GG_HAS_TRACK_CLUSTERS = 1
+GG_TRACK_MAX_CLUSTERS = 1024  # the most clusters per map of gg_track_clusters
+GG_TRACK_MAX_GATE = 4         # ... and its widest gate, in cells
+# the words of the contingency matrix a work-group of k23_tracks.hip holds at a time (gg_internal.h TRACK_SLAB_WORDS): with more than
+# TRACK_SLAB_WORDS / Kp current clusters the plane is walked once per slab, which is where the tests put their cluster counts
+GG_TRACK_SLAB_WORDS = 28 * 1024
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -532,6 +578,7 @@ def load():
     L.gg_footprint_spans.argtypes = [P(C.c_int32), C.c_int, P(C.c_int32), C.c_int, P(C.c_int32), P(C.c_int)]
     L.gg_route_headings.argtypes = [vp, P(GGHeadingRoutes), vp]
     L.gg_heading_moves.argtypes = [P(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int32)]
+    L.gg_track_clusters.argtypes = [vp, P(GGClusterTracks), vp]
     L.gg_get_map_position.argtypes =[vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

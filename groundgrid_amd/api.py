@@ -408,6 +408,49 @@ class HeadingOutputs:
     path_len: "object" = None      # torch.int32 [B]: the states of the whole path, also beyond max_len; 0: no start, or an unreached one
 
 
+# gg_track as a numpy record (TrackOutputs.table)
+TRACK_DTYPE = np.dtype([("track_id", "<i4"), ("age", "<i4"), ("prev", "<i4"), ("overlap", "<i4"), ("still", "<i4"), ("cells", "<i4"),
+                        ("sum_row", "<i4"), ("sum_col", "<i4")])
+
+
+@dataclass
+class TrackOutputs:
+    """what GroundSegmentation.track_clusters returns (CUDA torch tensors; None where nothing was asked for) -- and what the next frame's
+    call takes as `previous`"""
+
+    tracks: "object" = None        # torch.int32 [B, max_clusters, 8]: gg_track records; only the first heads[b, 1] of map b are written
+    heads: "object" = None         # torch.int32 [B, 4]: the next fresh id, the clusters of this scan, the tracks born, the tracks ended
+    cell_track: "object" = None    # torch.int32 [B, rows, cols] ([B, cols, rows] with order="col"): the cell's track id, -1 on a cell of no cluster
+    cell_cluster: "object" = None  # the id planes the call was given (kept alive for the next frame, which reads them as its previous scan)
+    order: str = "row"
+
+    def table(self, b: int):
+        """The heads[b, 1] records of map b as a numpy structured array (TRACK_DTYPE).  It synchronises: it reads the head on the host."""
+        k = min(max(int(self.heads[b, 1].item()), 0), int(self.tracks.shape[1]))
+        return self.tracks[b, :k].cpu().numpy().copy().view(TRACK_DTYPE).reshape(k)
+
+    def motion(self, previous: "TrackOutputs", shifts=None, resolution: float = 1.0):
+        """A host convenience, not part of the bit contract: the displacement of every cluster's centroid since `previous` (the
+        TrackOutputs this one was computed from) with the map's own move taken out, float64 [B, max_clusters, 2] in metres, (dx, dy) in
+        the map frame (a row index grows towards -x and a column index towards -y, as in grid_map); NaN for a cluster that continues
+        nothing and for the records beyond heads[b, 1].  shifts: what the call was given, [B, 2] or None.  It synchronises."""
+        cur, old = self.tracks.cpu().numpy(), previous.tracks.cpu().numpy()
+        n_cur = self.heads[:, 1].cpu().numpy()
+        B, M = cur.shape[:2]
+        s = np.zeros((B, 2), dtype=np.float64) if shifts is None else np.asarray(shifts, dtype=np.float64).reshape(B, 2)
+        out = np.full((B, M, 2), np.nan, dtype=np.float64)
+        for b in range(B):
+            rec = cur[b, :min(max(int(n_cur[b]), 0), M)]
+            k = np.nonzero(rec[:, 2] >= 0)[0]
+            if k.size == 0:
+                continue
+            pre = old[b, rec[k, 2]]
+            here = rec[k, 6:8] / rec[k, 5:6].astype(np.float64) + s[b]   # in the previous scan's index frame
+            there = pre[:, 6:8] / pre[:, 5:6].astype(np.float64)
+            out[b, k] = -(here - there) * float(resolution)
+        return out
+
+
 def heading_moves(rotations, *, step: int = 1, unit: int = 10, turn: int = 0, reverse_pct: int = 0, spin: int = 0):
     """The move table of a car-like vehicle for GroundSegmentation.route_headings (gg_heading_moves): int32 [K, 8, 4], entry m of heading
     k = (da, db, k2, s): from (k, (r, c)) to (k2, (r + da, c + db)) at cost s times the clamped cost of the cell entered; s == 0 marks an
@@ -1487,6 +1530,99 @@ class GroundSegmentation:
             x.d_paths, x.path_stride, x.max_len, x.d_path_len = res.paths.data_ptr(), 2 * int(max_len), int(max_len), res.path_len.data_ptr()
         stream = self._stream_arg(on_torch_stream, mask.device)
         _check(self._L, self._ctx, self._L.gg_route_headings(self._ctx, C.byref(x), stream), "gg_route_headings")
+        return res
+
+    def track_clusters(self, cell_cluster, previous: Optional[TrackOutputs] = None, shifts=None, max_clusters: int = 256, gate: int = 1,
+                       cell_track: bool = False, out: Optional[TrackOutputs] = None, on_torch_stream: bool = False, *,
+                       order: str = "row") -> TrackOutputs:
+        """Which object is which (gg_track_clusters): this scan's clusters associated with the last scan's.  cell_cluster: a contiguous
+        CUDA torch.int32 tensor [B, rows, cols] ([B, cols, rows] with order="col"), B <= n_slots -- ClusterOutputs.cell_cluster as it is:
+        -1 or the cell's cluster id; ids from max_clusters on belong to no cluster.  previous: the TrackOutputs of the last frame's call
+        (same B, max_clusters and order), or None for no prior: every cluster is then born, with ids 0, 1, ... in cluster order.  shifts:
+        what move_maps returned for the move between the two scans, [B, 2], or None for no move, with the meaning it has in fuse_states.
+        A current cluster c and a previous cluster p overlap by the number of (cell of c, offset within `gate` cells) pairs that land
+        on a cell of p; c names the p it overlaps most (the smallest among equals), p keeps the claimant that overlaps it most (the
+        smallest among equals), and that claimant inherits p's track id with age + 1; every other cluster gets a fresh id.
+        tracks int32 [B, max_clusters, 8]: per cluster track_id, age, prev, overlap, still (the gate-0 part of overlap), cells, sum_row,
+        sum_col -- TrackOutputs.table(b) gives them as records; heads int32 [B, 4]: the next fresh id, the clusters, born, ended;
+        cell_track=True adds the plane of track ids (-1 on a cell of no cluster).  The result keeps a reference to cell_cluster: the next
+        call reads it as its previous scan, so the caller alternates between two id planes (cluster_clouds(out=...)) and two
+        TrackOutputs.  `out`: a TrackOutputs of an earlier call with the same arguments, whose tensors are reused; it may not be
+        `previous`.  Integer arithmetic only: bit-identical from run to run.  Enqueued on the context's own stream or, with
+        on_torch_stream=True, on the current torch stream; nothing synchronises.  No map is read or changed."""
+        import torch
+
+        who = "track_clusters"
+        if order not in ("row", "col"):
+            raise ValueError(f"{who}: order is 'row' or 'col'")
+        for name, v in (("max_clusters", max_clusters), ("gate", gate)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{who}: {name} is an integer")
+        if not 1 <= max_clusters <= _lib.GG_TRACK_MAX_CLUSTERS:
+            raise ValueError(f"{who}: max_clusters lies in [1, {_lib.GG_TRACK_MAX_CLUSTERS}]")
+        if not 0 <= gate <= _lib.GG_TRACK_MAX_GATE:
+            raise ValueError(f"{who}: gate lies in [0, {_lib.GG_TRACK_MAX_GATE}]")
+        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
+
+        def is_int32(t, shape):
+            return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape and (
+                t is cell_cluster or t.device == cell_cluster.device)
+
+        if not (torch.is_tensor(cell_cluster) and cell_cluster.dim() == 3 and is_int32(cell_cluster, (int(cell_cluster.shape[0]),) + plane)):
+            raise ValueError(f"{who}: cell_cluster must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
+        B, M = int(cell_cluster.shape[0]), int(max_clusters)
+        if previous is not None:
+            if out is previous:
+                raise ValueError(f"{who}: out is `previous`: no update in place is defined, alternate between two TrackOutputs")
+            if previous.order != order:
+                raise ValueError(f"{who}: previous was computed with order={previous.order!r}")
+            if not (is_int32(previous.cell_cluster, (B,) + plane) and is_int32(previous.tracks, (B, M, 8)) and is_int32(previous.heads, (B, 4))):
+                raise ValueError(f"{who}: previous must be the TrackOutputs of a call with the same B, max_clusters and order")
+        host_shifts = None
+        if shifts is not None:
+            try:
+                given = np.asarray(shifts)
+                host_shifts = np.ascontiguousarray(given.astype(np.int32))
+                exact = given.shape == host_shifts.shape and np.array_equal(given, host_shifts)
+            except (TypeError, ValueError, OverflowError) as e:
+                raise ValueError(f"{who}: shifts must be [B, 2] int32: {e}") from None
+            if host_shifts.shape != (B, 2) or not exact:
+                raise ValueError(f"{who}: shifts of shape {host_shifts.shape} are not [B, 2] int32")
+        res = out if out is not None else TrackOutputs()
+        want = {"tracks": (B, M, 8), "heads": (B, 4), "cell_track": (B,) + plane if cell_track else None}
+        inputs = [cell_cluster.data_ptr()] + ([previous.cell_cluster.data_ptr(), previous.tracks.data_ptr(), previous.heads.data_ptr()] if previous is not None else [])
+        for field, sh in want.items():
+            t = getattr(res, field)
+            if sh is None:
+                if t is not None:
+                    raise ValueError(f"{who}: out.{field} is given but not asked for")
+                continue
+            if t is None:
+                continue
+            if not is_int32(t, sh):
+                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
+            if t.data_ptr() in inputs:
+                raise ValueError(f"{who}: out.{field} is an input of the call: no update in place is defined")
+        for field, sh in want.items():
+            if sh is not None and getattr(res, field) is None:
+                setattr(res, field, torch.empty(sh, dtype=torch.int32, device=cell_cluster.device))
+        res.cell_cluster, res.order = cell_cluster, order
+        self._torch_used = True
+        cells = self.rows * self.cols
+        x = _lib.GGClusterTracks()
+        x.n, x.d_cells, x.cells_stride = B, cell_cluster.data_ptr(), cells
+        if previous is not None:
+            x.d_cells_prev, x.prev_stride = previous.cell_cluster.data_ptr(), cells
+            x.d_tracks_in, x.d_heads_in = previous.tracks.data_ptr(), previous.heads.data_ptr()
+        if host_shifts is not None:
+            x.shifts = host_shifts.ctypes.data_as(C.POINTER(C.c_int32))
+        x.max_clusters, x.gate = M, int(gate)
+        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.d_tracks_out, x.d_heads_out = res.tracks.data_ptr(), res.heads.data_ptr()
+        if cell_track:
+            x.d_cell_track, x.track_stride = res.cell_track.data_ptr(), cells
+        stream = self._stream_arg(on_torch_stream, cell_cluster.device)
+        _check(self._L, self._ctx, self._L.gg_track_clusters(self._ctx, C.byref(x), stream), "gg_track_clusters")
         return res
 
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:

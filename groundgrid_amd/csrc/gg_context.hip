@@ -2545,6 +2545,88 @@ int gg_fuse_states(gg_context *ctx, const gg_state_fusion *x, void *stream)
     return map_call_end(ctx, f);
 }
 
+// This scan's clusters associated with the last scan's (k23_tracks.hip): a ring entry and the ordering of the export for maps 0 .. n-1, none
+// of which is read, as gg_fuse_states; the per-map shifts travel in the ring entry.  Nothing is synchronised, no map is filled and no
+// host-side flag changes.
+int gg_track_clusters(gg_context *ctx, const gg_cluster_tracks *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_track_clusters";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_cluster_tracks");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    const int rows = ctx->arena.g.rows, cols = ctx->arena.g.cols;
+    if (!x->d_cells || !x->d_tracks_out || !x->d_heads_out) return fail(ctx, GG_ERR_INVALID, who, "d_cells, d_tracks_out and d_heads_out are required");
+    const bool prior = x->d_cells_prev != nullptr;
+    if (prior != (x->d_tracks_in != nullptr) || prior != (x->d_heads_in != nullptr))
+        return fail(ctx, GG_ERR_INVALID, who, "d_cells_prev, d_tracks_in and d_heads_in are given together or not at all");
+    if (x->cells_stride < C) return fail(ctx, GG_ERR_INVALID, who, "cells_stride is smaller than rows * cols");
+    if (prior && x->prev_stride < C) return fail(ctx, GG_ERR_INVALID, who, "prev_stride is smaller than rows * cols");
+    if (x->d_cell_track && x->track_stride < C) return fail(ctx, GG_ERR_INVALID, who, "track_stride is smaller than rows * cols");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->max_clusters < 1 || x->max_clusters > GG_TRACK_MAX_CLUSTERS) return fail(ctx, GG_ERR_INVALID, who, "max_clusters lies in [1, 1024]");
+    if (x->gate < 0 || x->gate > 4) return fail(ctx, GG_ERR_INVALID, who, "gate lies in [0, 4]");
+    if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
+    // the coordinate sums of a cluster (and its overlap, <= 81 cells) must stay inside an int32
+    if ((uint64_t)C * (uint64_t)std::max(rows, cols) > 0x7FFFFFFFull) return fail(ctx, GG_ERR_GEOMETRY, who, "rows * cols * max(rows, cols) exceeds 2^31 - 1");
+    // no output may share a byte with an input or another output, by the ranges of gg_fuse_states
+    struct Range {
+        const char *name, *lo, *hi;
+        bool out;
+    };
+    const size_t M = (size_t)x->max_clusters;
+    const auto planes = [&](const char *name, const void *p, size_t stride, bool out) {
+        return Range{name, (const char *)p, (const char *)p + ((size_t)(x->n - 1) * stride + C) * sizeof(int32_t), out};
+    };
+    const auto rows_of = [&](const char *name, const void *p, size_t bytes, bool out) { return Range{name, (const char *)p, (const char *)p + (size_t)x->n * bytes, out}; };
+    const Range ranges[7] = {planes("d_cells", x->d_cells, x->cells_stride, false),
+                             planes("d_cells_prev", x->d_cells_prev, x->prev_stride, false),
+                             rows_of("d_tracks_in", x->d_tracks_in, M * sizeof(gg_track), false),
+                             rows_of("d_heads_in", x->d_heads_in, 4 * sizeof(int32_t), false),
+                             rows_of("d_tracks_out", x->d_tracks_out, M * sizeof(gg_track), true),
+                             rows_of("d_heads_out", x->d_heads_out, 4 * sizeof(int32_t), true),
+                             planes("d_cell_track", x->d_cell_track, x->track_stride, true)};
+    for (int i = 0; i < 7; ++i)
+        for (int j = i + 1; j < 7; ++j) {
+            const Range &p = ranges[i], &q = ranges[j];
+            if (!p.lo || !q.lo || !(p.out || q.out)) continue;
+            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
+                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
+        }
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    const bool row_major = x->order == GG_PLANES_ROWMAJOR;
+    TrackArgs ta{};
+    if (x->shifts) { // (rows, cols) -> (along a line, across lines), clamped: from |s| = side on nothing overlaps
+        int2 *hs = ctx->h_export_shifts + (size_t)f.g * ctx->n_slots, *ds = ctx->d_export_shifts + (size_t)f.g * ctx->n_slots;
+        for (int i = 0; i < x->n; ++i) {
+            const int s0 = std::min(std::max(x->shifts[2 * (size_t)i], -rows), rows), s1 = std::min(std::max(x->shifts[2 * (size_t)i + 1], -cols), cols);
+            hs[i] = row_major ? make_int2(s1, s0) : make_int2(s0, s1);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(int2) * x->n, hipMemcpyHostToDevice, f.st));
+        ta.shifts = ds;
+    }
+    ta.cells = x->d_cells;
+    ta.cells_stride = x->cells_stride;
+    ta.prev = x->d_cells_prev;
+    ta.prev_stride = x->prev_stride;
+    ta.tracks_in = x->d_tracks_in;
+    ta.heads_in = x->d_heads_in;
+    ta.nx = row_major ? cols : rows;
+    ta.ny = row_major ? rows : cols;
+    ta.row_major = row_major ? 1 : 0;
+    ta.M = x->max_clusters;
+    ta.gate = x->gate;
+    ta.slab_words = (int)std::min<size_t>(M * M, (size_t)TRACK_SLAB_WORDS);
+    ta.tracks_out = x->d_tracks_out;
+    ta.heads_out = x->d_heads_out;
+    ta.cell_track = x->d_cell_track;
+    ta.track_stride = x->track_stride;
+    launch_tracks(ta, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
 // The cost-to-go fields and paths of many maps (k19_route.hip): a ring entry and the ordering of the export for maps 0 .. n-1, none of which
 // is read, as gg_fuse_states; the per-map start cells travel in the ring entry.  Nothing is synchronised, no map is filled and no host-side
 // flag changes.

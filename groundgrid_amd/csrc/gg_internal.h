@@ -589,6 +589,34 @@ struct HeadingsArgs {
     int32_t *path_len;             // [map]
 };
 
+// gg_track_clusters (k23_tracks.hip): what its one launch takes.  Map i of the call is row i of every buffer.  A plane is `ny` lines of `nx`
+// contiguous words and the kernel works on (x along a line, y across): row-major x = col, column-major x = row; the gate is a square, so
+// only the shift's components and the two coordinate sums follow the order.  `shifts` holds (sx, sy), clamped to [-nx, nx] x [-ny, ny].
+constexpr int TRACK_THREADS = 1024;          // one work-group per map; thread c speaks for cluster c in the per-cluster steps
+constexpr int TRACK_SLAB_WORDS = 28 * 1024;  // the most words of the contingency matrix a work-group holds at a time (112 KiB)
+constexpr int TRACK_FIXED_WORDS = 9;         // LDS words per cluster beside the slab (track_lds_bytes)
+constexpr int TRACK_MISC_WORDS = 64;
+static_assert(TRACK_THREADS >= GG_TRACK_MAX_CLUSTERS, "one thread per cluster");
+static_assert(TRACK_SLAB_WORDS >= GG_TRACK_MAX_CLUSTERS, "a slab holds at least one row");
+struct TrackArgs {
+    const int32_t *cells;          // this scan's id planes
+    size_t cells_stride;
+    const int32_t *prev;           // the previous scan's; nullable: no prior (then tracks_in and heads_in are not read)
+    size_t prev_stride;
+    const gg_track *tracks_in;     // [map][M]
+    const int32_t *heads_in;       // [map][4]
+    const int2 *shifts;            // device [map] (the call's ring entry); nullable: (0, 0)
+    int nx, ny;
+    int row_major;                 // sum_row is the sum over y (else over x)
+    int M, gate;
+    int slab_words;                // min(M * M, TRACK_SLAB_WORDS)
+    gg_track *tracks_out;          // [map][M]
+    int32_t *heads_out;            // [map][4]
+    int32_t *cell_track;           // nullable
+    size_t track_stride;
+};
+inline size_t track_lds_bytes(int M, int slab_words) { return sizeof(uint32_t) * ((size_t)TRACK_FIXED_WORDS * M + TRACK_MISC_WORDS + slab_words); }
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -641,6 +669,7 @@ void launch_route(const RouteArgs &x, int n_maps, hipStream_t s);               
 void launch_match(const MatchArgs &x, int n_maps, hipStream_t s);                                // k20_match.hip: k_match_scores, k_match_best
 void launch_footprint(const FootprintArgs &x, int n_maps, hipStream_t s);                        // k21_footprint.hip: (counts := 0,) k_footprint_planes
 void launch_headings(const HeadingsArgs &x, int n_maps, hipStream_t s);                          // k22_headings.hip: relax, (counts := 0, next,) (paths)
+void launch_tracks(const TrackArgs &x, int n_maps, hipStream_t s);                                // k23_tracks.hip: k_track_clusters
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

@@ -1372,6 +1372,85 @@ int gg_route_headings(gg_context *ctx, const gg_heading_routes *x, void *stream)
 int gg_heading_moves(const int32_t *rotations, int n_rotations, int step, int unit, int turn, int reverse_pct, int spin, int32_t *moves);
 #define GG_HAS_ROUTE_HEADINGS 1
 
+/* WHICH OBJECT IS WHICH, for many maps in DEVICE memory: gg_cluster_clouds numbers the clusters of ONE scan by their smallest cell, so the
+ * same car is cluster 17 in one frame and cluster 4 in the next.  gg_track_clusters is the data association of this scan's clusters with the
+ * last scan's: it counts, for every pair of a current and a previous cluster, the cells of the one that lie on (or within `gate` cells of)
+ * the other once the previous plane is shifted by what gg_move_maps returned, lets every current cluster name its best predecessor and every
+ * predecessor keep its best claimant, and hands down a PERSISTENT track id, an age and the overlap figures; clusters without a predecessor
+ * get fresh ids.  What a caller otherwise gets per map and per frame from a download of two id planes, a contingency table on the host and
+ * an upload.  Map i of the call is row i of every buffer and of `shifts`.  Everything is 32-bit integer and in (row, col) terms whatever
+ * `order` is; with M = max_clusters, g = gate and (s0, s1) = (shifts[2 i], shifts[2 i + 1]) (both 0 when `shifts` is NULL), per map:
+ *   clusters     Kc = min(1 + the largest word of the current plane, M), 0 for a plane without a word >= 0.  A cell whose word is < 0 or >= M
+ *                belongs to no cluster (a d_cell_cluster plane of gg_cluster_clouds as it stands: -1 or the id).  Kp = min(max(heads_in[1],
+ *                0), M), heads_in being map i's four words of d_heads_in; a previous cell whose word is < 0 or >= Kp holds nothing.  WITHOUT
+ *                A PRIOR (d_cells_prev, d_tracks_in and d_heads_in all NULL) Kp = 0 and next_id = 0; otherwise next_id = heads_in[0].
+ *   overlap      O[c][p] = the number of pairs (cell (r, q) of current cluster c, offset (a, b) in [-g, g]^2) such that (r + s0 + a,
+ *                q + s1 + b) lies inside the map and the previous plane holds p there.  THE SHIFT HAS THE MEANING IT HAS IN gg_fuse_states:
+ *                current cell (r, q) lies over previous cell (r + s0, q + s1); nothing wraps.  From |s0| >= rows or |s1| >= cols on O is 0
+ *                everywhere, whatever the gate.  S[c][p] counts the pairs with (a, b) = (0, 0) alone.
+ *   candidate    p*(c) = the p with the largest O[c][p] > 0, the smallest such p among equals; undefined when row c of O is 0.
+ *   winner       of p: among the c with p*(c) = p the one with the largest O[c][p], the smallest such c among equals.
+ *   inheritance  c CONTINUES p*(c) iff it is that p's winner: prev = p, track_id = tracks_in[p].track_id, age = min(tracks_in[p].age,
+ *                INT32_MAX - 1) + 1, overlap = O[c][p], still = S[c][p].  tracks_in is map i's row of d_tracks_in, M records long.  Of a
+ *                SPLIT the part with the larger overlap keeps the track and the others are new; a MERGE ends the tracks that lost.
+ *   birth        every other cluster is new: prev = -1, overlap = still = 0, age = 0, track_id = (next_id + j) & 0x7FFFFFFF with j its rank
+ *                among the new clusters in ascending c.
+ *   records      d_tracks_out[i][k], k < Kc, describes cluster k of THIS scan: the above and cells, sum_row, sum_col over its cells (the
+ *                centroid is sum / cells).  Records k >= Kc are never written.
+ *   heads        d_heads_out[i] = {(next_id + born) & 0x7FFFFFFF, Kc, born, ended}: born = the new clusters, ended = Kp - the inheriting
+ *                ones.  The four words are what the next call takes as d_heads_in, with d_tracks_out as d_tracks_in and d_cells as
+ *                d_cells_prev: the caller alternates between two id planes and two record buffers.
+ *   d_cell_track nullable: the track id of the cell's cluster, -1 on a cell of no cluster.  Every cell inside rows * cols is written.
+ *   limits       1 <= M <= GG_TRACK_MAX_CLUSTERS = 1024; 0 <= g <= 4; rows * cols * max(rows, cols) <= 2^31 - 1 (GG_ERR_GEOMETRY beyond), so
+ *                the coordinate sums and O (<= 81 rows * cols) stay inside an int32.
+ *   addressing   map i's plane of rows * cols int32 at d_cells + i * cells_stride, d_cells_prev + i * prev_stride, d_cell_track + i *
+ *                track_stride; cell (row, col) where `order` puts it, the same order for every plane of the call.  The words between
+ *                rows * cols and a stride are never written, and a NULL output is not touched.  4-byte alignment.
+ *   no overlap   no output may share a byte with an input or with another output; the call compares the address ranges as gg_fuse_states
+ *                does and answers GG_ERR_INVALID.  The inputs may overlap each other.
+ *   determinism  integer arithmetic and integer atomics only (adds, and maxima of keys that differ): the result is a function of the
+ *                inputs alone, bit-identical from run to run and independent of scheduling.
+ * The contract is that of gg_fuse_states: NO MAP IS READ OR CHANGED -- no layer, position, freshness, configuration, score or liveness flag,
+ * and the lazily kept layers stay pending; the tracks live in the caller's buffers, not in the context.  n <= n_slots (GG_ERR_CAPACITY):
+ * the call takes an entry of the same ring of parameter entries (the shifts travel in it) and orders itself on `stream` as that call does;
+ * it enqueues and returns, and `shifts` may be freed on return.  The caller's device buffers must stay valid and unmodified until `stream`
+ * has passed the call.  One work-group computes one map, so many maps fill the device and a single map runs on one compute unit.
+ * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
+ * n > 0: null d_cells, d_tracks_out or d_heads_out, only some of d_cells_prev, d_tracks_in and d_heads_in given, cells_stride < rows * cols,
+ * prev_stride < rows * cols with a prior, track_stride < rows * cols with d_cell_track, an unknown order, max_clusters outside [1, 1024], gate
+ * outside [0, 4], overlapping buffers; GG_ERR_CAPACITY for n > n_slots; GG_ERR_GEOMETRY for a map beyond the limit above.  n == 0 is GG_OK
+ * before anything else is looked at.  The first many-map call of a context may allocate (GG_ERR_NOMEM) and block; later calls only enqueue.
+ * Capture into a caller's graph is not supported. */
+#define GG_TRACK_MAX_CLUSTERS 1024
+typedef struct gg_track {      /* 32 bytes: record k describes cluster k of THIS scan */
+    int32_t track_id;          /* persistent id: inherited, or newly given */
+    int32_t age;               /* 0 for a new track, the predecessor's age + 1 otherwise (saturating) */
+    int32_t prev;              /* cluster index in the previous scan it continues, or -1 */
+    int32_t overlap;           /* O[k][prev], 0 when prev == -1 */
+    int32_t still;             /* the offset-(0,0) part of overlap: cells that lie exactly on the predecessor */
+    int32_t cells;             /* cells of cluster k */
+    int32_t sum_row, sum_col;  /* sums of (row, col) over its cells: centroid = sum / cells */
+} gg_track;
+typedef struct gg_cluster_tracks {
+    int n;                        /* maps */
+    const int32_t *d_cells;       /* [n] id planes of this scan, cells_stride apart (gg_cluster_clouds' d_cell_cluster as it stands); required */
+    size_t cells_stride;          /* int32 words, >= rows * cols */
+    const int32_t *d_cells_prev;  /* [n] id planes of the previous scan, prev_stride apart; NULL: no prior */
+    size_t prev_stride;           /* >= rows * cols with a prior */
+    const gg_track *d_tracks_in;  /* [n][max_clusters]: the previous call's d_tracks_out; NULL: no prior */
+    const int32_t *d_heads_in;    /* [n][4]: the previous call's d_heads_out; NULL: no prior */
+    const int32_t *shifts;        /* host [n][2] index shifts (rows, cols) as gg_fuse_states takes them; NULL: all (0, 0) */
+    int max_clusters;             /* M, 1 .. GG_TRACK_MAX_CLUSTERS */
+    int gate;                     /* g, 0 .. 4 cells */
+    int order;                    /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR, of every plane of the call */
+    gg_track *d_tracks_out;       /* [n][max_clusters]; required */
+    int32_t *d_heads_out;         /* [n][4]: next_id, clusters, born, ended; required */
+    int32_t *d_cell_track;        /* [n] planes, track_stride apart: the cell's track id, -1 elsewhere; nullable */
+    size_t track_stride;          /* >= rows * cols with d_cell_track */
+} gg_cluster_tracks;
+int gg_track_clusters(gg_context *ctx, const gg_cluster_tracks *x, void *stream);
+#define GG_HAS_TRACK_CLUSTERS 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
