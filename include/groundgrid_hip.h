@@ -975,6 +975,14 @@ int gg_visibility_clouds(gg_context *ctx, const gg_cloud_visibility *x, void *st
  * (GG_ERR_CAPACITY): the call takes an entry of the same ring of parameter entries (the shifts travel in it) and orders itself on `stream`
  * exactly as that call does; it enqueues and returns, and `shifts` may be freed on return.  The caller's device buffers must stay valid and
  * unmodified until `stream` has passed the call.
+ * ORDER OF THE MANY-MAP CALLS ACROSS STREAMS, for the caller's buffers too: a call that takes a `stream` (gg_filter_batch, gg_reset_maps,
+ * gg_move_maps, gg_export_layers, gg_import_layers and every call declared below gg_export_layers, this one and the five plane calls after it
+ * included) starts its device work only when the device work of every such call the host issued earlier on the same context has finished,
+ * on whichever stream either one runs (the context's own, GG_STREAM_DEFAULT or a caller's).  So a plane this call reads may be one that an
+ * earlier call on another stream writes (d_state straight from gg_visibility_clouds, d_evidence_in from the last gg_fuse_states), and a
+ * buffer this call writes may be one that an earlier call on another stream still reads (the evidence buffer of two calls ago), with no event
+ * or synchronisation of the caller's between the two.  What the caller itself enqueues -- a fill, a copy, a kernel of its own -- is ordered by
+ * its stream alone: work on `stream` in front of the call is seen by it, work behind it sees the call, and nothing else is promised.
  * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
  * n > 0: null d_state or d_evidence_out, state_stride or plane_stride < rows * cols, an unknown order, a parameter outside the limits above,
  * overlapping buffers; GG_ERR_CAPACITY for n > n_slots.  n == 0 is GG_OK before anything else is looked at.  The first many-map call of a
@@ -1048,6 +1056,7 @@ int gg_fuse_states(gg_context *ctx, const gg_state_fusion *x, void *stream);
  * of the same ring of parameter entries (the starts travel in it) and orders itself on `stream` as those calls do; it enqueues and returns
  * with no synchronisation, and `starts` may be freed on return.  The caller's device buffers must stay valid and unmodified until `stream`
  * has passed the call.  One work-group computes one map's D, so many maps fill the device and a single map runs on one compute unit.
+ * Across streams the call is ordered, for the caller's buffers too, as gg_state_fusion has it: ORDER OF THE MANY-MAP CALLS ACROSS STREAMS.
  * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
  * n > 0: null d_goals or d_dist, a stride < rows * cols for a given plane, an unknown order, connectivity not 4 or 8, a parameter outside
  * the limits above, max_cost < 0, `starts` given without d_paths, d_path_len or max_path >= 1, a starts[i] < -1 or >= rows * cols,
@@ -1127,6 +1136,7 @@ int gg_route_planes(gg_context *ctx, const gg_plane_routes *x, void *stream);
  * (the shifts, the pivots and the rotation table travel in it) and orders itself on `stream` as those calls do; it enqueues and returns with
  * no synchronisation, and the host arrays may be freed on return.  The caller's device buffers must stay valid and unmodified until
  * `stream` has passed the call.
+ * Across streams the call is ordered, for the caller's buffers too, as gg_state_fusion has it: ORDER OF THE MANY-MAP CALLS ACROSS STREAMS.
  * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
  * n > 0: null d_scan, d_field or d_best, scan_stride or field_stride < rows * cols, score_stride < K (2 W + 1)^2 with d_scores given, an
  * unknown order, window outside [0, 32], field_max < 1 or beyond the limit, n_rotations outside [1, 64] with `rotations` given or != 0
@@ -1192,6 +1202,7 @@ int gg_match_planes(gg_context *ctx, const gg_plane_matches *x, void *stream);
  * ring of parameter entries (the span table travels in it) and orders itself on `stream` as those calls do; it enqueues and returns with
  * no synchronisation, and the host table may be freed on return.  The caller's device buffers must stay valid and unmodified until
  * `stream` has passed the call.
+ * Across streams the call is ordered, for the caller's buffers too, as gg_state_fusion has it: ORDER OF THE MANY-MAP CALLS ACROSS STREAMS.
  * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
  * n > 0: null d_blocked, null spans, no output at all, a stride < rows * cols, an unknown order, n_headings outside [1, 32], radius outside
  * [0, 32], min_fit outside [1, n_headings], outside_free not 0 or 1, a non-empty row with lo < -R or hi > R, a heading that is not
@@ -1307,6 +1318,7 @@ int gg_footprint_spans(const int32_t *rotations, int n_rotations, const int32_t 
  * enqueues and returns with no synchronisation, and the host arrays may be freed on return.  The caller's device buffers must stay valid
  * and unmodified until `stream` has passed the call.  One work-group computes one map's D, so many maps fill the device and a single map
  * runs on one compute unit.
+ * Across streams the call is ordered, for the caller's buffers too, as gg_state_fusion has it: ORDER OF THE MANY-MAP CALLS ACROSS STREAMS.
  * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
  * n > 0: null d_mask, d_goals, d_dist or moves, n_headings outside [1, 32], a stride smaller than stated above for a given buffer, an
  * unknown order, cost_max < 1, max_cost < 0, a present move with s outside [1, 32767], |da| or |db| > 3, k2 outside [0, K) or (0, 0, k), a
@@ -1415,6 +1427,7 @@ int gg_heading_moves(const int32_t *rotations, int n_rotations, int step, int un
  * the call takes an entry of the same ring of parameter entries (the shifts travel in it) and orders itself on `stream` as that call does;
  * it enqueues and returns, and `shifts` may be freed on return.  The caller's device buffers must stay valid and unmodified until `stream`
  * has passed the call.  One work-group computes one map, so many maps fill the device and a single map runs on one compute unit.
+ * Across streams the call is ordered, for the caller's buffers too, as gg_state_fusion has it: ORDER OF THE MANY-MAP CALLS ACROSS STREAMS.
  * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
  * n > 0: null d_cells, d_tracks_out or d_heads_out, only some of d_cells_prev, d_tracks_in and d_heads_in given, cells_stride < rows * cols,
  * prev_stride < rows * cols with a prior, track_stride < rows * cols with d_cell_track, an unknown order, max_clusters outside [1, 1024], gate

@@ -21,8 +21,13 @@ labels from an earlier filter_batch of the sequence (chained: that batch's devic
 data that belong to no batch (foreign).  The model derives what they return from the slot's OracleMap as it stands and the references
 of tests/cloud_refs.py, slopes_ref.py, cluster_ref.py, clearance_ref.py and visibility_ref.py; the driver hands them sentinel-filled
 destinations with slack words and padded strides, and compares at the next checkpoint, untouched words included.
-The three plane calls (gg_fuse_states, gg_route_planes, gg_match_planes) stay out: they read and write no map state, so the order of
-the calls around them cannot change their result, and test_the_chain_from_a_drive covers their chain.
+The six calls on caller-held planes (PLANE_KINDS: gg_fuse_states, gg_route_planes, gg_match_planes, gg_footprint_planes,
+gg_route_headings, gg_track_clusters) read and write no map state, so their arithmetic cannot depend on the calls around them -- but they
+run in the frame of the other many-map calls (the shared ring of parameter entries, the context's batch and map events), and what they
+read is what an earlier call, often on another stream, wrote into a buffer the caller holds.  A third generator stream inserts them the
+same way (make_sequence(.., plane_calls=False) is the list as it was); tests/seq_planes.py holds that generator, their part of the model
+(the references fusion_ref, route_ref, match_ref, footprint_ref, headings_ref, tracks_ref on the model's own copy of the chained planes)
+and their part of the driver.
 """
 from __future__ import annotations
 
@@ -36,7 +41,7 @@ import numpy as np
 
 from groundgrid_amd import kitti
 from oracle import oracle
-from tests import clearance_ref, cloud_refs, slopes_ref
+from tests import clearance_ref, cloud_refs, seq_planes, slopes_ref
 
 LAYERS = list(oracle.LAYERS)
 PER_CALL = [k for k in LAYERS if k not in ("ground", "groundpatch")]
@@ -90,9 +95,12 @@ NEW_READERS = LAYER_READERS + CLOUD_KINDS
 NEW_KINDS = ["import_layers"] + NEW_READERS
 MUTATING = MUTATING + ["import_layers"]
 OBSERVING = OBSERVING + NEW_READERS
+# the six calls on caller-held planes (tests/seq_planes.py): a third generator stream, inserted the same way
+PLANE_KINDS = list(seq_planes.PLANE_KINDS)
+OBSERVING = OBSERVING + PLANE_KINDS
 KINDS = MUTATING + OBSERVING
 GLOBAL_KINDS = {"set_config", "set_conventions", "set_score_labels", "set_flags", "synchronize", "batch_fence", "checkpoint"}
-DEVICE_KINDS = {"reset_maps", "move_maps", "filter_batch", "export_layers", "batch_fence"} | set(NEW_KINDS)   # enqueue and return (on a caller stream)
+DEVICE_KINDS = {"reset_maps", "move_maps", "filter_batch", "export_layers", "batch_fence"} | set(NEW_KINDS) | set(PLANE_KINDS)   # enqueue and return (on a caller stream)
 MUTATING_DEVICE_KINDS = {"reset_maps", "move_maps", "filter_batch", "import_layers"}
 PARAM_RING = 4   # (gg_context.hip: the entries of the ring of parameter blocks the many-map calls share)
 SLOPE_CHANNELS = ["grad_x", "grad_y", "tangent", "normal_z", "step", "min_confidence"]
@@ -1089,12 +1097,29 @@ class _Ins:
         return self.out
 
 
-def make_sequence(seed, shape, device_calls=True):
+def make_sequence(seed, shape, device_calls=True, plane_calls=True):
     """The op list of (seed, shape): deterministic, JSON-serialisable.  The first record ("tunings") fixes the launch tunings of the
     context for the whole sequence.  device_calls=False: without the ops of NEW_KINDS (and the few ops of other kinds that the last
-    scripts put in front of theirs) -- the list as it was before those calls were added, and a subsequence of the full one."""
+    scripts put in front of theirs) -- the list as it was before those calls were added, and a subsequence of the full one.
+    plane_calls=False: without what the third generator stream adds (every op that carries "g3": the ops of PLANE_KINDS, the cloud calls
+    their chains read and the scaffolding of their last scripts) -- the list as it was before the plane calls were added.  A chained
+    cloud call of the second stream names its batch by the index in THAT list (mid_indices)."""
     old = _Gen(seed, shape).run()
-    return _Ins(seed, shape, old).run() if device_calls else old
+    if not device_calls:
+        return old
+    mid = _Ins(seed, shape, old).run()
+    return seq_planes.PlaneGen(_this_module(), seed, shape, mid).run() if plane_calls else mid
+
+
+def _this_module():
+    import sys
+
+    return sys.modules[__name__]
+
+
+def mid_indices(ops):
+    """the index in `ops` of every op of the list without the third generator stream's, in order"""
+    return [i for i, op in enumerate(ops) if "g3" not in op]
 
 
 def touched(op, n_slots):
@@ -1102,6 +1127,8 @@ def touched(op, n_slots):
     k = op["op"]
     if k == "reset_maps":
         return list(range(op["first"], op["first"] + op["n"]))
+    if k in PLANE_KINDS:   # (map i of a plane call is row i of its buffers: the call's frame is filled from slots 0 .. n - 1)
+        return list(range(min(op["n"], n_slots) if n_slots else op["n"]))
     if k == "filter_async2":
         return [i["slot"] for i in op["items"]]
     if "slots" in op:
@@ -1126,7 +1153,7 @@ class Predicates:
       scoring        set_scoring switched it on
       partly-live    since its last cloud a per-call layer was set, or read whole"""
 
-    KEEP_FRESH = {"export_layers", "scores", "set_position", "get_position", "slot_config", "set_slot_configs", "set_scoring", "reset_scores"} | set(NEW_READERS)
+    KEEP_FRESH = {"export_layers", "scores", "set_position", "get_position", "slot_config", "set_slot_configs", "set_scoring", "reset_scores"} | set(NEW_READERS) | set(PLANE_KINDS)
 
     def __init__(self, n_slots):
         self.n = n_slots
@@ -1219,7 +1246,8 @@ MUTANTS = [
     "fresh_map_read_as_before_reset",           # a reader of a fresh map gets the terrain from before the reset, not the constant odom_z
     "images_read_lazy_layer_uncomputed",        # export_images of one of the three lazily kept layers while it is owed: the stale plane
     "foreign_point_outside_gets_finite_height",  # a selected point outside the map (labels that belong to no batch): 0.0 instead of the quiet NaN
-]
+    # -- the calls on caller-held planes (tests/seq_planes.py)
+] + list(seq_planes.PLANE_MUTANTS)
 LAZY_MUTANTS = {"import_drops_lazy_layers", "images_read_lazy_layer_uncomputed"}   # (they need what the three layers held before the cloud)
 
 
@@ -1257,6 +1285,10 @@ class ContextModel:
         self.pred = Predicates(self.n)   # (mutants: which slots are fresh as the header has it)
         self.batches = {}                # op index of a filter_batch -> per row (map-frame cloud, label bytes), until the next checkpoint
         self.at = -1                     # index of the op being applied
+        self.outs = {}                   # op index -> {output name: the logical planes per map} of the ops whose planes a plane call may read
+        self.shift_log = []              # (op index, slot, shift) of every move: a chain's shifts are sums over it
+        self.mid = None                  # bind(): the full index of every op that is not of the third generator stream
+        self.mid_seen = []
 
     # -- helpers
     def cloud(self, spec):
@@ -1355,6 +1387,7 @@ class ContextModel:
         if m == "cloud_reader_ground_before_last_scroll":
             sl.prev_ground = sl.ref.layer("ground").copy()
         moved, shift = sl.ref.update(float(odom[0]), float(odom[1]), pose, "kdl")
+        self.shift_log.append((self.at, s, (int(shift[0]), int(shift[1]))))
         if shift == (0, 0):
             sl.prev_ground = None
         sl.prev_pos = before
@@ -1387,6 +1420,8 @@ class ContextModel:
         k = op["op"]
         m = self.mutant
         self.at = self.at + 1 if index is None else index
+        if "g3" not in op:
+            self.mid_seen.append(self.at)
         if k == "checkpoint":
             self.batches.clear()   # (the driver lets go of the batches' device buffers there)
         if k in ("tunings", "synchronize", "batch_fence", "checkpoint"):
@@ -1395,7 +1430,21 @@ class ContextModel:
         self.pred.apply(op)
         return res
 
+    def bind(self, ops):
+        """the list the ops come from, for a caller that applies only some of them: a chained cloud call of the second generator stream
+        names its batch by its index among the ops that carry no "g3" """
+        self.mid = mid_indices(ops)
+        return self
+
+    def batch_key(self, src):
+        """the index (in the full list) of the batch a chained cloud call names"""
+        if src.get("full"):
+            return src["batch"]
+        table = self.mid if self.mid is not None else self.mid_seen
+        return table[src["batch"]] if src["batch"] < len(table) else None
+
     def run(self, ops):
+        self.bind(ops)
         return [self.apply(op, i) for i, op in enumerate(ops)]
 
     def do_reset_maps(self, op, m):
@@ -1755,7 +1804,7 @@ class ContextModel:
         (a list with ops deleted)"""
         src = op["source"]
         if src["mode"] == "chained":
-            rows = self.batches.get(src["batch"])
+            rows = self.batches.get(self.batch_key(src))
             if rows is None or len(rows) < src["row0"] + len(op["slots"]):
                 return None
             return [(s,) + rows[src["row0"] + i] for i, s in enumerate(op["slots"])]
@@ -1780,6 +1829,8 @@ class ContextModel:
                 res = {k: (np.where(np.isnan(v), np.float32(0.0), v) if k.endswith("height") else v) for k, v in res.items()}
             for k, v in res.items():
                 out[f"cloud {i} (slot {s}) {k}"] = v
+                if k in ("state", "cell ids"):   # (planes a plane call may be chained to)
+                    self.outs.setdefault(self.at, {"_op": op}).setdefault(k, []).append(v)
         return out
 
     def do_split_clouds(self, op, m):
@@ -1848,6 +1899,9 @@ class ContextModel:
 
         return self._cloud_call(op, m, expect)
 
+
+for _kind in PLANE_KINDS:
+    setattr(ContextModel, "do_" + _kind, lambda self, op, m: seq_planes.model_op(self, op, m))
 
 _MEMO = {}
 
@@ -1919,6 +1973,10 @@ class Driver:
         self.planes = {}
         self.batches = {}          # op index of a filter_batch -> its device buffers, until the next checkpoint (chained cloud calls)
         self.at = -1
+        self.dev_outs = {}         # op index -> {output name: (tensor, stride in words, maps, row_major)}: what a plane call may be chained to
+        self.chain_bufs = {}       # (chain, name, which of the two) -> the chain's own device buffer; both outlive checkpoints
+        self.shift_log = []        # (op index, slot, shift as the library returned it) of every move
+        self.mid = []
 
     def cloud(self, spec):
         return cached_cloud(spec, self.shape)
@@ -1949,6 +2007,7 @@ class Driver:
     def run(self, ops):
         from groundgrid_amd import api
 
+        self.mid = mid_indices(ops)
         for i, op in enumerate(ops):
             self.at = i
             try:
@@ -2000,6 +2059,8 @@ class Driver:
     def do_move_maps(self, op):
         before = self.fresh_count()
         shifts = self.seg.move_maps(op["odoms"], op["poses"], slots=op["slots"], stream=self.handle(op["stream"]))
+        for s, sh in zip(op["slots"], np.asarray(shifts).reshape(-1, 2)):
+            self.shift_log.append((self.at, s, (int(sh[0]), int(sh[1]))))
         if op["stream"] != "ctx":
             self.used.add(op["stream"])
         # (a fresh map that scrolls is written; every other fresh map of the context stays fresh, and so does one whose shift is (0, 0))
@@ -2008,6 +2069,7 @@ class Driver:
     def do_map_move(self, op):
         m = self.seg.map(op["slot"])
         shift = m.move(op["odom"][0], op["odom"][1], op["pose"])
+        self.shift_log.append((self.at, op["slot"], (int(shift[0]), int(shift[1]))))
         return {"shift": np.array(shift, dtype=np.int32), "position": np.array(m.getPosition(), dtype=np.float64)}
 
     def do_set_position(self, op):
@@ -2393,7 +2455,7 @@ class Driver:
 
         src, n = op["source"], len(op["slots"])
         if src["mode"] == "chained":   # the batch's own device buffers, wherever that batch stands in its stream
-            pts, out, n_pts, tfs = self.batches[src["batch"]]
+            pts, out, n_pts, tfs = self.batches[src["batch"] if src.get("full") else self.mid[src["batch"]]]
             rec, stride, row0 = int(pts.shape[2]), int(pts.shape[1]), src["row0"]
             d_points = pts.data_ptr() + row0 * stride * rec
             n_pts = n_pts[row0: row0 + n]
@@ -2522,6 +2584,7 @@ class Driver:
             x.d_clusters, x.max_clusters = (table.data_ptr() if cap else None), cap
             marks = self._enqueue(op, lambda st: self.seg._L.gg_cluster_clouds(self.seg._ctx, C.byref(x), st))
         self.keep.append((planes, count, table, ids))
+        self.dev_outs[self.at] = {"cell ids": (planes, pstride, n, op["row_major"])}
 
         def collect():
             res = self._marks_kept(marks)
@@ -2608,6 +2671,7 @@ class Driver:
             x.d_counts = counts.data_ptr() if counts is not None else None
             marks = self._enqueue(op, lambda st: self.seg._L.gg_visibility_clouds(self.seg._ctx, C.byref(x), st))
         self.keep.append((state, counts))
+        self.dev_outs[self.at] = {"state": (state, pstride, n, op["row_major"])}
 
         def collect():
             res = self._marks_kept(marks)
@@ -2639,6 +2703,10 @@ class Driver:
         for planes in self.planes.values():
             self.seg.release_layers(planes)
         self.planes = {}
+
+
+for _kind in PLANE_KINDS:
+    setattr(Driver, "do_" + _kind, lambda self, op: seq_planes.device_op(self, op))
 
 
 class _NoContext:

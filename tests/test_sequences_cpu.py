@@ -3,6 +3,10 @@ cover, few ops are inert, and the model tells every deliberate bookkeeping slip 
 device calls (seq_model.NEW_KINDS): the committed seeds keep every op they had before those were inserted, every call occurs in every
 shape, follows and precedes a writer of its map on another stream with no host synchronisation between them, one run of them is longer
 than the ring they share, and every cloud call occurs chained to a batch (also on another stream than the batch) and foreign.
+For the six calls on caller-held planes (seq_model.PLANE_KINDS, tests/seq_planes.py): the lists from before them are kept, every chain the
+header names occurs, every kind reads what an op on another stream wrote since the last checkpoint, a chain's buffer is overwritten
+while a call on another stream may still read it, one run per sequence holds all six on two caller streams and goes round the ring,
+shifts are sums of several moves, end with a reset and reach a side, the rows of a call are used to the last, and few calls are inert.
 
 `python -m tests.test_sequences_cpu` prints the coverage table and the mutant table of DESIGN.md.
 """
@@ -19,6 +23,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from tests import seq_model as sm  # noqa: E402
+from tests import seq_planes as sp  # noqa: E402
 
 # the committed seeds: tests/test_sequences_gpu.py runs exactly these
 SEEDS = {"latency": [0, 1], "fleet": [0, 1], "server": [0, 1]}
@@ -32,15 +37,16 @@ def sequence(shape, seed):
 
 @functools.lru_cache(maxsize=None)
 def truth(shape, seed):
-    """(results per op, state per slot, [(op index, points inside the map)] per filtered cloud) of the true model"""
-    model = sm.ContextModel(shape)
+    """(results per op, state per slot, [(op index, points inside the map)] per filtered cloud, the planes and notes the model keeps per op)
+    of the true model"""
+    model = sm.ContextModel(shape).bind(sequence(shape, seed))
     inside = []
     results = []
     for i, op in enumerate(sequence(shape, seed)):
         results.append(model.apply(op, i))
         for s in (sm.touched(op, model.n) if op["op"] in sm.FILTERS else []):
             inside.append((i, int((model.slots[s].last[0] != sm.oracle.OUTSIDE).sum())))
-    return results, [model.state(s) for s in range(model.n)], inside
+    return results, [model.state(s) for s in range(model.n)], inside, model.outs
 
 
 def differs(a, b):
@@ -52,8 +58,8 @@ def differs(a, b):
 def distinguishes(shape, seed, mutant=None, drop=None):
     """None, or where a wrong model (`mutant`) / the sequence without its ops of kind `drop` first differs from the truth in something the
     driver compares: an op's results, or a slot's final state"""
-    results, states, _ = truth(shape, seed)
-    model = sm.ContextModel(shape, mutant=mutant)
+    results, states = truth(shape, seed)[:2]
+    model = sm.ContextModel(shape, mutant=mutant).bind(sequence(shape, seed))
     for i, op in enumerate(sequence(shape, seed)):
         if op["op"] == drop:
             continue
@@ -229,10 +235,11 @@ def test_the_import_follows_and_precedes_batches_and_exports_of_its_map_on_anoth
 
 
 def longest_run_of_device_calls(ops):
-    """the longest run of ops of sm.NEW_KINDS with nothing between them: (length, kinds, streams)"""
+    """the longest run of ops of sm.NEW_KINDS and sm.PLANE_KINDS (argument errors apart: they take no ring entry) with nothing between
+    them: (length, kinds, streams)"""
     best, run = (0, set(), set()), []
     for op in ops + [{"op": "checkpoint"}]:
-        if op["op"] in sm.NEW_KINDS:
+        if op["op"] in sm.NEW_KINDS + sm.PLANE_KINDS and "expect" not in op:
             run.append(op)
             continue
         if len(run) > best[0]:
@@ -244,6 +251,9 @@ def longest_run_of_device_calls(ops):
 def test_one_run_of_device_calls_takes_every_entry_of_the_shared_ring_again():
     runs = [longest_run_of_device_calls(sequence(shape, seed)) for shape, seed in CASES]
     assert any(n > sm.PARAM_RING and len(kinds) >= 3 and len(streams) >= 2 for n, kinds, streams in runs), runs
+    # ... and in every sequence, in one run on two caller streams, every entry by a plane kind and again by another kind
+    for shape, seed in CASES:
+        assert any(goes_round_the_ring(r) for r in runs_on_two_caller_streams(sequence(shape, seed))), (shape, seed)
 
 
 @pytest.mark.parametrize("kind", sm.CLOUD_KINDS)
@@ -255,7 +265,8 @@ def test_every_cloud_call_occurs_chained_and_foreign(kind):
             if op["op"] == kind:
                 src = op["source"]
                 modes.add(src["mode"])
-                if src["mode"] == "chained":
+                if src["mode"] == "chained":   # (the second generator stream names a batch by its index in the list without the third's ops)
+                    src = dict(src, batch=src["batch"] if src.get("full") else sm.mid_indices(ops)[src["batch"]])
                     batch = ops[src["batch"]]
                     assert batch["op"] == "filter_batch" and batch["slots"][src["row0"]: src["row0"] + len(op["slots"])] == op["slots"]
                     assert ("masks" if op["masks"] else "labels") in batch["outputs"]
@@ -267,6 +278,257 @@ def test_every_cloud_call_occurs_chained_and_foreign(kind):
                     assert not op["masks"] or src["stride"] % 4 == 0
     assert modes == {"chained", "foreign"}, (kind, modes)
     assert across >= 1, f"{kind} never reads the labels of a batch on another stream"
+
+
+# ---------------------------------------------------------------------------------------------------------------- the calls on caller-held planes
+
+# length and digest (as above) of every committed list as it was before the third generator stream's ops were inserted
+BEFORE_THE_PLANE_CALLS = {
+    ("latency", 0): (198, "9f692db75a1f651586bba06528f4f9ab"),
+    ("latency", 1): (198, "7848a27c641b5e9e10601c382a621805"),
+    ("fleet", 0): (368, "a7510db42e99f09af022e2ad55063545"),
+    ("fleet", 1): (341, "7fe47bddfd500b604d2f695e3525d786"),
+    ("server", 0): (204, "dea37734b6ac68173b8943a02dd224e3"),
+    ("server", 1): (196, "a3ded0ee8d89f556693b32d42ed6d353"),
+}
+CALLER_STREAMS = ("s1", "s2", "default")
+
+
+def plane_ops(shape=None):
+    """(shape, seed, index, op, list) of every plane op of the committed sequences that is no argument error"""
+    for sh, seed in CASES:
+        if shape in (None, sh):
+            ops = sequence(sh, seed)
+            for i, op in enumerate(ops):
+                if op["op"] in sm.PLANE_KINDS and "expect" not in op:
+                    yield sh, seed, i, op, ops
+
+
+def chained_inputs(op):
+    return {name: src for name, src in sp.sources_of(op).items() if sp.is_chained(src)}
+
+
+def last_checkpoint(ops, i):
+    return max((j for j in range(i) if ops[j]["op"] == "checkpoint"), default=-1)
+
+
+def test_the_committed_seeds_keep_every_op_they_had_before_the_plane_calls():
+    """make_sequence(.., plane_calls=False) is the list from before the plane calls were added, dict for dict, and a subsequence of the
+    full list; the third generator stream's ops are the ones that carry "g3", and every op of a plane kind is one of them"""
+    for shape, seed in CASES:
+        mid = sm.make_sequence(seed, shape, plane_calls=False)
+        assert (len(mid), hashlib.sha256(json.dumps(mid, sort_keys=True).encode()).hexdigest()[:32]) == BEFORE_THE_PLANE_CALLS[(shape, seed)], (shape, seed)
+        full = sequence(shape, seed)
+        assert [op for op in full if "g3" not in op] == mid
+        assert all("g3" in op for op in full if op["op"] in sm.PLANE_KINDS) and not any(op["op"] in sm.PLANE_KINDS for op in mid)
+        assert [op["g3"] for op in full if "g3" in op] == list(range(len(full) - len(mid)))
+
+
+def test_every_plane_call_occurs_in_every_shape_on_every_kind_of_stream_chained_and_foreign():
+    for shape in sm.SHAPES:
+        seen = {op["op"] for _, _, _, op, _ in plane_ops(shape)}
+        assert seen == set(sm.PLANE_KINDS), (shape, set(sm.PLANE_KINDS) - seen)
+    for kind in sm.PLANE_KINDS:
+        mine = [op for _, _, _, op, _ in plane_ops() if op["op"] == kind]
+        streams = {op["stream"] for op in mine}
+        assert streams & {"s1", "s2"} and {"default", "ctx"} <= streams, (kind, streams)
+        assert any(chained_inputs(op) for op in mine), f"{kind} never reads what an earlier op wrote"
+        assert any(not chained_inputs(op) for op in mine), f"{kind} never reads planes that belong to no call"
+        assert {op["row_major"] for op in mine} == {False, True} and {bool(op["pad"]) for op in mine} == {False, True}, kind
+    # every nullable output is left out somewhere, and given somewhere
+    for kind, names in (("fuse_states", ["fused", "frontier", "counts"]), ("route_planes", ["next", "counts"]), ("footprint_planes", ["mask", "fit", "counts"]),
+                        ("route_headings", ["next", "best", "best_heading", "counts"])):
+        wants = [set(op["want"]) for _, _, _, op, _ in plane_ops() if op["op"] == kind]
+        for name in names:
+            assert any(name in w for w in wants) and any(name not in w for w in wants), (kind, name)
+    for kind, key in (("route_planes", "starts"), ("route_headings", "starts"), ("match_planes", "pivots"), ("match_planes", "angles"), ("route_planes", "blocked"),
+                      ("route_planes", "cost"), ("route_headings", "cost"), ("fuse_states", "evidence_in"), ("fuse_states", "shifts"), ("track_clusters", "prev")):
+        given = {op[key] is not None for _, _, _, op, _ in plane_ops() if op["op"] == kind}
+        assert given == {False, True}, (kind, key)
+    assert {op["scores"] for _, _, _, op, _ in plane_ops() if op["op"] == "match_planes"} == {False, True}
+    assert {op["cell_track"] for _, _, _, op, _ in plane_ops() if op["op"] == "track_clusters"} == {False, True}
+    assert {op["M"] for _, _, _, op, _ in plane_ops() if op["op"] == "track_clusters"} == {1, 3, 64, 1024}
+    assert {op["gate"] for _, _, _, op, _ in plane_ops() if op["op"] == "track_clusters"} == {0, 1, 2, 3, 4}
+    # the sizes the issue keeps small
+    for shape, _, _, op, _ in plane_ops():
+        k = op["op"]
+        assert k not in ("footprint_planes", "route_headings") or op["K"] <= (4 if shape == "latency" else 8)
+        assert k != "footprint_planes" or op["radius"] <= 3
+        assert k != "match_planes" or (op["window"] <= 4 and (op["angles"] is None or len(op["angles"]) <= 8))
+        assert k != "track_clusters" or op["M"] < 1024 or op["n"] <= 2
+
+
+def test_every_chain_the_header_names_occurs_and_a_chained_plane_keeps_its_producer_s_order():
+    seen = {key: set() for key in sp.CHAIN_TABLE}
+    for _, _, i, op, ops in plane_ops():
+        for name, src in chained_inputs(op).items():
+            made = ops[src["op"]]
+            assert src["op"] < i and not (made["op"] in sm.PLANE_KINDS and "expect" in made)
+            assert made["row_major"] == op["row_major"], "a chained plane is taken in the order it was written in"
+            assert (made["n"] if made["op"] in sm.PLANE_KINDS else len(made["slots"])) >= src["row0"] + op["n"]
+            seen[(op["op"], name)].add(src["out"])
+    assert seen == sp.CHAIN_TABLE, {k: sp.CHAIN_TABLE[k] - v for k, v in seen.items() if sp.CHAIN_TABLE[k] - v}
+
+
+@pytest.mark.parametrize("kind", sm.PLANE_KINDS)
+def test_every_plane_call_reads_what_an_op_on_another_stream_wrote_since_the_last_checkpoint(kind):
+    found = 0
+    for _, _, i, op, ops in plane_ops():
+        if op["op"] == kind:
+            cp = last_checkpoint(ops, i)
+            found += any(src["op"] > cp and ops[src["op"]]["stream"] != op["stream"] for src in chained_inputs(op).values())
+    assert found, kind
+
+
+def overwrites_what_another_stream_read(ops, i):
+    """does plane op i write a chain buffer that an earlier op on another stream has read since the last checkpoint?"""
+    op = ops[i]
+    outs = {"fuse_states": ("evidence",), "track_clusters": ("tracks", "heads")}[op["op"]]
+    if op.get("chain") is None:
+        return False
+    for j in range(last_checkpoint(ops, i) + 1, i):
+        other = ops[j]
+        if other["op"] in sm.PLANE_KINDS and other["stream"] != op["stream"]:
+            for src in chained_inputs(other).values():
+                made = ops[src["op"]]
+                if src["out"] in outs and made["op"] == op["op"] and (made.get("chain"), made.get("buf")) == (op["chain"], op["buf"]):
+                    return True
+    return False
+
+
+@pytest.mark.parametrize("kind", ["fuse_states", "track_clusters"])
+def test_a_chain_s_buffer_is_overwritten_while_a_call_on_another_stream_may_still_read_it(kind):
+    assert any(overwrites_what_another_stream_read(ops, i) for _, _, i, op, ops in plane_ops() if op["op"] == kind), kind
+
+
+def test_a_chain_buffer_is_written_once_between_two_checkpoints():
+    """... so that what every call wrote can still be compared at the checkpoint"""
+    for shape, seed in CASES:
+        written = set()
+        for op in sequence(shape, seed):
+            if op["op"] == "checkpoint":
+                written = set()
+            elif op["op"] in ("fuse_states", "track_clusters") and op.get("chain") is not None:
+                key = (op["op"], op["chain"], op["buf"])
+                assert key not in written, (shape, seed, key)
+                written.add(key)
+
+
+RING_TAKERS = set(sm.NEW_KINDS) | set(sm.PLANE_KINDS) | {"export_layers"}   # (gg_context.hip: the calls that go through map_call_begin)
+
+
+def runs_on_two_caller_streams(ops):
+    """the maximal runs of device ops on caller streams (nothing in them synchronises the host: no op on the context's own stream, for
+    which the driver waits for its own uploads)"""
+    runs, run = [], []
+    for op in ops + [{"op": "checkpoint"}]:
+        if op["op"] in sm.DEVICE_KINDS and op.get("stream") in CALLER_STREAMS and "expect" not in op:
+            run.append(op)
+        else:
+            if run:
+                runs.append(run)
+            run = []
+    return [r for r in runs if len({op["stream"] for op in r}) == 2]
+
+
+def goes_round_the_ring(run):
+    """every entry of the ring is taken by a plane kind and later by another kind"""
+    takers = [op["op"] for op in run if op["op"] in RING_TAKERS]
+    for e in range(sm.PARAM_RING):
+        mine = takers[e:: sm.PARAM_RING]
+        if not any(a in sm.PLANE_KINDS and any(b != a for b in mine[k + 1:]) for k, a in enumerate(mine)):
+            return False
+    return True
+
+
+def test_one_run_per_sequence_holds_the_six_plane_kinds_on_two_caller_streams_and_goes_round_the_ring():
+    for shape, seed in CASES:
+        good = [r for r in runs_on_two_caller_streams(sequence(shape, seed))
+                if len(r) >= 7 and set(sm.PLANE_KINDS) <= {op["op"] for op in r} and {op["op"] for op in r} & {"filter_batch", "move_maps", "export_layers"}]
+        assert good, (shape, seed)
+        assert any(goes_round_the_ring(r) for r in good), (shape, seed, "the same run goes round the ring")
+
+
+def moves_since(ops, i, spec):
+    """per slot of a shift spec, how many moves of it stand between the chain's previous observation and op i"""
+    out = []
+    for s in spec["of"]:
+        out.append(sum(1 for j in range(spec["since"] + 1, i)
+                       if (ops[j]["op"] == "move_maps" and s in ops[j]["slots"]) or (ops[j]["op"] == "map_move" and ops[j]["slot"] == s)))
+    return out
+
+
+@pytest.mark.parametrize("kind", sp.SHIFTED_KINDS)
+def test_the_shifts_of_a_chain_are_sums_of_several_moves_end_with_a_reset_and_reach_a_side(kind):
+    """For fuse and tracks "behind a reset" is behaviour: the call has no prior and names what it lost, which the mutant that lets a prior
+    survive takes instead.  gg_match_planes has no prior of its own: behind a reset it stands behind the chain's first fuse, reads that
+    call's evidence with no shift, and carries an empty "lost" as a MARK only -- no mutant can be told at such an op."""
+    several = lost = far = 0
+    for shape, seed, i, op, ops in plane_ops():
+        if op["op"] != kind:
+            continue
+        lost += "lost" in op
+        if op["shifts"] is not None:
+            if "since" in op["shifts"]:
+                several += max(moves_since(ops, i, op["shifts"])) >= 2
+            far += any(max(abs(a), abs(b)) >= sp.side_of(sm, shape) for a, b in truth(shape, seed)[3][i]["_shifts"])
+    assert several and lost and far, (kind, several, lost, far)
+
+
+def test_a_reset_of_a_chain_s_slot_stands_in_front_of_every_call_that_names_what_it_lost():
+    for _, _, i, op, ops in plane_ops():
+        if "lost" in op and op["op"] != "match_planes":
+            since, of = op["lost"]["shifts"]["since"], op["lost"]["shifts"]["of"]
+            assert any(o["op"] in ("reset_maps", "map_reset", "set_position") and set(sm.touched(o, 0)) & set(of) for o in ops[since:i]), (i, op["op"])
+            assert all(op[name] is None for name in op["lost"] if name != "shifts"), "no prior"
+
+
+def test_at_most_a_tenth_of_the_shifted_plane_calls_have_an_all_zero_shift():
+    total = still = 0
+    for shape, seed, i, op, _ in plane_ops():
+        if op["op"] in sp.SHIFTED_KINDS and op["shifts"] is not None:
+            total += 1
+            still += not any(a or b for a, b in truth(shape, seed)[3][i]["_shifts"])
+    assert total > 60 and still <= 0.10 * total, (still, total)
+
+
+def test_at_most_a_tenth_of_the_routes_have_nowhere_to_go_and_of_the_tracks_no_predecessor():
+    for kinds in (("route_planes", "route_headings"), ("track_clusters",)):
+        total = inert = 0
+        for shape, seed, i, op, _ in plane_ops():
+            if op["op"] in kinds:
+                total += 1
+                inert += not any(truth(shape, seed)[3][i]["_live"])
+        assert total > 40 and inert <= 0.10 * total, (kinds, inert, total)
+    # the track calls on a chain's own id planes alone, foreign ones apart.  A call without a prior cannot have a predecessor (the header:
+    # Kp = 0), so the cap is over those that have one
+    total = inert = 0
+    for shape, seed, i, op, _ in plane_ops():
+        if op["op"] == "track_clusters" and sp.is_chained(op["cells"]) and op["prev"] is not None:
+            total += 1
+            inert += not any(truth(shape, seed)[3][i]["_live"])
+    assert total >= 10 and inert <= 0.10 * total, ("chained tracks with a prior", inert, total)
+
+
+def test_once_per_shape_a_call_fills_the_rows_to_the_last_and_one_map_more_is_refused():
+    for shape in sm.SHAPES:
+        n_slots = sm.SHAPES[shape]["n_slots"]
+        full = {op["op"]: op for _, _, _, op, _ in plane_ops(shape) if op["n"] == n_slots}
+        assert {"fuse_states", "route_planes"} <= set(full), (shape, set(full))
+        sh = full["fuse_states"]["shifts"]["values"]
+        st = full["route_planes"]["starts"]
+        assert len({tuple(v) for v in sh}) == n_slots, "another shift for every map of the call"
+        assert all(sh[i] != sh[i + 1] for i in range(n_slots - 1)) and all(st[i] != st[i + 1] or st[i] is None for i in range(n_slots - 1))
+        refused = 0
+        for seed in SEEDS[shape]:
+            ops = sequence(shape, seed)
+            for i, op in enumerate(ops):
+                if "expect" in op:
+                    assert op["n"] == n_slots + 1 and op["expect"] == "GG_ERR_CAPACITY"
+                    nxt = ops[i + 1]   # (the op behind it shows that the refused call took no ring entry and left no event behind)
+                    assert nxt["op"] == op["op"] and "expect" not in nxt and nxt["stream"] == op["stream"]
+                    refused += 1
+        assert refused, shape
 
 
 # ---------------------------------------------------------------------------------------------------------------- inertness caps
@@ -350,6 +612,10 @@ def tables():
         modes = [op["source"]["mode"] for shape, seed in CASES for op in sequence(shape, seed) if op["op"] == k and "source" in op]
         rows.append(f"| {k} | " + ", ".join(o for o in others if (o, k) in pairs and o != k) + " | " + ", ".join(o for o in others if (k, o) in pairs and o != k)
                     + " | " + (f"{modes.count('chained')} / {modes.count('foreign')}" if modes else "n/a") + " |")
+    for k in sm.PLANE_KINDS:   # (a plane call "names" slots 0 .. n - 1; chained: at least one input is an earlier op's buffer)
+        mine = [op for _, _, _, op, _ in plane_ops() if op["op"] == k]
+        rows.append(f"| {k} | " + ", ".join(o for o in others if (o, k) in pairs) + " | " + ", ".join(o for o in others if (k, o) in pairs)
+                    + f" | {sum(1 for op in mine if chained_inputs(op))} / {sum(1 for op in mine if not chained_inputs(op))} |")
     n, kinds, streams = max((longest_run_of_device_calls(sequence(shape, seed)) for shape, seed in CASES), key=lambda r: r[0])
     rows += ["", f"longest run of device calls: {n} ops of {len(kinds)} kinds on {len(streams)} streams (the shared ring has {sm.PARAM_RING} entries)"]
     return "\n".join(rows)
