@@ -73,9 +73,9 @@ template <class Placer> void lay_out_arena(Placer &place, const ArenaShape &in, 
     a.slot_layer_stride = align_up(T * PERCALL_BLOCK * 4, A) / 4;
     place(a.layers, slots * a.slot_layer_stride);
     a.gpl = make_gp_layout(in.g.rows);
-    // (a slot's written-cell bits -- FRESH maps, gg_internal.h -- live behind its layer: one buffer descriptor reaches both)
+    // (a reserved region behind each slot's layer, gg_internal.h Arena::gp_bits: the slots keep the spacing they always had)
     a.gp_bits_off = (int)align_up((size_t)a.gpl.elems, 16);
-    a.gp_bits_words = (a.gpl.elems / 64 + 2 + 1) & ~1; // (8-byte words; even: k_reset_fresh copies 16 bytes at a time)
+    a.gp_bits_words = (a.gpl.elems / 64 + 2 + 1) & ~1; // (8-byte words, an even number)
     a.gp2_stride = align_up(((size_t)a.gp_bits_off + (size_t)a.gp_bits_words) * 8, A) / 8;
     a.gp_bits_stride = a.gp2_stride;
     place(a.gp2, slots * a.gp2_stride);

@@ -115,9 +115,16 @@ struct gg_context : ContextBuffers {
     std::vector<double> pos_x, pos_y; // per slot map position
     std::vector<char> slot_seen;      // scratch of check_slot_list
     std::vector<char> no_confidence;  // per slot: groundpatch <= 0.01 everywhere for sure (set by gg_reset_map, cleared by any writer)
-    // per slot: the map is FRESH -- gg_reset_maps left the interior of its (ground, confidence) layer unwritten (gg_internal.h Arena::gp_bits);
+    // per slot: the map is FRESH -- gg_reset_maps left the interior of its (ground, confidence) layer unwritten (gg_internal.h Arena::gp_fresh_cell);
     // a batch of at least FRESH_MIN_CLOUDS fresh maps sweeps them as they are, anything else that touches the layer fills it first (make_real)
     std::vector<char> fresh;
+    // per slot: the layer's memory may hold a confidence with bit 31 set that is NOT a fresh launch's tag of its own call -- a caller's plane
+    // (gg_set_layer, gg_import_layers of groundpatch: negatives, NaN), a stage run on such a layer, a batch that a device-side error cut short.
+    // A fresh launch would take such a cell for one k_patch wrote: the slot's next gg_reset_maps fills every cell once and clears the flag.
+    // Also set by a batch on a slot whose configuration does not keep k_patch's confidences positive (confidences_stay_positive): such a
+    // slot is never swept fresh.  After a device-side error the flags are set when the error is READ (device_error, behind a synchronisation):
+    // a reset and batch pipelined behind the voided batch before that belong to the batches the report voids (every batch since the last one).
+    std::vector<char> gp_tainted;
     std::vector<float> fresh_z;       // ... and the ground height its cells hold by definition
     bool fresh_enabled = true;        // env GG_FRESH_MAPS=0 / tuning "fresh_maps": gg_reset_maps writes every cell, as before
     // GG_FLAG_MINIMAL_LAYERS: the slot's last cloud left maxGroundHeight / groundCandidates / planeDist unwritten; a reader of one of
@@ -318,6 +325,15 @@ int fail(gg_context *ctx, int code, const char *who, const char *what) { return 
         if (e__ != hipSuccess) return fail((ctx), GG_ERR_HIP, #call, e__);     \
     } while (0)
 
+// The sign tag of fresh maps (gg_internal.h Arena::gp_fresh_cell) needs every confidence the path writes to be positive.  The sweep's is
+// (max(w - w / f, 0.001), unless f is NaN), k_patch's min(old + 0.1, 0.5) is, and its :387 min((sum / (2 * factor) + old) / 2, 1) is for a
+// positive, finite occupied_cells_point_count_factor -- nothing else in gg_config enters a confidence.
+static bool confidences_stay_positive(const gg_config &c)
+{
+    return c.occupied_cells_point_count_factor > 0 && std::isfinite((double)c.occupied_cells_point_count_factor) &&
+           c.occupied_cells_decrease_factor == c.occupied_cells_decrease_factor;
+}
+
 // After a synchronisation: did a kernel give up a bounded wait (Arena::dev_error)?  The reference has no error path at all
 // (SURVEY 5); a library that spins inside kernels must at least say so instead of hanging or returning garbage silently.
 // The word is read AND cleared here: the report is about the batches enqueued since the last report -- their outputs are void, the
@@ -328,6 +344,7 @@ int device_error(gg_context *ctx)
     const uint32_t code = ctx->h_dev_error ? *ctx->h_dev_error : 0u;
     if (code == GG_DEVERR_NONE) return GG_OK;
     *ctx->h_dev_error = GG_DEVERR_NONE;
+    std::fill(ctx->gp_tainted.begin(), ctx->gp_tainted.end(), (char)1); // (a fresh launch cut short may have left tagged confidences behind)
     return fail(ctx, GG_ERR_HIP, code == GG_DEVERR_FRONT_WAIT ? "k_classify: a cloud's tile scan never completed (bounded wait ran out); the outputs of that batch are void"
                                  : code == GG_DEVERR_SCAN_WAIT ? "k_scan: the sums of an earlier part of a cloud never arrived (bounded wait ran out); the outputs of that batch are void"
                                  : code == GG_DEVERR_SWEEP_WAIT ? "k_sweep: a hand-over between work-groups never arrived (bounded wait ran out); the outputs of that batch are void"
@@ -877,6 +894,7 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
         p.label_shift = nb == 1 ? ctx->next_label_shift : 0;
         p.io_index = i;
         p.cfg_index = ctx->slot_own[slot] ? slot : -1;
+        if (!confidences_stay_positive(ctx->slot_own[slot] ? ctx->slot_cfg[slot] : ctx->cfg)) ctx->gp_tainted[slot] = 1; // (filled first below, and by its next reset)
         max_n[half] = std::max(max_n[half], p.n_points);
         ctx->lazy_pending[slot] = lazy ? 1 : 0;
         if (lazy) ctx->lazy_params[slot] = p;
@@ -888,12 +906,12 @@ int enqueue_batch(gg_context *ctx, const gg_batch *b, hipStream_t s, const Layer
         for (int i = 0; i < nb; ++i) score_half[i < n_first ? 0 : 1] |= ctx->score_on[hp[i].slot] != 0;
     const bool own_masks = (score_half[0] || score_half[1]) && !b->d_label_masks;
     // FRESH maps (gg_context::fresh): a (half) launch whose maps are all fresh, and large enough for the plain k_sweep, takes them as they
-    // are -- k_patch marks what it writes, the sweep reads nothing else of the layer --; in any other launch they are filled first
+    // are -- k_patch tags what it writes, the sweep takes nothing else of the layer as it is --; in any other launch they are filled first
     bool fresh_half[2] = {false, false};
     for (int h = 0; h < (split ? 2 : 1); ++h) {
         const int lo = h ? n_first : 0, hi = h ? nb : n_first;
         bool all = ctx->fresh_enabled && !plan && !ctx->d_sweep_dbg && sweep_takes_fresh(ctx->arena, ctx->sweep_params, hi - lo);
-        for (int i = lo; i < hi && all; ++i) all = ctx->fresh[hp[i].slot] != 0;
+        for (int i = lo; i < hi && all; ++i) all = ctx->fresh[hp[i].slot] != 0 && !ctx->gp_tainted[hp[i].slot];
         fresh_half[h] = all;
         if (all)
             for (int i = lo; i < hi; ++i) hp[i].fresh = 1, ctx->fresh[hp[i].slot] = 0;
@@ -1165,6 +1183,7 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
     ctx->no_confidence.assign(n_slots, 0); // layers start as zeros, but only gg_reset_map makes a slot usable
     ctx->fresh.assign(n_slots, 0);
     ctx->fresh_z.assign(n_slots, 0.0f);
+    ctx->gp_tainted.assign(n_slots, 0); // (the arena starts zeroed)
     ctx->fresh_enabled = env_int("GG_FRESH_MAPS", 1) != 0;
     ctx->lazy_pending.assign(n_slots, 0);
     ctx->lazy_params.assign(n_slots, CloudParams{});
@@ -1321,6 +1340,13 @@ int gg_create(const gg_geometry *geom_in, int n_slots, size_t max_points, int de
         a.dev_error = (uint32_t *)dptr;
     }
     CREATE_CHK(hipMemcpyAsync(const_cast<int *>(a.gp_border), gp_border.data(), gp_border.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    {   // does detect_ground_patches visit a cell of ring >= c?  (rebuild_patch_table's "visited": rows 2 .. 2 (cols / 2) - 3, columns 2 .. rows - 3)
+        const int c = n / 2 - 1;
+        a.gp_border_patched = 0;
+        for (int col = 2; col < n - 2; ++col)
+            for (int row = 2; row < 2 * (n / 2) - 2; ++row)
+                if (std::max(std::abs(row - c), std::abs(col - c)) >= c) a.gp_border_patched = 1;
+    }
     CREATE_CHK(hipStreamSynchronize(ctx->stream));
     if (ctx->d_sweep_dbg) {
         const unsigned long long mode = getenv("GG_SWEEP_DEBUG") ? strtoull(getenv("GG_SWEEP_DEBUG"), nullptr, 0) : 0ull;
@@ -1764,12 +1790,24 @@ int gg_reset_maps(gg_context *ctx, int first_slot, int n, double pos_x, double p
             launch_fill_bytes((uint8_t *)(a.tile_live + (size_t)first * a.tile_live_stride), (size_t)count * a.tile_live_stride * 4, 0xFF, on);
         }
         if (ctx->fresh_enabled) { // the interior stays unwritten: the next batch's sweep rewrites it anyway (make_real() for everybody else)
-            static const bool probe_all = env_int("GG_FRESH_MAPS", 1) == 2; // (measurement: every cell written AND marked)
-            if (probe_all) launch_fill2_strided(gp2_ptr(a, first), (size_t)a.gpl.elems, a.gp2_stride, count, init[GG_LAYER_GROUND], init[GG_LAYER_GROUNDPATCH], a.gp_valid, on);
-            launch_reset_fresh(a, first, count, init[GG_LAYER_GROUND], init[GG_LAYER_GROUNDPATCH], on, probe_all ? 1 : 0);
+            // ... unless a slot's memory may hold sign bits from outside the path (gp_tainted): those runs of slots get the real fill, once
+            for (int s = first; s < first + count;) {
+                if (!ctx->gp_tainted[s]) {
+                    ++s;
+                    continue;
+                }
+                int e = s + 1;
+                while (e < first + count && ctx->gp_tainted[e]) ++e;
+                launch_fill2_strided(gp2_ptr(a, s), (size_t)a.gpl.elems, a.gp2_stride, e - s, init[GG_LAYER_GROUND], init[GG_LAYER_GROUNDPATCH], a.gp_valid, on);
+                for (int k = s; k < e; ++k) ctx->gp_tainted[k] = 0;
+                s = e;
+            }
+            launch_reset_fresh(a, first, count, init[GG_LAYER_GROUND], init[GG_LAYER_GROUNDPATCH], on);
             for (int s = first; s < first + count; ++s) ctx->fresh[s] = 1, ctx->fresh_z[s] = odom_z;
-        } else
+        } else {
             launch_fill2_strided(gp2_ptr(a, first), (size_t)a.gpl.elems, a.gp2_stride, count, init[GG_LAYER_GROUND], init[GG_LAYER_GROUNDPATCH], a.gp_valid, on);
+            for (int s = first; s < first + count; ++s) ctx->gp_tainted[s] = 0;
+        }
     };
     if (split) {
         if (!ctx->probe_no_fork) {
@@ -2118,7 +2156,7 @@ static int transfer_layers(gg_context *ctx, bool import, int n, const int32_t *s
     for (int i = 0; i < n; ++i) {
         const int slot = slot_of(slots, first_slot, i);
         if (gp_mask) ctx->fresh[slot] = 0; // (the kernel wrote the pair of every cell)
-        if (layer_mask & (1u << GG_LAYER_GROUNDPATCH)) ctx->no_confidence[slot] = 0;
+        if (layer_mask & (1u << GG_LAYER_GROUNDPATCH)) ctx->no_confidence[slot] = 0, ctx->gp_tainted[slot] = 1;
         if (percall_mask) ctx->lazy_pending[slot] = 0; // (computed above, or all three imported)
     }
     return GG_OK;
@@ -3167,7 +3205,7 @@ int gg_set_layer(gg_context *ctx, int slot, int layer, const float *src)
     if (!src || layer < 0 || layer >= GG_NUM_LAYERS) return GG_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (const int rc = own_stream_waits_for_batches(ctx)) return rc;
-    if (layer == GG_LAYER_GROUNDPATCH) ctx->no_confidence[slot] = 0;
+    if (layer == GG_LAYER_GROUNDPATCH) ctx->no_confidence[slot] = 0, ctx->gp_tainted[slot] = 1;
     // both kinds of layer have a device representation of their own (sheared pairs / sparse tile blocks): converted at the host boundary
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_image, src, (size_t)ctx->arena.g.C * 4, hipMemcpyHostToDevice, ctx->stream));
     if (const int rc = insert_planes(ctx, slot, 1u << layer, ctx->d_image, (size_t)ctx->arena.g.C, ctx->stream)) return rc;
@@ -3934,6 +3972,7 @@ int gg_run_stage(gg_context *ctx, int slot, int stage, const gg_stage_args *args
         HIPCHK(ctx, hipGetLastError());
     }
     ctx->no_confidence[slot] = 0; // (every stage may write confidences)
+    ctx->gp_tainted[slot] = 1;    // (... from whatever the caller put into the layers)
     if (const int rc = own_stream_mutated_map(ctx)) return rc;
     SYNCCHK(ctx, hipStreamSynchronize(s));
     return GG_OK;

@@ -84,7 +84,7 @@ struct CloudParams {
     double pos_x, pos_y;
     int has_tf;     // points are in the sensor frame: p_map = (float)(R p + t) first (src/GroundGridNodelet.cpp:166-181)
     int fresh;      // the slot's (ground, confidence) layer holds the reset values by DEFINITION -- only its never-swept border, Arena::gp_fresh_cell
-                    // and what k_patch writes in this call (Arena::gp_bits) are in memory; the sweep of this call makes the layer real
+                    // and what k_patch writes in this call (tagged in bit 31 of the confidence word) count; the sweep of this call makes the layer real
     int no_confidence; // the slot's groundpatch layer is known to hold nothing above 0.01 (fresh or only scrolled since
                     // gg_reset_map): the line-of-sight test (:269 needs groundpatch(I) > 0.01f) cannot fire, K1 skips the walks
     double tf[12];  // map <- cloud frame, 3x4 row-major (R | t)
@@ -113,13 +113,19 @@ struct Arena {
     float *layers;  size_t slot_layer_stride;  // the nine per-call layers of slot s, TILE BY TILE (percall_block below): layers + s*slot_layer_stride
     const uint32_t *gp_valid;     // one bit per element of the gp2 order: does gg_reset_maps fill it (the 128-byte lines that hold cells; the rest is padding)
     float2 *gp2;    size_t gp2_stride;    GpLayout gpl;              // (ground, confidence) of slot s: gp2 + s*gp2_stride, element order gp_layout.h
-    // FRESH maps (gg_reset_maps did not write the interior: CloudParams::fresh).  gp_bits: per slot one bit per element of the gp2 order, bit
-    // (e - 1) of the slot's words -- a wave-step of k_sweep (64 consecutive elements from 1 + 64 k) is ONE 64-bit word; zeroed by the reset,
-    // set by k_patch for the cells it writes.  gp_fresh_cell: a padding element that holds the reset values (ground = odom_z, confidence
-    // = 1e-7): where a fresh map's unwritten cells are read from
+    // FRESH maps (gg_reset_maps did not write the interior: CloudParams::fresh).  The layer's memory is whatever the slot's last use left
+    // there -- positive confidences, always: every confidence the path writes is positive (k_patch: min(old + 0.1, 0.5) or a positive average;
+    // the sweep: max(w - w / f, 0.001); the reset: 1e-7), and a slot whose memory may hold anything else is filled by its next reset
+    // (gg_context::gp_tainted).  On a fresh launch k_patch stores its confidences with bit 31 SET; k_sweep<FRESH> loads the cells the plain
+    // kernel loads and takes a cell as it is (confidence |w|) iff the bit is set, else the reset's pair (sweep_core.h sw_untag).  Every cell
+    // the sweep visits is stored positive, the tagged cells nobody visits (ring >= c) are cleared when the kernel ends: after a complete call
+    // no cell carries the tag, which is why stale memory always reads as "not written in this call".
+    // gp_fresh_cell: a padding element that holds the reset values (ground = odom_z, confidence = 1e-7).
+    // gp_bits*: a region behind each slot's layer, RESERVED -- it held one written-cell bit per element before the tag; no kernel touches it
     unsigned long long *gp_bits;  size_t gp_bits_stride;  int gp_fresh_cell;
-    int gp_bits_off, gp_bits_words;           // the bits of a slot sit behind its layer: 8-byte element gp_bits_off of the slot's gp2 region (gp_bits = gp2 + that)
-    const int *gp_border;  int gp_border_n;   // the elements of the cells no sweep visits (ring >= c): k_sweep<FRESH> writes the reset's pair into them
+    int gp_bits_off, gp_bits_words;           // (the reserved region: 8-byte element gp_bits_off of the slot's gp2 region, gp_bits = gp2 + that)
+    const int *gp_border;  int gp_border_n;   // the elements of the cells no sweep visits (ring >= c): k_sweep<FRESH> writes the reset's pair into the untagged ones
+    int gp_border_patched;                    // k_patch's quadrant loops (:325-328) reach a cell of ring >= c (maps with an odd number of rows): border cells can carry the tag
     int fresh_launch;                         // this launch's maps are all fresh (CloudParams::fresh): k_sweep's FRESH variant
     uint2 *rec;     uint2 *sorted;  size_t point_stride;            // per slot Nmax
     float *zcell;   size_t zcell_stride;  // per slot: the KEPT heights grouped by cell (K2's stable cell sort), Nmax + 32 T + 64
@@ -699,7 +705,7 @@ void launch_fill_strided(float *dst, size_t n, size_t stride, int count, float v
 void launch_fill_percall(const Arena &a, int first_slot, int n_slots, const float init[GG_NUM_LAYERS], hipStream_t s); // every per-call layer of the slots := init[layer]
 void launch_fill2_strided(float2 *dst, size_t n, size_t stride, int count, float x, float y, const uint32_t *valid, hipStream_t s);
 void launch_fill2(float2 *dst, size_t n, float x, float y, hipStream_t s);
-void launch_reset_fresh(const Arena &a, int first_slot, int count, float x, float y, hipStream_t s, int all_ones = 0); // k1_classify.hip k_reset_fresh
+void launch_reset_fresh(const Arena &a, int first_slot, int count, float x, float y, hipStream_t s); // k1_classify.hip k_reset_fresh
 void launch_layer_to_u8(const float *layer, int rows, int cols, float *d_bounds, uint8_t *d_img, hipStream_t s);
 void launch_terrain_image(const Arena &a, int slot, float *d_img, hipStream_t s);
 void launch_scroll(const Arena &a, int slot, float2 *scratch, int s0, int s1, double pos_x, double pos_y, const double plane[4], hipStream_t s);

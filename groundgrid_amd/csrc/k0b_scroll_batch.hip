@@ -4,7 +4,7 @@
 // place without a grid-wide barrier.  Two passes per chunk of maps instead:
 //   k_scroll_gather: one thread per cell of one map (grid.y = the chunk's maps) computes the cell's new value into a compact scratch row
 //   k_scroll_commit: copies the scratch row back into the map's (ground, confidence) layer -- cell elements only, so that padding
-//                    (the fresh padding element Arena::gp_fresh_cell, the written-cell bits behind the layer) stays as it is.
+//                    (the fresh padding element Arena::gp_fresh_cell among it) stays as it is.
 // Cells are taken in the layer's element order (`cells`: the element and (row, col) of cell t, ascending elements, built once on the
 // host): the scratch rows are written and read contiguously, the commit writes runs of consecutive elements, and the 64 cells of a wave
 // mostly come from 64 consecutive rings of one wedge whose sources lie a near-constant distance away in the same wedge.

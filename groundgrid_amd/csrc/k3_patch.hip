@@ -110,8 +110,9 @@ GG_DEV void patch_sums(const Arena &a, const DevConfig &cfg, const float (*pts)[
 }
 
 // second half (:360-393): the decision against the old cell, one block later
-// bits: the fresh map's written-cell bits (Arena::gp_bits of the slot), or null
-GG_DEV void detect_ground_patch_b(const DevConfig &cfg, const PatchCarry &pc, float2 *gp2, unsigned long long *bits)
+// tag: 0x80000000 on a FRESH map, else 0 -- OR-ed into the stored confidence word.  Both confidences written here are positive (old
+// confidence 1e-7 on a fresh map), so bit 31 is free: it tells this call's sweep that the cell was written in this call (sweep_core.h sw_untag)
+GG_DEV void detect_ground_patch_b(const DevConfig &cfg, const PatchCarry &pc, float2 *gp2, uint32_t tag)
 {
     if (!pc.live) return;
     const float oldConfidence = pc.old.y;   // :360
@@ -129,14 +130,9 @@ GG_DEV void detect_ground_patch_b(const DevConfig &cfg, const PatchCarry &pc, fl
         const float G = (groundlevel * newConfidence + (oldConfidence * oldGroundheight) * 2.0f) / (newConfidence + oldConfidence * 2.0f); // :385
         const float Cf =
             (float)std_min(((double)pointsblockSum / cfg.occupied_cells_point_count_factor_x2 + (double)oldConfidence) / 2.0, 1.0); // :387
-        gp2[pc.gidx] = make_float2(G, Cf);
+        gp2[pc.gidx] = make_float2(G, __uint_as_float(__float_as_uint(Cf) | tag));
     } else if (pc.localmin < oldGroundheight) { // :389
-        gp2[pc.gidx] = make_float2(pc.localmin, std_min(oldConfidence + 0.1f, 0.5f)); // :391, :393
-    } else
-        return;
-    if (bits) { // (the centre cell, element 0, is the sweep's own: :405-411 overwrite it)
-        const unsigned e = (unsigned)pc.gidx - 1u;
-        if (pc.gidx > 0) __hip_atomic_fetch_or(bits + (e >> 6), 1ull << (e & 63u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        gp2[pc.gidx] = make_float2(pc.localmin, __uint_as_float(__float_as_uint(std_min(oldConfidence + 0.1f, 0.5f)) | tag)); // :391, :393
     }
 }
 
@@ -222,9 +218,8 @@ __global__ __launch_bounds__(256) void k_patch(const Arena a, const CloudParams 
     const float *gp_min = L + percall_index(0, PL_MINGROUNDHEIGHT, 0);
     float2 *gp2 = gp2_ptr(a, cp.slot);
     // a FRESH map: every cell's old (ground, confidence) is the reset's pair -- read from the one padding element that holds it --, and the
-    // cells written here are marked for the sweep, which reads nothing else of the layer
-    const bool fresh = !STAGE && (cp.fresh != 0 || GG_DEBUG_SWITCH(a, k3_debug) == 7);
-    unsigned long long *bits = fresh ? a.gp_bits + (size_t)cp.slot * a.gp_bits_stride : nullptr;
+    // cells written here carry the tag for the sweep, which takes nothing else of the layer as it is
+    const uint32_t tag = (!STAGE && cp.fresh != 0) ? 0x80000000u : 0u;
 
     // staging registers: LC columns x LR rows = 12 x 9 QUADS of four rows, the three layers of one quad per thread (threads
     // 0 .. 107): a tile's block of a layer holds a column's 16 rows contiguously and the window starts at a tile row, so a quad
@@ -310,7 +305,7 @@ __global__ __launch_bounds__(256) void k_patch(const Arena a, const CloudParams 
         req_cols = nb == b + 1 ? PC : LC;
         request(nb, req_first, req_cols);
         __syncthreads();
-        detect_ground_patch_b(cfg, consume, gp2, bits); // the previous block's cell: its old (ground, confidence) has arrived meanwhile
+        detect_ground_patch_b(cfg, consume, gp2, tag); // the previous block's cell: its old (ground, confidence) has arrived meanwhile
         consume.live = false;
 
         const int base = (PC * b) & (RING - 1); // 0, 8, 16 or 24: the window is slots base .. base + LC - 1
@@ -374,8 +369,8 @@ __global__ __launch_bounds__(256) void k_patch(const Arena a, const CloudParams 
         if (b >= n_blocks) break;
         block_step(c1, c0);
     }
-    detect_ground_patch_b(cfg, c0, gp2, bits);
-    detect_ground_patch_b(cfg, c1, gp2, bits);
+    detect_ground_patch_b(cfg, c0, gp2, tag);
+    detect_ground_patch_b(cfg, c1, gp2, tag);
 }
 
 void launch_patch(const Arena &a, const CloudParams *d_params, int n_clouds, hipStream_t s)

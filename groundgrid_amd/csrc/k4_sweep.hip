@@ -43,9 +43,12 @@ typedef __attribute__((address_space(3))) int lds_int;
 typedef __attribute__((address_space(3))) uint64_t lds_u64;
 
 // The kernel's only static LDS, 16 bytes and 16-byte aligned, so that the dynamic region behind it (64-bit accesses all over) keeps
-// its alignment: [0] ticket, [1] epoch (k_sweep), [2] a wavefront gave up a bounded wait (DevMemT::give_up).
+// its alignment: [0] ticket, [1] epoch (k_sweep), [2] a wavefront gave up a bounded wait (DevMemT::give_up), [3] FRESH maps whose border
+// k_patch can reach: wavefronts of the work-group that are done (low 16 bits) | BORDER_TAGS: some border cell carries the tag.
 __shared__ __attribute__((aligned(16))) uint32_t sweep_static[4];
 #define sweep_wait_failed sweep_static[2]
+#define sweep_border_word sweep_static[3]
+constexpr uint32_t BORDER_TAGS = 0x10000u;
 
 template <bool DBG> struct DevMemT {
     __amdgpu_buffer_rsrc_t rsrc; // the interleaved (ground, confidence) layer of this cloud
@@ -131,17 +134,8 @@ template <bool DBG> struct DevMemT {
         return Cell{__uint_as_float(v.x), __uint_as_float(v.y)};
     }
     GG_DEV Cell load_value(const Cell &queued, bool, int) const { return queued; }
-    // FRESH maps (gg_internal.h Arena::gp_bits): is the cell's element in memory?  The slot's bit words lie behind its layer, inside the
-    // same buffer descriptor, from byte bits_byte0.  (Per-lane gather: the corner lanes' cells and the two cells of a chain that lie off its
-    // lines; the cells ON the lines are looked up a wave-step at a time, run_chain)
-    uint32_t bits_byte0 = 0u;
-    GG_DEV uint32_t bits_dword(uint32_t voffset, uint32_t soffset) const { return __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, soffset, 0); }
-    GG_DEV bool bit_of(int cell) const
-    {
-        const unsigned e = (unsigned)cell - 1u;
-        const uint32_t w = bits_dword(bits_byte0 + (e >> 5) * 4u, 0u);
-        return cell <= 0 || ((w >> (e & 31u)) & 1u) != 0u; // (element 0, the centre cell, is written when the kernel starts)
-    }
+    // FRESH maps: the arriving cell or the reset's pair (sweep_core.h sw_untag).  The selects write registers of their own, like fresh()
+    GG_DEV Cell untag(const Cell &v, const Cell &reset) const { return sw_untag(v, reset); }
     GG_DEV Cell fresh(const Cell &v) const
     {
         Cell o;
@@ -275,8 +269,9 @@ template <bool S, int B, int J> struct TripKind {
 
 // SPLIT: a preparing wavefront (run_prep) does the layer half of every step (sweep_core.h "Split steps")
 template <int SIDE, bool DBG, bool SPLIT, bool FRESH = false>
-GG_DEV void run_chain(const Params &P, const LdsMap &L, DevMemT<DBG> &mem, int wave_of_side, int lane, WaveClockT<DBG> &clk, int g0, int g1)
+GG_DEV void run_chain(const Params &P, const LdsMap &L, DevMemT<DBG> &mem, int wave_of_side, int lane, WaveClockT<DBG> &clk, int g0, int g1, const Cell &reset = Cell{0.f, 0.f})
 {
+    (void)reset; // (FRESH: the slot's reset pair, sweep_core.h sw_untag)
     static_assert(!(FRESH && SPLIT), "fresh maps: the plain chain only");
     ChainLane<SIDE> st;
     int have_prep = 0; // (split steps) cached count of prepared wave-steps
@@ -289,27 +284,6 @@ GG_DEV void run_chain(const Params &P, const LdsMap &L, DevMemT<DBG> &mem, int w
         st.init(lane, r0, nl, group, P, L);
         const int t_first = group_first_step(), t_last = group_last_step<SIDE>(r0, nl);
         const int has_next = __builtin_amdgcn_readfirstlane(group + 1 < P.groups ? 1 : 0);
-        // FRESH: the requests of wave-step t name elements ownA + 64 (t + 1 + PF) and outA + 64 (t + 1 + PF): bit (X - 1) & 63 of word
-        // ((X - 1) >> 6) + t + 1 + PF of the slot's bit map (a wave-step of the own line is one word, gp_layout.h; of the outer line bits 1 .. 63
-        // of a word and, for lane 63, bit 0 of a word of the next storage group).  Each lane fetches the 32-bit half that holds its bit, two
-        // steps ahead and BEFORE that step's cell requests: loads return in order, and by then only cells the step needs anyway are older.
-        // (Measured per 1024 clouds, k_sweep 0.88 ms on written maps: this 0.98 ms; the words as scalar loads a step ahead, or 64 steps' words
-        // in one coalesced load and v_readlane per step -- lane masks in scalar registers either way -- 1.06 ms: scalar-register spills.)
-        uint32_t fo_own = 0u, fo_out = 0u, sh_own = 0u, sh_out = 0u, mq_own[2] = {0u, 0u}, mq_out[2] = {0u, 0u};
-        if constexpr (FRESH) {
-            const unsigned eo = (unsigned)st.ownA - 1u, eu = (unsigned)st.outA - 1u;
-            fo_own = mem.bits_byte0 + 8u * (unsigned)((int)(eo >> 6) + t_first + 1 + (int)PF) + 4u * ((eo & 63u) >> 5);
-            fo_out = mem.bits_byte0 + 8u * (unsigned)((int)(eu >> 6) + t_first + 1 + (int)PF) + 4u * ((eu & 63u) >> 5);
-            sh_own = eo & 31u;
-            sh_out = eu & 31u;
-            st.xold_bit = mem.bit_of(st.xold_cell);
-            st.end_bit = mem.bit_of(st.own_end);
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                mq_own[k] = mem.bits_dword(fo_own, 8u * (unsigned)k);
-                mq_out[k] = mem.bits_dword(fo_out, 8u * (unsigned)k);
-            }
-        }
         // TRIP steps per trip, no per-step condition: a step past t_last finds every lane idle (no loads, no stores, nothing
         // to wait for), and without a conditional around it the queue registers of a slot never meet a control-flow join --
         // a join makes the compiler copy freshly loaded registers, i.e. wait for the loads it has just issued
@@ -409,13 +383,7 @@ GG_DEV void run_chain(const Params &P, const LdsMap &L, DevMemT<DBG> &mem, int w
                     st.template take<STARTS, K::bnd>(t, tmod, rec, x_in, group > 0, mem);
                     mem.set_counter(w_take, step_no + 1 + AHEAD); // (after the reads above: the DS queue is in order)
                 } else if constexpr (FRESH) {
-                    static_assert((int)TRIP % 2 == 0, "the bit queue's slot is a constant of the unrolled trip");
-                    const uint32_t w_own = mq_own[u & 1], w_out = mq_out[u & 1]; // (requested two steps ago)
-                    const uint32_t ahead = 8u * (unsigned)(t + 2 - t_first);
-                    mq_own[u & 1] = mem.bits_dword(fo_own, ahead);
-                    mq_out[u & 1] = mem.bits_dword(fo_out, ahead);
-                    const bool own_bit = ((w_own >> sh_own) & 1u) != 0u, out_bit = ((w_out >> sh_out) & 1u) != 0u;
-                    st.template step_a<STARTS, K::bnd, true>(t, u % (int)PF, tmod, x_in, P, L, K::bnd == 3 ? trip_bnd : group > 0, mem, own_bit, out_bit);
+                    st.template step_a<STARTS, K::bnd, true>(t, u % (int)PF, tmod, x_in, P, L, K::bnd == 3 ? trip_bnd : group > 0, mem, reset);
                 } else {
                     st.template step_a<STARTS, K::bnd>(t, u % (int)PF, tmod, x_in, P, L, K::bnd == 3 ? trip_bnd : group > 0, mem);
                 }
@@ -480,7 +448,8 @@ template <int SIDE, bool DBG> GG_DEV void run_prep(const Params &P, const LdsMap
     }
 }
 
-template <int CD, bool DBG, bool FRESH = false> GG_DEV void run_corner(const Params &P, const LdsMap &L, DevMemT<DBG> &mem, int lane, WaveClockT<DBG> &clk, int g0, int g1)
+template <int CD, bool DBG, bool FRESH = false>
+GG_DEV void run_corner(const Params &P, const LdsMap &L, DevMemT<DBG> &mem, int lane, WaveClockT<DBG> &clk, int g0, int g1, const Cell &reset = Cell{0.f, 0.f})
 {
     (void)clk;
     CornerRing<CD> st;
@@ -488,8 +457,8 @@ template <int CD, bool DBG, bool FRESH = false> GG_DEV void run_corner(const Par
         const int r0 = LANES * group + 1;
         const int nl = min(P.rings - (r0 - 1), (int)LANES);
         // prepare: 64 rings at once
-        st.template issue<FRESH>(r0 + lane, P, mem);
-        st.finish(P, mem);
+        st.issue(r0 + lane, P, mem);
+        st.template finish<FRESH>(P, mem, reset);
         // a part that does not start at the centre: the ring before its first one comes from another work-group (the importer
         // wavefront sets the counter once the two corner values of that ring are in this work-group's table)
         if (group == g0 && g0 > 0)
@@ -632,7 +601,7 @@ template <bool DBG> GG_DEV void run_export(const Params &P, const LdsMap &L, Dev
 // per CU spills and is 1.6x slower at 1024 clouds per launch.)
 // PARTS: the launch cuts every cloud into several work-groups (tickets, importer / exporter wavefronts, the exchange region); the
 // throughput launches -- one work-group per cloud -- are compiled without any of that.
-// FRESH: every map of the launch is fresh (gg_internal.h Arena::gp_bits; no split steps): a variant of its own --
+// FRESH: every map of the launch is fresh (gg_internal.h Arena::gp_fresh_cell; no split steps): a variant of its own --
 // the work-groups of a throughput launch share the instruction cache, a kernel that carried both step codes was the slower one for both
 // SC (SLOT_CFG): some cloud of the launch has its slot's own configuration: the decay of :463-464 (decrease, its inverse and the fast /
 // exact split) is the cloud's -- three values per work-group, uniform, in scalar registers
@@ -712,14 +681,29 @@ __global__ __launch_bounds__(1024, 5) void k_sweep(const Arena a, const Params P
     }
     // FRESH maps: the cells no sweep visits (ring >= c) were not written by the reset either: unless k_patch has written them (maps with an
     // odd number of rows: its quadrant loops reach one line into ring c, :325-328) they take the reset's pair now, from the padding element
-    // that holds it.  (Nobody reads these before the launch ends: where the bit is 0 the sweep reads the padding element.)
+    // that holds it.  On maps with an even number of rows k_patch reaches no such cell (Arena::gp_border_patched = 0): plain stores, shared by
+    // the parts.  Otherwise a cell k_patch wrote keeps its tag (sweep_core.h sw_untag) until the wavefronts that read it are done.  Only the
+    // work-group of a cloud's LAST part reads cells of ring >= c (the outer line of ring c - 1, the old cells of the last corner rings), so
+    // that work-group alone looks at them: now it writes the reset's pair into the untagged ones -- a chain that reads such a cell before or
+    // after this store selects the reset's pair either way --, and its last wavefront to finish clears the tags (the end of this kernel).
+    Cell reset{0.f, 0.f};
+    bool border_tags = false; // (uniform per wavefront) some border cell of this wavefront's share carries the tag
+    const bool border_mine = FRESH && a.gp_border_patched && g1 >= P_arg.groups;
     if (FRESH) {
         const float2 init = gp2[a.gp_fresh_cell];
-        const unsigned long long *bw = a.gp_bits + (size_t)cp.slot * a.gp_bits_stride;
-        for (int k = (int)threadIdx.x + part * nthreads; k < a.gp_border_n; k += nthreads * n_parts) {
-            const int e = a.gp_border[k];
-            const unsigned q = (unsigned)e - 1u;
-            if (((bw[q >> 6] >> (q & 63u)) & 1ull) == 0ull) gp2[e] = init;
+        reset = Cell{__uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(init.x))), __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(init.y)))};
+        if (threadIdx.x == 0) sweep_border_word = 0u;
+        if (!a.gp_border_patched) {
+            for (int k = (int)threadIdx.x + part * nthreads; k < a.gp_border_n; k += nthreads * n_parts) gp2[a.gp_border[k]] = init;
+        } else if (border_mine) {
+            bool mine = false;
+            for (int k = (int)threadIdx.x; k < a.gp_border_n; k += nthreads) {
+                const int e = a.gp_border[k];
+                const bool tagged = (int)__float_as_uint(gp2[e].y) < 0;
+                if (!tagged) gp2[e] = init;
+                mine |= tagged;
+            }
+            border_tags = __any(mine) != 0;
         }
     }
     // :147 map["points"].setConstant(0.0) -- K3 was the last reader of the KEPT counts; K5 re-counts non-ground points.  Only the
@@ -740,13 +724,13 @@ __global__ __launch_bounds__(1024, 5) void k_sweep(const Arena a, const Params P
         }
     }
     __syncthreads(); // the only barrier of the sweep
+    if (FRESH && border_tags && (threadIdx.x & 63u) == 0u) __hip_atomic_fetch_or(&sweep_border_word, BORDER_TAGS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); // (zeroed in front of the barrier)
 
     DevMemT<DBG> mem;
-    mem.rsrc = __builtin_amdgcn_make_buffer_rsrc(gp2, 0, FRESH ? (a.gp_bits_off + a.gp_bits_words) * 8 : P.gl.elems * 8, 0x00020000); // (FRESH: the layer and its bit words)
+    mem.rsrc = __builtin_amdgcn_make_buffer_rsrc(gp2, 0, P.gl.elems * 8, 0x00020000);
     mem.lds = (lds_int *)lds;
     mem.xchg = a.sweep_xchg + (size_t)cp.slot * a.sweep_xchg_stride;
     mem.seq = epoch;
-    if (FRESH) mem.bits_byte0 = (uint32_t)a.gp_bits_off * 8u;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63u);
     const int W = P.waves_per_side;
     WaveClockT<DBG> clk;
@@ -778,22 +762,37 @@ __global__ __launch_bounds__(1024, 5) void k_sweep(const Arena a, const Params P
         } else if (PARTS && g1 < P.groups)
             run_export<DBG>(P, L, mem, lane, g1);
     } else if (wave < 4 * W && side == SIDE_A)
-        run_chain<SIDE_A, DBG, false, FRESH>(P, L, mem, w_of_side, lane, clk, g0, g1);
+        run_chain<SIDE_A, DBG, false, FRESH>(P, L, mem, w_of_side, lane, clk, g0, g1, reset);
     else if (wave < 4 * W && side == SIDE_B)
-        run_chain<SIDE_B, DBG, false, FRESH>(P, L, mem, w_of_side, lane, clk, g0, g1);
+        run_chain<SIDE_B, DBG, false, FRESH>(P, L, mem, w_of_side, lane, clk, g0, g1, reset);
     else if (wave < 4 * W && side == SIDE_C)
-        run_chain<SIDE_C, DBG, false, FRESH>(P, L, mem, w_of_side, lane, clk, g0, g1);
+        run_chain<SIDE_C, DBG, false, FRESH>(P, L, mem, w_of_side, lane, clk, g0, g1, reset);
     else if (wave < 4 * W)
-        run_chain<SIDE_D, DBG, false, FRESH>(P, L, mem, w_of_side, lane, clk, g0, g1);
+        run_chain<SIDE_D, DBG, false, FRESH>(P, L, mem, w_of_side, lane, clk, g0, g1, reset);
     else if (wave == 4 * W)
-        run_corner<0, DBG, FRESH>(P, L, mem, lane, clk, g0, g1);
+        run_corner<0, DBG, FRESH>(P, L, mem, lane, clk, g0, g1, reset);
     else if (wave == 4 * W + 1)
-        run_corner<1, DBG, FRESH>(P, L, mem, lane, clk, g0, g1);
+        run_corner<1, DBG, FRESH>(P, L, mem, lane, clk, g0, g1, reset);
     else if (PARTS && wave == 4 * W + 2) {
         if (part > 0) run_import<DBG>(P, L, mem, lane, g0);
     } else if (PARTS && g1 < P.groups)
         run_export<DBG>(P, L, mem, lane, g1);
     clk.end(wave, lane);
+    if (FRESH && border_mine) {
+        // A wavefront that gets here has consumed every cell it requested (a valid request of wave-step t is used at t + PF, within the
+        // chain's steps; the release orders whatever is still in flight).  The LAST wavefront of the work-group to get here turns the tagged
+        // border cells into plain cells: after this launch no cell of the map carries the tag.  No barrier: a wavefront that is done leaves,
+        // and its registers are the next work-group's (a barrier here cost the launch 0.33 ms of 0.92: DESIGN 4 "Fresh maps").
+        uint32_t before = 0u;
+        if (lane == 0) before = __hip_atomic_fetch_add(&sweep_border_word, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+        before = __builtin_amdgcn_readfirstlane(before);
+        if ((before & 0xFFFFu) == (uint32_t)(nthreads >> 6) - 1u && (before & BORDER_TAGS))
+            for (int k = lane; k < a.gp_border_n; k += 64) {
+                const int e = a.gp_border[k];
+                const float2 v = gp2[e];
+                if ((int)__float_as_uint(v.y) < 0) gp2[e] = make_float2(v.x, __uint_as_float(__float_as_uint(v.y) & 0x7FFFFFFFu));
+            }
+    }
     if (PARTS) { // the last work-group of the launch re-arms the tickets and advances the epoch (never 0: the arena starts zeroed)
         __syncthreads();
         if (threadIdx.x == 0 && sweep_wait_failed) __hip_atomic_store(a.dev_error, (uint32_t)GG_DEVERR_SWEEP_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -822,7 +821,7 @@ size_t sweep_lds_bytes(const Params &P) { return parts_lds_bytes(P, 1); }
 size_t sweep_xchg_entries(const Params &P) { return (size_t)xchg_entries(P.groups); }
 
 // Would launch_sweep give this launch the plain k_sweep -- one work-group per cloud, no split steps, nothing forced?  (What a launch of FRESH
-// maps needs, gg_internal.h Arena::gp_bits: decided before k_patch runs.)
+// maps needs, gg_internal.h Arena::gp_fresh_cell: decided before k_patch runs.)
 bool sweep_takes_fresh(const Arena &a, const Params &P_in, int n_clouds)
 {
     if (P_in.rings <= 0 || n_clouds <= SWEEP_PAIR_MAX_CLOUDS || a.tune_sweep_gpw || a.tune_sweep_split == 1 || a.tune_sweep_fault || a.tune_sweep_pair == 4) return false;

@@ -83,7 +83,7 @@ struct Params {
     int waves_per_side;
     int gpw;    // ring groups per work-group ("part"); >= groups: one work-group sweeps the whole map (see "Parts" below)
     int split_steps; // 1: every chain wavefront has a PREPARING wavefront next to it (see "Split steps"; needs gpw == 1)
-    int fresh_cell; // FRESH maps (gg_internal.h Arena::gp_bits): the layer element that holds the reset's (ground, confidence)
+    int fresh_cell; // FRESH maps (gg_internal.h Arena::gp_fresh_cell): the layer element that holds the reset's (ground, confidence)
     int r2min;  // the confidence decay (:463-464) applies to cell (x, y) iff (x-c)^2 + (y-c)^2 >= r2min (host-computed, exact)
     double decrease, inv_decrease;
     int decay_fast;
@@ -160,6 +160,28 @@ SW_HD bool sw_any(bool b) { return __any(b) != 0; }
 SW_HD bool sw_any(bool b) { return b; }
 #define SW_KEEP_BRANCH() ((void)0)
 #endif
+
+// FRESH maps (gg_internal.h Arena::gp_fresh_cell): a cell k_patch wrote in this call carries bit 31 of its confidence word -- every
+// confidence the path writes is positive, so the bit is free --, anything else in memory is stale and stands for the reset's pair.  Decided
+// where a loaded cell arrives, on the integer bit: -0 and NaN must not decide.
+SW_HD Cell sw_untag(const Cell &v, const Cell &reset)
+{
+    uint32_t u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    u = __float_as_uint(v.w);
+#else
+    memcpy(&u, &v.w, 4);
+#endif
+    const bool tagged = (int32_t)u < 0;
+    const uint32_t m = u & 0x7FFFFFFFu;
+    float w;
+#if defined(__HIP_DEVICE_COMPILE__)
+    w = __uint_as_float(m);
+#else
+    memcpy(&w, &m, 4);
+#endif
+    return Cell{tagged ? v.g : reset.g, tagged ? w : reset.w};
+}
 
 SW_HD float decayed_confidence(float occupied, bool decay, const Params &P)
 {
@@ -326,6 +348,7 @@ SW_HD LdsMap lds_layout(int c, int groups, int g0 = 0, int g1 = -1, bool split_s
 //   Cell  load_issue(bool valid, int cell)    start a load of the interleaved layer element (invalid: no traffic, value 0)
 //   Cell  load_value(const Cell &queued, bool valid, int cell)   the value at use time (device: `queued` itself)
 //   Cell  fresh(Cell v)                   v in registers of its own (host: identity)
+//   Cell  untag(Cell v, Cell reset)       FRESH maps: sw_untag(v, reset), likewise in registers of its own
 //   void  mark(int k)                     timing instrumentation point (no-op unless a tool asks for it)
 //   void  store(bool valid, int cell, Cell v)
 //   int   counter(int word)               read a progress counter (LDS)
@@ -462,7 +485,6 @@ template <int SIDE> struct ChainLane {
     // handed from the first half of a step to the second
     WP xa, cs0, cs1, cpred;
     float w_new_;
-    bool xold_bit = true, end_bit = true; // FRESH maps: are the two cells off the lines (xold_cell, own_end) in memory
 
     SW_HD void init(int lane, int r0, int nl, int group, const Params &P, const LdsMap &L)
     {
@@ -542,11 +564,11 @@ template <int SIDE> struct ChainLane {
     //                    step outside a range that its trip touches reads a value no lane selects, and publishes from no active lane)
     // (1 = test per step).  A range test is seven scalar instructions and a taken branch, the blocks meet the step at control-flow
     // joins that cost register copies, and a lone wavefront pays ~5 cycles for an instruction of any kind.
-    // FRESH (device only; gg_internal.h Arena::gp_bits): the map's layer holds the reset's pair by definition, only the cells marked in the
-    // bit map are in memory -- own_bit / out_bit say so for the cells this step REQUESTS on the own and the outer line; the others are read
-    // from P.fresh_cell, the one element that holds the reset's pair
+    // FRESH (gg_internal.h Arena::gp_fresh_cell): the map's layer holds the reset's pair by definition, only the cells k_patch wrote in this
+    // call count -- they carry the tag (sw_untag).  The step makes the plain step's loads, cell for cell, and decides where the two cells
+    // arrive: tagged -> the cell, anything else -> `reset`, the slot's reset pair (uniform: loaded once per cloud)
     template <bool STARTS = true, int BND = 1, bool FRESH = false, class Mem>
-    SW_HD void step_a(int t, int slot, int tmod, WP x_in, const Params &P, const LdsMap &L, bool has_prev_group, Mem &mem, bool own_bit = true, bool out_bit = true)
+    SW_HD void step_a(int t, int slot, int tmod, WP x_in, const Params &P, const LdsMap &L, bool has_prev_group, Mem &mem, const Cell &reset = Cell{0.f, 0.f})
     {
         (void)L;
         // ---- the visited cell's new confidence depends on its old one only (its rare exact path is the step's only branch
@@ -572,23 +594,16 @@ template <int SIDE> struct ChainLane {
         const int own_col = ownA + 64 * (t + 1);
         int own_now = (int)ua == len + 1 ? own_end : own_col;
         own_now = ua == 0u ? xold_cell : own_now;
-        const Cell own = mem.fresh(mem.load_value(q_own[slot], col, own_now));
-        const Cell out = mem.fresh(mem.load_value(q_out[slot], col, outA + 64 * (t + 1)));
+        const Cell own = FRESH ? mem.untag(mem.load_value(q_own[slot], col, own_now), reset) : mem.fresh(mem.load_value(q_own[slot], col, own_now));
+        const Cell out = FRESH ? mem.untag(mem.load_value(q_out[slot], col, outA + 64 * (t + 1)), reset) : mem.fresh(mem.load_value(q_out[slot], col, outA + 64 * (t + 1)));
         // ---- and the one to request for step s + PF
         const unsigned uq = ua + (unsigned)PF;
         const bool colq = uq < (unsigned)lim;
         const int own_colq = ownA + 64 * (t + 1 + PF);
         int own_req = (int)uq == len + 1 ? own_end : own_colq; // (two selects on ready values: no branch)
         own_req = uq == 0u ? xold_cell : own_req;
-        int out_req = outA + 64 * (t + 1 + PF);
-        if (FRESH) {
-            bool ob = (int)uq == len + 1 ? end_bit : own_bit;
-            ob = uq == 0u ? xold_bit : ob;
-            own_req = ob ? own_req : P.fresh_cell;
-            out_req = out_bit ? out_req : P.fresh_cell;
-        }
         q_own[slot] = mem.load_issue(colq, own_req);
-        q_out[slot] = mem.load_issue(colq, out_req);
+        q_out[slot] = mem.load_issue(colq, outA + 64 * (t + 1 + PF));
         // ---- advance the window
         Sg = Ng;
         Sw = Nw;
@@ -804,25 +819,24 @@ template <int CD> struct CornerRing {
     }
 
     // ---- prepare, part 1: request the ring's old cells
-    template <bool FRESH = false, class Mem> SW_HD void issue(int ring, const Params &P, Mem &mem)
+    template <class Mem> SW_HD void issue(int ring, const Params &P, Mem &mem)
     {
         live = ring <= P.rings;
         r = live ? ring : P.rings; // (idle lanes keep valid addresses)
         for (int a = -1; a <= 1; ++a)
             for (int b = -2; b <= 1; ++b) {
-                int cell = cell_at(P, r, a, b);
-                if constexpr (FRESH) cell = mem.bit_of(cell) ? cell : P.fresh_cell; // (a FRESH map: step_a)
-                q[a + 1][b + 2] = mem.load_issue(live && is_old(r, a, b), cell);
+                q[a + 1][b + 2] = mem.load_issue(live && is_old(r, a, b), cell_at(P, r, a, b));
             }
         e00 = cell_at(P, r, 0, 0);
         e0m1 = cell_at(P, r, 0, -1);
     }
-    // ---- prepare, part 2: products and the three confidences
-    template <class Mem> SW_HD void finish(const Params &P, Mem &mem)
+    // ---- prepare, part 2: products and the three confidences (a FRESH map: the arriving cells decided like step_a's, sw_untag)
+    template <bool FRESH = false, class Mem> SW_HD void finish(const Params &P, Mem &mem, const Cell &reset = Cell{0.f, 0.f})
     {
         for (int a = -1; a <= 1; ++a)
             for (int b = -2; b <= 1; ++b) {
-                const Cell v = mem.load_value(q[a + 1][b + 2], live && is_old(r, a, b), cell_at(P, r, a, b)); // (the element only matters to the host's late loads)
+                Cell v = mem.load_value(q[a + 1][b + 2], live && is_old(r, a, b), cell_at(P, r, a, b)); // (the element only matters to the host's late loads)
+                if (FRESH) v = sw_untag(v, reset);
                 ow[a + 1][b + 2] = v.w;
                 op[a + 1][b + 2] = v.w * v.g;
                 if (a == 0 && b == 0) g00 = v.g;

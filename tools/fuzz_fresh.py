@@ -1,5 +1,5 @@
-"""Batches of FRESH maps (gg_reset_maps leaves the (ground, confidence) layer unwritten; k_patch marks what it writes, k_sweep<FRESH> reads
-nothing else) on random geometries -- odd and even sizes, one to four ring groups, one or several work-groups per cloud -- with random
+"""Batches of FRESH maps (gg_reset_maps leaves the (ground, confidence) layer unwritten; k_patch tags what it writes in the sign bit of the
+confidence, k_sweep<FRESH> takes every untagged cell for the reset's pair) on random geometries -- odd and even sizes, one to four ring groups, one or several work-groups per cloud -- with random
 clouds, heights and batch sizes, then a second call on the maps the first left and a third after a re-initialisation of a random subset
 (a launch that mixes fresh and warm maps fills the fresh ones first): labels and the two persistent layers of EVERY map against the
 oracle.  On the GPU box:  python tools/fuzz_fresh.py [first] [last]"""
