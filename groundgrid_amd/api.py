@@ -69,6 +69,76 @@ def _check(L, ctx, rc, what):
         raise GroundGridError(f"{what}: {_lib.STATUS.get(rc, rc)} {msg}")
 
 
+# -- the argument frame of the plane methods (fuse_states, route_planes, match_planes, footprint_planes, route_headings, track_clusters)
+
+def _plane_order(who, order, rows, cols):
+    """`order` checked: (the shape of one plane, GG_PLANES_*)"""
+    if order not in ("row", "col"):
+        raise ValueError(f"{who}: order is 'row' or 'col'")
+    return ((rows, cols), _lib.GG_PLANES_ROWMAJOR) if order == "row" else ((cols, rows), _lib.GG_PLANES_COLMAJOR)
+
+
+def _check_integers(who, **named):
+    for name, v in named.items():
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{who}: {name} is an integer")
+
+
+def _is_int32(t, shape, device):
+    import torch
+
+    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == device
+
+
+def _is_planes(t, plane):
+    """a contiguous CUDA torch.int32 tensor [B, *plane]"""
+    import torch
+
+    return torch.is_tensor(t) and t.dim() == 3 and _is_int32(t, (int(t.shape[0]),) + plane, t.device)
+
+
+def _int32_array(who, name, given, shape_text, ok, suffix=""):
+    """anything np.asarray turns into exact int32 of a shape that `ok` accepts, as a contiguous host array"""
+    try:
+        given = np.asarray(given)
+        host = np.ascontiguousarray(given.astype(np.int32))
+        exact = given.shape == host.shape and np.array_equal(given, host)
+    except (TypeError, ValueError, OverflowError) as e:
+        raise ValueError(f"{who}: {name} must be {shape_text} int32: {e}") from None
+    if not ok(host.shape) or not exact:
+        raise ValueError(f"{who}: {name} of shape {host.shape} are not {shape_text} int32{suffix}")
+    return host
+
+
+def _int32_ptr(host):
+    return host.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _reuse_outputs(who, res, want, device, inputs, fill=None, in_place="is an input of the call: no update in place is defined"):
+    """The `out` of a plane method.  want: {field of res: shape, or None for a field not asked for}.  A tensor that res holds must be
+    asked for, be int32 of that shape on `device`, and start at none of the `inputs` (data_ptr()s); nothing is allocated before every
+    field has passed, then the missing ones are (fill: {field: the word a fresh tensor is filled with})."""
+    import torch
+
+    for field, shape in want.items():
+        t = getattr(res, field)
+        if shape is None:
+            if t is not None:
+                raise ValueError(f"{who}: out.{field} is given but not asked for")
+        elif t is not None:
+            if not _is_int32(t, shape, device):
+                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {shape}")
+            if t.data_ptr() in inputs:
+                raise ValueError(f"{who}: out.{field} {in_place}")
+    for field, shape in want.items():
+        if shape is not None and getattr(res, field) is None:
+            if fill and field in fill:
+                setattr(res, field, torch.full(shape, fill[field], dtype=torch.int32, device=device))
+            else:
+                setattr(res, field, torch.empty(shape, dtype=torch.int32, device=device))
+    return res
+
+
 class GridMap:
     """Handle to one device-resident map state (the reference's grid_map::GridMap with its 11 layers)."""
 
@@ -1038,15 +1108,9 @@ class GroundSegmentation:
         `evidence` or `states` -- no update in place is defined, alternate between two FusionOutputs.  Integer arithmetic only:
         bit-identical from run to run.  Enqueued on the context's own stream or, with on_torch_stream=True, on the current torch stream;
         nothing synchronises.  No map is read or changed."""
-        import torch
-
         who = "fuse_states"
-        if order not in ("row", "col"):
-            raise ValueError(f"{who}: order is 'row' or 'col'")
-        par = {"hit": hit, "miss": miss, "decay": decay, "e_min": e_min, "e_max": e_max, "free_threshold": free_threshold, "occ_threshold": occ_threshold}
-        for name, v in par.items():
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"{who}: {name} is an integer")
+        plane, c_order = _plane_order(who, order, self.rows, self.cols)
+        _check_integers(who, hit=hit, miss=miss, decay=decay, e_min=e_min, e_max=e_max, free_threshold=free_threshold, occ_threshold=occ_threshold)
         lim = _lib.GG_FUSE_LIMIT
         if not (0 <= hit <= lim and 0 <= miss <= lim and 0 <= decay <= lim):
             raise ValueError(f"{who}: hit, miss and decay lie in [0, 2^30 - 1]")
@@ -1054,54 +1118,24 @@ class GroundSegmentation:
             raise ValueError(f"{who}: -(2^30 - 1) <= e_min <= 0 <= e_max <= 2^30 - 1")
         if not (e_min <= free_threshold <= -1 and 1 <= occ_threshold <= e_max):
             raise ValueError(f"{who}: e_min <= free_threshold <= -1 and 1 <= occ_threshold <= e_max")
-        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
-
-        def is_planes(t):
-            return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 3 and t.is_contiguous() and tuple(t.shape[1:]) == plane
-
-        if not is_planes(states):
+        if not _is_planes(states, plane):
             raise ValueError(f"{who}: states must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
         B = int(states.shape[0])
-        if evidence is not None and not (is_planes(evidence) and evidence.shape[0] == B and evidence.device == states.device):
+        if evidence is not None and not (_is_planes(evidence, plane) and evidence.shape[0] == B and evidence.device == states.device):
             raise ValueError(f"{who}: evidence must be a contiguous CUDA torch.int32 tensor of the shape and device of states")
-        host_shifts = None
-        if shifts is not None:
-            try:
-                given = np.asarray(shifts)
-                host_shifts = np.ascontiguousarray(given.astype(np.int32))
-                exact = given.shape == host_shifts.shape and np.array_equal(given, host_shifts)
-            except (TypeError, ValueError, OverflowError) as e:
-                raise ValueError(f"{who}: shifts must be [B, 2] int32: {e}") from None
-            if host_shifts.shape != (B, 2) or not exact:
-                raise ValueError(f"{who}: shifts of shape {host_shifts.shape} are not [B, 2] int32")
-        res = out if out is not None else FusionOutputs()
+        host_shifts = _int32_array(who, "shifts", shifts, "[B, 2]", lambda sh: sh == (B, 2)) if shifts is not None else None
         shape = (B,) + plane
         want = {"evidence": shape, "state": shape if fused else None, "frontier": shape if frontier else None, "counts": (B, 4) if counts else None}
-        inputs = [t.data_ptr() for t in (states, evidence) if t is not None]
-        for field, sh in want.items():
-            t = getattr(res, field)
-            if sh is None:
-                if t is not None:
-                    raise ValueError(f"{who}: out.{field} is given but not asked for")
-                continue
-            if t is None:
-                continue
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == sh and t.is_contiguous() and t.device == states.device):
-                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
-            if t.data_ptr() in inputs:
-                raise ValueError(f"{who}: out.{field} is an input of the call: no update in place is defined")
-        for field, sh in want.items():
-            if sh is not None and getattr(res, field) is None:
-                setattr(res, field, torch.empty(sh, dtype=torch.int32, device=states.device))
+        res = _reuse_outputs(who, out if out is not None else FusionOutputs(), want, states.device, [t.data_ptr() for t in (states, evidence) if t is not None])
         self._torch_used = True
         x = _lib.GGStateFusion()
         x.n, x.d_state, x.state_stride = B, states.data_ptr(), self.rows * self.cols
         x.d_evidence_in = evidence.data_ptr() if evidence is not None else None
         if host_shifts is not None:
-            x.shifts = host_shifts.ctypes.data_as(C.POINTER(C.c_int32))
+            x.shifts = _int32_ptr(host_shifts)
         x.hit, x.miss, x.decay, x.e_min, x.e_max = int(hit), int(miss), int(decay), int(e_min), int(e_max)
         x.free_threshold, x.occ_threshold = int(free_threshold), int(occ_threshold)
-        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.order = c_order
         x.d_evidence_out, x.plane_stride = res.evidence.data_ptr(), self.rows * self.cols
         x.d_fused = res.state.data_ptr() if fused else None
         x.d_frontier = res.frontier.data_ptr() if frontier else None
@@ -1129,15 +1163,9 @@ class GroundSegmentation:
         earlier call with the same arguments, whose tensors are reused; it may not hold an input.  Integer arithmetic only: bit-identical
         from run to run.  Enqueued on the context's own stream or, with on_torch_stream=True, on the current torch stream; nothing
         synchronises.  No map is read or changed."""
-        import torch
-
         who = "route_planes"
-        if order not in ("row", "col"):
-            raise ValueError(f"{who}: order is 'row' or 'col'")
-        par = {"connectivity": connectivity, "straight": straight, "diagonal": diagonal, "cost_max": cost_max, "max_cost": max_cost, "max_path": max_path}
-        for name, v in par.items():
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"{who}: {name} is an integer")
+        plane, c_order = _plane_order(who, order, self.rows, self.cols)
+        _check_integers(who, connectivity=connectivity, straight=straight, diagonal=diagonal, cost_max=cost_max, max_cost=max_cost, max_path=max_path)
         if connectivity not in (4, 8):
             raise ValueError(f"{who}: connectivity is 4 or 8")
         if not (1 <= straight <= 65535 and (connectivity == 4 or 1 <= diagonal <= 65535)):
@@ -1150,55 +1178,26 @@ class GroundSegmentation:
             raise ValueError(f"{who}: max_path is >= 1 with starts and 0 without")
         if max(straight, diagonal if connectivity == 8 else 0) * cost_max * self.rows * self.cols > _lib.GG_ROUTE_LIMIT:
             raise ValueError(f"{who}: max(straight, diagonal) * cost_max * rows * cols exceeds 2^31 - 2")
-        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
-
-        def is_planes(t):
-            return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 3 and t.is_contiguous() and tuple(t.shape[1:]) == plane
-
-        if not is_planes(goals):
+        if not _is_planes(goals, plane):
             raise ValueError(f"{who}: goals must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
         B = int(goals.shape[0])
         for name, t in (("blocked", blocked), ("cost", cost)):
-            if t is not None and not (is_planes(t) and t.shape[0] == B and t.device == goals.device):
+            if t is not None and not (_is_planes(t, plane) and t.shape[0] == B and t.device == goals.device):
                 raise ValueError(f"{who}: {name} must be a contiguous CUDA torch.int32 tensor of the shape and device of goals")
         host_starts = None
         if starts is not None:
-            try:
-                given = np.asarray(starts)
-                host_starts = np.ascontiguousarray(given.astype(np.int32))
-                exact = given.shape == host_starts.shape and np.array_equal(given, host_starts)
-            except (TypeError, ValueError, OverflowError) as e:
-                raise ValueError(f"{who}: starts must be [B] int32: {e}") from None
-            if host_starts.shape != (B,) or not exact:
-                raise ValueError(f"{who}: starts of shape {host_starts.shape} are not [B] int32")
+            host_starts = _int32_array(who, "starts", starts, "[B]", lambda sh: sh == (B,))
             if ((host_starts < -1) | (host_starts >= self.rows * self.cols)).any():
                 raise ValueError(f"{who}: a start lies outside [-1, rows * cols)")
             if max_path < 1:
                 raise ValueError(f"{who}: starts needs max_path >= 1")
-        res = out if out is not None else RouteOutputs()
         shape = (B,) + plane
         with_paths = host_starts is not None
         want = {"dist": shape, "next": shape if next else None, "counts": (B, 3) if counts else None,
                 "paths": (B, max_path) if with_paths else None, "path_len": (B,) if with_paths else None}
-        inputs = [t.data_ptr() for t in (goals, blocked, cost) if t is not None]
-        for field, sh in want.items():
-            t = getattr(res, field)
-            if sh is None:
-                if t is not None:
-                    raise ValueError(f"{who}: out.{field} is given but not asked for")
-                continue
-            if t is None:
-                continue
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == sh and t.is_contiguous() and t.device == goals.device):
-                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
-            if t.data_ptr() in inputs:
-                raise ValueError(f"{who}: out.{field} is an input of the call: no update in place is defined")
-        for field, sh in want.items():
-            if sh is not None and getattr(res, field) is None:
-                if field == "paths":  # (the call leaves the words behind a path alone)
-                    setattr(res, field, torch.full(sh, -1, dtype=torch.int32, device=goals.device))
-                else:
-                    setattr(res, field, torch.empty(sh, dtype=torch.int32, device=goals.device))
+        # (the call leaves the words behind a path alone: -1 in a tensor allocated here)
+        res = _reuse_outputs(who, out if out is not None else RouteOutputs(), want, goals.device, [t.data_ptr() for t in (goals, blocked, cost) if t is not None],
+                             fill={"paths": -1})
         self._torch_used = True
         x = _lib.GGPlaneRoutes()
         cells = self.rows * self.cols
@@ -1206,12 +1205,12 @@ class GroundSegmentation:
         x.d_blocked, x.blocked_stride = (blocked.data_ptr(), cells) if blocked is not None else (None, 0)
         x.d_cost, x.cost_stride = (cost.data_ptr(), cells) if cost is not None else (None, 0)
         x.connectivity, x.straight, x.diagonal, x.cost_max, x.max_cost = int(connectivity), int(straight), int(diagonal), int(cost_max), int(max_cost)
-        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.order = c_order
         x.d_dist, x.plane_stride = res.dist.data_ptr(), cells
         x.d_next = res.next.data_ptr() if next else None
         x.d_counts = res.counts.data_ptr() if counts else None
         if with_paths:
-            x.starts = host_starts.ctypes.data_as(C.POINTER(C.c_int32))
+            x.starts = _int32_ptr(host_starts)
             x.d_paths, x.max_path, x.d_path_len = res.paths.data_ptr(), int(max_path), res.path_len.data_ptr()
         stream = self._stream_arg(on_torch_stream, goals.device)
         _check(self._L, self._ctx, self._L.gg_route_planes(self._ctx, C.byref(x), stream), "gg_route_planes")
@@ -1235,14 +1234,9 @@ class GroundSegmentation:
         earlier call with the same arguments, whose tensors are reused; it may not hold an input.  Integer sums only: bit-identical from
         run to run.  Enqueued on the context's own stream or, with on_torch_stream=True, on the current torch stream; nothing
         synchronises.  No map is read or changed."""
-        import torch
-
         who = "match_planes"
-        if order not in ("row", "col"):
-            raise ValueError(f"{who}: order is 'row' or 'col'")
-        for name, v in {"window": window, "field_max": field_max}.items():
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"{who}: {name} is an integer")
+        plane, c_order = _plane_order(who, order, self.rows, self.cols)
+        _check_integers(who, window=window, field_max=field_max)
         if not 0 <= window <= _lib.GG_MATCH_MAX_WINDOW:
             raise ValueError(f"{who}: window lies in [0, {_lib.GG_MATCH_MAX_WINDOW}]")
         if field_max < 1 or field_max * self.rows * self.cols > _lib.GG_MATCH_LIMIT:
@@ -1250,70 +1244,38 @@ class GroundSegmentation:
         if self.rows > _lib.GG_MATCH_MAX_SIDE or self.cols > _lib.GG_MATCH_MAX_SIDE:
             raise ValueError(f"{who}: the map has more than {_lib.GG_MATCH_MAX_SIDE} rows or columns")
 
-        def int32_rows(name, given, shape_text, ok):
-            try:
-                given = np.asarray(given)
-                host = np.ascontiguousarray(given.astype(np.int32))
-                exact = given.shape == host.shape and np.array_equal(given, host)
-            except (TypeError, ValueError, OverflowError) as e:
-                raise ValueError(f"{who}: {name} must be {shape_text} int32: {e}") from None
-            if not ok(host.shape) or not exact:
-                raise ValueError(f"{who}: {name} of shape {host.shape} are not {shape_text} int32")
-            return host
-
         host_rotations = None
         if rotations is not None:
-            host_rotations = int32_rows("rotations", rotations, "[K, 2]", lambda s: len(s) == 2 and s[1] == 2)
+            host_rotations = _int32_array(who, "rotations", rotations, "[K, 2]", lambda sh: len(sh) == 2 and sh[1] == 2)
             if not 1 <= host_rotations.shape[0] <= _lib.GG_MATCH_MAX_ROTATIONS:
                 raise ValueError(f"{who}: rotations holds 1 to {_lib.GG_MATCH_MAX_ROTATIONS} candidates")
             if (np.abs(host_rotations.astype(np.int64)) > _lib.GG_MATCH_UNIT).any():
                 raise ValueError(f"{who}: a word of rotations lies outside [-{_lib.GG_MATCH_UNIT}, {_lib.GG_MATCH_UNIT}]")
         K = host_rotations.shape[0] if host_rotations is not None else 1
-        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
-
-        def is_planes(t):
-            return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 3 and t.is_contiguous() and tuple(t.shape[1:]) == plane
-
-        if not is_planes(scan):
+        if not _is_planes(scan, plane):
             raise ValueError(f"{who}: scan must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
         B = int(scan.shape[0])
-        if not (is_planes(field) and field.shape[0] == B and field.device == scan.device):
+        if not (_is_planes(field, plane) and field.shape[0] == B and field.device == scan.device):
             raise ValueError(f"{who}: field must be a contiguous CUDA torch.int32 tensor of the shape and device of scan")
-        host_shifts = int32_rows("shifts", shifts, "[B, 2]", lambda s: s == (B, 2)) if shifts is not None else None
-        host_pivots = int32_rows("pivots", pivots, "[B, 2]", lambda s: s == (B, 2)) if pivots is not None else None
+        host_shifts = _int32_array(who, "shifts", shifts, "[B, 2]", lambda sh: sh == (B, 2)) if shifts is not None else None
+        host_pivots = _int32_array(who, "pivots", pivots, "[B, 2]", lambda sh: sh == (B, 2)) if pivots is not None else None
         if host_pivots is not None and ((host_pivots < 0) | (host_pivots >= np.array([self.rows, self.cols]))).any():
             raise ValueError(f"{who}: a pivot lies outside the map")
-        res = out if out is not None else MatchOutputs()
         D = 2 * int(window) + 1
         want = {"best": (B, 6), "scores": (B, K, D, D) if scores else None}
-        inputs = [scan.data_ptr(), field.data_ptr()]
-        for name, sh in want.items():
-            t = getattr(res, name)
-            if sh is None:
-                if t is not None:
-                    raise ValueError(f"{who}: out.{name} is given but not asked for")
-                continue
-            if t is None:
-                continue
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == sh and t.is_contiguous() and t.device == scan.device):
-                raise ValueError(f"{who}: out.{name} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
-            if t.data_ptr() in inputs:
-                raise ValueError(f"{who}: out.{name} is an input of the call")
-        for name, sh in want.items():
-            if sh is not None and getattr(res, name) is None:
-                setattr(res, name, torch.empty(sh, dtype=torch.int32, device=scan.device))
+        res = _reuse_outputs(who, out if out is not None else MatchOutputs(), want, scan.device, [scan.data_ptr(), field.data_ptr()])
         self._torch_used = True
         x = _lib.GGPlaneMatches()
         cells = self.rows * self.cols
         x.n, x.d_scan, x.scan_stride, x.d_field, x.field_stride = B, scan.data_ptr(), cells, field.data_ptr(), cells
         x.field_max, x.window = int(field_max), int(window)
         if host_shifts is not None:
-            x.shifts = host_shifts.ctypes.data_as(C.POINTER(C.c_int32))
+            x.shifts = _int32_ptr(host_shifts)
         if host_pivots is not None:
-            x.pivots = host_pivots.ctypes.data_as(C.POINTER(C.c_int32))
+            x.pivots = _int32_ptr(host_pivots)
         if host_rotations is not None:
-            x.rotations, x.n_rotations = host_rotations.ctypes.data_as(C.POINTER(C.c_int32)), K
-        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+            x.rotations, x.n_rotations = _int32_ptr(host_rotations), K
+        x.order = c_order
         x.d_best = res.best.data_ptr()
         x.d_scores, x.score_stride = (res.scores.data_ptr(), K * D * D) if scores else (None, 0)
         stream = self._stream_arg(on_torch_stream, scan.device)
@@ -1337,21 +1299,11 @@ class GroundSegmentation:
         reused; it may not hold the input.  Bit operations and integer sums only: bit-identical from run to run.  Enqueued on the
         context's own stream or, with on_torch_stream=True, on the current torch stream; nothing synchronises.  No map is read or
         changed."""
-        import torch
-
         who = "footprint_planes"
-        if order not in ("row", "col"):
-            raise ValueError(f"{who}: order is 'row' or 'col'")
+        plane, c_order = _plane_order(who, order, self.rows, self.cols)
         if not isinstance(outside_free, (bool, np.bool_)):
             raise ValueError(f"{who}: outside_free is True or False")
-        try:
-            given = np.asarray(spans)
-            host_spans = np.ascontiguousarray(given.astype(np.int32))
-            exact = given.shape == host_spans.shape and np.array_equal(given, host_spans)
-        except (TypeError, ValueError, OverflowError) as e:
-            raise ValueError(f"{who}: spans must be [K, 2 R + 1, 2] int32: {e}") from None
-        if host_spans.ndim != 3 or host_spans.shape[2] != 2 or host_spans.shape[1] % 2 != 1 or not exact:
-            raise ValueError(f"{who}: spans of shape {host_spans.shape} are not [K, 2 R + 1, 2] int32")
+        host_spans = _int32_array(who, "spans", spans, "[K, 2 R + 1, 2]", lambda sh: len(sh) == 3 and sh[2] == 2 and sh[1] % 2 == 1)
         K, R = int(host_spans.shape[0]), int(host_spans.shape[1]) // 2
         if not 1 <= K <= _lib.GG_FOOTPRINT_MAX_HEADINGS or R > _lib.GG_FOOTPRINT_MAX_RADIUS:
             raise ValueError(f"{who}: spans hold 1 to {_lib.GG_FOOTPRINT_MAX_HEADINGS} headings of radius 0 to {_lib.GG_FOOTPRINT_MAX_RADIUS}")
@@ -1361,35 +1313,18 @@ class GroundSegmentation:
             raise ValueError(f"{who}: min_fit is an integer in [1, {K}] or None")
         if not (mask or fit or counts):
             raise ValueError(f"{who}: at least one of mask, fit and counts must be asked for")
-        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
-        if not (torch.is_tensor(blocked) and blocked.is_cuda and blocked.dtype == torch.int32 and blocked.dim() == 3 and blocked.is_contiguous()
-                and tuple(blocked.shape[1:]) == plane):
+        if not _is_planes(blocked, plane):
             raise ValueError(f"{who}: blocked must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
         B = int(blocked.shape[0])
-        res = out if out is not None else FootprintOutputs()
         want = {"mask": (B,) + plane if mask else None, "fit": (B,) + plane if fit else None, "counts": (B, 3) if counts else None}
-        for name, sh in want.items():
-            t = getattr(res, name)
-            if sh is None:
-                if t is not None:
-                    raise ValueError(f"{who}: out.{name} is given but not asked for")
-                continue
-            if t is None:
-                continue
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == sh and t.is_contiguous() and t.device == blocked.device):
-                raise ValueError(f"{who}: out.{name} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
-            if t.data_ptr() == blocked.data_ptr():
-                raise ValueError(f"{who}: out.{name} is the input of the call")
-        for name, sh in want.items():
-            if sh is not None and getattr(res, name) is None:
-                setattr(res, name, torch.empty(sh, dtype=torch.int32, device=blocked.device))
+        res = _reuse_outputs(who, out if out is not None else FootprintOutputs(), want, blocked.device, [blocked.data_ptr()], in_place="is the input of the call")
         self._torch_used = True
         x = _lib.GGPlaneFootprints()
         cells = self.rows * self.cols
         x.n, x.d_blocked, x.blocked_stride = B, blocked.data_ptr(), cells
-        x.spans, x.n_headings, x.radius = host_spans.ctypes.data_as(C.POINTER(C.c_int32)), K, R
+        x.spans, x.n_headings, x.radius = _int32_ptr(host_spans), K, R
         x.min_fit, x.outside_free = int(min_fit), int(bool(outside_free))
-        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.order = c_order
         x.d_mask, x.mask_stride = (res.mask.data_ptr(), cells) if mask else (None, 0)
         x.d_fit, x.fit_stride = (res.fit.data_ptr(), cells) if fit else (None, 0)
         x.d_counts = res.counts.data_ptr() if counts else None
@@ -1419,15 +1354,9 @@ class GroundSegmentation:
         leave those out (None).  `out`: a HeadingOutputs of an earlier call with the same arguments, whose tensors are reused; it may not
         hold an input.  Integer arithmetic only: bit-identical from run to run.  Enqueued on the context's own stream or, with
         on_torch_stream=True, on the current torch stream; nothing synchronises.  No map is read or changed."""
-        import torch
-
         who = "route_headings"
-        if order not in ("row", "col"):
-            raise ValueError(f"{who}: order is 'row' or 'col'")
-        par = {"goal_headings": goal_headings, "cost_max": cost_max, "max_cost": max_cost, "max_len": max_len}
-        for name, v in par.items():
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"{who}: {name} is an integer")
+        plane, c_order = _plane_order(who, order, self.rows, self.cols)
+        _check_integers(who, goal_headings=goal_headings, cost_max=cost_max, max_cost=max_cost, max_len=max_len)
         if not 0 <= goal_headings <= 0xFFFFFFFF:
             raise ValueError(f"{who}: goal_headings is a uint32 mask")
         if not 1 <= cost_max <= _lib.GG_ROUTE_NONE:
@@ -1436,14 +1365,9 @@ class GroundSegmentation:
             raise ValueError(f"{who}: max_cost lies in [0, 2^31 - 1]")
         if max_len < 0 or max_len > _lib.GG_ROUTE_NONE or (starts is None and max_len != 0):
             raise ValueError(f"{who}: max_len is >= 1 with starts and 0 without")
-        try:
-            given = np.asarray(moves)
-            host_moves = np.ascontiguousarray(given.astype(np.int32))
-            exact = given.shape == host_moves.shape and np.array_equal(given, host_moves)
-        except (TypeError, ValueError, OverflowError) as e:
-            raise ValueError(f"{who}: moves must be [K, 8, 4] int32: {e}") from None
-        if host_moves.ndim != 3 or host_moves.shape[1:] != (_lib.GG_HEADINGS_MAX_MOVES, 4) or not exact or not 1 <= host_moves.shape[0] <= _lib.GG_HEADINGS_MAX:
-            raise ValueError(f"{who}: moves of shape {host_moves.shape} are not [K, 8, 4] int32 with 1 <= K <= {_lib.GG_HEADINGS_MAX}")
+        host_moves = _int32_array(who, "moves", moves, "[K, 8, 4]",
+                                  lambda sh: len(sh) == 3 and sh[1:] == (_lib.GG_HEADINGS_MAX_MOVES, 4) and 1 <= sh[0] <= _lib.GG_HEADINGS_MAX,
+                                  suffix=f" with 1 <= K <= {_lib.GG_HEADINGS_MAX}")
         K = int(host_moves.shape[0])
         present = host_moves[:, :, 3] != 0
         s = host_moves[:, :, 3][present]
@@ -1459,27 +1383,15 @@ class GroundSegmentation:
             raise ValueError(f"{who}: a move leads to its own state")
         if (int(s.max()) if s.size else 0) * cost_max * self.rows * self.cols * K > _lib.GG_HEADINGS_LIMIT:
             raise ValueError(f"{who}: max s * cost_max * rows * cols * K exceeds 2^31 - 2")
-        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
-
-        def is_planes(t):
-            return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 3 and t.is_contiguous() and tuple(t.shape[1:]) == plane
-
-        if not is_planes(mask):
+        if not _is_planes(mask, plane):
             raise ValueError(f"{who}: mask must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
         B = int(mask.shape[0])
         for name, t in (("goals", goals), ("cost", cost)):
-            if (t is not None or name == "goals") and not (is_planes(t) and t.shape[0] == B and t.device == mask.device):
+            if (t is not None or name == "goals") and not (_is_planes(t, plane) and t.shape[0] == B and t.device == mask.device):
                 raise ValueError(f"{who}: {name} must be a contiguous CUDA torch.int32 tensor of the shape and device of mask")
         host_starts = None
         if starts is not None:
-            try:
-                given = np.asarray(starts)
-                host_starts = np.ascontiguousarray(given.astype(np.int32))
-                exact = given.shape == host_starts.shape and np.array_equal(given, host_starts)
-            except (TypeError, ValueError, OverflowError) as e:
-                raise ValueError(f"{who}: starts must be [B, 2] int32: {e}") from None
-            if host_starts.shape != (B, 2) or not exact:
-                raise ValueError(f"{who}: starts of shape {host_starts.shape} are not [B, 2] int32")
+            host_starts = _int32_array(who, "starts", starts, "[B, 2]", lambda sh: sh == (B, 2))
             cell, heading = host_starts[:, 0], host_starts[:, 1]
             if ((cell < -1) | (cell >= self.rows * self.cols)).any():
                 raise ValueError(f"{who}: a start cell lies outside [-1, rows * cols)")
@@ -1487,38 +1399,21 @@ class GroundSegmentation:
                 raise ValueError(f"{who}: a start heading lies outside [0, K)")
             if max_len < 1:
                 raise ValueError(f"{who}: starts needs max_len >= 1")
-        res = out if out is not None else HeadingOutputs()
         with_paths = host_starts is not None
         want = {"dist": (B, K) + plane, "next": (B, K) + plane if next else None, "best": (B,) + plane if best else None,
                 "best_heading": (B,) + plane if best else None, "counts": (B, 3) if counts else None,
                 "paths": (B, max_len, 2) if with_paths else None, "path_len": (B,) if with_paths else None}
-        inputs = [t.data_ptr() for t in (mask, goals, cost) if t is not None]
-        for field, sh in want.items():
-            t = getattr(res, field)
-            if sh is None:
-                if t is not None:
-                    raise ValueError(f"{who}: out.{field} is given but not asked for")
-                continue
-            if t is None:
-                continue
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == sh and t.is_contiguous() and t.device == mask.device):
-                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
-            if t.data_ptr() in inputs:
-                raise ValueError(f"{who}: out.{field} is an input of the call: no update in place is defined")
-        for field, sh in want.items():
-            if sh is not None and getattr(res, field) is None:
-                if field == "paths":  # (the call leaves the pairs behind a path alone)
-                    setattr(res, field, torch.full(sh, -1, dtype=torch.int32, device=mask.device))
-                else:
-                    setattr(res, field, torch.empty(sh, dtype=torch.int32, device=mask.device))
+        # (the call leaves the pairs behind a path alone: -1 in a tensor allocated here)
+        res = _reuse_outputs(who, out if out is not None else HeadingOutputs(), want, mask.device, [t.data_ptr() for t in (mask, goals, cost) if t is not None],
+                             fill={"paths": -1})
         self._torch_used = True
         x = _lib.GGHeadingRoutes()
         cells = self.rows * self.cols
         x.n, x.d_mask, x.mask_stride, x.d_goals, x.goal_stride = B, mask.data_ptr(), cells, goals.data_ptr(), cells
         x.d_cost, x.cost_stride = (cost.data_ptr(), cells) if cost is not None else (None, 0)
-        x.goal_headings, x.n_headings, x.moves = int(goal_headings), K, host_moves.ctypes.data_as(C.POINTER(C.c_int32))
+        x.goal_headings, x.n_headings, x.moves = int(goal_headings), K, _int32_ptr(host_moves)
         x.cost_max, x.max_cost = int(cost_max), int(max_cost)
-        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.order = c_order
         x.d_dist, x.dist_stride, x.plane_stride = res.dist.data_ptr(), K * cells, cells
         if next:
             x.d_next, x.next_stride, x.next_plane_stride = res.next.data_ptr(), K * cells, cells
@@ -1526,7 +1421,7 @@ class GroundSegmentation:
             x.d_best, x.best_stride, x.d_best_heading, x.best_heading_stride = res.best.data_ptr(), cells, res.best_heading.data_ptr(), cells
         x.d_counts = res.counts.data_ptr() if counts else None
         if with_paths:
-            x.starts = host_starts.ctypes.data_as(C.POINTER(C.c_int32))
+            x.starts = _int32_ptr(host_starts)
             x.d_paths, x.path_stride, x.max_len, x.d_path_len = res.paths.data_ptr(), 2 * int(max_len), int(max_len), res.path_len.data_ptr()
         stream = self._stream_arg(on_torch_stream, mask.device)
         _check(self._L, self._ctx, self._L.gg_route_headings(self._ctx, C.byref(x), stream), "gg_route_headings")
@@ -1550,25 +1445,14 @@ class GroundSegmentation:
         TrackOutputs.  `out`: a TrackOutputs of an earlier call with the same arguments, whose tensors are reused; it may not be
         `previous`.  Integer arithmetic only: bit-identical from run to run.  Enqueued on the context's own stream or, with
         on_torch_stream=True, on the current torch stream; nothing synchronises.  No map is read or changed."""
-        import torch
-
         who = "track_clusters"
-        if order not in ("row", "col"):
-            raise ValueError(f"{who}: order is 'row' or 'col'")
-        for name, v in (("max_clusters", max_clusters), ("gate", gate)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"{who}: {name} is an integer")
+        plane, c_order = _plane_order(who, order, self.rows, self.cols)
+        _check_integers(who, max_clusters=max_clusters, gate=gate)
         if not 1 <= max_clusters <= _lib.GG_TRACK_MAX_CLUSTERS:
             raise ValueError(f"{who}: max_clusters lies in [1, {_lib.GG_TRACK_MAX_CLUSTERS}]")
         if not 0 <= gate <= _lib.GG_TRACK_MAX_GATE:
             raise ValueError(f"{who}: gate lies in [0, {_lib.GG_TRACK_MAX_GATE}]")
-        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
-
-        def is_int32(t, shape):
-            return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape and (
-                t is cell_cluster or t.device == cell_cluster.device)
-
-        if not (torch.is_tensor(cell_cluster) and cell_cluster.dim() == 3 and is_int32(cell_cluster, (int(cell_cluster.shape[0]),) + plane)):
+        if not _is_planes(cell_cluster, plane):
             raise ValueError(f"{who}: cell_cluster must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
         B, M = int(cell_cluster.shape[0]), int(max_clusters)
         if previous is not None:
@@ -1576,36 +1460,12 @@ class GroundSegmentation:
                 raise ValueError(f"{who}: out is `previous`: no update in place is defined, alternate between two TrackOutputs")
             if previous.order != order:
                 raise ValueError(f"{who}: previous was computed with order={previous.order!r}")
-            if not (is_int32(previous.cell_cluster, (B,) + plane) and is_int32(previous.tracks, (B, M, 8)) and is_int32(previous.heads, (B, 4))):
+            if not all(_is_int32(t, sh, cell_cluster.device) for t, sh in ((previous.cell_cluster, (B,) + plane), (previous.tracks, (B, M, 8)), (previous.heads, (B, 4)))):
                 raise ValueError(f"{who}: previous must be the TrackOutputs of a call with the same B, max_clusters and order")
-        host_shifts = None
-        if shifts is not None:
-            try:
-                given = np.asarray(shifts)
-                host_shifts = np.ascontiguousarray(given.astype(np.int32))
-                exact = given.shape == host_shifts.shape and np.array_equal(given, host_shifts)
-            except (TypeError, ValueError, OverflowError) as e:
-                raise ValueError(f"{who}: shifts must be [B, 2] int32: {e}") from None
-            if host_shifts.shape != (B, 2) or not exact:
-                raise ValueError(f"{who}: shifts of shape {host_shifts.shape} are not [B, 2] int32")
-        res = out if out is not None else TrackOutputs()
+        host_shifts = _int32_array(who, "shifts", shifts, "[B, 2]", lambda sh: sh == (B, 2)) if shifts is not None else None
         want = {"tracks": (B, M, 8), "heads": (B, 4), "cell_track": (B,) + plane if cell_track else None}
         inputs = [cell_cluster.data_ptr()] + ([previous.cell_cluster.data_ptr(), previous.tracks.data_ptr(), previous.heads.data_ptr()] if previous is not None else [])
-        for field, sh in want.items():
-            t = getattr(res, field)
-            if sh is None:
-                if t is not None:
-                    raise ValueError(f"{who}: out.{field} is given but not asked for")
-                continue
-            if t is None:
-                continue
-            if not is_int32(t, sh):
-                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {sh}")
-            if t.data_ptr() in inputs:
-                raise ValueError(f"{who}: out.{field} is an input of the call: no update in place is defined")
-        for field, sh in want.items():
-            if sh is not None and getattr(res, field) is None:
-                setattr(res, field, torch.empty(sh, dtype=torch.int32, device=cell_cluster.device))
+        res = _reuse_outputs(who, out if out is not None else TrackOutputs(), want, cell_cluster.device, inputs)
         res.cell_cluster, res.order = cell_cluster, order
         self._torch_used = True
         cells = self.rows * self.cols
@@ -1615,9 +1475,9 @@ class GroundSegmentation:
             x.d_cells_prev, x.prev_stride = previous.cell_cluster.data_ptr(), cells
             x.d_tracks_in, x.d_heads_in = previous.tracks.data_ptr(), previous.heads.data_ptr()
         if host_shifts is not None:
-            x.shifts = host_shifts.ctypes.data_as(C.POINTER(C.c_int32))
+            x.shifts = _int32_ptr(host_shifts)
         x.max_clusters, x.gate = M, int(gate)
-        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
+        x.order = c_order
         x.d_tracks_out, x.d_heads_out = res.tracks.data_ptr(), res.heads.data_ptr()
         if cell_track:
             x.d_cell_track, x.track_stride = res.cell_track.data_ptr(), cells

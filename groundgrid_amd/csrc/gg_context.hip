@@ -17,6 +17,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 #include <chrono>
 
@@ -28,6 +29,7 @@
 #include "arena_layout.h"
 #include "hip_owned.h"
 #include "host_helper.h"
+#include "plane_args.h"
 #include "scroll_core.h"
 #include "sweep_core.h"
 
@@ -91,6 +93,23 @@ struct ParamRing {
 struct CallScratch {
     DeviceBlock<char> dev;
     PinnedBlock<char> pinned;
+};
+
+// One kind of table that a many-map call sends along in its ring entry: `per_entry` elements for each of the PARAM_RING entries, in the
+// call scratch's pinned block and in its device block (RingPart: where, in bytes).  ring_entry() and ring_upload() below use it.
+struct RingPart {
+    size_t dev, pinned, per_entry;
+};
+template <typename T>
+struct RingTable {
+    T *host = nullptr, *dev = nullptr;
+    size_t per_entry = 0;
+    void bind(const CallScratch &m, const RingPart &p)
+    {
+        host = (T *)(m.pinned + p.pinned);
+        dev = (T *)(m.dev + p.dev);
+        per_entry = p.per_entry;
+    }
 };
 
 } // namespace
@@ -229,14 +248,15 @@ struct gg_context : ContextBuffers {
     const uint16_t *d_export_cell = nullptr;
     ExportMap *d_export_maps = nullptr, *h_export_maps = nullptr;
     CloudParams *d_export_lazy = nullptr, *h_export_lazy = nullptr;
-    int2 *d_export_shifts = nullptr, *h_export_shifts = nullptr; // gg_fuse_states: the per-map index shifts of a call, [PARAM_RING][n_slots]
-    int32_t *d_export_starts = nullptr, *h_export_starts = nullptr; // gg_route_planes: the per-map start cells of a call, [PARAM_RING][n_slots]
-    int2 *d_export_pivots = nullptr, *h_export_pivots = nullptr; // gg_match_planes: the per-map pivots of a call, [PARAM_RING][n_slots] (its shifts: d_export_shifts)
-    int2 *d_export_rotations = nullptr, *h_export_rotations = nullptr; // ... the rotation table of a call, [PARAM_RING][MATCH_MAX_ROTATIONS]
+    // the tables a plane call sends along in its ring entry (RingTable; laid out by ensure_export_scratch)
+    RingTable<int2> ring_shifts;       // gg_fuse_states, gg_track_clusters, gg_match_planes: the per-map index shifts, [n_slots]
+    RingTable<int32_t> ring_starts;    // gg_route_planes: the per-map start cells, [n_slots]
+    RingTable<int2> ring_pivots;       // gg_match_planes: the per-map pivots, [n_slots]
+    RingTable<int2> ring_rotations;    // ... its rotation table, [MATCH_MAX_ROTATIONS]
     MatchPartial *d_match_partials = nullptr; // ... what its two launches hand over, [PARAM_RING][n_slots][MATCH_MAX_ROTATIONS], device only
-    uint32_t *d_export_footprint = nullptr, *h_export_footprint = nullptr; // gg_footprint_planes: the packed span table of a call, [PARAM_RING][FOOTPRINT_TABLE]
-    uint32_t *d_export_moves = nullptr, *h_export_moves = nullptr; // gg_route_headings: the packed move table of a call, [PARAM_RING][HEADINGS_TABLE]
-    int2 *d_export_poses = nullptr, *h_export_poses = nullptr; // gg_route_headings: the per-map start (cell, heading) of a call, [PARAM_RING][n_slots]
+    RingTable<uint32_t> ring_footprint; // gg_footprint_planes: the packed span table, [FOOTPRINT_TABLE]
+    RingTable<uint32_t> ring_moves;    // gg_route_headings: the packed move table, [HEADINGS_TABLE]
+    RingTable<int2> ring_poses;        // ... the per-map start (cell, heading), [n_slots]
     ParamRing export_ring;
     int slopes_variant = 0; // tuning "slopes_variant": 0 = k_slopes_tiled, 1 = k_slopes_gather (the A/B of tools/bench_slopes.py)
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
@@ -2002,68 +2022,52 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
         }
         off[(size_t)b + 1] = (uint32_t)elem.size();
     }
-    const size_t ring = (size_t)PARAM_RING * ctx->n_slots;
-    const size_t o_off = 0;
-    const size_t o_elem = align_up(o_off + off.size() * sizeof(uint32_t), 256);
-    const size_t o_cell = align_up(o_elem + elem.size() * sizeof(uint32_t), 256);
-    const size_t o_maps = align_up(o_cell + cell.size() * sizeof(uint16_t), 256);
-    const size_t o_lazy = align_up(o_maps + ring * sizeof(ExportMap), 256);
-    const size_t h_lazy = align_up(ring * sizeof(ExportMap), 256);
+    // both blocks are carved in one order, every part aligned to 256 bytes; a ring table has a part of the same size in either
+    size_t dev_end = 0, pinned_end = 0;
+    const auto take = [](size_t &end, size_t bytes) {
+        const size_t at = align_up(end, 256);
+        end = at + bytes;
+        return at;
+    };
+    const auto ring_part = [&](size_t per_entry, size_t elem_bytes) {
+        const size_t bytes = PARAM_RING * per_entry * elem_bytes;
+        return RingPart{take(dev_end, bytes), take(pinned_end, bytes), per_entry};
+    };
+    const size_t slots = (size_t)ctx->n_slots;
+    const size_t o_off = take(dev_end, off.size() * sizeof(uint32_t));
+    const size_t o_elem = take(dev_end, elem.size() * sizeof(uint32_t));
+    const size_t o_cell = take(dev_end, cell.size() * sizeof(uint16_t));
+    const RingPart maps = ring_part(slots, sizeof(ExportMap)), lazy = ring_part(slots, sizeof(CloudParams));
     // (gg_export_images: the partial bounds of either variant's bounds launch, per ring entry)
     const int parts_cap = std::max(image_parts(a.g, 0), image_parts(a.g, 1));
-    const size_t o_partials = align_up(o_lazy + ring * sizeof(CloudParams), 256);
-    // (gg_fuse_states: the index shifts of its maps, per ring entry)
-    const size_t o_shifts = align_up(o_partials + ring * GG_NUM_LAYERS * (size_t)parts_cap * 2 * sizeof(float), 256);
-    const size_t h_shifts = align_up(h_lazy + ring * sizeof(CloudParams), 256);
-    // (gg_route_planes: the start cells of its maps, per ring entry)
-    const size_t o_starts = align_up(o_shifts + ring * sizeof(int2), 256);
-    const size_t h_starts = align_up(h_shifts + ring * sizeof(int2), 256);
-    // (gg_match_planes: the pivots of its maps and its rotation table, per ring entry, and the partial results between its two launches)
-    const size_t o_pivots = align_up(o_starts + ring * sizeof(int32_t), 256);
-    const size_t h_pivots = align_up(h_starts + ring * sizeof(int32_t), 256);
-    const size_t o_rotations = align_up(o_pivots + ring * sizeof(int2), 256);
-    const size_t h_rotations = align_up(h_pivots + ring * sizeof(int2), 256);
-    const size_t rotations_bytes = (size_t)PARAM_RING * MATCH_MAX_ROTATIONS * sizeof(int2);
-    const size_t o_match = align_up(o_rotations + rotations_bytes, 256);
-    // (gg_footprint_planes: its packed span table, per ring entry)
-    const size_t o_footprint = align_up(o_match + ring * MATCH_MAX_ROTATIONS * sizeof(MatchPartial), 256);
-    const size_t h_footprint = align_up(h_rotations + rotations_bytes, 256);
-    const size_t footprint_bytes = (size_t)PARAM_RING * FOOTPRINT_TABLE * sizeof(uint32_t);
-    // (gg_route_headings: its packed move table and the start poses of its maps, per ring entry)
-    const size_t o_moves = align_up(o_footprint + footprint_bytes, 256);
-    const size_t h_moves = align_up(h_footprint + footprint_bytes, 256);
-    const size_t moves_bytes = (size_t)PARAM_RING * HEADINGS_TABLE * sizeof(uint32_t);
-    const size_t o_poses = align_up(o_moves + moves_bytes, 256);
-    const size_t h_poses = align_up(h_moves + moves_bytes, 256);
-    if (const int rc = alloc_call_scratch(ctx, who, st, o_poses + ring * sizeof(int2), h_poses + ring * sizeof(int2),
+    const size_t o_partials = take(dev_end, PARAM_RING * slots * GG_NUM_LAYERS * (size_t)parts_cap * 2 * sizeof(float));
+    // (the plane calls' tables, in the order the calls were added; between them the partial results of gg_match_planes' two launches)
+    const RingPart shifts = ring_part(slots, sizeof(int2)), starts = ring_part(slots, sizeof(int32_t)), pivots = ring_part(slots, sizeof(int2));
+    const RingPart rotations = ring_part(MATCH_MAX_ROTATIONS, sizeof(int2));
+    const size_t o_match = take(dev_end, PARAM_RING * slots * MATCH_MAX_ROTATIONS * sizeof(MatchPartial));
+    const RingPart footprint = ring_part(FOOTPRINT_TABLE, sizeof(uint32_t)), moves = ring_part(HEADINGS_TABLE, sizeof(uint32_t)), poses = ring_part(slots, sizeof(int2));
+    if (const int rc = alloc_call_scratch(ctx, who, st, dev_end, pinned_end,
                                           {{o_off, off.data(), off.size() * sizeof(uint32_t)}, {o_elem, elem.data(), elem.size() * sizeof(uint32_t)}, {o_cell, cell.data(), cell.size() * sizeof(uint16_t)}},
                                           &ctx->export_mem, &ctx->export_ring))
         return rc;
-    char *block = ctx->export_mem.dev, *h = ctx->export_mem.pinned;
-    ctx->d_export_off = (const uint32_t *)(block + o_off);
-    ctx->d_export_elem = (const uint32_t *)(block + o_elem);
-    ctx->d_export_cell = (const uint16_t *)(block + o_cell);
-    ctx->d_export_maps = (ExportMap *)(block + o_maps);
-    ctx->d_export_lazy = (CloudParams *)(block + o_lazy);
-    ctx->d_image_partials = (float *)(block + o_partials);
+    const CallScratch &m = ctx->export_mem;
+    ctx->d_export_off = (const uint32_t *)(m.dev + o_off);
+    ctx->d_export_elem = (const uint32_t *)(m.dev + o_elem);
+    ctx->d_export_cell = (const uint16_t *)(m.dev + o_cell);
+    ctx->d_export_maps = (ExportMap *)(m.dev + maps.dev);
+    ctx->h_export_maps = (ExportMap *)(m.pinned + maps.pinned);
+    ctx->d_export_lazy = (CloudParams *)(m.dev + lazy.dev);
+    ctx->h_export_lazy = (CloudParams *)(m.pinned + lazy.pinned);
+    ctx->d_image_partials = (float *)(m.dev + o_partials);
     ctx->image_parts_cap = parts_cap;
-    ctx->h_export_maps = (ExportMap *)h;
-    ctx->h_export_lazy = (CloudParams *)(h + h_lazy);
-    ctx->d_export_shifts = (int2 *)(block + o_shifts);
-    ctx->h_export_shifts = (int2 *)(h + h_shifts);
-    ctx->d_export_starts = (int32_t *)(block + o_starts);
-    ctx->h_export_starts = (int32_t *)(h + h_starts);
-    ctx->d_export_pivots = (int2 *)(block + o_pivots);
-    ctx->h_export_pivots = (int2 *)(h + h_pivots);
-    ctx->d_export_rotations = (int2 *)(block + o_rotations);
-    ctx->h_export_rotations = (int2 *)(h + h_rotations);
-    ctx->d_match_partials = (MatchPartial *)(block + o_match);
-    ctx->d_export_footprint = (uint32_t *)(block + o_footprint);
-    ctx->h_export_footprint = (uint32_t *)(h + h_footprint);
-    ctx->d_export_moves = (uint32_t *)(block + o_moves);
-    ctx->h_export_moves = (uint32_t *)(h + h_moves);
-    ctx->d_export_poses = (int2 *)(block + o_poses);
-    ctx->h_export_poses = (int2 *)(h + h_poses);
+    ctx->d_match_partials = (MatchPartial *)(m.dev + o_match);
+    ctx->ring_shifts.bind(m, shifts);
+    ctx->ring_starts.bind(m, starts);
+    ctx->ring_pivots.bind(m, pivots);
+    ctx->ring_rotations.bind(m, rotations);
+    ctx->ring_footprint.bind(m, footprint);
+    ctx->ring_moves.bind(m, moves);
+    ctx->ring_poses.bind(m, poses);
     return GG_OK;
 }
 
@@ -2119,6 +2123,37 @@ static int map_call_end(gg_context *ctx, const MapCall &f)
     // whatever reads or writes one of these maps next on another stream waits for the call (and for the lazily kept layers it computed)
     return call_recorded(ctx, f.st, true);
 }
+
+extern "C++" { // (templates, amid the extern "C" of the ABI)
+// A table of the call's ring entry (the entry is the call's own from map_call_begin on): ring_entry() is where the host fills it, and
+// ring_upload() enqueues the copy of its first `count` elements on f.st and returns where the kernels read them -- null when the copy
+// could not be enqueued, and the context then holds the error
+template <typename T>
+static T *ring_entry(const RingTable<T> &t, const MapCall &f)
+{
+    return t.host + (size_t)f.g * t.per_entry;
+}
+template <typename T>
+static const T *ring_upload(gg_context *ctx, const RingTable<T> &t, const MapCall &f, int count)
+{
+    const size_t at = (size_t)f.g * t.per_entry;
+    const hipError_t e = hipMemcpyAsync(t.dev + at, t.host + at, sizeof(T) * count, hipMemcpyHostToDevice, f.st);
+    if (e == hipSuccess) return t.dev + at;
+    fail(ctx, GG_ERR_HIP, "hipMemcpyAsync of a ring table", e);
+    return nullptr;
+}
+
+// The plane calls' overlap test (plane_args.h first_overlap): no output may share a byte with an input or another output.  The ranges run
+// from a buffer's first word to the last cell of its last plane, a call lists them in the order of its header, and the first pair of that
+// order is the one named
+template <size_t N>
+static int check_no_overlap(gg_context *ctx, const char *who, const BufferRange (&ranges)[N])
+{
+    const std::pair<int, int> hit = first_overlap(ranges, (int)N);
+    if (hit.first < 0) return GG_OK;
+    return fail(ctx, GG_ERR_INVALID, who, (std::string(ranges[hit.first].name) + " and " + ranges[hit.second].name + " overlap").c_str());
+}
+} // extern "C++"
 
 // gg_export_layers and gg_import_layers, its inverse, are one call in two directions; `d_planes` is the destination of the one and the
 // source of the other.
@@ -2526,40 +2561,26 @@ int gg_fuse_states(gg_context *ctx, const gg_state_fusion *x, void *stream)
     if (x->free_threshold > -1 || x->free_threshold < x->e_min) return fail(ctx, GG_ERR_INVALID, who, "e_min <= free_threshold <= -1");
     if (x->occ_threshold < 1 || x->occ_threshold > x->e_max) return fail(ctx, GG_ERR_INVALID, who, "1 <= occ_threshold <= e_max");
     if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
-    // no output may share a byte with an input or another output: the scroll reads d_evidence_in at shifted cells and the frontier reads
-    // neighbours, so no update in place is defined.  The ranges run from a buffer's first word to the last cell of its last plane
-    struct Range {
-        const char *name, *lo, *hi;
-        bool out;
-    };
-    const auto planes = [&](const char *name, const void *p, size_t stride, bool out) {
-        return Range{name, (const char *)p, (const char *)p + ((size_t)(x->n - 1) * stride + C) * sizeof(int32_t), out};
-    };
-    const Range ranges[6] = {planes("d_state", x->d_state, x->state_stride, false),
-                             planes("d_evidence_in", x->d_evidence_in, x->plane_stride, false),
-                             planes("d_evidence_out", x->d_evidence_out, x->plane_stride, true),
-                             planes("d_fused", x->d_fused, x->plane_stride, true),
-                             planes("d_frontier", x->d_frontier, x->plane_stride, true),
-                             Range{"d_counts", (const char *)x->d_counts, (const char *)x->d_counts + (size_t)x->n * 4 * sizeof(int32_t), true}};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i + 1; j < 6; ++j) {
-            const Range &p = ranges[i], &q = ranges[j];
-            if (!p.lo || !q.lo || !(p.out || q.out)) continue;
-            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
-                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
-        }
+    // the scroll reads d_evidence_in at shifted cells and the frontier reads neighbours, so no update in place is defined
+    const int n = x->n;
+    const BufferRange ranges[] = {plane_range("d_state", x->d_state, n, x->state_stride, C, false),
+                                  plane_range("d_evidence_in", x->d_evidence_in, n, x->plane_stride, C, false),
+                                  plane_range("d_evidence_out", x->d_evidence_out, n, x->plane_stride, C, true),
+                                  plane_range("d_fused", x->d_fused, n, x->plane_stride, C, true),
+                                  plane_range("d_frontier", x->d_frontier, n, x->plane_stride, C, true),
+                                  row_range("d_counts", x->d_counts, n, 4 * sizeof(int32_t), true)};
+    if (const int rc = check_no_overlap(ctx, who, ranges)) return rc;
     MapCall f;
-    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    if (const int rc = map_call_begin(ctx, who, n, nullptr, 0, stream, false, &f)) return rc;
     const bool row_major = x->order == GG_PLANES_ROWMAJOR;
     FuseArgs fa{};
     if (x->shifts) { // (rows, cols) -> (along a line, across lines), clamped: from |s| = side on no prior lies inside the map
-        int2 *hs = ctx->h_export_shifts + (size_t)f.g * ctx->n_slots, *ds = ctx->d_export_shifts + (size_t)f.g * ctx->n_slots;
-        for (int i = 0; i < x->n; ++i) {
-            const int s0 = std::min(std::max(x->shifts[2 * (size_t)i], -rows), rows), s1 = std::min(std::max(x->shifts[2 * (size_t)i + 1], -cols), cols);
-            hs[i] = row_major ? make_int2(s1, s0) : make_int2(s0, s1);
+        int2 *hs = ring_entry(ctx->ring_shifts, f);
+        for (int i = 0; i < n; ++i) {
+            const Shift s = clamped_shift(x->shifts, i, rows, cols);
+            hs[i] = row_major ? make_int2(s.s1, s.s0) : make_int2(s.s0, s.s1);
         }
-        HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(int2) * x->n, hipMemcpyHostToDevice, f.st));
-        fa.shifts = ds;
+        if (!(fa.shifts = ring_upload(ctx, ctx->ring_shifts, f, n))) return GG_ERR_HIP;
     }
     fa.state = x->d_state;
     fa.state_stride = x->state_stride;
@@ -2571,15 +2592,14 @@ int gg_fuse_states(gg_context *ctx, const gg_state_fusion *x, void *stream)
     fa.e_max = x->e_max;
     fa.free_threshold = x->free_threshold;
     fa.occ_threshold = x->occ_threshold;
-    fa.nx = row_major ? cols : rows;
-    fa.ny = row_major ? rows : cols;
+    std::tie(fa.nx, fa.ny) = plane_sides(row_major, rows, cols);
     fa.tiles_x = (fa.nx + FUSE_TILE_X - 1) / FUSE_TILE_X;
     fa.evidence_out = x->d_evidence_out;
     fa.fused = x->d_fused;
     fa.frontier = x->d_frontier;
     fa.plane_stride = x->plane_stride;
     fa.counts = x->d_counts;
-    launch_fuse(fa, x->n, f.st);
+    launch_fuse(fa, n, f.st);
     return map_call_end(ctx, f);
 }
 
@@ -2608,42 +2628,27 @@ int gg_track_clusters(gg_context *ctx, const gg_cluster_tracks *x, void *stream)
     if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
     // the coordinate sums of a cluster (and its overlap, <= 81 cells) must stay inside an int32
     if ((uint64_t)C * (uint64_t)std::max(rows, cols) > 0x7FFFFFFFull) return fail(ctx, GG_ERR_GEOMETRY, who, "rows * cols * max(rows, cols) exceeds 2^31 - 1");
-    // no output may share a byte with an input or another output, by the ranges of gg_fuse_states
-    struct Range {
-        const char *name, *lo, *hi;
-        bool out;
-    };
+    const int n = x->n;
     const size_t M = (size_t)x->max_clusters;
-    const auto planes = [&](const char *name, const void *p, size_t stride, bool out) {
-        return Range{name, (const char *)p, (const char *)p + ((size_t)(x->n - 1) * stride + C) * sizeof(int32_t), out};
-    };
-    const auto rows_of = [&](const char *name, const void *p, size_t bytes, bool out) { return Range{name, (const char *)p, (const char *)p + (size_t)x->n * bytes, out}; };
-    const Range ranges[7] = {planes("d_cells", x->d_cells, x->cells_stride, false),
-                             planes("d_cells_prev", x->d_cells_prev, x->prev_stride, false),
-                             rows_of("d_tracks_in", x->d_tracks_in, M * sizeof(gg_track), false),
-                             rows_of("d_heads_in", x->d_heads_in, 4 * sizeof(int32_t), false),
-                             rows_of("d_tracks_out", x->d_tracks_out, M * sizeof(gg_track), true),
-                             rows_of("d_heads_out", x->d_heads_out, 4 * sizeof(int32_t), true),
-                             planes("d_cell_track", x->d_cell_track, x->track_stride, true)};
-    for (int i = 0; i < 7; ++i)
-        for (int j = i + 1; j < 7; ++j) {
-            const Range &p = ranges[i], &q = ranges[j];
-            if (!p.lo || !q.lo || !(p.out || q.out)) continue;
-            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
-                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
-        }
+    const BufferRange ranges[] = {plane_range("d_cells", x->d_cells, n, x->cells_stride, C, false),
+                                  plane_range("d_cells_prev", x->d_cells_prev, n, x->prev_stride, C, false),
+                                  row_range("d_tracks_in", x->d_tracks_in, n, M * sizeof(gg_track), false),
+                                  row_range("d_heads_in", x->d_heads_in, n, 4 * sizeof(int32_t), false),
+                                  row_range("d_tracks_out", x->d_tracks_out, n, M * sizeof(gg_track), true),
+                                  row_range("d_heads_out", x->d_heads_out, n, 4 * sizeof(int32_t), true),
+                                  plane_range("d_cell_track", x->d_cell_track, n, x->track_stride, C, true)};
+    if (const int rc = check_no_overlap(ctx, who, ranges)) return rc;
     MapCall f;
-    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    if (const int rc = map_call_begin(ctx, who, n, nullptr, 0, stream, false, &f)) return rc;
     const bool row_major = x->order == GG_PLANES_ROWMAJOR;
     TrackArgs ta{};
     if (x->shifts) { // (rows, cols) -> (along a line, across lines), clamped: from |s| = side on nothing overlaps
-        int2 *hs = ctx->h_export_shifts + (size_t)f.g * ctx->n_slots, *ds = ctx->d_export_shifts + (size_t)f.g * ctx->n_slots;
-        for (int i = 0; i < x->n; ++i) {
-            const int s0 = std::min(std::max(x->shifts[2 * (size_t)i], -rows), rows), s1 = std::min(std::max(x->shifts[2 * (size_t)i + 1], -cols), cols);
-            hs[i] = row_major ? make_int2(s1, s0) : make_int2(s0, s1);
+        int2 *hs = ring_entry(ctx->ring_shifts, f);
+        for (int i = 0; i < n; ++i) {
+            const Shift s = clamped_shift(x->shifts, i, rows, cols);
+            hs[i] = row_major ? make_int2(s.s1, s.s0) : make_int2(s.s0, s.s1);
         }
-        HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(int2) * x->n, hipMemcpyHostToDevice, f.st));
-        ta.shifts = ds;
+        if (!(ta.shifts = ring_upload(ctx, ctx->ring_shifts, f, n))) return GG_ERR_HIP;
     }
     ta.cells = x->d_cells;
     ta.cells_stride = x->cells_stride;
@@ -2651,8 +2656,7 @@ int gg_track_clusters(gg_context *ctx, const gg_cluster_tracks *x, void *stream)
     ta.prev_stride = x->prev_stride;
     ta.tracks_in = x->d_tracks_in;
     ta.heads_in = x->d_heads_in;
-    ta.nx = row_major ? cols : rows;
-    ta.ny = row_major ? rows : cols;
+    std::tie(ta.nx, ta.ny) = plane_sides(row_major, rows, cols);
     ta.row_major = row_major ? 1 : 0;
     ta.M = x->max_clusters;
     ta.gate = x->gate;
@@ -2661,7 +2665,7 @@ int gg_track_clusters(gg_context *ctx, const gg_cluster_tracks *x, void *stream)
     ta.heads_out = x->d_heads_out;
     ta.cell_track = x->d_cell_track;
     ta.track_stride = x->track_stride;
-    launch_tracks(ta, x->n, f.st);
+    launch_tracks(ta, n, f.st);
     return map_call_end(ctx, f);
 }
 
@@ -2703,45 +2707,25 @@ int gg_route_planes(gg_context *ctx, const gg_plane_routes *x, void *stream)
     if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
     const bool row_major = x->order == GG_PLANES_ROWMAJOR;
     RouteArgs ra{};
-    ra.nx = row_major ? cols : rows;
-    ra.ny = row_major ? rows : cols;
+    std::tie(ra.nx, ra.ny) = plane_sides(row_major, rows, cols);
     ra.tiles_x = (ra.nx + ROUTE_TILE - 1) / ROUTE_TILE;
     ra.tiles_y = (ra.ny + ROUTE_TILE - 1) / ROUTE_TILE;
     if ((int64_t)ra.tiles_x * ra.tiles_y > ROUTE_MAX_TILES) return fail(ctx, GG_ERR_GEOMETRY, who, "the map has more than 4096 tiles of 64 x 64 cells");
-    // no output may share a byte with an input or another output, by the ranges of gg_fuse_states: from a buffer's first word to the last
-    // cell of its last plane
-    struct Range {
-        const char *name, *lo, *hi;
-        bool out;
-    };
-    const auto planes = [&](const char *name, const void *p, size_t stride, bool out) {
-        return Range{name, (const char *)p, (const char *)p + ((size_t)(x->n - 1) * stride + C) * sizeof(int32_t), out};
-    };
-    const auto rows_of = [&](const char *name, const void *p, size_t words) {
-        return Range{name, (const char *)p, (const char *)p + (size_t)x->n * words * sizeof(int32_t), true};
-    };
-    const Range ranges[8] = {planes("d_blocked", x->d_blocked, x->blocked_stride, false),
-                             planes("d_cost", x->d_cost, x->cost_stride, false),
-                             planes("d_goals", x->d_goals, x->goal_stride, false),
-                             planes("d_dist", x->d_dist, x->plane_stride, true),
-                             planes("d_next", x->d_next, x->plane_stride, true),
-                             rows_of("d_counts", x->d_counts, 3),
-                             rows_of("d_paths", x->starts ? x->d_paths : nullptr, x->starts ? (size_t)x->max_path : 0),
-                             rows_of("d_path_len", x->starts ? x->d_path_len : nullptr, 1)};
-    for (int i = 0; i < 8; ++i)
-        for (int j = i + 1; j < 8; ++j) {
-            const Range &p = ranges[i], &q = ranges[j];
-            if (!p.lo || !q.lo || !(p.out || q.out)) continue;
-            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
-                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
-        }
+    const int n = x->n;
+    const BufferRange ranges[] = {plane_range("d_blocked", x->d_blocked, n, x->blocked_stride, C, false),
+                                  plane_range("d_cost", x->d_cost, n, x->cost_stride, C, false),
+                                  plane_range("d_goals", x->d_goals, n, x->goal_stride, C, false),
+                                  plane_range("d_dist", x->d_dist, n, x->plane_stride, C, true),
+                                  plane_range("d_next", x->d_next, n, x->plane_stride, C, true),
+                                  row_range("d_counts", x->d_counts, n, 3 * sizeof(int32_t), true),
+                                  row_range("d_paths", x->starts ? x->d_paths : nullptr, n, (size_t)x->max_path * sizeof(int32_t), true),
+                                  row_range("d_path_len", x->starts ? x->d_path_len : nullptr, n, sizeof(int32_t), true)};
+    if (const int rc = check_no_overlap(ctx, who, ranges)) return rc;
     MapCall f;
-    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    if (const int rc = map_call_begin(ctx, who, n, nullptr, 0, stream, false, &f)) return rc;
     if (x->starts) {
-        int32_t *hs = ctx->h_export_starts + (size_t)f.g * ctx->n_slots, *ds = ctx->d_export_starts + (size_t)f.g * ctx->n_slots;
-        std::copy(x->starts, x->starts + x->n, hs);
-        HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(int32_t) * x->n, hipMemcpyHostToDevice, f.st));
-        ra.starts = ds;
+        std::copy(x->starts, x->starts + n, ring_entry(ctx->ring_starts, f));
+        if (!(ra.starts = ring_upload(ctx, ctx->ring_starts, f, n))) return GG_ERR_HIP;
         ra.paths = x->d_paths;
         ra.max_path = x->max_path;
         ra.path_len = x->d_path_len;
@@ -2762,7 +2746,7 @@ int gg_route_planes(gg_context *ctx, const gg_plane_routes *x, void *stream)
     ra.next = x->d_next;
     ra.plane_stride = x->plane_stride;
     ra.counts = x->d_counts;
-    launch_route(ra, x->n, f.st);
+    launch_route(ra, n, f.st);
     return map_call_end(ctx, f);
 }
 
@@ -2800,46 +2784,30 @@ int gg_match_planes(gg_context *ctx, const gg_plane_matches *x, void *stream)
             if (pr < 0 || pr >= rows || pc < 0 || pc >= cols) return fail(ctx, GG_ERR_INVALID, who, "a pivot lies outside the map");
         }
     if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
-    // no output may share a byte with an input or the other output, by the ranges of gg_route_planes: from a buffer's first word to the
-    // last cell of its last plane, or the last word of its last volume
-    struct Range {
-        const char *name, *lo, *hi;
-        bool out;
-    };
-    const auto planes = [&](const char *name, const void *p, size_t stride, size_t words, bool out) {
-        return Range{name, (const char *)p, (const char *)p + ((size_t)(x->n - 1) * stride + words) * sizeof(int32_t), out};
-    };
-    const Range ranges[4] = {planes("d_scan", x->d_scan, x->scan_stride, C, false), planes("d_field", x->d_field, x->field_stride, C, false),
-                             planes("d_best", x->d_best, 6, 6, true), planes("d_scores", x->d_scores, x->score_stride, volume, true)};
-    for (int i = 0; i < 4; ++i)
-        for (int j = i + 1; j < 4; ++j) {
-            const Range &p = ranges[i], &q = ranges[j];
-            if (!p.lo || !q.lo || !(p.out || q.out)) continue;
-            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
-                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
-        }
+    const int n = x->n;
+    const BufferRange ranges[] = {plane_range("d_scan", x->d_scan, n, x->scan_stride, C, false), plane_range("d_field", x->d_field, n, x->field_stride, C, false),
+                                  plane_range("d_best", x->d_best, n, 6, 6, true), plane_range("d_scores", x->d_scores, n, x->score_stride, volume, true)};
+    if (const int rc = check_no_overlap(ctx, who, ranges)) return rc;
     MapCall f;
-    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    if (const int rc = map_call_begin(ctx, who, n, nullptr, 0, stream, false, &f)) return rc;
     MatchArgs ma{};
-    const size_t entry = (size_t)f.g * ctx->n_slots;
-    if (x->shifts) { // clamped as gg_fuse_states clamps them: from |s| = side on no cell lies inside the map
-        int2 *hs = ctx->h_export_shifts + entry, *ds = ctx->d_export_shifts + entry;
-        for (int i = 0; i < x->n; ++i)
-            hs[i] = make_int2(std::min(std::max(x->shifts[2 * (size_t)i], -rows), rows), std::min(std::max(x->shifts[2 * (size_t)i + 1], -cols), cols));
-        HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(int2) * x->n, hipMemcpyHostToDevice, f.st));
-        ma.shifts = ds;
+    if (x->shifts) { // clamped as gg_fuse_states clamps them, and kept in (rows, cols) whatever the order: the kernel works in (row, col)
+        int2 *hs = ring_entry(ctx->ring_shifts, f);
+        for (int i = 0; i < n; ++i) {
+            const Shift s = clamped_shift(x->shifts, i, rows, cols);
+            hs[i] = make_int2(s.s0, s.s1);
+        }
+        if (!(ma.shifts = ring_upload(ctx, ctx->ring_shifts, f, n))) return GG_ERR_HIP;
     }
     if (x->pivots) {
-        int2 *hp = ctx->h_export_pivots + entry, *dp = ctx->d_export_pivots + entry;
-        for (int i = 0; i < x->n; ++i) hp[i] = make_int2(x->pivots[2 * (size_t)i], x->pivots[2 * (size_t)i + 1]);
-        HIPCHK(ctx, hipMemcpyAsync(dp, hp, sizeof(int2) * x->n, hipMemcpyHostToDevice, f.st));
-        ma.pivots = dp;
+        int2 *hp = ring_entry(ctx->ring_pivots, f);
+        for (int i = 0; i < n; ++i) hp[i] = make_int2(x->pivots[2 * (size_t)i], x->pivots[2 * (size_t)i + 1]);
+        if (!(ma.pivots = ring_upload(ctx, ctx->ring_pivots, f, n))) return GG_ERR_HIP;
     }
     if (x->rotations) {
-        int2 *hr = ctx->h_export_rotations + (size_t)f.g * MATCH_MAX_ROTATIONS, *dr = ctx->d_export_rotations + (size_t)f.g * MATCH_MAX_ROTATIONS;
+        int2 *hr = ring_entry(ctx->ring_rotations, f);
         for (int k = 0; k < K; ++k) hr[k] = make_int2(x->rotations[2 * (size_t)k], x->rotations[2 * (size_t)k + 1]);
-        HIPCHK(ctx, hipMemcpyAsync(dr, hr, sizeof(int2) * K, hipMemcpyHostToDevice, f.st));
-        ma.rotations = dr;
+        if (!(ma.rotations = ring_upload(ctx, ctx->ring_rotations, f, K))) return GG_ERR_HIP;
     }
     const bool row_major = x->order == GG_PLANES_ROWMAJOR;
     ma.scan = x->d_scan;
@@ -2849,14 +2817,13 @@ int gg_match_planes(gg_context *ctx, const gg_plane_matches *x, void *stream)
     ma.field_max = x->field_max;
     ma.n_rotations = K;
     ma.window = x->window;
-    ma.nx = row_major ? cols : rows;
-    ma.ny = row_major ? rows : cols;
+    std::tie(ma.nx, ma.ny) = plane_sides(row_major, rows, cols);
     ma.row_major = row_major;
-    ma.partials = ctx->d_match_partials + entry * MATCH_MAX_ROTATIONS;
+    ma.partials = ctx->d_match_partials + (size_t)f.g * ctx->n_slots * MATCH_MAX_ROTATIONS;
     ma.best = x->d_best;
     ma.scores = x->d_scores;
     ma.score_stride = x->score_stride;
-    launch_match(ma, x->n, f.st);
+    launch_match(ma, n, f.st);
     return map_call_end(ctx, f);
 }
 
@@ -2945,51 +2912,38 @@ int gg_footprint_planes(gg_context *ctx, const gg_plane_footprints *x, void *str
         }
     }
     if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
-    // no output may share a byte with the input or another output, by the ranges of gg_route_planes
-    struct Range {
-        const char *name, *lo, *hi;
-    };
-    const auto planes = [&](const char *name, const void *p, size_t stride, size_t words) {
-        return Range{name, (const char *)p, (const char *)p + ((size_t)(x->n - 1) * stride + words) * sizeof(int32_t)};
-    };
-    const Range ranges[4] = {planes("d_blocked", x->d_blocked, x->blocked_stride, C), planes("d_mask", x->d_mask, x->mask_stride, C),
-                             planes("d_fit", x->d_fit, x->fit_stride, C), planes("d_counts", x->d_counts, 3, 3)};
-    for (int i = 0; i < 4; ++i)
-        for (int j = i + 1; j < 4; ++j) {
-            const Range &p = ranges[i], &q = ranges[j];
-            if (!p.lo || !q.lo) continue;
-            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
-                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
-        }
+    // (one input and outputs only: every pair of the table holds an output, so every pair is tested)
+    const int n = x->n;
+    const BufferRange ranges[] = {plane_range("d_blocked", x->d_blocked, n, x->blocked_stride, C, false), plane_range("d_mask", x->d_mask, n, x->mask_stride, C, true),
+                                  plane_range("d_fit", x->d_fit, n, x->fit_stride, C, true), plane_range("d_counts", x->d_counts, n, 3, 3, true)};
+    if (const int rc = check_no_overlap(ctx, who, ranges)) return rc;
     MapCall f;
-    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
+    if (const int rc = map_call_begin(ctx, who, n, nullptr, 0, stream, false, &f)) return rc;
     const bool row_major = x->order == GG_PLANES_ROWMAJOR;
-    uint32_t *ht = ctx->h_export_footprint + (size_t)f.g * FOOTPRINT_TABLE, *dt = ctx->d_export_footprint + (size_t)f.g * FOOTPRINT_TABLE;
+    uint32_t *ht = ring_entry(ctx->ring_footprint, f);
     const int32_t *per_line = row_major ? x->spans : across.data();
     int n_levels = 1;
     for (int e = 0; e < K * D; ++e) {
         ht[e] = footprint_pack(per_line[2 * e], per_line[2 * e + 1]);
         if (ht[e] != FOOTPRINT_EMPTY) n_levels = std::max(n_levels, (int)(ht[e] >> 16) + 1);
     }
-    HIPCHK(ctx, hipMemcpyAsync(dt, ht, sizeof(uint32_t) * K * D, hipMemcpyHostToDevice, f.st));
     FootprintArgs fa{};
+    if (!(fa.table = ring_upload(ctx, ctx->ring_footprint, f, K * D))) return GG_ERR_HIP;
     fa.blocked = x->d_blocked;
     fa.blocked_stride = x->blocked_stride;
-    fa.table = dt;
     fa.n_headings = K;
     fa.radius = R;
     fa.n_levels = n_levels;
     fa.min_fit = x->min_fit;
     fa.outside_free = x->outside_free;
-    fa.nx = row_major ? cols : rows;
-    fa.ny = row_major ? rows : cols;
+    std::tie(fa.nx, fa.ny) = plane_sides(row_major, rows, cols);
     fa.tiles_x = (fa.nx + FOOTPRINT_TILE - 1) / FOOTPRINT_TILE;
     fa.mask = x->d_mask;
     fa.mask_stride = x->mask_stride;
     fa.fit = x->d_fit;
     fa.fit_stride = x->fit_stride;
     fa.counts = x->d_counts;
-    launch_footprint(fa, x->n, f.st);
+    launch_footprint(fa, n, f.st);
     return map_call_end(ctx, f);
 }
 
@@ -3097,40 +3051,27 @@ int gg_route_headings(gg_context *ctx, const gg_heading_routes *x, void *stream)
     if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
     const bool row_major = x->order == GG_PLANES_ROWMAJOR;
     HeadingsArgs ha{};
-    ha.nx = row_major ? cols : rows;
-    ha.ny = row_major ? rows : cols;
+    std::tie(ha.nx, ha.ny) = plane_sides(row_major, rows, cols);
     ha.tile = headings_tile(K);
     ha.tiles_x = (ha.nx + ha.tile - 1) / ha.tile;
     ha.tiles_y = (ha.ny + ha.tile - 1) / ha.tile;
     if ((int64_t)ha.tiles_x * ha.tiles_y > HEADINGS_MAX_TILES) return fail(ctx, GG_ERR_GEOMETRY, who, "the map has more than 4096 tiles");
-    // no output may share a byte with an input or another output, by the ranges of gg_route_planes: from a buffer's first word to the last
-    // cell of its last plane
-    struct Range {
-        const char *name, *lo, *hi;
-        bool out;
-    };
-    const auto span = [&](const char *name, const void *p, size_t words, bool out) { return Range{name, (const char *)p, (const char *)p + words * sizeof(int32_t), out}; };
-    const size_t last = (size_t)(x->n - 1);
-    const Range ranges[10] = {span("d_mask", x->d_mask, last * x->mask_stride + C, false),
-                              span("d_cost", x->d_cost, last * x->cost_stride + C, false),
-                              span("d_goals", x->d_goals, last * x->goal_stride + C, false),
-                              span("d_dist", x->d_dist, last * x->dist_stride + (size_t)(K - 1) * x->plane_stride + C, true),
-                              span("d_next", x->d_next, last * x->next_stride + (size_t)(K - 1) * x->next_plane_stride + C, true),
-                              span("d_best", x->d_best, last * x->best_stride + C, true),
-                              span("d_best_heading", x->d_best_heading, last * x->best_heading_stride + C, true),
-                              span("d_counts", x->d_counts, (size_t)x->n * 3, true),
-                              span("d_paths", x->starts ? x->d_paths : nullptr, x->starts ? last * x->path_stride + 2 * (size_t)x->max_len : 0, true),
-                              span("d_path_len", x->starts ? x->d_path_len : nullptr, (size_t)x->n, true)};
-    for (int i = 0; i < 10; ++i)
-        for (int j = i + 1; j < 10; ++j) {
-            const Range &p = ranges[i], &q = ranges[j];
-            if (!p.lo || !q.lo || !(p.out || q.out)) continue;
-            if (std::less<const char *>()(p.lo, q.hi) && std::less<const char *>()(q.lo, p.hi))
-                return fail(ctx, GG_ERR_INVALID, who, (std::string(p.name) + " and " + q.name + " overlap").c_str());
-        }
+    // (d_dist and d_next: K planes per map, so a map's last plane ends (K - 1) plane strides and a plane into it)
+    const int n = x->n;
+    const BufferRange ranges[] = {plane_range("d_mask", x->d_mask, n, x->mask_stride, C, false),
+                                  plane_range("d_cost", x->d_cost, n, x->cost_stride, C, false),
+                                  plane_range("d_goals", x->d_goals, n, x->goal_stride, C, false),
+                                  plane_range("d_dist", x->d_dist, n, x->dist_stride, (size_t)(K - 1) * x->plane_stride + C, true),
+                                  plane_range("d_next", x->d_next, n, x->next_stride, (size_t)(K - 1) * x->next_plane_stride + C, true),
+                                  plane_range("d_best", x->d_best, n, x->best_stride, C, true),
+                                  plane_range("d_best_heading", x->d_best_heading, n, x->best_heading_stride, C, true),
+                                  row_range("d_counts", x->d_counts, n, 3 * sizeof(int32_t), true),
+                                  plane_range("d_paths", x->starts ? x->d_paths : nullptr, n, x->path_stride, 2 * (size_t)x->max_len, true),
+                                  row_range("d_path_len", x->starts ? x->d_path_len : nullptr, n, sizeof(int32_t), true)};
+    if (const int rc = check_no_overlap(ctx, who, ranges)) return rc;
     MapCall f;
-    if (const int rc = map_call_begin(ctx, who, x->n, nullptr, 0, stream, false, &f)) return rc;
-    uint32_t *ht = ctx->h_export_moves + (size_t)f.g * HEADINGS_TABLE, *dt = ctx->d_export_moves + (size_t)f.g * HEADINGS_TABLE;
+    if (const int rc = map_call_begin(ctx, who, n, nullptr, 0, stream, false, &f)) return rc;
+    uint32_t *ht = ring_entry(ctx->ring_moves, f);
     for (int k = 0; k < K; ++k) {
         // the heading's first translating move decides how a slot walks the tile for it: along the axis the move is longer in, against the move
         int first_line = 0, first_pos = 0;
@@ -3152,12 +3093,11 @@ int gg_route_headings(gg_context *ctx, const gg_heading_routes *x, void *stream)
         }
         ha.walk[k] = walk;
     }
-    HIPCHK(ctx, hipMemcpyAsync(dt, ht, sizeof(uint32_t) * K * HEADINGS_MAX_MOVES, hipMemcpyHostToDevice, f.st));
+    if (!(ha.table = ring_upload(ctx, ctx->ring_moves, f, K * HEADINGS_MAX_MOVES))) return GG_ERR_HIP;
     if (x->starts) {
-        int2 *hs = ctx->h_export_poses + (size_t)f.g * ctx->n_slots, *ds = ctx->d_export_poses + (size_t)f.g * ctx->n_slots;
-        for (int i = 0; i < x->n; ++i) hs[i] = make_int2(x->starts[2 * i], x->starts[2 * i] >= 0 ? x->starts[2 * i + 1] : 0);
-        HIPCHK(ctx, hipMemcpyAsync(ds, hs, sizeof(int2) * x->n, hipMemcpyHostToDevice, f.st));
-        ha.starts = ds;
+        int2 *hs = ring_entry(ctx->ring_poses, f);
+        for (int i = 0; i < n; ++i) hs[i] = make_int2(x->starts[2 * i], x->starts[2 * i] >= 0 ? x->starts[2 * i + 1] : 0);
+        if (!(ha.starts = ring_upload(ctx, ctx->ring_poses, f, n))) return GG_ERR_HIP;
         ha.paths = x->d_paths;
         ha.path_stride = x->path_stride;
         ha.max_len = x->max_len;
@@ -3171,7 +3111,6 @@ int gg_route_headings(gg_context *ctx, const gg_heading_routes *x, void *stream)
     ha.goal_stride = x->goal_stride;
     ha.goal_headings = x->goal_headings;
     ha.n_headings = K;
-    ha.table = dt;
     ha.cost_max = x->cost_max;
     ha.reach = x->max_cost > 0 ? (uint32_t)x->max_cost : (uint32_t)GG_ROUTE_NONE - 1u;
     ha.max_rounds = (int)std::min<uint64_t>(states, (uint64_t)GG_ROUTE_NONE - 1);
@@ -3187,7 +3126,7 @@ int gg_route_headings(gg_context *ctx, const gg_heading_routes *x, void *stream)
     ha.best_heading = x->d_best_heading;
     ha.best_heading_stride = x->best_heading_stride;
     ha.counts = x->d_counts;
-    launch_headings(ha, x->n, f.st);
+    launch_headings(ha, n, f.st);
     return map_call_end(ctx, f);
 }
 
