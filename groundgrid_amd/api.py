@@ -69,7 +69,40 @@ def _check(L, ctx, rc, what):
         raise GroundGridError(f"{what}: {_lib.STATUS.get(rc, rc)} {msg}")
 
 
-# -- the argument frame of the plane methods (fuse_states, route_planes, match_planes, footprint_planes, route_headings, track_clusters)
+# -- the argument frame of the methods over the device calls: the plane methods (fuse_states, route_planes, match_planes, footprint_planes,
+# route_headings, track_clusters), the transfers (export_layers, export_slopes, import_layers), export_images and the cloud methods
+
+def _name_mask(who, names, known, ordered, unknown=None, empty_ok=False):
+    """(names as a list, their bit mask): distinct names of `known`, in its order.  ordered: the text when they are not -- or, unless
+    empty_ok, when none is named.  unknown: what the text calls a name that is not known; None leaves it to list.index's ValueError."""
+    names = list(names)
+    strangers = [k for k in names if k not in known]
+    if strangers and unknown:
+        raise ValueError(f"{who}: unknown {unknown} {strangers}; known: {list(known)}")
+    mask = sum(1 << known.index(k) for k in names)
+    if [k for k in known if k in names] != names or not (names or empty_ok):
+        raise ValueError(f"{who}: {ordered}")
+    return names, mask
+
+
+_LAYER_NAMES = (LAYERS, "names must be distinct and in gg_layer order", None, True)
+_SLOPE_NAMES = (_lib.SLOPE_CHANNELS, "names must be distinct and in GG_SLOPE_* order", "channels")
+
+
+def _occupancy(who, min_points, min_height, max_height):
+    """the thresholds of an occupied cell, checked: (min_points, min_height, max_height)"""
+    if int(min_points) < 1:
+        raise ValueError(f"{who}: min_points < 1")
+    if math.isnan(float(min_height)) or math.isnan(float(max_height)):
+        raise ValueError(f"{who}: min_height or max_height is NaN")
+    return int(min_points), float(min_height), float(max_height)
+
+
+def _max_cells(who, max_cells):
+    if int(max_cells) != max_cells or int(max_cells) < 0 or int(max_cells) > 0x7FFFFFFF:
+        raise ValueError(f"{who}: max_cells is an integer >= 0")
+    return int(max_cells)
+
 
 def _plane_order(who, order, rows, cols):
     """`order` checked: (the shape of one plane, GG_PLANES_*)"""
@@ -84,17 +117,19 @@ def _check_integers(who, **named):
             raise ValueError(f"{who}: {name} is an integer")
 
 
-def _is_int32(t, shape, device):
+def _is_dense(t, shape, dtype=None, device=None):
+    """a contiguous CUDA tensor of that shape and dtype (None: torch.int32), on `device` where one is named"""
     import torch
 
-    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == device
+    return (torch.is_tensor(t) and t.is_cuda and t.dtype == (dtype or torch.int32) and tuple(t.shape) == shape and t.is_contiguous()
+            and (device is None or t.device == device))
 
 
 def _is_planes(t, plane):
     """a contiguous CUDA torch.int32 tensor [B, *plane]"""
     import torch
 
-    return torch.is_tensor(t) and t.dim() == 3 and _is_int32(t, (int(t.shape[0]),) + plane, t.device)
+    return torch.is_tensor(t) and t.dim() == 3 and _is_dense(t, (int(t.shape[0]),) + plane)
 
 
 def _int32_array(who, name, given, shape_text, ok, suffix=""):
@@ -114,28 +149,30 @@ def _int32_ptr(host):
     return host.ctypes.data_as(C.POINTER(C.c_int32))
 
 
-def _reuse_outputs(who, res, want, device, inputs, fill=None, in_place="is an input of the call: no update in place is defined"):
-    """The `out` of a plane method.  want: {field of res: shape, or None for a field not asked for}.  A tensor that res holds must be
-    asked for, be int32 of that shape on `device`, and start at none of the `inputs` (data_ptr()s); nothing is allocated before every
-    field has passed, then the missing ones are (fill: {field: the word a fresh tensor is filled with})."""
+def _reuse_outputs(who, res, want, device, inputs=(), fill=None, in_place="is an input of the call: no update in place is defined"):
+    """The structured `out` of a method.  want: {field of res: shape (of an int32 tensor), (shape, dtype), or None for a field not asked
+    for}.  A tensor that res holds must be asked for, be of that dtype and shape on `device`, and start at none of the `inputs`
+    (data_ptr()s); nothing is allocated before every field has passed, then the missing ones are (fill: {field: the word a fresh
+    tensor is filled with})."""
     import torch
 
-    for field, shape in want.items():
+    want = {field: spec if spec is None or isinstance(spec[-1], torch.dtype) else (spec, torch.int32) for field, spec in want.items()}
+    for field, spec in want.items():
         t = getattr(res, field)
-        if shape is None:
+        if spec is None:
             if t is not None:
                 raise ValueError(f"{who}: out.{field} is given but not asked for")
         elif t is not None:
-            if not _is_int32(t, shape, device):
-                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {shape}")
+            if not _is_dense(t, *spec, device):
+                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA {spec[1]} tensor of shape {spec[0]}")
             if t.data_ptr() in inputs:
                 raise ValueError(f"{who}: out.{field} {in_place}")
-    for field, shape in want.items():
-        if shape is not None and getattr(res, field) is None:
+    for field, spec in want.items():
+        if spec is not None and getattr(res, field) is None:
             if fill and field in fill:
-                setattr(res, field, torch.full(shape, fill[field], dtype=torch.int32, device=device))
+                setattr(res, field, torch.full(spec[0], fill[field], dtype=spec[1], device=device))
             else:
-                setattr(res, field, torch.empty(shape, dtype=torch.int32, device=device))
+                setattr(res, field, torch.empty(spec[0], dtype=spec[1], device=device))
     return res
 
 
@@ -681,28 +718,33 @@ class GroundSegmentation:
         own_stream: enqueue on the context's own stream instead (the caller orders its own streams around the call).  plane_stride
         (in floats, >= rows * cols): the planes lie that far apart in a flat [n * K * plane_stride] tensor, which is returned (or `out`
         of that size reused); the elements between a plane's end and the next plane are not written."""
+        return self._transfer("export_layers", names, _LAYER_NAMES, out, slots, first_slot, n, row_major, stream, own_stream, plane_stride)
+
+    def _transfer(self, who, names, known, planes, slots, first_slot, n, row_major, stream, own_stream, plane_stride):
+        """export_layers, export_slopes and import_layers (`who`): the names of `known` (_name_mask's arguments) to their mask, the shape of
+        the three forms, `planes` checked -- the `out` of an export, made when there is none; the source of the import --, the call."""
         import torch
 
         self._torch_used = True
-        names = list(LAYERS) if names is None else list(names)
-        mask = 0
-        for k in names:
-            mask |= 1 << LAYERS.index(k)
-        if bin(mask).count("1") != len(names) or [k for k in LAYERS if k in names] != names:
-            raise ValueError("export_layers: names must be distinct and in gg_layer order")
+        names, mask = _name_mask(who, known[0] if names is None else names, *known)
         cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
         shape = (cnt, len(names), self.rows, self.cols) if row_major else (cnt, len(names), self.cols, self.rows)
         if plane_stride is not None:
             shape = (cnt * len(names) * int(plane_stride),)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", self.device))
-        assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()
-        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._L.gg_export_layers(self._ctx, cnt, ptr, first, mask, _lib.GG_PLANES_ROWMAJOR if row_major else _lib.GG_PLANES_COLMAJOR,
-                                      C.c_void_p(out.data_ptr()), self.rows * self.cols if plane_stride is None else int(plane_stride),
-                                      None if own_stream else C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
-        _check(self._L, self._ctx, rc, "gg_export_layers")
-        return out
+        if who == "import_layers":
+            if not (torch.is_tensor(planes) and planes.is_cuda and planes.dtype == torch.float32 and planes.is_contiguous()):
+                raise ValueError(f"{who}: planes must be a contiguous CUDA float32 tensor")
+            if tuple(planes.shape) != shape:
+                raise ValueError(f"{who}: planes has shape {tuple(planes.shape)}, these arguments need {shape}")
+        elif planes is None:
+            planes = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", self.device))
+        elif not _is_dense(planes, shape, torch.float32):
+            raise ValueError(f"{who}: out must be a contiguous CUDA float32 tensor of shape {shape}")
+        rc = getattr(self._L, "gg_" + who)(self._ctx, cnt, ptr, first, mask, _lib.GG_PLANES_ROWMAJOR if row_major else _lib.GG_PLANES_COLMAJOR,
+                                           C.c_void_p(planes.data_ptr()), self.rows * self.cols if plane_stride is None else int(plane_stride),
+                                           self._stream_arg(not own_stream, handle=stream))
+        _check(self._L, self._ctx, rc, "gg_" + who)
+        return planes
 
     def export_slopes(self, names=None, *, slots=None, first_slot: int = 0, n: Optional[int] = None, out=None, row_major: bool = False,
                       stream=None, own_stream: bool = False, plane_stride: Optional[int] = None):
@@ -715,29 +757,7 @@ class GroundSegmentation:
         Computed from the maps' ground / groundpatch layers as they stand, in one launch, without synchronising; nothing of a map
         changes, fresh maps stay fresh and the lazily kept layers stay pending.  Map selection, `out`, `stream`, `own_stream` and
         `plane_stride` are those of export_layers."""
-        import torch
-
-        self._torch_used = True
-        names = list(_lib.SLOPE_CHANNELS) if names is None else list(names)
-        unknown = [k for k in names if k not in _lib.SLOPE_CHANNELS]
-        if unknown:
-            raise ValueError(f"export_slopes: unknown channels {unknown}; known: {list(_lib.SLOPE_CHANNELS)}")
-        if not names or [k for k in _lib.SLOPE_CHANNELS if k in names] != names:
-            raise ValueError("export_slopes: names must be distinct and in GG_SLOPE_* order")
-        mask = sum(1 << _lib.SLOPE_CHANNELS.index(k) for k in names)
-        cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
-        shape = (cnt, len(names), self.rows, self.cols) if row_major else (cnt, len(names), self.cols, self.rows)
-        if plane_stride is not None:
-            shape = (cnt * len(names) * int(plane_stride),)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", self.device))
-        assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()
-        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._L.gg_export_slopes(self._ctx, cnt, ptr, first, mask, _lib.GG_PLANES_ROWMAJOR if row_major else _lib.GG_PLANES_COLMAJOR,
-                                      C.c_void_p(out.data_ptr()), self.rows * self.cols if plane_stride is None else int(plane_stride),
-                                      None if own_stream else C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
-        _check(self._L, self._ctx, rc, "gg_export_slopes")
-        return out
+        return self._transfer("export_slopes", names, _SLOPE_NAMES, out, slots, first_slot, n, row_major, stream, own_stream, plane_stride)
 
     def import_layers(self, planes, names=None, *, slots=None, first_slot: int = 0, n: Optional[int] = None, row_major: bool = False,
                       stream=None, own_stream: bool = False, plane_stride: Optional[int] = None):
@@ -748,28 +768,7 @@ class GroundSegmentation:
         values; positions, configurations and scores are untouched.  Enqueued on the current torch stream (or on `stream`) without
         synchronising: `planes` must stay unmodified until that stream has passed the call, which torch ops enqueued there afterwards
         do by themselves.  own_stream: on the context's own stream instead (the caller orders its own streams around the call)."""
-        import torch
-
-        self._torch_used = True
-        names = list(LAYERS) if names is None else list(names)
-        mask = 0
-        for k in names:
-            mask |= 1 << LAYERS.index(k)
-        if bin(mask).count("1") != len(names) or [k for k in LAYERS if k in names] != names:
-            raise ValueError("import_layers: names must be distinct and in gg_layer order")
-        cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
-        shape = (cnt, len(names), self.rows, self.cols) if row_major else (cnt, len(names), self.cols, self.rows)
-        if plane_stride is not None:
-            shape = (cnt * len(names) * int(plane_stride),)
-        if not (torch.is_tensor(planes) and planes.is_cuda and planes.dtype == torch.float32 and planes.is_contiguous()):
-            raise ValueError("import_layers: planes must be a contiguous CUDA float32 tensor")
-        if tuple(planes.shape) != shape:
-            raise ValueError(f"import_layers: planes has shape {tuple(planes.shape)}, these arguments need {shape}")
-        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._L.gg_import_layers(self._ctx, cnt, ptr, first, mask, _lib.GG_PLANES_ROWMAJOR if row_major else _lib.GG_PLANES_COLMAJOR,
-                                      C.c_void_p(planes.data_ptr()), self.rows * self.cols if plane_stride is None else int(plane_stride),
-                                      None if own_stream else C.c_void_p(s if s else _lib.GG_STREAM_DEFAULT))
-        _check(self._L, self._ctx, rc, "gg_import_layers")
+        self._transfer("import_layers", names, _LAYER_NAMES, planes, slots, first_slot, n, row_major, stream, own_stream, plane_stride)
 
     def export_images(self, names=None, *, terrain: bool = False, chw: bool = False, slots=None, first_slot: int = 0, n: Optional[int] = None,
                       out=None, on_torch_stream: bool = False) -> ImageExport:
@@ -784,29 +783,14 @@ class GroundSegmentation:
         import torch
 
         self._torch_used = True
-        names = list(LAYERS) if names is None else list(names)
-        mask = 0
-        for k in names:
-            mask |= 1 << LAYERS.index(k)
-        if bin(mask).count("1") != len(names) or [k for k in LAYERS if k in names] != names:
-            raise ValueError("export_images: names must be distinct and in gg_layer order")
+        names, mask = _name_mask("export_images", LAYERS if names is None else names, *_LAYER_NAMES)
         if not names and not terrain:
             raise ValueError("export_images: neither a layer nor the terrain image is asked for")
         cnt, ptr, keep, first = self._slot_args(slots, first_slot, n)
-        K, dev = len(names), torch.device("cuda", self.device)
-        res = out if out is not None else ImageExport()
+        K = len(names)
         want = {"images": ((cnt, K, self.rows, self.cols), torch.uint8) if K else None, "bounds": ((cnt, K, 2), torch.float32) if K else None,
                 "terrain": ((cnt, 3, self.rows, self.cols) if chw else (cnt, self.rows, self.cols, 3), torch.float32) if terrain else None}
-        for field, spec in want.items():
-            t = getattr(res, field)
-            if spec is None:
-                if t is not None:
-                    raise ValueError(f"export_images: out.{field} is given but not asked for")
-                continue
-            if t is None:
-                setattr(res, field, torch.empty(spec[0], dtype=spec[1], device=dev))
-            elif not (t.is_cuda and t.dtype == spec[1] and tuple(t.shape) == spec[0] and t.is_contiguous()):
-                raise ValueError(f"export_images: out.{field} must be a contiguous CUDA {spec[1]} tensor of shape {spec[0]}")
+        res = _reuse_outputs("export_images", out if out is not None else ImageExport(), want, torch.device("cuda", self.device))
         x = _lib.GGImageExport()
         x.n, x.first_slot, x.slots, x.layer_mask = cnt, first, ptr, mask
         x.d_images = res.images.data_ptr() if K else None
@@ -836,22 +820,12 @@ class GroundSegmentation:
         self._torch_used = True
         x = _lib.GGCloudSplit()
         B, stride, keep = self._labelled_clouds("split_clouds", x, points, n_points, labels, masks, transforms, slots, first_slot)
-        res = out if out is not None else SplitOutputs()
-        want = {"counts": ((B, 2), torch.int32)}
+        want = {"counts": (B, 2)}
         for name, on in (("ground", ground), ("nonground", nonground)):
             want[f"{name}_points"] = ((B, stride, 16), torch.uint8) if on else None
             want[f"{name}_height"] = ((B, stride), torch.float32) if on and heights else None
-            want[f"{name}_source"] = ((B, stride), torch.int32) if on and sources else None
-        for field, spec in want.items():
-            t = getattr(res, field)
-            if spec is None:
-                if t is not None:
-                    raise ValueError(f"split_clouds: out.{field} is given but not asked for")
-                continue
-            if t is None:
-                setattr(res, field, torch.empty(spec[0], dtype=spec[1], device=points.device))
-            elif not (t.is_cuda and t.dtype == spec[1] and tuple(t.shape) == spec[0] and t.is_contiguous()):
-                raise ValueError(f"split_clouds: out.{field} must be a contiguous CUDA {spec[1]} tensor of shape {spec[0]}")
+            want[f"{name}_source"] = (B, stride) if on and sources else None
+        res = _reuse_outputs("split_clouds", out if out is not None else SplitOutputs(), want, points.device)
         for name, dst in (("ground", x.ground), ("nonground", x.nonground)):
             for k in ("points", "height", "source"):
                 t = getattr(res, f"{name}_{k}")
@@ -878,21 +852,14 @@ class GroundSegmentation:
         self._torch_used = True
         x = _lib.GGCloudRaster()
         B, stride, keep = self._labelled_clouds("rasterize_clouds", x, points, n_points, labels, masks, transforms, slots, first_slot)
-        channels = list(channels)
-        unknown = [k for k in channels if k not in _lib.RASTER_CHANNELS]
-        if unknown:
-            raise ValueError(f"rasterize_clouds: unknown channels {unknown}; known: {list(_lib.RASTER_CHANNELS)}")
-        if not channels or [k for k in _lib.RASTER_CHANNELS if k in channels] != channels:
-            raise ValueError("rasterize_clouds: channels must be distinct, in GG_RASTER_* order, and at least one")
-        if order not in ("row", "col"):
-            raise ValueError("rasterize_clouds: order is 'row' or 'col'")
-        shape = (B, len(channels), self.rows, self.cols) if order == "row" else (B, len(channels), self.cols, self.rows)
+        channels, x.channel_mask = _name_mask("rasterize_clouds", channels, _lib.RASTER_CHANNELS, "channels must be distinct, in GG_RASTER_* order, and at least one",
+                                              "channels")
+        plane, x.order = _plane_order("rasterize_clouds", order, self.rows, self.cols)
+        shape = (B, len(channels)) + plane
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=points.device)
-        elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+        elif not _is_dense(out, shape, torch.float32):
             raise ValueError(f"rasterize_clouds: out must be a contiguous CUDA float32 tensor of shape {shape}")
-        x.channel_mask = sum(1 << _lib.RASTER_CHANNELS.index(k) for k in channels)
-        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
         x.d_dst, x.plane_stride = out.data_ptr(), self.rows * self.cols
         stream = self._stream_arg(on_torch_stream, points.device)
         _check(self._L, self._ctx, self._L.gg_rasterize_clouds(self._ctx, C.byref(x), stream), "gg_rasterize_clouds")
@@ -913,33 +880,19 @@ class GroundSegmentation:
         rasterize_clouds.  `out`: a ClusterOutputs of an earlier call with the same arguments, whose tensors are reused.  Only integer
         atomics: bit-identical from run to run.  Enqueued on the current torch stream or, with on_torch_stream=False, on the context's own
         stream; nothing synchronises.  No map changes; fresh maps stay fresh."""
-        import torch
-
         self._torch_used = True
         x = _lib.GGCloudClusters()
         B, stride, keep = self._labelled_clouds("cluster_clouds", x, points, n_points, labels, masks, transforms, slots, first_slot)
         if connectivity not in (4, 8):
             raise ValueError("cluster_clouds: connectivity is 4 or 8")
-        if order not in ("row", "col"):
-            raise ValueError("cluster_clouds: order is 'row' or 'col'")
+        plane, x.order = _plane_order("cluster_clouds", order, self.rows, self.cols)
         max_clusters = int(max_clusters)
         if max_clusters < 0:
             raise ValueError("cluster_clouds: max_clusters < 0")
-        res = out if out is not None else ClusterOutputs()
-        want = {"cell_cluster": (B, self.rows, self.cols) if order == "row" else (B, self.cols, self.rows), "n_clusters": (B,),
-                "clusters": (B, max_clusters, 8) if max_clusters else None, "point_cluster": (B, stride) if point_clusters else None}
-        for field, shape in want.items():
-            t = getattr(res, field)
-            if shape is None:
-                if t is not None:
-                    raise ValueError(f"cluster_clouds: out.{field} is given but not asked for")
-                continue
-            if t is None:
-                setattr(res, field, torch.empty(shape, dtype=torch.int32, device=points.device))
-            elif not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()):
-                raise ValueError(f"cluster_clouds: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {shape}")
+        want = {"cell_cluster": (B,) + plane, "n_clusters": (B,), "clusters": (B, max_clusters, 8) if max_clusters else None,
+                "point_cluster": (B, stride) if point_clusters else None}
+        res = _reuse_outputs("cluster_clouds", out if out is not None else ClusterOutputs(), want, points.device)
         x.min_points, x.min_height, x.max_height, x.connectivity = int(min_points), float(min_height), float(max_height), int(connectivity)
-        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
         x.d_cell_cluster, x.plane_stride = res.cell_cluster.data_ptr(), self.rows * self.cols
         x.d_point_cluster = res.point_cluster.data_ptr() if point_clusters else None
         x.d_n_clusters = res.n_clusters.data_ptr()
@@ -949,27 +902,14 @@ class GroundSegmentation:
         _check(self._L, self._ctx, self._L.gg_cluster_clouds(self._ctx, C.byref(x), stream), "gg_cluster_clouds")
         return res
 
-    def _clearance_call(self, who, x, B, device, max_cells, order, nearest, distance, out, on_torch_stream):
+    def _clearance_call(self, who, x, B, device, max_cells, plane, nearest, distance, out, on_torch_stream):
         """What clearance_clouds and clearance_planes (`who`) share: the outputs of B maps on `device`, the rest of `x`, the call."""
         import torch
 
-        res = out if out is not None else ClearanceOutputs()
-        plane = (B, self.rows, self.cols) if order == "row" else (B, self.cols, self.rows)
-        want = {"dist2": (plane, torch.int32), "nearest": (plane, torch.int32) if nearest else None,
-                "distance": (plane, torch.float32) if distance else None, "n_occupied": ((B,), torch.int32)}
-        for field, spec in want.items():
-            t = getattr(res, field)
-            if spec is None:
-                if t is not None:
-                    raise ValueError(f"{who}: out.{field} is given but not asked for")
-                continue
-            shape, dtype = spec
-            if t is None:
-                setattr(res, field, torch.empty(shape, dtype=dtype, device=device))
-            elif not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
-                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA {dtype} tensor of shape {shape}")
+        want = {"dist2": (B,) + plane, "nearest": (B,) + plane if nearest else None,
+                "distance": ((B,) + plane, torch.float32) if distance else None, "n_occupied": (B,)}
+        res = _reuse_outputs(who, out if out is not None else ClearanceOutputs(), want, device)
         x.max_cells = max_cells
-        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
         x.d_dist2, x.plane_stride = res.dist2.data_ptr(), self.rows * self.cols
         x.d_nearest = res.nearest.data_ptr() if nearest else None
         x.d_distance = res.distance.data_ptr() if distance else None
@@ -977,14 +917,6 @@ class GroundSegmentation:
         stream = self._stream_arg(on_torch_stream, device)
         _check(self._L, self._ctx, self._L.gg_clearance_clouds(self._ctx, C.byref(x), stream), "gg_clearance_clouds")
         return res
-
-    @staticmethod
-    def _clearance_args(who, max_cells, order):
-        if order not in ("row", "col"):
-            raise ValueError(f"{who}: order is 'row' or 'col'")
-        if int(max_cells) != max_cells or int(max_cells) < 0 or int(max_cells) > 0x7FFFFFFF:
-            raise ValueError(f"{who}: max_cells is an integer >= 0")
-        return int(max_cells)
 
     def clearance_clouds(self, points, n_points: Sequence[int], *, labels=None, masks=None, transforms=None, slots=None, first_slot: int = 0,
                          min_points: int = 1, min_height: float = -math.inf, max_height: float = math.inf, max_cells: int = 0,
@@ -1000,16 +932,13 @@ class GroundSegmentation:
         arguments, whose tensors are reused.  Integer arithmetic only: bit-identical from run to run.  Enqueued on the current torch
         stream or, with on_torch_stream=False, on the context's own stream; nothing synchronises.  No map changes; fresh maps stay fresh."""
         who = "clearance_clouds"
-        max_cells = self._clearance_args(who, max_cells, order)
-        if int(min_points) < 1:
-            raise ValueError(f"{who}: min_points < 1")
-        if math.isnan(float(min_height)) or math.isnan(float(max_height)):
-            raise ValueError(f"{who}: min_height or max_height is NaN")
-        self._torch_used = True
         x = _lib.GGCloudClearance()
+        plane, x.order = _plane_order(who, order, self.rows, self.cols)
+        max_cells = _max_cells(who, max_cells)
+        x.min_points, x.min_height, x.max_height = _occupancy(who, min_points, min_height, max_height)
+        self._torch_used = True
         B, stride, keep = self._labelled_clouds(who, x, points, n_points, labels, masks, transforms, slots, first_slot)
-        x.min_points, x.min_height, x.max_height = int(min_points), float(min_height), float(max_height)
-        return self._clearance_call(who, x, B, points.device, max_cells, order, nearest, distance, out, on_torch_stream)
+        return self._clearance_call(who, x, B, points.device, max_cells, plane, nearest, distance, out, on_torch_stream)
 
     def clearance_planes(self, seeds, *, max_cells: int = 0, order: str = "row", nearest: bool = True, distance: bool = True,
                          out: Optional[ClearanceOutputs] = None, on_torch_stream: bool = True) -> ClearanceOutputs:
@@ -1020,19 +949,19 @@ class GroundSegmentation:
         import torch
 
         who = "clearance_planes"
-        max_cells = self._clearance_args(who, max_cells, order)
+        x = _lib.GGCloudClearance()
+        plane, x.order = _plane_order(who, order, self.rows, self.cols)
+        max_cells = _max_cells(who, max_cells)
         if not (torch.is_tensor(seeds) and seeds.is_cuda and seeds.dtype == torch.int32 and seeds.dim() == 3 and seeds.is_contiguous()):
             raise ValueError(f"{who}: seeds must be a contiguous CUDA torch.int32 tensor [B, rows, cols]")
         B = int(seeds.shape[0])
-        plane = (self.rows, self.cols) if order == "row" else (self.cols, self.rows)
         if tuple(seeds.shape[1:]) != plane:
             raise ValueError(f"{who}: seeds of shape {tuple(seeds.shape)} do not fit planes of {plane}")
         if out is not None and out.dist2 is not None and torch.is_tensor(out.dist2) and out.dist2.data_ptr() == seeds.data_ptr():
             raise ValueError(f"{who}: seeds may not be an output")
         self._torch_used = True
-        x = _lib.GGCloudClearance()
         x.n, x.d_seeds, x.seed_stride = B, seeds.data_ptr(), self.rows * self.cols
-        return self._clearance_call(who, x, B, seeds.device, max_cells, order, nearest, distance, out, on_torch_stream)
+        return self._clearance_call(who, x, B, seeds.device, max_cells, plane, nearest, distance, out, on_torch_stream)
 
     def visibility_clouds(self, points, n_points: Sequence[int], origins, *, labels=None, masks=None, transforms=None, slots=None,
                           first_slot: int = 0, min_points: int = 1, min_height: float = -math.inf, max_height: float = math.inf,
@@ -1053,11 +982,10 @@ class GroundSegmentation:
         import torch
 
         who = "visibility_clouds"
-        max_cells = self._clearance_args(who, max_cells, order)
-        if int(min_points) < 1:
-            raise ValueError(f"{who}: min_points < 1")
-        if math.isnan(float(min_height)) or math.isnan(float(max_height)):
-            raise ValueError(f"{who}: min_height or max_height is NaN")
+        x = _lib.GGCloudVisibility()
+        plane, x.order = _plane_order(who, order, self.rows, self.cols)
+        x.max_cells = _max_cells(who, max_cells)
+        x.min_points, x.min_height, x.max_height = _occupancy(who, min_points, min_height, max_height)
         try:
             host_origins = np.ascontiguousarray(np.asarray(origins, dtype=np.float32))
         except (TypeError, ValueError) as e:
@@ -1065,24 +993,10 @@ class GroundSegmentation:
         if host_origins.ndim != 2 or host_origins.shape[1] != 3 or not torch.is_tensor(points) or host_origins.shape[0] != points.shape[0]:
             raise ValueError(f"{who}: origins of shape {host_origins.shape} are not [B, 3]")
         self._torch_used = True
-        x = _lib.GGCloudVisibility()
         B, stride, keep = self._labelled_clouds(who, x, points, n_points, labels, masks, transforms, slots, first_slot)
-        res = out if out is not None else VisibilityOutputs()
-        want = {"state": (B, self.rows, self.cols) if order == "row" else (B, self.cols, self.rows), "counts": (B, 3) if counts else None}
-        for field, shape in want.items():
-            t = getattr(res, field)
-            if shape is None:
-                if t is not None:
-                    raise ValueError(f"{who}: out.{field} is given but not asked for")
-                continue
-            if t is None:
-                setattr(res, field, torch.empty(shape, dtype=torch.int32, device=points.device))
-            elif not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()):
-                raise ValueError(f"{who}: out.{field} must be a contiguous CUDA torch.int32 tensor of shape {shape}")
-        x.min_points, x.min_height, x.max_height = int(min_points), float(min_height), float(max_height)
+        want = {"state": (B,) + plane, "counts": (B, 3) if counts else None}
+        res = _reuse_outputs(who, out if out is not None else VisibilityOutputs(), want, points.device)
         x.origins = host_origins.ctypes.data_as(C.POINTER(C.c_float))
-        x.max_cells = max_cells
-        x.order = _lib.GG_PLANES_ROWMAJOR if order == "row" else _lib.GG_PLANES_COLMAJOR
         x.d_state, x.plane_stride = res.state.data_ptr(), self.rows * self.cols
         x.d_counts = res.counts.data_ptr() if counts else None
         stream = self._stream_arg(on_torch_stream, points.device)
@@ -1460,7 +1374,7 @@ class GroundSegmentation:
                 raise ValueError(f"{who}: out is `previous`: no update in place is defined, alternate between two TrackOutputs")
             if previous.order != order:
                 raise ValueError(f"{who}: previous was computed with order={previous.order!r}")
-            if not all(_is_int32(t, sh, cell_cluster.device) for t, sh in ((previous.cell_cluster, (B,) + plane), (previous.tracks, (B, M, 8)), (previous.heads, (B, 4)))):
+            if not all(_is_dense(t, sh, device=cell_cluster.device) for t, sh in ((previous.cell_cluster, (B,) + plane), (previous.tracks, (B, M, 8)), (previous.heads, (B, 4)))):
                 raise ValueError(f"{who}: previous must be the TrackOutputs of a call with the same B, max_clusters and order")
         host_shifts = _int32_array(who, "shifts", shifts, "[B, 2]", lambda sh: sh == (B, 2)) if shifts is not None else None
         want = {"tracks": (B, M, 8), "heads": (B, 4), "cell_track": (B,) + plane if cell_track else None}

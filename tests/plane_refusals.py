@@ -181,13 +181,13 @@ def c_cases(name):
 class Device:
     """one context of the baseline size and one zeroed device arena"""
 
-    def __init__(self):
+    def __init__(self, words=None):
         import torch
 
         self.torch = torch
         self.seg = api.GroundSegmentation().init(*GEOMETRY, n_slots=N_SLOTS, max_points=4096)
         assert self.seg.rows == self.seg.cols == SIDE
-        self.arena = torch.zeros(ARENA_WORDS, dtype=torch.int32, device="cuda")
+        self.arena = torch.zeros(ARENA_WORDS if words is None else words, dtype=torch.int32, device="cuda")
 
     def close(self):
         self.torch.cuda.synchronize()
@@ -395,8 +395,8 @@ def observe_gpu():
     return seen
 
 
-def recorded(which):
-    with open(os.path.join(GOLDEN, f"plane_refusals_{which}.json")) as f:
+def recorded(which, name="plane_refusals"):
+    with open(os.path.join(GOLDEN, f"{name}_{which}.json")) as f:
         return json.load(f)
 
 
@@ -411,17 +411,22 @@ def first_difference(seen, want):
     return f"{extra[0]}: observed, not recorded" if extra else None
 
 
-if __name__ == "__main__":
+def record_main(name, observe_cpu, observe_gpu):
+    """`python -m tests.NAME --record [--out DIR]`: the CPU table, and on a machine with a device the GPU table, into NAME_{cpu,gpu}.json"""
     import torch
 
     if "--record" not in sys.argv[1:]:
-        sys.exit("usage: python -m tests.plane_refusals --record [--out DIR]")
+        sys.exit(f"usage: python -m tests.{name} --record [--out DIR]")
     out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else GOLDEN
     tables = {"cpu": observe_cpu()}
     if torch.cuda.is_available():
         tables["gpu"] = observe_gpu()
     for which, seen in tables.items():
-        with open(os.path.join(out, f"plane_refusals_{which}.json"), "w") as f:
+        with open(os.path.join(out, f"{name}_{which}.json"), "w") as f:
             json.dump(seen, f, indent=0, sort_keys=False)
             f.write("\n")
         print(f"recorded {len(seen)} {which} cases")
+
+
+if __name__ == "__main__":
+    record_main("plane_refusals", observe_cpu, observe_gpu)
