@@ -61,6 +61,7 @@ SYMBOLS = [
     "gg_route_headings",
     "gg_heading_moves",
     "gg_track_clusters",
+    "gg_box_clusters",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -494,6 +495,52 @@ GG_TRACK_MAX_GATE = 4         # ... and its widest gate, in cells
 GG_TRACK_SLAB_WORDS = 28 * 1024
 
 
+class GGBox(C.Structure):
+    """gg_box: record c of a cloud is the oriented box of its cluster c (gg_box_clusters), 32 bytes"""
+
+    _fields_ = [
+        ("heading", C.c_int32),
+        ("points", C.c_int32),
+        ("a_min", C.c_int32),
+        ("a_max", C.c_int32),
+        ("b_min", C.c_int32),
+        ("b_max", C.c_int32),
+        ("cost_lo", C.c_int32),
+        ("cost_hi", C.c_int32),
+    ]
+
+
+class GGClusterBoxes(C.Structure):
+    """gg_cluster_boxes: the oriented boxes of the obstacle clusters of many clouds, in device memory (gg_box_clusters)"""
+
+    _fields_ = _LABELLED_CLOUDS[:8] + [
+        ("d_point_cluster", C.c_void_p),
+        ("d_n_clusters", C.c_void_p),
+        ("rotations", C.POINTER(C.c_int32)),
+        ("n_rotations", C.c_int),
+        ("criterion", C.c_int),
+        ("max_clusters", C.c_int),
+        ("d_boxes", C.c_void_p),
+        ("d_costs", C.c_void_p),
+    ]
+
+
+GG_HAS_BOX_CLUSTERS = 1
+GG_BOX_UNIT = 16              # units per cell of gg_box_clusters' quantisation
+GG_BOX_MAX_HEADINGS = 32      # the most candidate headings of a call
+GG_BOX_MAX_CLUSTERS = 4096    # ... and the most clusters per cloud
+GG_BOX_AREA, GG_BOX_EDGE = 0, 1
+BOX_CRITERIA = ("area", "edge")
+# the bytes of LDS a work-group of k24_boxes.hip fills with clusters at a time (gg_internal.h BOX_LDS_BUDGET): 24 per (cluster, heading) and
+# 4 per cluster; with more clusters the ids are walked once per slab, which is where the tests put their cluster counts
+GG_BOX_LDS_BUDGET = 144 * 1024
+
+
+def box_slab_clusters(n_headings: int, max_clusters: int) -> int:
+    """the clusters a work-group of k24_boxes.hip holds at a time (gg_internal.h box_slab_clusters)"""
+    return min(max_clusters, GG_BOX_LDS_BUDGET // (24 * n_headings + 4))
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -579,6 +626,7 @@ def load():
     L.gg_route_headings.argtypes = [vp, P(GGHeadingRoutes), vp]
     L.gg_heading_moves.argtypes = [P(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int32)]
     L.gg_track_clusters.argtypes = [vp, P(GGClusterTracks), vp]
+    L.gg_box_clusters.argtypes = [vp, P(GGClusterBoxes), vp]
     L.gg_get_map_position.argtypes =[vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

@@ -558,6 +558,40 @@ class TrackOutputs:
         return out
 
 
+BOX_DTYPE = np.dtype([("heading", "<i4"), ("points", "<i4"), ("a_min", "<i4"), ("a_max", "<i4"), ("b_min", "<i4"), ("b_max", "<i4"),
+                      ("cost_lo", "<i4"), ("cost_hi", "<i4")])
+
+
+@dataclass
+class BoxOutputs:
+    """what GroundSegmentation.box_clusters returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    boxes: "object" = None  # torch.int32 [B, max_clusters, 8]: gg_box records; only the first min(max(n_clusters[b], 0), max_clusters) of cloud b are written
+    costs: "object" = None  # torch.int64 [B, max_clusters, K]: the bits of the uint64 cost of every (cluster, heading); -1 (all ones): no point
+
+    def metric(self, b: int, rotations, resolution: float, position=(0.0, 0.0)):
+        """A host convenience, not part of the bit contract: the rectangles of cloud b in metres, float64 [max_clusters, 5] = centre x,
+        centre y (map frame), length (along the heading), width (across it) and yaw = atan2(sq, cq) of the chosen table entry; NaN for a
+        record without a heading (its words may be whatever the tensor held).  rotations: the table the call was given; resolution and
+        position: the map's.  The centre of the box in (a, b) is rotated back by the transpose of the heading and moved by half a unit
+        for the floor of the quantisation.  It synchronises."""
+        rec = self.boxes[b].cpu().numpy().astype(np.int64)
+        rot = np.asarray(rotations, dtype=np.int64).reshape(-1, 2)
+        out = np.full((rec.shape[0], 5), np.nan, dtype=np.float64)
+        ok = (rec[:, 0] >= 0) & (rec[:, 0] < rot.shape[0])
+        k = rec[ok, 0]
+        unit = float(resolution) / float(_lib.GG_BOX_UNIT)       # metres per unit
+        q = float(_lib.GG_MATCH_UNIT)
+        cq, sq = rot[k, 0] / q, rot[k, 1] / q
+        ca, cb = 0.5 * (rec[ok, 2] + rec[ok, 3]) / q, 0.5 * (rec[ok, 4] + rec[ok, 5]) / q  # the centre, in units, in the heading's frame
+        out[ok, 0] = float(position[0]) + (ca * cq - cb * sq + 0.5) * unit
+        out[ok, 1] = float(position[1]) + (ca * sq + cb * cq + 0.5) * unit
+        out[ok, 2] = (rec[ok, 3] - rec[ok, 2]) / q * unit
+        out[ok, 3] = (rec[ok, 5] - rec[ok, 4]) / q * unit
+        out[ok, 4] = np.arctan2(sq, cq)
+        return out
+
+
 def heading_moves(rotations, *, step: int = 1, unit: int = 10, turn: int = 0, reverse_pct: int = 0, spin: int = 0):
     """The move table of a car-like vehicle for GroundSegmentation.route_headings (gg_heading_moves): int32 [K, 8, 4], entry m of heading
     k = (da, db, k2, s): from (k, (r, c)) to (k2, (r + da, c + db)) at cost s times the clamped cost of the cell entered; s == 0 marks an
@@ -1399,6 +1433,55 @@ class GroundSegmentation:
         _check(self._L, self._ctx, self._L.gg_track_clusters(self._ctx, C.byref(x), stream), "gg_track_clusters")
         return res
 
+    def box_clusters(self, points, n_points: Sequence[int], point_cluster, n_clusters, rotations, *, transforms=None, slots=None,
+                     first_slot: int = 0, criterion: str = "edge", max_clusters: int = 256, costs: bool = False,
+                     out: Optional[BoxOutputs] = None, on_torch_stream: bool = False) -> BoxOutputs:
+        """The shape of every object (gg_box_clusters): a rectangle fitted to every cluster of many clouds by a search over candidate
+        headings.  points / n_points / transforms / slots / first_slot as for cluster_clouds, which this call follows: point_cluster is
+        its ClusterOutputs.point_cluster (contiguous CUDA int32 [B, stride]) and n_clusters its ClusterOutputs.n_clusters (int32 [B]) as
+        they stand.  rotations: rotation_table(angles), int32 [K, 2] with 1 <= K <= 32; for a rectangle list angles in [0, pi/2).  A
+        point takes part when its id lies in [0, min(n_clusters, max_clusters)) and it lies inside its map; its position is quantised
+        to 16 units per cell relative to the map's position and projected on every heading.  criterion "area": the heading of the
+        smallest rectangle; "edge": the heading under which the points lie closest to the rectangle's edges (the L-shape of a car seen
+        from one corner); among equal costs the earlier table entry.  boxes int32 [B, max_clusters, 8]: heading, points, a_min, a_max,
+        b_min, b_max, cost_lo, cost_hi per cluster (heading -1 and zeros for a cluster without a point; BoxOutputs.metric gives centre,
+        length, width and yaw in metres); costs=True adds int64 [B, max_clusters, K], the bits of every uint64 cost (-1: no point).
+        Records and rows from min(n_clusters, max_clusters) on are never written.  `out`: a BoxOutputs of an earlier call with the same
+        arguments, whose tensors are reused.  Integer arithmetic only: bit-identical from run to run.  Enqueued on the context's own
+        stream or, with on_torch_stream=True, on the current torch stream; nothing synchronises.  No map is read beyond its position
+        or changed; fresh maps stay fresh."""
+        import torch
+
+        who = "box_clusters"
+        x = _lib.GGClusterBoxes()
+        B, stride, keep = self._labelled_clouds(who, x, points, n_points, None, None, transforms, slots, first_slot, labelled=False)
+        if criterion not in _lib.BOX_CRITERIA:
+            raise ValueError(f"{who}: criterion is one of {list(_lib.BOX_CRITERIA)}")
+        _check_integers(who, max_clusters=max_clusters)
+        if not 1 <= max_clusters <= _lib.GG_BOX_MAX_CLUSTERS:
+            raise ValueError(f"{who}: max_clusters lies in [1, {_lib.GG_BOX_MAX_CLUSTERS}]")
+        rot = _int32_array(who, "rotations", rotations, "[K, 2]", lambda sh: len(sh) == 2 and sh[1] == 2 and 1 <= sh[0] <= _lib.GG_BOX_MAX_HEADINGS,
+                           f" with 1 <= K <= {_lib.GG_BOX_MAX_HEADINGS}")
+        if int(np.abs(rot).max()) > _lib.GG_MATCH_UNIT:
+            raise ValueError(f"{who}: a rotation word lies outside [-{_lib.GG_MATCH_UNIT}, {_lib.GG_MATCH_UNIT}]")
+        if not _is_dense(point_cluster, (B, stride), device=points.device):
+            raise ValueError(f"{who}: point_cluster must be a contiguous CUDA torch.int32 tensor of shape {(B, stride)}")
+        if not _is_dense(n_clusters, (B,), device=points.device):
+            raise ValueError(f"{who}: n_clusters must be a contiguous CUDA torch.int32 tensor of shape {(B,)}")
+        M, K = int(max_clusters), int(rot.shape[0])
+        want = {"boxes": (B, M, 8), "costs": ((B, M, K), torch.int64) if costs else None}
+        inputs = [points.data_ptr(), point_cluster.data_ptr(), n_clusters.data_ptr()]
+        res = _reuse_outputs(who, out if out is not None else BoxOutputs(), want, points.device, inputs)
+        self._torch_used = True
+        x.d_point_cluster, x.d_n_clusters = point_cluster.data_ptr(), n_clusters.data_ptr()
+        x.rotations, x.n_rotations = _int32_ptr(rot), K
+        x.criterion, x.max_clusters = _lib.BOX_CRITERIA.index(criterion), M
+        x.d_boxes = res.boxes.data_ptr()
+        x.d_costs = res.costs.data_ptr() if costs else None
+        stream = self._stream_arg(on_torch_stream, points.device)
+        _check(self._L, self._ctx, self._L.gg_box_clusters(self._ctx, C.byref(x), stream), "gg_box_clusters")
+        return res
+
     def snapshot_maps(self, slots=None, first_slot: int = 0, n: Optional[int] = None) -> dict:
         """A checkpoint of the named maps: {"planes": export_layers() of all eleven layers [n, 11, cols, rows] (on the device, enqueued on
         the current torch stream), "positions": their map positions, float64 [n, 2]}.  restore_maps puts it back -- into these maps, other
@@ -1479,21 +1562,23 @@ class GroundSegmentation:
             handle = torch.cuda.current_stream(self.device if device is None else device).cuda_stream
         return C.c_void_p(handle if handle else _lib.GG_STREAM_DEFAULT)
 
-    def _labelled_clouds(self, who, x, points, n_points, labels, masks, transforms, slots, first_slot):
+    def _labelled_clouds(self, who, x, points, n_points, labels, masks, transforms, slots, first_slot, labelled: bool = True):
         """What split_clouds, rasterize_clouds and cluster_clouds (`who`) share: checks points and labels / masks and fills the ten leading
-        members of the fresh gg_cloud_* structure `x`.  Returns (B, stride, keep): `keep` holds the host arrays `x` points to, and the
-        caller keeps it referenced until the C call has returned."""
+        members of the fresh gg_cloud_* structure `x` (labelled=False, box_clusters: the eight in front of the labels, which `x` does not
+        have).  Returns (B, stride, keep): `keep` holds the host arrays `x` points to, and the caller keeps it referenced until the C
+        call has returned."""
         import torch
 
         assert points.is_cuda and points.dtype == torch.uint8 and points.dim() == 3 and points.is_contiguous()
         B, stride, rec = points.shape
         assert rec in (16, 32)
-        if (labels is None) == (masks is None):
-            raise ValueError(f"{who}: exactly one of labels and masks")
-        given = labels if labels is not None else masks
-        want_shape = (B, stride) if labels is not None else (B, (stride + 3) // 4)
-        if not (torch.is_tensor(given) and given.is_cuda and given.dtype == torch.uint8 and given.is_contiguous() and tuple(given.shape) == want_shape):
-            raise ValueError(f"{who}: {'labels' if labels is not None else 'masks'} must be a contiguous CUDA uint8 tensor of shape {want_shape}")
+        if labelled:
+            if (labels is None) == (masks is None):
+                raise ValueError(f"{who}: exactly one of labels and masks")
+            given = labels if labels is not None else masks
+            want_shape = (B, stride) if labels is not None else (B, (stride + 3) // 4)
+            if not (torch.is_tensor(given) and given.is_cuda and given.dtype == torch.uint8 and given.is_contiguous() and tuple(given.shape) == want_shape):
+                raise ValueError(f"{who}: {'labels' if labels is not None else 'masks'} must be a contiguous CUDA uint8 tensor of shape {want_shape}")
         keep = [(C.c_int32 * max(B, 1))(*[int(v) for v in n_points])]
         x.n, x.first_slot, x.point_format = B, int(first_slot), _lib.GG_POINT16 if rec == 16 else _lib.GG_POINT32
         x.d_points, x.cloud_stride, x.n_points = points.data_ptr(), stride, keep[0]
@@ -1503,6 +1588,8 @@ class GroundSegmentation:
         if transforms is not None:  # [B, 3, 4] map <- cloud frame, as for filter_batch
             keep.append(np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(B, 12)))
             x.transforms = keep[-1].ctypes.data_as(C.POINTER(C.c_double))
+        if not labelled:
+            return B, stride, keep
         x.d_labels = labels.data_ptr() if labels is not None else None
         x.d_label_masks = masks.data_ptr() if masks is not None else None
         return B, stride, keep

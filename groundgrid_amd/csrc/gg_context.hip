@@ -2669,6 +2669,57 @@ int gg_track_clusters(gg_context *ctx, const gg_cluster_tracks *x, void *stream)
     return map_call_end(ctx, f);
 }
 
+// The oriented boxes of the obstacle clusters of many clouds (k24_boxes.hip), in the frame of gg_split_clouds with the same per-cloud records
+// and without labels (the ids stand in where the frame wants a label pointer): nothing is synchronised, no map is filled, no layer is read and no host-side flag changes.
+int gg_box_clusters(gg_context *ctx, const gg_cluster_boxes *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_box_clusters";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_cluster_boxes");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    if (!x->d_point_cluster || !x->d_n_clusters || !x->d_boxes) return fail(ctx, GG_ERR_INVALID, who, "d_point_cluster, d_n_clusters and d_boxes are required");
+    if (!x->rotations) return fail(ctx, GG_ERR_INVALID, who, "rotations is required");
+    if (x->n_rotations < 1 || x->n_rotations > GG_BOX_MAX_HEADINGS) return fail(ctx, GG_ERR_INVALID, who, "n_rotations lies in [1, 32]");
+    for (int k = 0; k < 2 * x->n_rotations; ++k)
+        if (x->rotations[k] < -GG_MATCH_UNIT || x->rotations[k] > GG_MATCH_UNIT) return fail(ctx, GG_ERR_INVALID, who, "a rotation word lies outside [-16384, 16384]");
+    if (x->criterion != GG_BOX_AREA && x->criterion != GG_BOX_EDGE) return fail(ctx, GG_ERR_INVALID, who, "criterion");
+    if (x->max_clusters < 1 || x->max_clusters > GG_BOX_MAX_CLUSTERS) return fail(ctx, GG_ERR_INVALID, who, "max_clusters lies in [1, 4096]");
+    // |u| <= 8 * side + 1, so both projections stay inside an int32 (k24_boxes.hip relies on it)
+    if (ctx->arena.g.rows > BOX_MAX_SIDE || ctx->arena.g.cols > BOX_MAX_SIDE) return fail(ctx, GG_ERR_GEOMETRY, who, "the map has more than 4096 rows or columns");
+    const int n = x->n, K = x->n_rotations;
+    const size_t M = (size_t)x->max_clusters;
+    if (x->cloud_stride > ctx->max_points) return fail(ctx, GG_ERR_CAPACITY, who, "cloud_stride is larger than max_points"); // (the frame's, ahead of the ranges it sizes)
+    if (x->d_points && x->n <= ctx->n_slots) { // (a null d_points and n > n_slots are refused by the frame below)
+        const size_t rec = x->point_format == GG_POINT16 ? sizeof(gg_point16) : sizeof(gg_point32);
+        const BufferRange ranges[] = {row_range("d_points", x->d_points, n, x->cloud_stride * rec, false),
+                                      row_range("d_point_cluster", x->d_point_cluster, n, x->cloud_stride * sizeof(int32_t), false),
+                                      row_range("d_n_clusters", x->d_n_clusters, n, sizeof(int32_t), false),
+                                      row_range("d_boxes", x->d_boxes, n, M * sizeof(gg_box), true),
+                                      row_range("d_costs", x->d_costs, n, M * K * sizeof(uint64_t), true)};
+        if (const int rc = check_no_overlap(ctx, who, ranges)) return rc;
+    }
+    MapCall f;
+    BoxArgs ba;
+    // The frame is entered as it stands.  It asks for exactly one of labels and masks and reads neither; this call has no labels, so the ids
+    // stand in for the label bytes: CloudArgs::labels is then not null and k24_boxes.hip never looks at it.
+    const LabelledClouds in{x->n, x->first_slot, x->slots, x->point_format, x->d_points, x->cloud_stride, x->n_points, x->transforms,
+                            reinterpret_cast<const uint8_t *>(x->d_point_cluster), nullptr};
+    if (const int rc = labelled_clouds_begin(ctx, who, in, stream, &f, &ba.cl)) return rc;
+    ba.point_cluster = x->d_point_cluster;
+    ba.n_clusters = x->d_n_clusters;
+    ba.K = K;
+    ba.criterion = x->criterion;
+    ba.M = x->max_clusters;
+    ba.slab = box_slab_clusters(K, x->max_clusters);
+    ba.scale = (double)GG_BOX_UNIT / ctx->arena.g.resolution;
+    for (int k = 0; k < 2 * GG_BOX_MAX_HEADINGS; ++k) ba.rot[k] = k < 2 * K ? x->rotations[k] : 0;
+    ba.boxes = x->d_boxes;
+    ba.costs = reinterpret_cast<unsigned long long *>(x->d_costs);
+    launch_boxes(ctx->arena, ba, n, f.st);
+    return map_call_end(ctx, f);
+}
+
 // The cost-to-go fields and paths of many maps (k19_route.hip): a ring entry and the ordering of the export for maps 0 .. n-1, none of which
 // is read, as gg_fuse_states; the per-map start cells travel in the ring entry.  Nothing is synchronised, no map is filled and no host-side
 // flag changes.

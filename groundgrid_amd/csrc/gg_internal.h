@@ -623,6 +623,32 @@ struct TrackArgs {
 };
 inline size_t track_lds_bytes(int M, int slab_words) { return sizeof(uint32_t) * ((size_t)TRACK_FIXED_WORDS * M + TRACK_MISC_WORDS + slab_words); }
 
+// gg_box_clusters (k24_boxes.hip): what its one launch takes.  The per-cloud records are gg_split_clouds' (SplitCloud, the same ring; the call
+// has no labels: cl.labels holds the ids' address as a stand-in that the kernel never reads, cl.masks is null).  A work-group holds `slab` clusters at a time: per (cluster, heading) one 64-bit sum and
+// four int32 extrema, per cluster one point count.
+constexpr int BOX_THREADS = 1024;             // one work-group per cloud
+constexpr int BOX_LDS_BUDGET = 144 * 1024;    // the most bytes of a slab
+constexpr int BOX_PAIR_BYTES = 24;            // LDS bytes per (cluster, heading)
+constexpr int BOX_MAX_SIDE = 4096;            // rows and cols the entry point admits (GG_ERR_GEOMETRY beyond): |u| <= 8 * side + 1
+static_assert((8LL * BOX_MAX_SIDE + 1) * 2 * GG_MATCH_UNIT < (1LL << 31), "a = ux * cq + uy * sq and b = uy * cq - ux * sq fit an int32");
+// (groundgrid_amd/_lib.py restates BOX_LDS_BUDGET and box_slab_clusters for the tests and tools/bench_boxes.py, which place their cluster
+// counts by them: a change of the budget, of BOX_PAIR_BYTES or of the 4 bytes per cluster is made there too; tests/test_box_clusters_cpu.py
+// holds the two constants to this text)
+struct BoxArgs {
+    CloudArgs cl;
+    const int32_t *point_cluster;  // [cloud][cloud_stride]
+    const int32_t *n_clusters;     // [cloud]
+    int K, criterion, M;
+    int slab;                      // box_slab_clusters(K, M)
+    double scale;                  // GG_BOX_UNIT / resolution
+    int32_t rot[2 * GG_BOX_MAX_HEADINGS]; // (cq, sq) of heading k at rot[2 k], rot[2 k + 1]
+    gg_box *boxes;                 // [cloud][M]
+    unsigned long long *costs;     // [cloud][M][K]; nullable
+};
+inline int box_slab_clusters(int K, int M) { const int most = BOX_LDS_BUDGET / (BOX_PAIR_BYTES * K + 4); return M < most ? M : most; }
+inline size_t box_lds_bytes(int K, int slab) { return ((size_t)BOX_PAIR_BYTES * K + 4) * (size_t)slab + 8 * (size_t)K + 8; } // (+ the rotation table)
+static_assert(BOX_LDS_BUDGET / (BOX_PAIR_BYTES * GG_BOX_MAX_HEADINGS + 4) >= 1, "a slab holds at least one cluster");
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -676,6 +702,7 @@ void launch_match(const MatchArgs &x, int n_maps, hipStream_t s);               
 void launch_footprint(const FootprintArgs &x, int n_maps, hipStream_t s);                        // k21_footprint.hip: (counts := 0,) k_footprint_planes
 void launch_headings(const HeadingsArgs &x, int n_maps, hipStream_t s);                          // k22_headings.hip: relax, (counts := 0, next,) (paths)
 void launch_tracks(const TrackArgs &x, int n_maps, hipStream_t s);                                // k23_tracks.hip: k_track_clusters
+void launch_boxes(const Arena &a, const BoxArgs &x, int n_clouds, hipStream_t s);                 // k24_boxes.hip: k_box_clusters
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

@@ -1464,6 +1464,86 @@ typedef struct gg_cluster_tracks {
 int gg_track_clusters(gg_context *ctx, const gg_cluster_tracks *x, void *stream);
 #define GG_HAS_TRACK_CLUSTERS 1
 
+/* THE SHAPE OF AN OBJECT, for the clusters of many clouds in DEVICE memory: a gg_cluster has an axis-aligned cell box and a gg_track a cell
+ * centroid, and on 0.33 m cells neither says which way a car points, how long and wide it is or where its centre lies.  gg_box_clusters fits
+ * a search-based rectangle to every cluster: for each of up to 32 candidate headings the extent of the cluster's points along and across the
+ * heading, the heading chosen by an integer criterion, one 32-byte record per cluster.  What a caller otherwise gets from a download of the
+ * per-point ids and the points, or from one scatter_reduce per heading and per map.  It runs right behind gg_cluster_clouds on that call's
+ * points, d_point_cluster and d_n_clusters, and reads no layer.  One call for many maps; cloud i meets map slots ? slots[i] : first_slot + i
+ * (distinct, inside the context).  All arithmetic is integer after one quantisation step; with M = max_clusters and K = n_rotations:
+ *   clusters     M_i = min(max(d_n_clusters[i], 0), M), read on the device.
+ *   participation  point p < n_points[i] of cloud i participates when (1) its id d_point_cluster[i][p] lies in [0, M_i) and (2) its
+ *                map-frame position lies inside its map under the map's current position, by the path's own inside test (:222-231) -- with
+ *                `transforms` tested on the map-frame point the path computes (tf2::doTransform in double, cast to float), as
+ *                gg_cluster_clouds has it.  Any other id, any coordinates (NaN, inf) and any d_n_clusters word are memory-safe and select
+ *                nothing.
+ *   quantisation GG_BOX_UNIT = 16 units per cell: ux = (int32_t)floor(((double)px - pos_x) * s) and uy likewise from py and pos_y, with
+ *                s = 16.0 / resolution computed once on the host in double from the resolution the inside test uses; (pos_x, pos_y) is the
+ *                map's position.  A subtraction, then a multiplication: nothing can be contracted.  A map with more than 4096 rows or
+ *                columns is GG_ERR_GEOMETRY, so |u| <= 8 * side + 1 <= 32769.
+ *   headings     `rotations` is a host table [K][2] of Q14 pairs (cq, sq) = (16384 cos, 16384 sin), the table gg_match_planes takes;
+ *                1 <= K <= GG_BOX_MAX_HEADINGS = 32 and every word lies in [-16384, 16384].  For a rectangle the caller lists angles in
+ *                [0, pi/2).  The projections of a point are a = ux * cq + uy * sq and b = uy * cq - ux * sq; both fit an int32
+ *                (32769 * 32768 < 2^31).
+ *   extents      per cluster c and heading k: a_min, a_max, b_min, b_max over the participating points with id c; A = a_max - a_min and
+ *                B = b_max - b_min are taken in 64 bits (they can reach 2^31 + 2^16).
+ *   criterion    GG_BOX_AREA: cost[c][k] = A * B, the minimum-area rectangle.  GG_BOX_EDGE: cost[c][k] = the sum over the cluster's
+ *                participating points of min(a - a_min, a_max - a, b - b_min, b_max - b), the closeness criterion of L-shape fitting: the
+ *                points of a car seen from one corner hug two edges of the right rectangle.  Both are uint64 and cannot overflow
+ *                (A * B < 2^63; the sum stays below 2^31 * 2^24).
+ *   choice       k* = the heading with the smallest cost, the smallest k among equals: a cluster of one point takes heading 0.
+ *   d_boxes[i][c]  for c < M_i, every field: heading = k*, points = its participating points, the four extents at k*, and the cost at k* as
+ *                two words.  A cluster c < M_i without a participating point gets heading = -1 and zeros.  Records at and beyond M_i are
+ *                never written.
+ *   d_costs      nullable, uint64 [n][M][K]: every cost[c][k] for c < M_i, all ones (UINT64_MAX) for a cluster without a participating
+ *                point; never written from M_i on.  The ambiguity measure of a square-ish cluster.  8-byte alignment.
+ *   no overlap   no output may share a byte with an input or with another output (GG_ERR_INVALID).  The inputs may overlap each other.
+ *   determinism  integer arithmetic and integer atomics (min, max, add) only, no float is ever added: the result is a function of the
+ *                inputs alone, bit-identical from run to run and independent of scheduling.
+ * The contract is that of gg_split_clouds, minus the labels: the call reads the caller's buffers and the maps' positions and NO LAYER; a
+ * fresh map stays fresh; no layer, position, configuration, score or liveness flag changes and the lazily kept layers stay pending.
+ * `stream`, ordering and the lifetime of the host arrays (slots, n_points, transforms, rotations: free on return) are those of
+ * gg_split_clouds.  One work-group computes one cloud, so many clouds fill the device and a single cloud runs on one compute unit.
+ * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
+ * n > 0: every error of gg_cloud_clusters' members of the same name (null d_points or n_points, an unknown point_format, a bad slot list,
+ * n_points[i] < 0 or > cloud_stride; GG_ERR_CAPACITY beyond max_points), null d_point_cluster, d_n_clusters, d_boxes or rotations,
+ * n_rotations outside [1, 32], a rotation word outside [-16384, 16384], an unknown criterion, max_clusters outside [1, 4096], overlapping
+ * buffers; GG_ERR_GEOMETRY for a map of more than 4096 rows or columns (no kernel is launched; gg_create refuses such a map today, its own
+ * limits end below that side, so the bound is the call's arithmetic stated, not a case a context can reach).  n == 0 is GG_OK before anything else is
+ * looked at.  The first call of a context may allocate (GG_ERR_NOMEM) and block; later calls only enqueue.  Capture into a caller's graph
+ * is not supported. */
+#define GG_BOX_UNIT 16
+#define GG_BOX_MAX_HEADINGS 32
+#define GG_BOX_MAX_CLUSTERS 4096
+enum { GG_BOX_AREA = 0, GG_BOX_EDGE = 1 };
+typedef struct gg_box {            /* 32 bytes: record c describes cluster c of the cloud */
+    int32_t heading;               /* k*, the index into `rotations`; -1: no participating point */
+    int32_t points;                /* participating points of the cluster */
+    int32_t a_min, a_max;          /* the extent along heading k*, in Q14 units of GG_BOX_UNIT-ths of a cell */
+    int32_t b_min, b_max;          /* ... and across it */
+    int32_t cost_lo, cost_hi;      /* the uint64 cost at k*, low word first */
+} gg_box;
+typedef struct gg_cluster_boxes {
+    int n;                         /* clouds */
+    int first_slot;                /* cloud i meets map first_slot + i when slots == NULL */
+    const int32_t *slots;          /* host [n], nullable, distinct */
+    int point_format;              /* GG_POINT32 / GG_POINT16 */
+    const void *d_points;          /* [n][cloud_stride], as gg_batch.d_points */
+    size_t cloud_stride;           /* points */
+    const int32_t *n_points;       /* host [n] */
+    const double *transforms;      /* host [n][12], nullable, as gg_batch.transforms */
+    const int32_t *d_point_cluster; /* [n][cloud_stride]: gg_cluster_clouds' d_point_cluster as it stands; required */
+    const int32_t *d_n_clusters;   /* [n]: gg_cluster_clouds' d_n_clusters as it stands; required */
+    const int32_t *rotations;      /* host [n_rotations][2] Q14 pairs (cq, sq); required */
+    int n_rotations;               /* K, 1 .. GG_BOX_MAX_HEADINGS */
+    int criterion;                 /* GG_BOX_AREA / GG_BOX_EDGE */
+    int max_clusters;              /* M, 1 .. GG_BOX_MAX_CLUSTERS */
+    gg_box *d_boxes;               /* [n][max_clusters]; required */
+    uint64_t *d_costs;             /* [n][max_clusters][n_rotations], nullable */
+} gg_cluster_boxes;
+int gg_box_clusters(gg_context *ctx, const gg_cluster_boxes *x, void *stream);
+#define GG_HAS_BOX_CLUSTERS 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
