@@ -62,6 +62,7 @@ SYMBOLS = [
     "gg_heading_moves",
     "gg_track_clusters",
     "gg_box_clusters",
+    "gg_score_rollouts",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -541,6 +542,46 @@ def box_slab_clusters(n_headings: int, max_clusters: int) -> int:
     return min(max_clusters, GG_BOX_LDS_BUDGET // (24 * n_headings + 4))
 
 
+class GGRollouts(C.Structure):
+    """gg_rollouts: the scores of candidate trajectories of many maps over the planes of the device chain (gg_score_rollouts)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("d_mask", C.c_void_p),
+        ("mask_stride", C.c_size_t),
+        ("d_cost", C.c_void_p),
+        ("cost_stride", C.c_size_t),
+        ("d_dist", C.c_void_p),
+        ("dist_stride", C.c_size_t),
+        ("plane_stride", C.c_size_t),
+        ("d_clear", C.c_void_p),
+        ("clear_stride", C.c_size_t),
+        ("n_headings", C.c_int),
+        ("starts", C.POINTER(C.c_int32)),
+        ("rotations", C.POINTER(C.c_int32)),
+        ("frame", C.c_int),
+        ("d_table", C.c_void_p),
+        ("table_stride", C.c_size_t),
+        ("n_rollouts", C.c_int),
+        ("n_steps", C.c_int),
+        ("cost_max", C.c_int),
+        ("reach", C.c_int),
+        ("order", C.c_int),
+        ("d_records", C.c_void_p),
+        ("record_stride", C.c_size_t),
+        ("d_best", C.c_void_p),
+    ]
+
+
+GG_HAS_SCORE_ROLLOUTS = 1
+GG_ROLLOUTS_MAX = 65536        # the most rollouts per map of gg_score_rollouts
+GG_ROLLOUTS_MAX_STEPS = 128    # ... steps per rollout
+GG_ROLLOUTS_MAX_REACH = 63     # ... and the widest reach, in cells
+GG_ROLLOUTS_RECORD_WORDS = 8   # words of a record
+GG_ROLLOUTS_RELATIVE, GG_ROLLOUTS_ABSOLUTE = 0, 1
+GG_ROLLOUTS_LIMIT = (1 << 31) - 2  # the largest n_steps * 32767 * cost_max
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -627,6 +668,7 @@ def load():
     L.gg_heading_moves.argtypes = [P(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int32)]
     L.gg_track_clusters.argtypes = [vp, P(GGClusterTracks), vp]
     L.gg_box_clusters.argtypes = [vp, P(GGClusterBoxes), vp]
+    L.gg_score_rollouts.argtypes = [vp, P(GGRollouts), vp]
     L.gg_get_map_position.argtypes =[vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

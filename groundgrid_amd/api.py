@@ -70,7 +70,7 @@ def _check(L, ctx, rc, what):
 
 
 # -- the argument frame of the methods over the device calls: the plane methods (fuse_states, route_planes, match_planes, footprint_planes,
-# route_headings, track_clusters), the transfers (export_layers, export_slopes, import_layers), export_images and the cloud methods
+# route_headings, score_rollouts, track_clusters), the transfers (export_layers, export_slopes, import_layers), export_images and the cloud methods
 
 def _name_mask(who, names, known, ordered, unknown=None, empty_ok=False):
     """(names as a list, their bit mask): distinct names of `known`, in its order.  ordered: the text when they are not -- or, unless
@@ -590,6 +590,69 @@ class BoxOutputs:
         out[ok, 3] = (rec[ok, 5] - rec[ok, 4]) / q * unit
         out[ok, 4] = np.arctan2(sq, cq)
         return out
+
+
+# a record of gg_score_rollouts as a numpy record (RolloutOutputs.table)
+ROLLOUT_DTYPE = np.dtype([("steps", "<i4"), ("len", "<i4"), ("cost", "<i4"), ("end_cell", "<i4"), ("end_heading", "<i4"), ("togo", "<i4"),
+                          ("clear", "<i4"), ("total", "<i4")])
+
+
+@dataclass
+class RolloutOutputs:
+    """what GroundSegmentation.score_rollouts returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    records: "object" = None  # torch.int32 [B, P, 8]: steps, len, cost, end_cell, end_heading, togo, clear, total of every rollout
+    best: "object" = None     # torch.int32 [B, 4]: the best rollout (-1: none), its total, the complete rollouts, the scored rollouts
+    step_major: "object" = None  # the step-major table the call read (kept alive until the stream has passed the call)
+
+    def table(self, b: int):
+        """The P records of map b as a numpy structured array (ROLLOUT_DTYPE).  It synchronises: it reads the records on the host."""
+        return self.records[b].cpu().numpy().copy().view(ROLLOUT_DTYPE).reshape(-1)
+
+
+def rollout_arcs(rotations, speeds, turns, steps: int, unit: int = 10):
+    """A library of constant-curvature arcs for GroundSegmentation.score_rollouts in the relative frame: int32 [P, T, 4] with
+    P = len(speeds) * len(turns), T = steps, rollout p = i * len(turns) + j pairing speeds[i] with turns[j].  A host convenience, not
+    part of the bit contract.  What it computes, in float64:
+      speeds[i] = v, cells per step along the heading (negative: backwards); turns[j] = w, radians per step (positive turns the forward
+      axis towards the side axis, as rotation_table).  After step t (t = 0 .. T - 1) the heading has turned by phi = (t + 1) * w and the
+      pose lies at (a, b) = (v / w) * (sin phi, 1 - cos phi) in (forward, side) cells, (v * (t + 1), 0) when w == 0.
+      da, db = 16 * a, 16 * b, each rounded half away from zero (units of 1/16 cell).
+      dk = the entry k of `rotations` (int32 [K, 2] as of rotation_table, 1 <= K <= 32) whose angle atan2(sq_k, cq_k) - atan2(sq_0, cq_0)
+      lies nearest to phi on the circle; among equally near entries the smallest k.  0 <= dk < K.
+      s = min(max(1, floor(unit * |v| + 0.5)), 32767), the same for every step of a rollout: proportional to the step length.
+    Entry (p, t) = (da, db, dk, s); no entry has s <= 0, so every rollout has length T."""
+    who = "rollout_arcs"
+    rot = _int32_array(who, "rotations", rotations, "[K, 2]", lambda sh: len(sh) == 2 and sh[1] == 2 and 1 <= sh[0] <= _lib.GG_HEADINGS_MAX,
+                       f" with 1 <= K <= {_lib.GG_HEADINGS_MAX}")
+    _check_integers(who, steps=steps, unit=unit)
+    if not 1 <= steps <= _lib.GG_ROLLOUTS_MAX_STEPS:
+        raise ValueError(f"{who}: steps lies in [1, {_lib.GG_ROLLOUTS_MAX_STEPS}]")
+    if not 1 <= unit <= 32767:
+        raise ValueError(f"{who}: unit lies in [1, 32767]")
+    v = np.atleast_1d(np.asarray(speeds, dtype=np.float64))
+    w = np.atleast_1d(np.asarray(turns, dtype=np.float64))
+    if v.ndim != 1 or w.ndim != 1 or v.size < 1 or w.size < 1 or not (np.isfinite(v).all() and np.isfinite(w).all()):
+        raise ValueError(f"{who}: speeds and turns are non-empty lists of finite numbers")
+    if v.size * w.size > _lib.GG_ROLLOUTS_MAX:
+        raise ValueError(f"{who}: more than {_lib.GG_ROLLOUTS_MAX} rollouts")
+    if np.abs(v).max() * steps * 16 >= 2 ** 30:
+        raise ValueError(f"{who}: a speed is too large")
+    vv, ww = [g.reshape(-1, 1) for g in np.meshgrid(v, w, indexing="ij")]       # [P, 1]
+    phi = ww * np.arange(1, steps + 1, dtype=np.float64)[None, :]               # [P, T]
+    straight = ww == 0.0
+    safe = np.where(straight, 1.0, ww)
+    a = np.where(straight, vv * np.arange(1, steps + 1, dtype=np.float64)[None, :], vv / safe * np.sin(phi))
+    b = np.where(straight, 0.0, vv / safe * (1.0 - np.cos(phi)))
+    rha = lambda x: (np.sign(x) * np.floor(np.abs(x) + 0.5)).astype(np.int64)
+    angle = np.arctan2(rot[:, 1].astype(np.float64), rot[:, 0].astype(np.float64))
+    angle = angle - angle[0]
+    apart = np.abs(np.angle(np.exp(1j * (phi[:, :, None] - angle[None, None, :]))))  # [P, T, K] in [0, pi]
+    out = np.empty((vv.shape[0], steps, 4), dtype=np.int32)
+    out[:, :, 0], out[:, :, 1] = rha(16.0 * a), rha(16.0 * b)
+    out[:, :, 2] = np.argmin(apart, axis=2)  # (the first of equal minima)
+    out[:, :, 3] = np.clip(np.floor(unit * np.abs(vv) + 0.5), 1, _lib.GG_HEADINGS_MAX_COST).astype(np.int32)
+    return out
 
 
 def heading_moves(rotations, *, step: int = 1, unit: int = 10, turn: int = 0, reverse_pct: int = 0, spin: int = 0):
@@ -1373,6 +1436,108 @@ class GroundSegmentation:
             x.d_paths, x.path_stride, x.max_len, x.d_path_len = res.paths.data_ptr(), 2 * int(max_len), int(max_len), res.path_len.data_ptr()
         stream = self._stream_arg(on_torch_stream, mask.device)
         _check(self._L, self._ctx, self._L.gg_route_headings(self._ctx, C.byref(x), stream), "gg_route_headings")
+        return res
+
+    def score_rollouts(self, mask, table, starts, *, rotations=None, relative: bool = True, cost=None, dist=None, clear=None,
+                       cost_max: int = 252, reach: int = 0, order: str = "row", step_major: bool = False, best: bool = True,
+                       out: Optional[RolloutOutputs] = None, on_torch_stream: bool = False, stream=None) -> RolloutOutputs:
+        """The score of candidate trajectories of many maps (gg_score_rollouts): which rollouts of a table fit the heading mask pose by
+        pose, what they cost on the cost plane, their least clearance, the cost-to-go of route_headings at their end, and the best of
+        every map.  mask: a contiguous CUDA torch.int32 tensor [B, rows, cols] ([B, cols, rows] with order="col"), B <= n_slots --
+        FootprintOutputs.mask as it is.  table: a CUDA torch.int32 tensor [P, T, 4] (one library for all maps) or [B, P, T, 4] (per-map
+        samples), entry (p, t) = (da, db, dk, s), 1 <= P <= 65536, 1 <= T <= 128; the call reads it step-major, so it is permuted with
+        one device copy on the current torch stream (and, unless the call is enqueued on that stream, the method waits for the copy)
+        unless step_major=True says it already is [T, P, 4] / [B, T, P, 4] and contiguous.  A rollout ends before its first entry with
+        s <= 0.  starts: [B, 3] host integers (r16, c16, k0): the position in 1/16 cell (16 * row + 8: a cell centre) and the heading;
+        r16 == -1: no start.  relative=True: the entries are offsets in the start pose's frame, rotated by heading k0 of `rotations`
+        (rotation_table(angles), int32 [K, 2]; required) and dk is added to k0 modulo K -- rollout_arcs() makes such a library.
+        relative=False: the entries are absolute (r16, c16, heading); K is then taken from `rotations` when given, else from dist.
+        cost: planes like mask, w = min(max(word, 1), cost_max), None: 1; a step costs min(s, 32767) * w of its cell.  dist:
+        HeadingOutputs.dist [B, K, rows, cols] as it is, None: togo = 0.  clear: ClearanceOutputs.dist2 as it is, or None.  reach R > 0:
+        poses more than R rows or columns from the start's cell are inadmissible (R <= 63).  The cells between consecutive poses are not
+        looked at: pad the footprint.  records int32 [B, P, 8]: steps (leading admissible poses), len, cost, end_cell (linear index in
+        `order`), end_heading, togo (dist at the end of a complete rollout, _lib.GG_ROUTE_NONE otherwise), clear, total = cost + togo
+        (_lib.GG_ROUTE_NONE unless complete and reached); RolloutOutputs.table(b) names them.  best int32 [B, 4]: the smallest p of
+        least total (-1: none), that total, the complete and the scored rollouts; best=False leaves it out (None).  The limit
+        T * 32767 * cost_max <= 2^31 - 2 keeps every cost inside an int32.  `out`: a RolloutOutputs of an earlier call with the same
+        arguments, whose tensors are reused; it may not hold an input.  Integer arithmetic only: bit-identical from run to run.
+        Enqueued on the context's own stream, with on_torch_stream=True on the current torch stream, or on `stream` (a raw handle);
+        nothing else synchronises.  No map is read or changed."""
+        import torch
+
+        who = "score_rollouts"
+        plane, c_order = _plane_order(who, order, self.rows, self.cols)
+        _check_integers(who, cost_max=cost_max, reach=reach)
+        if not 0 <= reach <= _lib.GG_ROLLOUTS_MAX_REACH:
+            raise ValueError(f"{who}: reach lies in [0, {_lib.GG_ROLLOUTS_MAX_REACH}]")
+        if not 1 <= cost_max <= _lib.GG_ROUTE_NONE:
+            raise ValueError(f"{who}: cost_max >= 1")
+        if not _is_planes(mask, plane):
+            raise ValueError(f"{who}: mask must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
+        B = int(mask.shape[0])
+        for name, t in (("cost", cost), ("clear", clear)):
+            if t is not None and not (_is_planes(t, plane) and t.shape[0] == B and t.device == mask.device):
+                raise ValueError(f"{who}: {name} must be a contiguous CUDA torch.int32 tensor of the shape and device of mask")
+        host_rot = None
+        if rotations is not None:
+            host_rot = _int32_array(who, "rotations", rotations, "[K, 2]", lambda sh: len(sh) == 2 and sh[1] == 2 and 1 <= sh[0] <= _lib.GG_HEADINGS_MAX,
+                                    f" with 1 <= K <= {_lib.GG_HEADINGS_MAX}")
+            if int(np.abs(host_rot).max()) > _lib.GG_MATCH_UNIT:
+                raise ValueError(f"{who}: a rotation word lies outside [-{_lib.GG_MATCH_UNIT}, {_lib.GG_MATCH_UNIT}]")
+        elif relative:
+            raise ValueError(f"{who}: the relative frame needs rotations")
+        if dist is not None and not (torch.is_tensor(dist) and dist.dim() == 4 and 1 <= dist.shape[1] <= _lib.GG_HEADINGS_MAX
+                                     and _is_dense(dist, (B, int(dist.shape[1])) + plane, device=mask.device)):
+            raise ValueError(f"{who}: dist must be a contiguous CUDA torch.int32 tensor [B, K, {plane[0]}, {plane[1]}] on the device of mask")
+        if host_rot is None and dist is None:
+            raise ValueError(f"{who}: the number of headings comes from rotations or from dist: give one of them")
+        K = int(host_rot.shape[0]) if host_rot is not None else int(dist.shape[1])
+        if dist is not None and int(dist.shape[1]) != K:
+            raise ValueError(f"{who}: dist has {int(dist.shape[1])} headings and rotations {K}")
+        if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int32 and table.dim() in (3, 4) and table.shape[-1] == 4
+                and table.device == mask.device and (table.dim() == 3 or table.shape[0] == B)):
+            raise ValueError(f"{who}: table must be a CUDA torch.int32 tensor [P, T, 4] or [B, P, T, 4] on the device of mask")
+        P, T = (int(table.shape[-2]), int(table.shape[-3])) if step_major else (int(table.shape[-3]), int(table.shape[-2]))
+        if not 1 <= P <= _lib.GG_ROLLOUTS_MAX or not 1 <= T <= _lib.GG_ROLLOUTS_MAX_STEPS:
+            raise ValueError(f"{who}: a table of {P} rollouts of {T} steps: 1 <= P <= {_lib.GG_ROLLOUTS_MAX} and 1 <= T <= {_lib.GG_ROLLOUTS_MAX_STEPS}")
+        if step_major and not table.is_contiguous():
+            raise ValueError(f"{who}: a step-major table must be contiguous")
+        if T * 32767 * cost_max > _lib.GG_ROLLOUTS_LIMIT:
+            raise ValueError(f"{who}: T * 32767 * cost_max exceeds 2^31 - 2")
+        host_starts = _int32_array(who, "starts", starts, "[B, 3]", lambda sh: sh == (B, 3))
+        given = host_starts[:, 0] != -1
+        r16, c16, k0 = (host_starts[given, j] for j in range(3))
+        if ((r16 < 0) | (r16 >= 16 * self.rows) | (c16 < 0) | (c16 >= 16 * self.cols)).any():
+            raise ValueError(f"{who}: a start lies outside the map")
+        if ((k0 < 0) | (k0 >= K)).any():
+            raise ValueError(f"{who}: a start heading lies outside [0, K)")
+        want = {"records": (B, P, _lib.GG_ROLLOUTS_RECORD_WORDS), "best": (B, 4) if best else None}
+        res = _reuse_outputs(who, out if out is not None else RolloutOutputs(), want, mask.device,
+                             [t.data_ptr() for t in (mask, cost, dist, clear, table) if t is not None])
+        self._torch_used = True
+        own_torch_stream = on_torch_stream and stream is None
+        if step_major:
+            res.step_major = table
+        else:
+            with torch.cuda.device(mask.device):
+                res.step_major = table.transpose(-3, -2).contiguous()
+                if not own_torch_stream:
+                    torch.cuda.current_stream(mask.device).synchronize()
+        x = _lib.GGRollouts()
+        cells = self.rows * self.cols
+        x.n, x.d_mask, x.mask_stride = B, mask.data_ptr(), cells
+        x.d_cost, x.cost_stride = (cost.data_ptr(), cells) if cost is not None else (None, 0)
+        x.d_dist, x.dist_stride, x.plane_stride = (dist.data_ptr(), K * cells, cells) if dist is not None else (None, 0, 0)
+        x.d_clear, x.clear_stride = (clear.data_ptr(), cells) if clear is not None else (None, 0)
+        x.n_headings, x.starts = K, _int32_ptr(host_starts)
+        x.rotations = _int32_ptr(host_rot) if host_rot is not None else None
+        x.frame = _lib.GG_ROLLOUTS_RELATIVE if relative else _lib.GG_ROLLOUTS_ABSOLUTE
+        x.d_table, x.table_stride = res.step_major.data_ptr(), 4 * P * T if table.dim() == 4 else 0
+        x.n_rollouts, x.n_steps, x.cost_max, x.reach, x.order = P, T, int(cost_max), int(reach), c_order
+        x.d_records, x.record_stride = res.records.data_ptr(), _lib.GG_ROLLOUTS_RECORD_WORDS * P
+        x.d_best = res.best.data_ptr() if best else None
+        handle = self._stream_arg(on_torch_stream or stream is not None, mask.device, handle=stream)
+        _check(self._L, self._ctx, self._L.gg_score_rollouts(self._ctx, C.byref(x), handle), "gg_score_rollouts")
         return res
 
     def track_clusters(self, cell_cluster, previous: Optional[TrackOutputs] = None, shifts=None, max_clusters: int = 256, gate: int = 1,

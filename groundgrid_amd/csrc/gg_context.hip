@@ -257,6 +257,7 @@ struct gg_context : ContextBuffers {
     RingTable<uint32_t> ring_footprint; // gg_footprint_planes: the packed span table, [FOOTPRINT_TABLE]
     RingTable<uint32_t> ring_moves;    // gg_route_headings: the packed move table, [HEADINGS_TABLE]
     RingTable<int2> ring_poses;        // ... the per-map start (cell, heading), [n_slots]
+    RingTable<int32_t> ring_rollout_starts; // gg_score_rollouts: the per-map start (r16, c16, k0), [n_slots][3]
     ParamRing export_ring;
     int slopes_variant = 0; // tuning "slopes_variant": 0 = k_slopes_tiled, 1 = k_slopes_gather (the A/B of tools/bench_slopes.py)
     int export_variant = EXPORT_VARIANT_DEFAULT; // tuning "export_variant": 0 = k_export_tiled, 1 = k_export_gather (the A/B of tools/bench_export.py)
@@ -2046,6 +2047,7 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     const RingPart rotations = ring_part(MATCH_MAX_ROTATIONS, sizeof(int2));
     const size_t o_match = take(dev_end, PARAM_RING * slots * MATCH_MAX_ROTATIONS * sizeof(MatchPartial));
     const RingPart footprint = ring_part(FOOTPRINT_TABLE, sizeof(uint32_t)), moves = ring_part(HEADINGS_TABLE, sizeof(uint32_t)), poses = ring_part(slots, sizeof(int2));
+    const RingPart rollout_starts = ring_part(3 * slots, sizeof(int32_t));
     if (const int rc = alloc_call_scratch(ctx, who, st, dev_end, pinned_end,
                                           {{o_off, off.data(), off.size() * sizeof(uint32_t)}, {o_elem, elem.data(), elem.size() * sizeof(uint32_t)}, {o_cell, cell.data(), cell.size() * sizeof(uint16_t)}},
                                           &ctx->export_mem, &ctx->export_ring))
@@ -2068,6 +2070,7 @@ static int ensure_export_scratch(gg_context *ctx, const char *who, hipStream_t s
     ctx->ring_footprint.bind(m, footprint);
     ctx->ring_moves.bind(m, moves);
     ctx->ring_poses.bind(m, poses);
+    ctx->ring_rollout_starts.bind(m, rollout_starts);
     return GG_OK;
 }
 
@@ -3178,6 +3181,99 @@ int gg_route_headings(gg_context *ctx, const gg_heading_routes *x, void *stream)
     ha.best_heading_stride = x->best_heading_stride;
     ha.counts = x->d_counts;
     launch_headings(ha, n, f.st);
+    return map_call_end(ctx, f);
+}
+
+// The score of candidate trajectories of many maps (k25_rollouts.hip): a ring entry and the ordering of the export for maps 0 .. n-1, none
+// of which is read, as gg_route_headings; the starts and, in the relative frame, the rotation table travel in the ring entry.  The
+// rollout table is the caller's device data and is not looked at here.  Nothing is synchronised, no map is filled and no host-side flag
+// changes.
+int gg_score_rollouts(gg_context *ctx, const gg_rollouts *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_score_rollouts";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_rollouts");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    const int rows = ctx->arena.g.rows, cols = ctx->arena.g.cols;
+    if (!x->d_mask || !x->d_table || !x->d_records || !x->starts) return fail(ctx, GG_ERR_INVALID, who, "d_mask, d_table, d_records and starts are required");
+    if (x->frame != GG_ROLLOUTS_RELATIVE && x->frame != GG_ROLLOUTS_ABSOLUTE) return fail(ctx, GG_ERR_INVALID, who, "frame");
+    const bool relative = x->frame == GG_ROLLOUTS_RELATIVE;
+    if (relative && !x->rotations) return fail(ctx, GG_ERR_INVALID, who, "rotations is required in the relative frame");
+    if (x->n_headings < 1 || x->n_headings > HEADINGS_MAX) return fail(ctx, GG_ERR_INVALID, who, "n_headings lies in [1, 32]");
+    if (x->n_rollouts < 1 || x->n_rollouts > GG_ROLLOUTS_MAX) return fail(ctx, GG_ERR_INVALID, who, "n_rollouts lies in [1, 65536]");
+    if (x->n_steps < 1 || x->n_steps > GG_ROLLOUTS_MAX_STEPS) return fail(ctx, GG_ERR_INVALID, who, "n_steps lies in [1, 128]");
+    const int K = x->n_headings, P = x->n_rollouts, T = x->n_steps;
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->reach < 0 || x->reach > GG_ROLLOUTS_MAX_REACH) return fail(ctx, GG_ERR_INVALID, who, "reach lies in [0, 63]");
+    if (x->mask_stride < C) return fail(ctx, GG_ERR_INVALID, who, "mask_stride is smaller than rows * cols");
+    if (x->d_cost && x->cost_stride < C) return fail(ctx, GG_ERR_INVALID, who, "cost_stride is smaller than rows * cols");
+    if (x->d_dist && (x->plane_stride < C || x->dist_stride / (size_t)K < x->plane_stride))
+        return fail(ctx, GG_ERR_INVALID, who, "plane_stride >= rows * cols and dist_stride >= n_headings * plane_stride");
+    if (x->d_clear && x->clear_stride < C) return fail(ctx, GG_ERR_INVALID, who, "clear_stride is smaller than rows * cols");
+    const size_t table_words = 4 * (size_t)P * (size_t)T; // <= 2^25
+    if (x->table_stride != 0 && x->table_stride < table_words) return fail(ctx, GG_ERR_INVALID, who, "table_stride is 0 or >= 4 * n_rollouts * n_steps");
+    if (x->record_stride < 8 * (size_t)P) return fail(ctx, GG_ERR_INVALID, who, "record_stride is smaller than 8 * n_rollouts");
+    if (relative)
+        for (int k = 0; k < 2 * K; ++k)
+            if (x->rotations[k] < -GG_MATCH_UNIT || x->rotations[k] > GG_MATCH_UNIT) return fail(ctx, GG_ERR_INVALID, who, "a rotation word lies outside [-16384, 16384]");
+    // the sum of a rollout's step costs fits an int32 (k25_rollouts.hip relies on it)
+    if (x->cost_max < 1 || (uint64_t)T * 32767u * (uint64_t)x->cost_max > (uint64_t)GG_ROUTE_NONE - 1)
+        return fail(ctx, GG_ERR_INVALID, who, "cost_max < 1 or n_steps * 32767 * cost_max exceeds 2^31 - 2");
+    if (x->n <= ctx->n_slots) // (beyond that the call is refused below, and starts[] is the caller's to size by n)
+        for (int i = 0; i < x->n; ++i) {
+            const int32_t *s = x->starts + 3 * (size_t)i;
+            if (s[0] == -1) continue;
+            if (s[0] < 0 || (int64_t)s[0] >= 16 * (int64_t)rows || s[1] < 0 || (int64_t)s[1] >= 16 * (int64_t)cols) return fail(ctx, GG_ERR_INVALID, who, "a start lies outside the map");
+            if (s[2] < 0 || s[2] >= K) return fail(ctx, GG_ERR_INVALID, who, "a start heading lies outside [0, n_headings)");
+        }
+    if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
+    const int n = x->n;
+    const BufferRange ranges[] = {plane_range("d_mask", x->d_mask, n, x->mask_stride, C, false),
+                                  plane_range("d_cost", x->d_cost, n, x->cost_stride, C, false),
+                                  plane_range("d_dist", x->d_dist, n, x->dist_stride, (size_t)(K - 1) * x->plane_stride + C, false),
+                                  plane_range("d_clear", x->d_clear, n, x->clear_stride, C, false),
+                                  plane_range("d_table", x->d_table, n, x->table_stride, table_words, false),
+                                  plane_range("d_records", x->d_records, n, x->record_stride, 8 * (size_t)P, true),
+                                  row_range("d_best", x->d_best, n, 4 * sizeof(int32_t), true)};
+    if (const int rc = check_no_overlap(ctx, who, ranges)) return rc;
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, n, nullptr, 0, stream, false, &f)) return rc;
+    RolloutArgs ra{};
+    int32_t *hs = ring_entry(ctx->ring_rollout_starts, f);
+    for (int i = 0; i < n; ++i) {
+        const int32_t *s = x->starts + 3 * (size_t)i;
+        const bool given = s[0] != -1;
+        hs[3 * i] = s[0], hs[3 * i + 1] = given ? s[1] : 0, hs[3 * i + 2] = given ? s[2] : 0;
+    }
+    if (!(ra.starts = ring_upload(ctx, ctx->ring_rollout_starts, f, 3 * n))) return GG_ERR_HIP;
+    if (relative) {
+        int2 *hr = ring_entry(ctx->ring_rotations, f);
+        for (int k = 0; k < K; ++k) hr[k] = make_int2(x->rotations[2 * (size_t)k], x->rotations[2 * (size_t)k + 1]);
+        if (!(ra.rotations = ring_upload(ctx, ctx->ring_rotations, f, K))) return GG_ERR_HIP;
+    }
+    ra.mask = x->d_mask;
+    ra.mask_stride = x->mask_stride;
+    ra.cost = x->d_cost;
+    ra.cost_stride = x->cost_stride;
+    ra.dist = x->d_dist;
+    ra.dist_stride = x->dist_stride;
+    ra.plane_stride = x->plane_stride;
+    ra.clear = x->d_clear;
+    ra.clear_stride = x->clear_stride;
+    ra.table = x->d_table;
+    ra.table_stride = x->table_stride;
+    ra.rows = rows, ra.cols = cols;
+    ra.row_major = x->order == GG_PLANES_ROWMAJOR;
+    ra.K = K, ra.P = P, ra.T = T;
+    ra.frame = x->frame;
+    ra.reach = x->reach;
+    ra.cost_max = x->cost_max;
+    ra.records = x->d_records;
+    ra.record_stride = x->record_stride;
+    ra.best = x->d_best;
+    launch_rollouts(ra, n, f.st);
     return map_call_end(ctx, f);
 }
 

@@ -649,6 +649,29 @@ inline int box_slab_clusters(int K, int M) { const int most = BOX_LDS_BUDGET / (
 inline size_t box_lds_bytes(int K, int slab) { return ((size_t)BOX_PAIR_BYTES * K + 4) * (size_t)slab + 8 * (size_t)K + 8; } // (+ the rotation table)
 static_assert(BOX_LDS_BUDGET / (BOX_PAIR_BYTES * GG_BOX_MAX_HEADINGS + 4) >= 1, "a slab holds at least one cluster");
 
+// gg_score_rollouts (k25_rollouts.hip): what its one launch takes.  Map i of the call is row i of every buffer.  The kernel works in
+// (row, col) and forms a cell's linear index by `row_major` alone; the starts arrive checked, three words per map.
+constexpr int ROLLOUT_THREADS = 1024;          // one work-group per map; thread t walks rollouts t, t + 1024, ...
+struct RolloutArgs {
+    const uint32_t *mask;          // map i's plane at mask + i * mask_stride: pose (k, q) is admissible where bit k of q's word is set
+    size_t mask_stride;
+    const int32_t *cost;           // ... at cost + i * cost_stride: w = min(max(word, 1), cost_max); nullable: w = 1
+    size_t cost_stride;
+    const int32_t *dist;           // plane k of map i at dist + i * dist_stride + k * plane_stride (gg_route_headings' D); nullable: togo = 0
+    size_t dist_stride, plane_stride;
+    const int32_t *clear;          // ... at clear + i * clear_stride: squared distances; nullable
+    size_t clear_stride;
+    const int32_t *table;          // entry (t, p) of map i at table + i * table_stride + (t * P + p) * 4; table_stride == 0: one table
+    size_t table_stride;
+    const int32_t *starts;         // device [map][3] (the call's ring entry): (r16, c16, k0); r16 == -1: no start
+    const int2 *rotations;         // device [K] (the call's ring entry): (cq, sq); null in the absolute frame
+    int rows, cols, row_major;
+    int K, P, T, frame, reach, cost_max;
+    int32_t *records;              // record p of map i at records + i * record_stride + 8 * p
+    size_t record_stride;
+    int32_t *best;                 // [map][4]; nullable
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: the launchers that need more than 64 KiB of dynamic
 // LDS opt in once per DEVICE (a process may hold contexts on several GPUs).  `opt_in` runs under a lock and the device is marked
 // only after it returned, so a second thread launching on the same device either sees the mark (the attribute is set) or waits for
@@ -703,6 +726,7 @@ void launch_footprint(const FootprintArgs &x, int n_maps, hipStream_t s);       
 void launch_headings(const HeadingsArgs &x, int n_maps, hipStream_t s);                          // k22_headings.hip: relax, (counts := 0, next,) (paths)
 void launch_tracks(const TrackArgs &x, int n_maps, hipStream_t s);                                // k23_tracks.hip: k_track_clusters
 void launch_boxes(const Arena &a, const BoxArgs &x, int n_clouds, hipStream_t s);                 // k24_boxes.hip: k_box_clusters
+void launch_rollouts(const RolloutArgs &x, int n_maps, hipStream_t s);                            // k25_rollouts.hip: k_score_rollouts
 // the cell-by-cell forms (k6_wire.hip), for any number of maps: every single-map getter and setter is a list of one map (gg_context::d_slot_maps).
 // They read x.maps, mask, n_planes, order, planes and plane_stride; the export table is the tiled kernels' alone
 void launch_planes_gather(const Arena &a, const PlaneArgs &x, int n_maps, hipStream_t s);   // layers -> dense planes (reset values outside the live half columns)

@@ -1,5 +1,5 @@
 // The argument frame of the plane calls (gg_fuse_states, gg_track_clusters, gg_route_planes, gg_match_planes, gg_footprint_planes,
-// gg_route_headings): the byte ranges of their device buffers and the test that no output shares a byte with another buffer, the clamp of
+// gg_route_headings, gg_score_rollouts): the byte ranges of their device buffers and the test that no output shares a byte with another buffer, the clamp of
 // a map's index shift, and the plane sides of an order.  Plain C++17: no HIP and no context (tests/cpp/test_plane_args.cpp).
 #pragma once
 

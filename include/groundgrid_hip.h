@@ -1544,6 +1544,113 @@ typedef struct gg_cluster_boxes {
 int gg_box_clusters(gg_context *ctx, const gg_cluster_boxes *x, void *stream);
 #define GG_HAS_BOX_CLUSTERS 1
 
+/* THE SCORE OF CANDIDATE TRAJECTORIES of many maps in DEVICE memory: gg_route_headings ends with the exact cost-to-go D(k, q) of every
+ * (cell, heading) state, and all a caller can do with it on the device is read one d_next chain per map.  A local planner (the arc library
+ * of a DWA or state-lattice planner, the sampled rollouts of MPPI) samples hundreds to thousands of short motions from the robot's pose
+ * and has to throw away those that touch something, score the rest by what they cost plus what is left to go at their end, and pick one.
+ * gg_score_rollouts does that on the planes the chain already holds: the heading mask of gg_footprint_planes, the cost plane, the D volume
+ * of gg_route_headings and a squared-distance plane of gg_clearance_planes, each as it stands.  What a caller otherwise gets from a download
+ * of K + 2 planes per map, or in torch from index arithmetic, three gathers, a cumprod and a cumsum over [maps, rollouts, steps] tensors.
+ * Map i of the call is row i of every buffer and of `starts`.  Everything is 32-bit integer unless 64 bits are named, and in (row, col)
+ * terms whatever `order` is; all of the following is per map:
+ *   headings     K = n_headings (1 .. 32).
+ *   start        `starts`, a HOST array [n][3] of (r16, c16, k0): the robot's position in units of 1/16 cell (16 * row + 8 is the centre of a
+ *                cell; GG_BOX_UNIT = 16 units per cell as in gg_box_clusters) and its heading.  0 <= r16 < 16 * rows, 0 <= c16 < 16 * cols,
+ *                0 <= k0 < K.  r16 == -1: the map has no start, and the other two words are not looked at.  The start state is NOT tested
+ *                against the mask: the robot is where it is.  Required.
+ *   table        d_table, a DEVICE buffer of int32: entry (t, p), step t < T = n_steps of rollout p < P = n_rollouts, is the four words
+ *                (da, db, dk, s) at d_table + i * table_stride + (t * P + p) * 4 -- step-major, so that consecutive rollouts are
+ *                consecutive in memory.  table_stride == 0: one table shared by all maps (an arc library); otherwise >= 4 * P * T words
+ *                (per-map samples).  1 <= P <= GG_ROLLOUTS_MAX = 65536, 1 <= T <= GG_ROLLOUTS_MAX_STEPS = 128.  The table is device data
+ *                and is NOT validated: every possible word has a meaning below, and no word makes the call read or write outside its
+ *                buffers.  Required.
+ *   len          len_p is the smallest t with s(t, p) <= 0, or T.  Entries at and behind it are not looked at.
+ *   pose t < len under frame == GG_ROLLOUTS_RELATIVE, with (cq, sq) the Q14 pair of heading k0 of the HOST table rotations[K][2] (the
+ *                table of gg_match_planes / gg_heading_moves, |word| <= 16384, used as given, required in this frame):
+ *                A = cq * da - sq * db and B = sq * da + cq * db, both in 64 bits; r16_t = r16 + rha(A), c16_t = c16 + rha(B) with
+ *                rha(v) = (|v| + 8192) >> 14 with the sign of v -- the rotation of gg_match_planes: the offset (1, 0) goes to the forward
+ *                axis; k_t = (k0 + dk) mod K, taken in [0, K) for any dk.
+ *                Under GG_ROLLOUTS_ABSOLUTE: (r16_t, c16_t) = (da, db) and k_t = dk mod K in [0, K); rotations may be NULL.
+ *                The pose's cell is (floor(r16_t / 16), floor(c16_t / 16)), flooring towards minus infinity.
+ *   admissible   a pose is, when its cell lies inside the map -- with reach = R > 0 also within R rows and R columns of the start's
+ *                cell -- and bit k_t of the cell's word of map i's d_mask plane is set (a d_mask plane of gg_footprint_planes as it
+ *                stands; required).  The cells BETWEEN consecutive poses are not looked at, as in gg_route_headings: pad the footprint.
+ *   step cost    min(s, 32767) * w(cell) with w = min(max(word of d_cost, 1), cost_max), 1 when d_cost is NULL: exactly gg_route_planes'.
+ *   d_records    eight int32 per rollout, record p of map i at d_records + i * record_stride + 8 * p, record_stride >= 8 * P words:
+ *                  0 steps        the number of leading admissible poses
+ *                  1 len          len_p
+ *                  2 cost         the sum of the step costs of poses 0 .. steps - 1
+ *                  3 end_cell     the linear index in `order` of the cell of pose steps - 1; the start's cell when steps == 0
+ *                  4 end_heading  k of pose steps - 1; k0 when steps == 0
+ *                  5 togo         when the rollout is COMPLETE (steps == len): the word D(end_heading, end_cell) of d_dist, 0 when d_dist
+ *                                 is NULL; GG_ROUTE_NONE when it is not complete.  d_dist is the [n][K] volume of gg_route_headings as it
+ *                                 stands, plane k of map i at d_dist + i * dist_stride + k * plane_stride, plane_stride >= rows * cols,
+ *                                 dist_stride >= K * plane_stride.
+ *                  6 clear        the signed minimum of the d_clear words over poses 0 .. steps - 1 (d_clear: a d_dist2 plane of
+ *                                 gg_clearance_planes as it stands, clear_stride >= rows * cols); GG_ROUTE_NONE when d_clear is NULL or
+ *                                 steps == 0.
+ *                  7 total        min(cost + togo, GG_ROUTE_NONE - 1), taken in 64 bits, when the rollout is complete,
+ *                                 togo != GG_ROUTE_NONE and togo >= 0; GG_ROUTE_NONE otherwise.
+ *                A rollout with len == 0 is complete: it stands for "stay", its end is the start state.  A map without a start gets
+ *                (0, 0, 0, -1, -1, NONE, NONE, NONE) in every record.
+ *   d_best[i]    nullable, four words per map: the smallest p that attains the least total among the rollouts with total !=
+ *                GG_ROUTE_NONE, or -1 when there is none; that total, or GG_ROUTE_NONE; the number of complete rollouts; the number of
+ *                rollouts with total != GG_ROUTE_NONE.  (-1, GG_ROUTE_NONE, 0, 0) for a map without a start.
+ *   limit        cost_max >= 1 and T * 32767 * cost_max <= 2^31 - 2, compared in 64 bits (GG_ERR_INVALID beyond): `cost` never wraps.
+ *   writes       every record p < P of every map is written; the words between 8 * P and record_stride never are; a NULL d_best is not
+ *                touched.  4-byte alignment (the kernel takes 16-byte accesses where a row's address allows them).
+ *   no overlap   neither output may share a byte with an input or with the other output; the call compares the address ranges as
+ *                gg_route_headings does (d_table: 4 * P * T words, of the last map's table when table_stride > 0) and answers
+ *                GG_ERR_INVALID.  The inputs may overlap each other.
+ *   determinism  integer arithmetic only; a record is a function of its rollout and the best of a map a minimum of distinct keys:
+ *                bit-identical from run to run and independent of scheduling.
+ * The contract is that of gg_route_headings: NO MAP IS READ OR CHANGED.  n <= n_slots (GG_ERR_CAPACITY): the call takes an entry of the
+ * same ring of parameter entries (the starts and the rotation table travel in it) and orders itself on `stream` as those calls do; it
+ * enqueues and returns with no synchronisation, and the host arrays may be freed on return.  The caller's device buffers must stay valid
+ * and unmodified until `stream` has passed the call.  One work-group scores one map's rollouts, so many maps fill the device and a single
+ * map runs on one compute unit.  Across streams the call is ordered as gg_state_fusion has it: ORDER OF THE MANY-MAP CALLS ACROSS STREAMS.
+ * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx, null x, n < 0; and with n > 0: null d_mask, d_table,
+ * d_records or starts, null rotations in the relative frame, n_headings outside [1, 32], n_rollouts outside [1, 65536], n_steps outside
+ * [1, 128], an unknown frame or order, reach outside [0, GG_ROLLOUTS_MAX_REACH = 63], a stride smaller than stated above for a given
+ * buffer, table_stride in (0, 4 * P * T), a rotation word beyond +-16384 (relative frame), a start out of range, cost_max < 1 or a product
+ * beyond the limit, overlapping buffers; GG_ERR_CAPACITY for n > n_slots.  n == 0 is GG_OK before anything else is looked at.  The first
+ * many-map call of a context may allocate (GG_ERR_NOMEM) and block; later calls only enqueue.  Capture into a caller's graph is not
+ * supported. */
+#define GG_ROLLOUTS_MAX 65536
+#define GG_ROLLOUTS_MAX_STEPS 128
+#define GG_ROLLOUTS_MAX_REACH 63
+#define GG_ROLLOUTS_RECORD_WORDS 8
+enum { GG_ROLLOUTS_RELATIVE = 0, /* table entries are offsets in the start pose's frame, rotated by heading k0 */
+       GG_ROLLOUTS_ABSOLUTE = 1 }; /* table entries are positions in 1/16 cell and headings */
+typedef struct gg_rollouts {
+    int n;                        /* maps */
+    const uint32_t *d_mask;       /* [n] planes, mask_stride apart: pose (k, q) is admissible where bit k is set; required */
+    size_t mask_stride;           /* words, >= rows * cols */
+    const int32_t *d_cost;        /* [n] planes, cost_stride apart: w = min(max(word, 1), cost_max); NULL: w = 1 everywhere */
+    size_t cost_stride;
+    const int32_t *d_dist;        /* [n][K] planes of gg_route_headings; NULL: togo = 0 */
+    size_t dist_stride;           /* between maps, >= K * plane_stride when d_dist is given */
+    size_t plane_stride;          /* between the headings of a map, >= rows * cols when d_dist is given */
+    const int32_t *d_clear;       /* [n] planes, clear_stride apart: squared distances; nullable */
+    size_t clear_stride;
+    int n_headings;               /* K, 1 .. 32 */
+    const int32_t *starts;        /* host [n][3]: (r16, c16, k0); r16 == -1: no start; required */
+    const int32_t *rotations;     /* host [K][2] Q14 (cq, sq); required in the relative frame */
+    int frame;                    /* GG_ROLLOUTS_RELATIVE / GG_ROLLOUTS_ABSOLUTE */
+    const int32_t *d_table;       /* (da, db, dk, s) of entry (t, p) at + i * table_stride + (t * P + p) * 4; required */
+    size_t table_stride;          /* 0: one table for all maps; otherwise >= 4 * P * T words */
+    int n_rollouts;               /* P, 1 .. GG_ROLLOUTS_MAX */
+    int n_steps;                  /* T, 1 .. GG_ROLLOUTS_MAX_STEPS */
+    int cost_max;                 /* >= 1; n_steps * 32767 * cost_max <= 2^31 - 2 */
+    int reach;                    /* 0: the whole map; R in 1 .. 63: poses within R rows and R columns of the start's cell */
+    int order;                    /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR, of every plane of the call */
+    int32_t *d_records;           /* [n] rows of P records of eight words, record_stride apart; required */
+    size_t record_stride;         /* words, >= 8 * P */
+    int32_t *d_best;              /* [n][4]: best p, its total, complete rollouts, scored rollouts; nullable */
+} gg_rollouts;
+int gg_score_rollouts(gg_context *ctx, const gg_rollouts *x, void *stream);
+#define GG_HAS_SCORE_ROLLOUTS 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
