@@ -1549,7 +1549,8 @@ int gg_box_clusters(gg_context *ctx, const gg_cluster_boxes *x, void *stream);
  * of a DWA or state-lattice planner, the sampled rollouts of MPPI) samples hundreds to thousands of short motions from the robot's pose
  * and has to throw away those that touch something, score the rest by what they cost plus what is left to go at their end, and pick one.
  * gg_score_rollouts does that on the planes the chain already holds: the heading mask of gg_footprint_planes, the cost plane, the D volume
- * of gg_route_headings and a squared-distance plane of gg_clearance_planes, each as it stands.  What a caller otherwise gets from a download
+ * of gg_route_headings and a squared-distance plane of gg_clearance_clouds in plane mode (`clearance_planes` in api.py), each as it stands.
+ * What a caller otherwise gets from a download
  * of K + 2 planes per map, or in torch from index arithmetic, three gathers, a cumprod and a cumsum over [maps, rollouts, steps] tensors.
  * Map i of the call is row i of every buffer and of `starts`.  Everything is 32-bit integer unless 64 bits are named, and in (row, col)
  * terms whatever `order` is; all of the following is per map:
@@ -1587,8 +1588,8 @@ int gg_box_clusters(gg_context *ctx, const gg_cluster_boxes *x, void *stream);
  *                                 stands, plane k of map i at d_dist + i * dist_stride + k * plane_stride, plane_stride >= rows * cols,
  *                                 dist_stride >= K * plane_stride.
  *                  6 clear        the signed minimum of the d_clear words over poses 0 .. steps - 1 (d_clear: a d_dist2 plane of
- *                                 gg_clearance_planes as it stands, clear_stride >= rows * cols); GG_ROUTE_NONE when d_clear is NULL or
- *                                 steps == 0.
+ *                                 gg_clearance_clouds in plane mode (`clearance_planes` in api.py) as it stands, clear_stride >=
+ *                                 rows * cols); GG_ROUTE_NONE when d_clear is NULL or steps == 0.
  *                  7 total        min(cost + togo, GG_ROUTE_NONE - 1), taken in 64 bits, when the rollout is complete,
  *                                 togo != GG_ROUTE_NONE and togo >= 0; GG_ROUTE_NONE otherwise.
  *                A rollout with len == 0 is complete: it stands for "stay", its end is the start state.  A map without a start gets

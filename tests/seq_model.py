@@ -28,6 +28,9 @@ read is what an earlier call, often on another stream, wrote into a buffer the c
 same way (make_sequence(.., plane_calls=False) is the list as it was); tests/seq_planes.py holds that generator, their part of the model
 (the references fusion_ref, route_ref, match_ref, footprint_ref, headings_ref, tracks_ref on the model's own copy of the chained planes)
 and their part of the driver.
+Three later calls (LATE_KINDS: gg_box_clusters, gg_score_rollouts, gg_clearance_clouds in plane mode) come from a fourth generator
+stream behind the third one's tail (make_sequence(.., late_calls=False) is the list as it was); tests/seq_late.py holds that generator,
+their part of the model (box_ref, rollouts_ref, clearance_ref) and their part of the driver.
 """
 from __future__ import annotations
 
@@ -41,7 +44,7 @@ import numpy as np
 
 from groundgrid_amd import kitti
 from oracle import oracle
-from tests import clearance_ref, cloud_refs, seq_planes, slopes_ref
+from tests import clearance_ref, cloud_refs, seq_late, seq_planes, slopes_ref
 
 LAYERS = list(oracle.LAYERS)
 PER_CALL = [k for k in LAYERS if k not in ("ground", "groundpatch")]
@@ -98,9 +101,13 @@ OBSERVING = OBSERVING + NEW_READERS
 # the six calls on caller-held planes (tests/seq_planes.py): a third generator stream, inserted the same way
 PLANE_KINDS = list(seq_planes.PLANE_KINDS)
 OBSERVING = OBSERVING + PLANE_KINDS
+# ... and three that came later (tests/seq_late.py): gg_box_clusters reads the positions of the maps it names, gg_score_rollouts and
+# gg_clearance_clouds in plane mode read no map: map i of theirs is row i of their buffers, as for the plane calls
+LATE_KINDS = list(seq_late.LATE_KINDS)
+OBSERVING = OBSERVING + LATE_KINDS
 KINDS = MUTATING + OBSERVING
 GLOBAL_KINDS = {"set_config", "set_conventions", "set_score_labels", "set_flags", "synchronize", "batch_fence", "checkpoint"}
-DEVICE_KINDS = {"reset_maps", "move_maps", "filter_batch", "export_layers", "batch_fence"} | set(NEW_KINDS) | set(PLANE_KINDS)   # enqueue and return (on a caller stream)
+DEVICE_KINDS = {"reset_maps", "move_maps", "filter_batch", "export_layers", "batch_fence"} | set(NEW_KINDS) | set(PLANE_KINDS) | set(LATE_KINDS)   # enqueue and return (on a caller stream)
 MUTATING_DEVICE_KINDS = {"reset_maps", "move_maps", "filter_batch", "import_layers"}
 PARAM_RING = 4   # (gg_context.hip: the entries of the ring of parameter blocks the many-map calls share)
 SLOPE_CHANNELS = ["grad_x", "grad_y", "tangent", "normal_z", "step", "min_confidence"]
@@ -1097,18 +1104,22 @@ class _Ins:
         return self.out
 
 
-def make_sequence(seed, shape, device_calls=True, plane_calls=True):
+def make_sequence(seed, shape, device_calls=True, plane_calls=True, late_calls=True):
     """The op list of (seed, shape): deterministic, JSON-serialisable.  The first record ("tunings") fixes the launch tunings of the
     context for the whole sequence.  device_calls=False: without the ops of NEW_KINDS (and the few ops of other kinds that the last
     scripts put in front of theirs) -- the list as it was before those calls were added, and a subsequence of the full one.
     plane_calls=False: without what the third generator stream adds (every op that carries "g3": the ops of PLANE_KINDS, the cloud calls
     their chains read and the scaffolding of their last scripts) -- the list as it was before the plane calls were added.  A chained
-    cloud call of the second stream names its batch by the index in THAT list (mid_indices)."""
+    cloud call of the second stream names its batch by the index in THAT list (mid_indices).
+    late_calls=False: without what the fourth generator stream adds behind the third's tail (every op that carries "g4": the ops of
+    LATE_KINDS and what their chains need) -- the list as it was before those calls were added.  Its ops stand behind every op of the
+    third stream, so no index that one's ops name moves; they carry "g3" too, which goes on counting the ops inserted behind the second
+    stream's list."""
     old = _Gen(seed, shape).run()
     if not device_calls:
         return old
     mid = _Ins(seed, shape, old).run()
-    return seq_planes.PlaneGen(_this_module(), seed, shape, mid).run() if plane_calls else mid
+    return seq_planes.PlaneGen(_this_module(), seed, shape, mid).run(late_calls) if plane_calls else mid
 
 
 def _this_module():
@@ -1127,8 +1138,10 @@ def touched(op, n_slots):
     k = op["op"]
     if k == "reset_maps":
         return list(range(op["first"], op["first"] + op["n"]))
-    if k in PLANE_KINDS:   # (map i of a plane call is row i of its buffers: the call's frame is filled from slots 0 .. n - 1)
+    if k in PLANE_KINDS or k in seq_late.ROW_KINDS:   # (map i of a plane call is row i of its buffers: the call's frame is filled from slots 0 .. n - 1)
         return list(range(min(op["n"], n_slots) if n_slots else op["n"]))
+    if k == "box_clusters":   # (a refused call names a slot beyond the context)
+        return [s for s in op["slots"] if not n_slots or s < n_slots]
     if k == "filter_async2":
         return [i["slot"] for i in op["items"]]
     if "slots" in op:
@@ -1153,7 +1166,7 @@ class Predicates:
       scoring        set_scoring switched it on
       partly-live    since its last cloud a per-call layer was set, or read whole"""
 
-    KEEP_FRESH = {"export_layers", "scores", "set_position", "get_position", "slot_config", "set_slot_configs", "set_scoring", "reset_scores"} | set(NEW_READERS) | set(PLANE_KINDS)
+    KEEP_FRESH = {"export_layers", "scores", "set_position", "get_position", "slot_config", "set_slot_configs", "set_scoring", "reset_scores"} | set(NEW_READERS) | set(PLANE_KINDS) | set(seq_late.LATE_KINDS)
 
     def __init__(self, n_slots):
         self.n = n_slots
@@ -1247,7 +1260,7 @@ MUTANTS = [
     "images_read_lazy_layer_uncomputed",        # export_images of one of the three lazily kept layers while it is owed: the stale plane
     "foreign_point_outside_gets_finite_height",  # a selected point outside the map (labels that belong to no batch): 0.0 instead of the quiet NaN
     # -- the calls on caller-held planes (tests/seq_planes.py)
-] + list(seq_planes.PLANE_MUTANTS)
+] + list(seq_planes.PLANE_MUTANTS) + list(seq_late.LATE_MUTANTS)   # (... and the three later calls, tests/seq_late.py)
 LAZY_MUTANTS = {"import_drops_lazy_layers", "images_read_lazy_layer_uncomputed"}   # (they need what the three layers held before the cloud)
 
 
@@ -1829,7 +1842,7 @@ class ContextModel:
                 res = {k: (np.where(np.isnan(v), np.float32(0.0), v) if k.endswith("height") else v) for k, v in res.items()}
             for k, v in res.items():
                 out[f"cloud {i} (slot {s}) {k}"] = v
-                if k in ("state", "cell ids"):   # (planes a plane call may be chained to)
+                if k in ("state", "cell ids", "point ids", "clusters", "dist2"):   # (what a plane call or one of tests/seq_late.py may be chained to)
                     self.outs.setdefault(self.at, {"_op": op}).setdefault(k, []).append(v)
         return out
 
@@ -1902,6 +1915,8 @@ class ContextModel:
 
 for _kind in PLANE_KINDS:
     setattr(ContextModel, "do_" + _kind, lambda self, op, m: seq_planes.model_op(self, op, m))
+for _kind in LATE_KINDS:
+    setattr(ContextModel, "do_" + _kind, lambda self, op, m: seq_late.model_op(self, op, m))
 
 _MEMO = {}
 
@@ -2485,6 +2500,7 @@ class Driver:
             keep.append(np.ascontiguousarray(np.asarray(tfs, dtype=np.float64).reshape(n, 12)))
             x.transforms = keep[-1].ctypes.data_as(C.POINTER(C.c_double))
         x.d_labels, x.d_label_masks = labels, masks
+        self.last_points = dict(ptr=d_points, stride=stride, n_points=list(n_pts), rec=rec, tfs=tfs)   # (gg_box_clusters runs on the same points)
         return n_pts, stride, keep
 
     @staticmethod
@@ -2584,7 +2600,9 @@ class Driver:
             x.d_clusters, x.max_clusters = (table.data_ptr() if cap else None), cap
             marks = self._enqueue(op, lambda st: self.seg._L.gg_cluster_clouds(self.seg._ctx, C.byref(x), st))
         self.keep.append((planes, count, table, ids))
-        self.dev_outs[self.at] = {"cell ids": (planes, pstride, n, op["row_major"])}
+        self.dev_outs[self.at] = {"cell ids": (planes, pstride, n, op["row_major"]), "clusters": (count, 1, n, op["row_major"]), "_points": self.last_points}
+        if ids is not None:
+            self.dev_outs[self.at]["point ids"] = (ids, stride, n, op["row_major"])
 
         def collect():
             res = self._marks_kept(marks)
@@ -2633,6 +2651,7 @@ class Driver:
             x.d_distance = distance.data_ptr() if distance is not None else None
             marks = self._enqueue(op, lambda st: self.seg._L.gg_clearance_clouds(self.seg._ctx, C.byref(x), st))
         self.keep.append((dist2, count, nearest, distance))
+        self.dev_outs[self.at] = {"dist2": (dist2, pstride, n, op["row_major"])}
 
         def collect():
             res = self._marks_kept(marks)
@@ -2707,6 +2726,8 @@ class Driver:
 
 for _kind in PLANE_KINDS:
     setattr(Driver, "do_" + _kind, lambda self, op: seq_planes.device_op(self, op))
+for _kind in LATE_KINDS:
+    setattr(Driver, "do_" + _kind, lambda self, op: seq_late.device_op(self, op))
 
 
 class _NoContext:

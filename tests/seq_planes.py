@@ -147,6 +147,7 @@ class PlaneGen:
         self.rows = side_of(sm, shape)
         self.big = self.rows > 200
         self.out, self.g3 = [], 0
+        self.g4 = None   # (the fourth generator stream, tests/seq_late.py, counts here while it adds its ops through this one's push)
         self.pos = [(0.0, 0.0)] * self.n
         self.alive = []
         self.pred = sm.Predicates(self.n)
@@ -186,6 +187,9 @@ class PlaneGen:
         if mine:
             op["g3"] = self.g3
             self.g3 += 1
+            if self.g4 is not None:
+                op["g4"] = self.g4
+                self.g4 += 1
         hit = []
         if k == "reset_maps":
             hit = list(range(op["first"], op["first"] + op["n"]))
@@ -594,11 +598,15 @@ class PlaneGen:
         self.emit(op)
         self.emit(self.mk_foreign(kind, 1, op["stream"]))   # (its result shows that the refused call took no ring entry and left no event behind)
 
-    def run(self):
+    def run(self, late_calls=True):
         n = len(self.mid)
         for j, op in enumerate(self.mid):
             if j == n - 1:
                 self.tail()
+                if late_calls:   # the fourth generator stream stands behind this one's tail: no index this one's ops name moves
+                    from tests import seq_late
+
+                    seq_late.LateGen(self).tail()
             elif j >= 2 and not self.sm._Ins.guarded(self.mid[j - 1]) and not self.sm._Ins.guarded(op):
                 self.anchors(j)
                 self.pairs(j)
@@ -770,7 +778,7 @@ def model_op(cm, op, m):
             c = ins["cost"][i] if ins["cost"] is not None else None
             r = sm._memo(("headings", _key(op, "want", "goal_headings", "max_len"), gh, order, dg(ins["mask"][i]), dg(ins["goals"][i]), dg(c) if c is not None else b""),
                          lambda: headings_ref.expected_headings(ins["mask"][i], ins["goals"][i], c, moves, gh, op["cost_max"], op["max_cost"], order, search=search))
-            put(i, "dist", r["dist"])
+            put(i, "dist", r["dist"], True)   # (kept: gg_score_rollouts may be chained to the D volume)
             reg["_live"].append(bool(r["counts"][1] > r["counts"][0]))
             for name in ("next", "best", "best_heading", "counts"):
                 if name in op["want"]:
@@ -940,6 +948,7 @@ def device_op(d, op):
             x.plane_stride = x.next_plane_stride = x.best_stride = x.best_heading_stride = stride
             x.dist_stride = x.next_stride = K * stride + 2
             x.d_dist = dest("dist", n * (K * stride + 2))
+            reg["dist"] = (bufs["dist"], K * stride + 2, n, op["row_major"], stride, K)   # (the [n][K] volume: dist_stride, then plane_stride and K)
             x.d_next = dest("next", n * (K * stride + 2)) if "next" in op["want"] else None
             x.d_best = dest("best", n * stride) if "best" in op["want"] else None
             x.d_best_heading = dest("best_heading", n * stride) if "best_heading" in op["want"] else None

@@ -7,6 +7,11 @@ For the six calls on caller-held planes (seq_model.PLANE_KINDS, tests/seq_planes
 header names occurs, every kind reads what an op on another stream wrote since the last checkpoint, a chain's buffer is overwritten
 while a call on another stream may still read it, one run per sequence holds all six on two caller streams and goes round the ring,
 shifts are sums of several moves, end with a reset and reach a side, the rows of a call are used to the last, and few calls are inert.
+For gg_box_clusters, gg_score_rollouts and gg_clearance_clouds in plane mode (seq_model.LATE_KINDS, tests/seq_late.py): the lists from
+before them are kept, every chain occurs, every kind reads what an op on another stream wrote since the last checkpoint, a box call
+follows and precedes a move of its map on another stream (one stands between it and the cluster call it reads), one run per sequence
+holds more rollout calls with different starts than the ring has entries, a distance buffer is overwritten that a rollout call on
+another stream read, the rows of a call are used to the last, the sizes stay small, and few calls are inert.
 
 `python -m tests.test_sequences_cpu` prints the coverage table and the mutant table of DESIGN.md.
 """
@@ -16,6 +21,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +29,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from tests import seq_model as sm  # noqa: E402
+from tests import seq_late as sl  # noqa: E402
 from tests import seq_planes as sp  # noqa: E402
 
 # the committed seeds: tests/test_sequences_gpu.py runs exactly these
@@ -414,7 +421,7 @@ def test_a_chain_buffer_is_written_once_between_two_checkpoints():
                 written.add(key)
 
 
-RING_TAKERS = set(sm.NEW_KINDS) | set(sm.PLANE_KINDS) | {"export_layers"}   # (gg_context.hip: the calls that go through map_call_begin)
+RING_TAKERS = set(sm.NEW_KINDS) | set(sm.PLANE_KINDS) | set(sm.LATE_KINDS) | {"export_layers"}   # (gg_context.hip: the calls that go through map_call_begin)
 
 
 def runs_on_two_caller_streams(ops):
@@ -431,12 +438,12 @@ def runs_on_two_caller_streams(ops):
     return [r for r in runs if len({op["stream"] for op in r}) == 2]
 
 
-def goes_round_the_ring(run):
-    """every entry of the ring is taken by a plane kind and later by another kind"""
+def goes_round_the_ring(run, kinds=tuple(sm.PLANE_KINDS)):
+    """every entry of the ring is taken by a plane kind (by one of `kinds`) and later by another kind"""
     takers = [op["op"] for op in run if op["op"] in RING_TAKERS]
     for e in range(sm.PARAM_RING):
         mine = takers[e:: sm.PARAM_RING]
-        if not any(a in sm.PLANE_KINDS and any(b != a for b in mine[k + 1:]) for k, a in enumerate(mine)):
+        if not any(a in kinds and any(b != a for b in mine[k + 1:]) for k, a in enumerate(mine)):
             return False
     return True
 
@@ -531,6 +538,243 @@ def test_once_per_shape_a_call_fills_the_rows_to_the_last_and_one_map_more_is_re
         assert refused, shape
 
 
+# ---------------------------------------------------------------------------------------------------------------- box_clusters, score_rollouts, clearance_planes
+
+# length and digest (as above) of every committed list as it was before the fourth generator stream's ops were inserted
+BEFORE_THE_LATE_CALLS = {
+    ("latency", 0): (230, "7f090c3d5b8cb47e90cfc27b168a7848"),
+    ("latency", 1): (231, "a8edbac1193d413d443638a9c35687c9"),
+    ("fleet", 0): (462, "74385f3ed659de8dac13340815b04a09"),
+    ("fleet", 1): (454, "e0317c5f7a724d873b605d5ebd4c928b"),
+    ("server", 0): (275, "ece77dd4cb93729ca53f5245a09dc3f7"),
+    ("server", 1): (310, "e74b7bccd63b4c39bc0af17e65c1fbe2"),
+}
+POSITION_WRITERS = ("move_maps", "reset_maps")
+
+
+def late_ops(shape=None, kind=None):
+    """(shape, seed, index, op, list) of every op of sm.LATE_KINDS of the committed sequences that is no argument error"""
+    for sh, seed in CASES:
+        if shape in (None, sh):
+            ops = sequence(sh, seed)
+            for i, op in enumerate(ops):
+                if op["op"] in sm.LATE_KINDS and "expect" not in op and kind in (None, op["op"]):
+                    yield sh, seed, i, op, ops
+
+
+def test_the_committed_seeds_keep_every_op_they_had_before_the_late_calls():
+    """make_sequence(.., late_calls=False) is the list from before the three calls were added, dict for dict; the fourth generator stream's
+    ops are the ones that carry "g4", every op of a late kind is one of them, and they stand behind every other op but the last checkpoint:
+    in front of its tail the stream adds nothing"""
+    for shape, seed in CASES:
+        old = sm.make_sequence(seed, shape, late_calls=False)
+        assert (len(old), hashlib.sha256(json.dumps(old, sort_keys=True).encode()).hexdigest()[:32]) == BEFORE_THE_LATE_CALLS[(shape, seed)], (shape, seed)
+        full = sequence(shape, seed)
+        assert [op for op in full if "g4" not in op] == old
+        assert all("g4" in op for op in full if op["op"] in sm.LATE_KINDS) and not any(op["op"] in sm.LATE_KINDS for op in old)
+        assert [op["g4"] for op in full if "g4" in op] == list(range(len(full) - len(old)))
+        assert full[: len(old) - 1] == old[:-1] and full[-1] == old[-1] == {"op": "checkpoint"}
+
+
+def test_every_late_call_occurs_in_every_shape_on_every_kind_of_stream_chained_and_foreign():
+    for shape in sm.SHAPES:
+        seen = {op["op"] for _, _, _, op, _ in late_ops(shape)}
+        assert seen == set(sm.LATE_KINDS), (shape, set(sm.LATE_KINDS) - seen)
+    for kind in sm.LATE_KINDS:
+        mine = [op for _, _, _, op, _ in late_ops(kind=kind)]
+        streams = {op["stream"] for op in mine}
+        assert streams & {"s1", "s2"} and {"default", "ctx"} <= streams, (kind, streams)
+        for name in sl.INPUTS[kind]:   # every input occurs chained, and foreign
+            given = [op[name] for op in mine if op[name] is not None]
+            assert any(sp.is_chained(src) for src in given) and any(not sp.is_chained(src) for src in given), (kind, name)
+    boxes = [op for _, _, _, op, _ in late_ops(kind="box_clusters")]
+    assert {op["criterion"] for op in boxes} == {"area", "edge"} and {op["costs"] for op in boxes} == {False, True}
+    assert {op["slot_list"] for op in boxes} == {False, True}
+    assert {(op["source"]["fmt"], op["source"]["tfs"] is not None) for op in boxes if op["source"]["mode"] == "foreign"} == {(16, False), (16, True), (32, False), (32, True)}
+    assert any(op["source"]["mode"] == "chained" for op in boxes)
+    rolls = [op for _, _, _, op, _ in late_ops(kind="score_rollouts")]
+    assert {op["row_major"] for op in rolls} == {False, True} and {bool(op["pad"]) for op in rolls} == {False, True}
+    assert {op["relative"] for op in rolls} == {False, True} and {op["best"] for op in rolls} == {False, True}
+    for name in ("cost", "dist", "clear"):
+        assert {op[name] is not None for op in rolls} == {False, True}, name
+    assert {op["reach"] for op in rolls} == {0, 1, 63}
+    pads = {op["table"]["pad"] for op in rolls if op["n"] >= 2}
+    assert 0 in pads and any(p % 2 for p in pads), "a shared table, and per-map tables an odd number of words apart"
+    assert all(not op["table"]["pad"] or (4 * op["table"]["P"] * op["table"]["T"] + op["table"]["pad"]) % 2 for op in rolls)
+    assert any(None in op["starts"] and any(s is not None for s in op["starts"]) for op in rolls), "a map without a start among maps with one"
+    clears = [op for _, _, _, op, _ in late_ops(kind="clearance_planes")]
+    assert {op["row_major"] for op in clears} == {False, True} and {bool(op["pad"]) for op in clears} == {False, True}
+    for key in ("nearest", "distance", "count"):
+        assert {op[key] for op in clears} == {False, True}, key
+
+
+def test_the_late_calls_stay_small():
+    """the references are plain loops"""
+    big = {shape: 0 for shape in sm.SHAPES}
+    for shape in sm.SHAPES:
+        assert set(sl.ROLLOUT_P) <= {op["table"]["P"] for _, _, _, op, _ in late_ops(shape, "score_rollouts")}, shape
+        assert {op["M"] for _, _, _, op, _ in late_ops(shape, "box_clusters")} <= set(sl.BOX_M)
+    for shape, _, _, op, _ in late_ops():
+        if op["op"] == "score_rollouts":
+            P, T = op["table"]["P"], op["table"]["T"]
+            assert op["K"] <= (4 if shape == "latency" else 8) and 1 <= T <= 12 and P * T <= 4096
+            if P == 1025:
+                assert T <= 3 and op["n"] <= 2
+                big[shape] += 1
+            else:
+                assert P <= 1024
+        elif op["op"] == "box_clusters":
+            assert op["M"] in sl.BOX_M and op["K"] in sl.BOX_K
+    assert all(v == 1 for v in big.values()), big   # (the stride loop of 1024 threads: once per shape)
+    assert {op["M"] for _, _, _, op, _ in late_ops(kind="box_clusters")} == set(sl.BOX_M)
+    assert {op["K"] for _, _, _, op, _ in late_ops(kind="box_clusters")} == set(sl.BOX_K)
+
+
+def test_every_late_chain_occurs_and_a_chained_buffer_is_taken_as_its_producer_left_it():
+    seen = {key: set() for key in sl.CHAIN_TABLE}
+    clear_made_by = set()
+    for _, _, i, op, ops in late_ops():
+        for name, src in sl.chained_inputs(op).items():
+            made = ops[src["op"]]
+            assert src["op"] < i and "expect" not in made
+            assert (made["n"] if "n" in made else len(made["slots"])) >= src["row0"] + op["n"]
+            seen[(op["op"], name)].add(src["out"])
+            if op["op"] == "box_clusters":   # the cluster call's ids and counts, on that call's points and maps, while its buffers are there
+                assert made["op"] == "cluster_clouds" and made["point_clusters"] and op["n_clusters"]["op"] == op["point_cluster"]["op"]
+                assert made["slots"] == op["slots"] and made["source"] == op["source"]
+                assert last_checkpoint(ops, i) < src["op"]
+            else:
+                assert made["row_major"] == op["row_major"], "a chained plane is taken in the order it was written in"
+            if name == "dist":
+                assert made["op"] == "route_headings" and made["K"] == op["K"]
+            if name == "clear":
+                clear_made_by.add(made["op"])
+        if op["op"] == "box_clusters" and op["source"]["mode"] == "chained":
+            assert last_checkpoint(ops, i) < op["source"]["batch"], "the batch's buffers are gone"
+    assert seen == sl.CHAIN_TABLE, {k: sl.CHAIN_TABLE[k] - v for k, v in seen.items() if sl.CHAIN_TABLE[k] - v}
+    assert clear_made_by == sl.CLEAR_PRODUCERS, clear_made_by
+    # a box call reads a cluster call of its batch's clouds, and one of clouds that belong to no batch
+    assert {op["source"]["mode"] for _, _, _, op, _ in late_ops(kind="box_clusters") if sl.chained_inputs(op)} == {"chained", "foreign"}
+
+
+def test_the_foreign_inputs_of_the_late_calls_hold_what_the_header_says_is_safe():
+    ids = np.concatenate([sl.foreign_ids(dict(seed=s), 0, 400, 3) for s in range(5)])
+    assert (ids < -1).any() and (ids == sl.I32_MIN).any() and (ids >= 3).any() and ((ids >= 0) & (ids < 3)).mean() > 0.7
+    counts = [sl.foreign_count(dict(seed=0), i, 64) for i in range(7)]
+    assert min(counts) < 0 and max(counts) > 64 and 64 in counts
+    vol = sl.dist_volume(dict(seed=3, kind="evidence", distinct=4), 1, 4, 79)
+    assert vol.shape == (4, 79, 79) and (vol == sl.NONE).any() and (vol < 0).any() and (vol > 0).any()
+    used = False
+    for _, _, _, op, _ in late_ops(kind="box_clusters"):
+        used |= not sp.is_chained(op["point_cluster"]) and not sp.is_chained(op["n_clusters"])
+    assert used
+
+
+
+@pytest.mark.parametrize("kind", sm.LATE_KINDS)
+def test_every_late_call_reads_what_an_op_on_another_stream_wrote_since_the_last_checkpoint(kind):
+    found = 0
+    for _, _, i, op, ops in late_ops(kind=kind):
+        cp = last_checkpoint(ops, i)
+        found += any(src["op"] > cp and ops[src["op"]]["stream"] != op["stream"] for src in sl.chained_inputs(op).values())
+    assert found, kind
+
+
+def test_the_box_call_follows_and_precedes_a_position_writer_of_its_map_on_another_stream():
+    pairs = all_ordered_pairs()
+    for w in POSITION_WRITERS:
+        assert (w, "box_clusters") in pairs, f"no box call behind a {w} of its map on another stream"
+    assert any(("box_clusters", w) in pairs for w in POSITION_WRITERS), "no position writer behind a box call on another stream"
+    assert ("box_clusters", "move_maps") in pairs
+    # ... and a move of one of its maps stands between the cluster call and the box call that reads it
+    between = 0
+    for _, _, i, op, ops in late_ops(kind="box_clusters"):
+        if sp.is_chained(op["point_cluster"]):
+            between += any(o["op"] == "move_maps" and set(o["slots"]) & set(op["slots"]) and o["stream"] != op["stream"] for o in ops[op["point_cluster"]["op"]: i])
+    assert between >= len(CASES)
+
+
+def test_one_run_per_sequence_holds_more_rollout_calls_than_the_ring_has_entries():
+    """... on two caller streams with nothing that synchronises the host: their starts differ pairwise (each travels in its ring entry),
+    other ring takers stand between them, and every entry is taken by a late kind and later by another kind"""
+    for shape, seed in CASES:
+        good = 0
+        for run in runs_on_two_caller_streams(sequence(shape, seed)):
+            takers = [op for op in run if op["op"] in RING_TAKERS]
+            at = [k for k, op in enumerate(takers) if op["op"] == "score_rollouts"]
+            starts = [json.dumps(takers[k]["starts"]) for k in at]
+            good += (len(at) > sm.PARAM_RING and len(set(starts)) == len(starts) and all(b - a >= 2 for a, b in zip(at, at[1:]))
+                     and goes_round_the_ring(run, tuple(sm.LATE_KINDS)) and set(sm.LATE_KINDS) <= {op["op"] for op in run})
+        assert good, (shape, seed)
+
+
+def test_a_distance_buffer_is_overwritten_while_a_rollout_call_on_another_stream_may_still_read_it():
+    for shape, seed in CASES:
+        ops = sequence(shape, seed)
+        hit, written = 0, set()
+        for i, op in enumerate(ops):
+            if op["op"] == "checkpoint":
+                written = set()
+            if op["op"] != "clearance_planes" or op.get("buf") is None or "expect" in op:
+                continue
+            key = (op["buf"], op["n"], op["pad"])
+            assert key not in written, (shape, seed, i, "written twice between two checkpoints")
+            written.add(key)
+            for j in range(last_checkpoint(ops, i) + 1, i):
+                other = ops[j]
+                src = other.get("clear") if other["op"] == "score_rollouts" else None
+                if sp.is_chained(src) and other["stream"] != op["stream"]:
+                    made = ops[src["op"]]
+                    hit += made["op"] == "clearance_planes" and (made.get("buf"), made["n"], made["pad"]) == key and src["op"] < last_checkpoint(ops, i)
+        assert hit, (shape, seed)
+
+
+def test_every_predicate_meets_every_late_kind_dealt_over_the_six_sequences():
+    dealt = [pair for shape, seed in CASES for pair in sl._late_pairs(sm, shape, seed)]
+    assert sorted(dealt) == sorted((p, k) for p in sm.PREDICATES for k in sm.LATE_KINDS)
+    table = coverage_table()
+    assert all(table[p][k] > 0 for p in sm.PREDICATES for k in sm.LATE_KINDS)
+
+
+def test_once_per_shape_and_late_kind_a_call_names_n_slots_maps_and_one_map_more_is_refused():
+    for shape in sm.SHAPES:
+        n_slots = sm.SHAPES[shape]["n_slots"]
+        full = {op["op"] for _, _, _, op, _ in late_ops(shape) if op["n"] == n_slots}
+        assert full == set(sm.LATE_KINDS), (shape, full)
+        refused = []
+        for seed in SEEDS[shape]:
+            ops = sequence(shape, seed)
+            for i, op in enumerate(ops):
+                if "expect" in op and op["op"] in sm.LATE_KINDS:
+                    assert op["n"] == n_slots + 1 and op["expect"] == "GG_ERR_CAPACITY" and op.get("buf") is None
+                    assert ops[i - 1]["op"] == op["op"] and ops[i - 1]["n"] == n_slots and ops[i - 1]["stream"] == op["stream"] != "ctx"
+                    assert ops[i + 1]["op"] == op["op"] and "expect" not in ops[i + 1] and ops[i + 1]["stream"] == op["stream"]   # (inside a run)
+                    refused.append(op["op"])
+        assert sorted(refused) == sorted(sm.LATE_KINDS), (shape, refused)
+
+
+@pytest.mark.parametrize("kind", sm.LATE_KINDS)
+def test_at_most_a_tenth_of_the_late_calls_are_inert(kind):
+    """a box call without a participating point in any cloud, a rollout call whose best p is -1 in every map, a clearance call without a seed"""
+    total = inert = 0
+    for shape, seed, i, op, _ in late_ops(kind=kind):
+        total += 1
+        inert += not any(truth(shape, seed)[3][i]["_live"])
+    assert total >= 30 and inert <= 0.10 * total, (kind, inert, total)
+
+
+def test_the_lazy_layer_mutant_trips_on_every_late_kind():
+    tripped = set()
+    for shape, seed in CASES:
+        results = truth(shape, seed)[0]
+        model = sm.ContextModel(shape, mutant="plane_call_computes_lazy_layers").bind(sequence(shape, seed))
+        for i, op in enumerate(sequence(shape, seed)):
+            got = model.apply(op, i)
+            if op["op"] in sm.LATE_KINDS and differs(results[i], got):
+                tripped.add(op["op"])
+    assert tripped == set(sm.LATE_KINDS), tripped
+
+
 # ---------------------------------------------------------------------------------------------------------------- inertness caps
 
 def test_at_most_a_tenth_of_the_filter_ops_have_no_point_inside_the_map():
@@ -616,6 +860,10 @@ def tables():
         mine = [op for _, _, _, op, _ in plane_ops() if op["op"] == k]
         rows.append(f"| {k} | " + ", ".join(o for o in others if (o, k) in pairs) + " | " + ", ".join(o for o in others if (k, o) in pairs)
                     + f" | {sum(1 for op in mine if chained_inputs(op))} / {sum(1 for op in mine if not chained_inputs(op))} |")
+    for k in sm.LATE_KINDS:   # (a box call names its slots, the other two slots 0 .. n - 1)
+        mine = [op for _, _, _, op, _ in late_ops(kind=k)]
+        rows.append(f"| {k} | " + ", ".join(o for o in others if (o, k) in pairs) + " | " + ", ".join(o for o in others if (k, o) in pairs)
+                    + f" | {sum(1 for op in mine if sl.chained_inputs(op))} / {sum(1 for op in mine if not sl.chained_inputs(op))} |")
     n, kinds, streams = max((longest_run_of_device_calls(sequence(shape, seed)) for shape, seed in CASES), key=lambda r: r[0])
     rows += ["", f"longest run of device calls: {n} ops of {len(kinds)} kinds on {len(streams)} streams (the shared ring has {sm.PARAM_RING} entries)"]
     return "\n".join(rows)
