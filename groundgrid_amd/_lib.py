@@ -63,6 +63,7 @@ SYMBOLS = [
     "gg_track_clusters",
     "gg_box_clusters",
     "gg_score_rollouts",
+    "gg_cluster_planes",
 ]
 
 GG_EIGEN_33, GG_EIGEN_34_SSE = 0, 1
@@ -582,6 +583,51 @@ GG_ROLLOUTS_RELATIVE, GG_ROLLOUTS_ABSOLUTE = 0, 1
 GG_ROLLOUTS_LIMIT = (1 << 31) - 2  # the largest n_steps * 32767 * cost_max
 
 
+class GGRegion(C.Structure):
+    """gg_region: record k of a map describes its kept component k (gg_cluster_planes), 48 bytes"""
+
+    _fields_ = [
+        ("cells", C.c_int32),
+        ("row_min", C.c_int32),
+        ("row_max", C.c_int32),
+        ("col_min", C.c_int32),
+        ("col_max", C.c_int32),
+        ("first_cell", C.c_int32),
+        ("value_cell", C.c_int32),
+        ("value_min", C.c_int32),
+        ("sum_row", C.c_int64),
+        ("sum_col", C.c_int64),
+    ]
+
+
+class GGPlaneClusters(C.Structure):
+    """gg_plane_clusters: the connected regions of any int32 plane of many maps, in device memory (gg_cluster_planes)"""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("d_seeds", C.c_void_p),
+        ("seed_stride", C.c_size_t),
+        ("lo", C.c_int32),
+        ("hi", C.c_int32),
+        ("connectivity", C.c_int),
+        ("min_cells", C.c_int),
+        ("order", C.c_int),
+        ("d_values", C.c_void_p),
+        ("value_stride", C.c_size_t),
+        ("d_cell_cluster", C.c_void_p),
+        ("plane_stride", C.c_size_t),
+        ("d_cell_size", C.c_void_p),
+        ("size_stride", C.c_size_t),
+        ("d_heads", C.c_void_p),
+        ("d_regions", C.c_void_p),
+        ("max_regions", C.c_int),
+    ]
+
+
+GG_HAS_CLUSTER_PLANES = 1
+GG_REGION_BYTES = 48           # sizeof(gg_region)
+
+
 GG_PC2_POINT_STEP = 18
 GG_SCORE_MAX_LABELS = 64
 
@@ -669,6 +715,7 @@ def load():
     L.gg_track_clusters.argtypes = [vp, P(GGClusterTracks), vp]
     L.gg_box_clusters.argtypes = [vp, P(GGClusterBoxes), vp]
     L.gg_score_rollouts.argtypes = [vp, P(GGRollouts), vp]
+    L.gg_cluster_planes.argtypes = [vp, P(GGPlaneClusters), vp]
     L.gg_get_map_position.argtypes =[vp, C.c_int, P(C.c_double), P(C.c_double)]
     L.gg_set_layer.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gg_get_layer.argtypes = [vp, C.c_int, C.c_int, vp]

@@ -592,6 +592,38 @@ class BoxOutputs:
         return out
 
 
+# gg_region as a numpy record (RegionOutputs.table), 48 bytes
+REGION_DTYPE = np.dtype([("cells", "<i4"), ("row_min", "<i4"), ("row_max", "<i4"), ("col_min", "<i4"), ("col_max", "<i4"), ("first_cell", "<i4"),
+                         ("value_cell", "<i4"), ("value_min", "<i4"), ("sum_row", "<i8"), ("sum_col", "<i8")])
+
+
+@dataclass
+class RegionOutputs:
+    """what GroundSegmentation.cluster_planes returns (CUDA torch tensors; None where nothing was asked for)"""
+
+    cell_cluster: "object" = None  # torch.int32 [B, rows, cols] ([B, cols, rows] with order="col"): -1 or the id of the cell's kept region
+    cell_size: "object" = None     # torch.int32 [B, rows, cols]: 0 on a non-member, else the size of the cell's component, dropped ones too
+    heads: "object" = None         # torch.int32 [B, 4]: K, dropped components, member cells, kept cells
+    regions: "object" = None       # torch.int32 [B, max_regions, 12]: gg_region records; only the first min(heads[b, 0], max_regions) of map b are written
+
+    def table(self, b: int):
+        """The first min(K, max_regions) records of map b as a numpy structured array (REGION_DTYPE).  It synchronises: it reads the
+        count on the host."""
+        k = min(max(int(self.heads[b, 0].item()), 0), int(self.regions.shape[1]))
+        return self.regions[b, :k].cpu().numpy().copy().view(REGION_DTYPE).reshape(k)
+
+    def centroids(self, b: int, resolution: float, length, position=(0.0, 0.0)):
+        """A host convenience, not part of the bit contract: the centroids of map b's regions in metres in the map frame, float64 [k, 2]
+        = (x, y), by grid_map's rule for the centre of a cell (a row index grows towards -x and a column index towards -y from the
+        corner position + length / 2).  resolution, length = (length_x, length_y) and position: the map's.  It synchronises."""
+        t = self.table(b)
+        n = np.maximum(t["cells"].astype(np.float64), 1.0)
+        out = np.empty((t.shape[0], 2), dtype=np.float64)
+        out[:, 0] = float(position[0]) + 0.5 * float(length[0]) - (t["sum_row"] / n + 0.5) * float(resolution)
+        out[:, 1] = float(position[1]) + 0.5 * float(length[1]) - (t["sum_col"] / n + 0.5) * float(resolution)
+        return out
+
+
 # a record of gg_score_rollouts as a numpy record (RolloutOutputs.table)
 ROLLOUT_DTYPE = np.dtype([("steps", "<i4"), ("len", "<i4"), ("cost", "<i4"), ("end_cell", "<i4"), ("end_heading", "<i4"), ("togo", "<i4"),
                           ("clear", "<i4"), ("total", "<i4")])
@@ -1598,6 +1630,63 @@ class GroundSegmentation:
         _check(self._L, self._ctx, self._L.gg_track_clusters(self._ctx, C.byref(x), stream), "gg_track_clusters")
         return res
 
+    def cluster_planes(self, seeds, *, lo: int = 0, hi: Optional[int] = None, connectivity: int = 8, min_cells: int = 1, values=None,
+                       max_regions: int = 256, order: str = "row", sizes: bool = False, out: Optional[RegionOutputs] = None,
+                       on_torch_stream: bool = False) -> RegionOutputs:
+        """The connected regions of planes the caller holds (gg_cluster_planes).  seeds: a contiguous CUDA torch.int32 tensor [B, rows,
+        cols] ([B, cols, rows] with order="col"), B <= n_slots; a cell is a member where lo <= word <= hi (hi=None: INT32_MAX, so the
+        default is the ">= 0" rule of clearance_planes: FusionOutputs.frontier or an id plane as it is; lo=hi=1: the occupied cells of
+        a state plane).  The members' connected components under `connectivity` 4 or 8 of at least min_cells cells are the regions,
+        numbered by ascending smallest linear cell index of `order`; smaller components are dropped.  cell_cluster: -1 or the region's
+        id -- what track_clusters and clearance_planes take as it stands; cell_size (with sizes=True, and always with min_cells > 1,
+        whose working memory it is): 0 or the size of the cell's component, dropped ones too; heads int32 [B, 4]: regions, dropped
+        components, member cells, kept cells; regions int32 [B, max_regions, 12] (max_regions=0: None): gg_region records --
+        RegionOutputs.table(b) gives them as REGION_DTYPE records with the int64 coordinate sums, centroids() in metres.  values: a
+        tensor like seeds (RouteOutputs.dist as it is): value_min is its minimum over a region and value_cell the cell that attains
+        it, the smallest index among equals -- the goal to hand to goal_planes(); without it INT32_MAX and -1.  `out`: a RegionOutputs
+        of an earlier call with the same arguments, whose tensors are reused; neither seeds nor values may be one of them.  Integer
+        arithmetic only: bit-identical from run to run.  Enqueued on the context's own stream or, with on_torch_stream=True, on the
+        current torch stream; nothing synchronises.  No map is read or changed."""
+        who = "cluster_planes"
+        plane, c_order = _plane_order(who, order, self.rows, self.cols)
+        hi = 0x7FFFFFFF if hi is None else hi
+        _check_integers(who, lo=lo, hi=hi, connectivity=connectivity, min_cells=min_cells, max_regions=max_regions)
+        if not -(1 << 31) <= lo <= hi <= 0x7FFFFFFF:
+            raise ValueError(f"{who}: -2^31 <= lo <= hi <= 2^31 - 1")
+        if connectivity not in (4, 8):
+            raise ValueError(f"{who}: connectivity is 4 or 8")
+        if not 1 <= min_cells <= 0x7FFFFFFF:
+            raise ValueError(f"{who}: min_cells is an integer >= 1")
+        if not 0 <= max_regions <= 0x7FFFFFFF:
+            raise ValueError(f"{who}: max_regions is an integer >= 0")
+        if not _is_planes(seeds, plane):
+            raise ValueError(f"{who}: seeds must be a contiguous CUDA torch.int32 tensor [B, {plane[0]}, {plane[1]}]")
+        B, M = int(seeds.shape[0]), int(max_regions)
+        if values is not None and not _is_dense(values, (B,) + plane, device=seeds.device):
+            raise ValueError(f"{who}: values must be a contiguous CUDA torch.int32 tensor of the shape of seeds, on their device")
+        with_sizes = bool(sizes) or min_cells > 1
+        want = {"cell_cluster": (B,) + plane, "cell_size": (B,) + plane if with_sizes else None, "heads": (B, 4),
+                "regions": (B, M, 12) if M else None}
+        inputs = [seeds.data_ptr()] + ([values.data_ptr()] if values is not None else [])
+        res = _reuse_outputs(who, out if out is not None else RegionOutputs(), want, seeds.device, inputs,
+                             in_place="is an input of the call: seeds and values may not be outputs")
+        self._torch_used = True
+        cells = self.rows * self.cols
+        x = _lib.GGPlaneClusters()
+        x.n, x.d_seeds, x.seed_stride = B, seeds.data_ptr(), cells
+        x.lo, x.hi, x.connectivity, x.min_cells, x.order = int(lo), int(hi), int(connectivity), int(min_cells), c_order
+        if values is not None:
+            x.d_values, x.value_stride = values.data_ptr(), cells
+        x.d_cell_cluster, x.plane_stride = res.cell_cluster.data_ptr(), cells
+        if with_sizes:
+            x.d_cell_size, x.size_stride = res.cell_size.data_ptr(), cells
+        x.d_heads = res.heads.data_ptr()
+        if M:
+            x.d_regions, x.max_regions = res.regions.data_ptr(), M
+        stream = self._stream_arg(on_torch_stream, seeds.device)
+        _check(self._L, self._ctx, self._L.gg_cluster_planes(self._ctx, C.byref(x), stream), "gg_cluster_planes")
+        return res
+
     def box_clusters(self, points, n_points: Sequence[int], point_cluster, n_clusters, rotations, *, transforms=None, slots=None,
                      first_slot: int = 0, criterion: str = "edge", max_clusters: int = 256, costs: bool = False,
                      out: Optional[BoxOutputs] = None, on_torch_stream: bool = False) -> BoxOutputs:
@@ -2067,6 +2156,17 @@ class GroundSegmentation:
         rc = fn(self._ctx, key.encode(), int(value))
         if rc < 0:
             raise GroundGridError(f"gg_debug_set_tuning({key}): {_lib.STATUS.get(rc, rc)}")
+        return rc
+
+    def debug_regions_tile(self, value: int = -1) -> int:
+        """Tools / tests: which path cluster_planes takes (gg_debug_regions_tile): 1 = 32 x 32 tiles labelled in LDS in front of the
+        flatten, 0 = the plain merge; the same results.  A negative value changes nothing.  Returns the path the library ships with."""
+        fn = self._L.gg_debug_regions_tile
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int]
+        rc = fn(self._ctx, int(value))
+        if rc < 0:
+            raise GroundGridError(f"gg_debug_regions_tile: {_lib.STATUS.get(rc, rc)}")
         return rc
 
     def set_conventions(self, eigen_reduction: int = 0):

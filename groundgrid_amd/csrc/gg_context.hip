@@ -30,6 +30,7 @@
 #include "hip_owned.h"
 #include "host_helper.h"
 #include "plane_args.h"
+#include "region_args.h"
 #include "scroll_core.h"
 #include "sweep_core.h"
 
@@ -321,6 +322,10 @@ struct gg_context : ContextBuffers {
     std::vector<hipEvent_t> free_single_events;
     double k_ms[GG_NUM_KERNELS + 1]{}; // (+ k_score, which gg_get_kernel_times' arrays have no room for: gg_get_score_kernel_time)
     int64_t k_launches[GG_NUM_KERNELS + 1]{};
+
+    // gg_cluster_planes (behind everything else: no other member moved for it)
+    int32_t *d_region_counts = nullptr;      // [ring entry][map] K, in cluster_mem behind the root counters
+    int regions_tile = REGIONS_TILE_DEFAULT; // 1 = the tile-local stage in front of the flatten (gg_debug_regions_tile)
 };
 
 namespace {
@@ -2400,9 +2405,11 @@ static int ensure_cluster_scratch(gg_context *ctx, const char *who, hipStream_t 
 {
     if (ctx->cluster_mem.dev) return GG_OK;
     const int chunks = (ctx->arena.g.C + CLUSTER_CHUNK_CELLS - 1) / CLUSTER_CHUNK_CELLS;
-    const size_t words = (size_t)PARAM_RING * ctx->n_slots * (size_t)chunks;
+    // (... and behind them one word per map and ring entry: the region count of gg_cluster_planes, which has no d_n_clusters to keep it in)
+    const size_t words = (size_t)PARAM_RING * ctx->n_slots * ((size_t)chunks + 1);
     if (const int rc = alloc_call_scratch(ctx, who, st, words * sizeof(uint32_t), 64, {}, &ctx->cluster_mem, nullptr)) return rc;
     ctx->d_cluster_counts = (uint32_t *)ctx->cluster_mem.dev.get();
+    ctx->d_region_counts = (int32_t *)(ctx->d_cluster_counts + (size_t)PARAM_RING * ctx->n_slots * (size_t)chunks);
     ctx->cluster_cell_chunks = chunks;
     return GG_OK;
 }
@@ -2442,6 +2449,68 @@ int gg_cluster_clouds(gg_context *ctx, const gg_cloud_clusters *x, void *stream)
     ca.cell_chunks = ctx->cluster_cell_chunks;
     ca.chunk_counts = ctx->d_cluster_counts + (size_t)f.g * ctx->n_slots * (size_t)ctx->cluster_cell_chunks;
     launch_cluster(ctx->arena, ca, x->n, f.st);
+    return map_call_end(ctx, f);
+}
+
+// The connected regions of any plane of many maps (k26_regions.hip): a ring entry and the ordering of the export for maps 0 .. n-1, none of
+// which is read, as gg_fuse_states; the forest, its scratch and four of its launches are gg_cluster_clouds'.  Nothing is synchronised, no
+// map is filled and no host-side flag changes.
+int gg_cluster_planes(gg_context *ctx, const gg_plane_clusters *x, void *stream)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    const char *who = "gg_cluster_planes";
+    if (!x) return fail(ctx, GG_ERR_INVALID, who, "null gg_plane_clusters");
+    if (x->n < 0) return fail(ctx, GG_ERR_INVALID, who, "n < 0");
+    if (x->n == 0) return GG_OK;
+    const size_t C = (size_t)ctx->arena.g.C;
+    if (!x->d_seeds || !x->d_cell_cluster) return fail(ctx, GG_ERR_INVALID, who, "d_seeds and d_cell_cluster are required");
+    if (x->lo > x->hi) return fail(ctx, GG_ERR_INVALID, who, "lo > hi");
+    if (x->connectivity != 4 && x->connectivity != 8) return fail(ctx, GG_ERR_INVALID, who, "connectivity is 4 or 8");
+    if (x->order != GG_PLANES_COLMAJOR && x->order != GG_PLANES_ROWMAJOR) return fail(ctx, GG_ERR_INVALID, who, "order");
+    if (x->seed_stride < C) return fail(ctx, GG_ERR_INVALID, who, "seed_stride is smaller than rows * cols");
+    if (x->plane_stride < C) return fail(ctx, GG_ERR_INVALID, who, "plane_stride is smaller than rows * cols");
+    if (x->d_values && x->value_stride < C) return fail(ctx, GG_ERR_INVALID, who, "value_stride is smaller than rows * cols");
+    if (x->d_cell_size && x->size_stride < C) return fail(ctx, GG_ERR_INVALID, who, "size_stride is smaller than rows * cols");
+    if (x->min_cells < 1) return fail(ctx, GG_ERR_INVALID, who, "min_cells < 1");
+    if (x->min_cells > 1 && !x->d_cell_size) return fail(ctx, GG_ERR_INVALID, who, "min_cells > 1 needs d_cell_size: it is the working memory of the filter");
+    if (x->max_regions < 0) return fail(ctx, GG_ERR_INVALID, who, "max_regions < 0");
+    if (x->d_regions && x->max_regions == 0) return fail(ctx, GG_ERR_INVALID, who, "d_regions is given with max_regions == 0");
+    if (reinterpret_cast<uintptr_t>(x->d_regions) % 8 != 0) return fail(ctx, GG_ERR_INVALID, who, "d_regions is not 8-byte aligned");
+    if (x->n > ctx->n_slots) return fail(ctx, GG_ERR_CAPACITY, who, "n is larger than n_slots");
+    const int n = x->n;
+    const BufferRange ranges[] = {plane_range("d_seeds", x->d_seeds, n, x->seed_stride, C, false),
+                                  plane_range("d_values", x->d_values, n, x->value_stride, C, false),
+                                  plane_range("d_cell_cluster", x->d_cell_cluster, n, x->plane_stride, C, true),
+                                  plane_range("d_cell_size", x->d_cell_size, n, x->size_stride, C, true),
+                                  row_range("d_heads", x->d_heads, n, 4 * sizeof(int32_t), true),
+                                  row_range("d_regions", x->d_regions, n, (size_t)x->max_regions * sizeof(gg_region), true)};
+    if (const int rc = check_no_overlap(ctx, who, ranges)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = ensure_cluster_scratch(ctx, who, pick_stream(ctx, stream))) return rc; // (checked arguments first, and no ring entry taken yet)
+    MapCall f;
+    if (const int rc = map_call_begin(ctx, who, n, nullptr, 0, stream, false, &f)) return rc;
+    RegionArgs ra{};
+    ra.forest.connectivity = x->connectivity;
+    ra.forest.order = x->order;
+    ra.forest.planes = reinterpret_cast<uint32_t *>(x->d_cell_cluster);
+    ra.forest.plane_stride = x->plane_stride;
+    ra.forest.n_clusters = ctx->d_region_counts + (size_t)f.g * ctx->n_slots;
+    ra.forest.cell_chunks = ctx->cluster_cell_chunks;
+    ra.forest.chunk_counts = ctx->d_cluster_counts + (size_t)f.g * ctx->n_slots * (size_t)ctx->cluster_cell_chunks;
+    ra.seeds = x->d_seeds;
+    ra.seed_stride = x->seed_stride;
+    ra.lo = x->lo;
+    ra.hi = x->hi;
+    ra.min_cells = x->min_cells;
+    ra.values = x->d_values;
+    ra.value_stride = x->value_stride;
+    ra.sizes = reinterpret_cast<uint32_t *>(x->d_cell_size);
+    ra.size_stride = x->size_stride;
+    ra.heads = x->d_heads;
+    ra.records = reinterpret_cast<uint32_t *>(x->d_regions);
+    ra.max_regions = x->d_regions ? x->max_regions : 0; // (without a table the kernels rank and count only)
+    ra.tile = ctx->regions_tile;
+    launch_regions(ctx->arena, ra, n, f.st);
     return map_call_end(ctx, f);
 }
 
@@ -4121,6 +4190,16 @@ int gg_insert_cloud(gg_context *ctx, int slot, const gg_point32 *cloud, size_t s
     if (const int rc = own_stream_mutated_map(ctx)) return rc;
     SYNCCHK(ctx, hipStreamSynchronize(s));
     return GG_OK;
+}
+
+// tools and tests only (not in the header): which path gg_cluster_planes takes.  value 1 = 32 x 32 tiles labelled in LDS first (k_region_tile +
+// k_region_rim), 0 = k_region_seed + k_cluster_merge; the same results.  A negative value changes nothing.  Returns the path the library
+// ships with (REGIONS_TILE_DEFAULT), GG_ERR_INVALID for a null context.
+extern "C" int gg_debug_regions_tile(gg_context *ctx, int value)
+{
+    if (!ctx) return GG_ERR_INVALID;
+    if (value >= 0) ctx->regions_tile = value ? 1 : 0;
+    return REGIONS_TILE_DEFAULT;
 }
 
 // tools and tests only (not in the header): override the launch geometry the library would pick from the batch size (0 = back

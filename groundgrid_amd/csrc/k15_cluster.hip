@@ -7,7 +7,9 @@
 // a parent only ever decreases, so every chain is strictly descending (find takes at most rows * cols steps and a union, whose larger end
 // strictly decreases from try to try, at most 2 * rows * cols tries), and the root of a finished component is its smallest cell index --
 // which is what the numbering asks for.  A stale parent (these loads ask for no freshness beyond a launch boundary) is a former ancestor of
-// the same component: it costs steps or a retry, because the atomic's return value is the truth, never a wrong union.
+// the same component: it costs steps or a retry, because the atomic's return value is the truth, never a wrong union.  The forest itself
+// (find, union, the runs of lanes that share an id) lives in cluster_core.h, and gg_cluster_planes (k26_regions.hip) drives the merge,
+// flatten, scan and rank launches of this file on its own seeds: launch_cluster_forest, launch_cluster_ranks.
 // Ten launches, all on the caller's buffers and one word per 256 cells of call scratch; L = the linear cell index of `order`:
 //   k_cluster_cells<ZERO>     plane[L] := 0
 //   k_cluster_points<COUNT>   the walk of cloud_walk.h; one atomic add per participating point into its cell
@@ -30,43 +32,13 @@
 // (the (ground, confidence) pair: only with a height band or a table) and one 4-byte atomic (COUNT) / 4 read + 4 written (IDS); per cell 4
 // written by ZERO, 4 + 4 by SEED, 4 + 4 by the flatten, 4 + 4 by the apply, 4 read by the rank; per occupied cell the parents the merge
 // walks; per cluster record 32 written and a handful of atomics per wavefront that touches it.
-#include "cloud_walk.h"
+#include "cluster_core.h"
+#include "region_args.h"
 
 namespace gg {
 
-constexpr uint32_t CLUSTER_EMPTY = 0xFFFFFFFFu; // an unoccupied cell, from the seed on (-1 as the caller reads it)
-constexpr int CLUSTER_WAVE_ROUNDS = 4; // ids a wavefront reduces over its lanes before the remaining lanes send their own atomics
-
-GG_DEV uint32_t cluster_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// (map, 256-cell chunk) of a work-group of the cell launches, grid (cell_chunks, clouds)
-GG_DEV void cluster_cell_item(int &cloud, int &chunk)
-{
-    const uint32_t item = xcd_contiguous_item(blockIdx.x + blockIdx.y * gridDim.x, gridDim.x * gridDim.y);
-    cloud = (int)(item / gridDim.x);
-    chunk = (int)(item % gridDim.x);
-}
-
 // a cluster's record as eight words: cells, points, row_min, row_max, col_min, col_max, height_max (its key while the call runs), first_cell
 GG_DEV uint32_t *cluster_record(const ClusterArgs &x, int io, int k) { return x.records + ((size_t)io * x.max_clusters + k) * 8; }
-
-// The lanes of a large cluster's interior all hold one id: one lane speaks for a run of them.  At most CLUSTER_WAVE_ROUNDS times, the first
-// lane that still holds an id (rid >= 0) names it and run(id, mine, count, speaker) is called by ALL lanes (it reduces over the lanes with
-// `mine`, and the `speaker` lane sends the result for the `count` of them); those lanes' rid becomes -1.  A lane whose rid is still >= 0
-// afterwards sends its own.  To be called in wavefront-uniform control flow.
-template <class Run> GG_DEV void cluster_id_runs(int &rid, int lane, Run &&run)
-{
-    unsigned long long todo = __ballot(rid >= 0);
-    for (int round = 0; round < CLUSTER_WAVE_ROUNDS && todo; ++round) {
-        const int src = __ffsll((long long)todo) - 1;
-        const int cur = __shfl(rid, src, 64);
-        const bool mine = rid == cur;
-        const unsigned long long m = __ballot(mine);
-        run(cur, mine, (int)__popcll(m), lane == src);
-        if (mine) rid = -1;
-        todo &= ~m;
-    }
-}
 
 template <bool SEED>
 __global__ __launch_bounds__(256) void k_cluster_cells(const Arena a, const ClusterArgs x)
@@ -75,35 +47,8 @@ __global__ __launch_bounds__(256) void k_cluster_cells(const Arena a, const Clus
     cluster_cell_item(cloud, chunk);
     const int L = chunk * 256 + (int)threadIdx.x;
     if (L >= a.g.C) return;
-    uint32_t *p = x.planes + (size_t)x.cl.clouds[cloud].io_index * x.plane_stride + L;
+    uint32_t *p = x.planes + (size_t)cluster_io(x, cloud) * x.plane_stride + L;
     *p = SEED ? (*p >= (uint32_t)x.min_points ? (uint32_t)L : CLUSTER_EMPTY) : 0u;
-}
-
-// find: at most x steps (every step goes to a smaller index; a word that is no smaller index ends the walk)
-GG_DEV uint32_t cluster_find(const uint32_t *parent, uint32_t x)
-{
-    for (;;) {
-        const uint32_t p = cluster_load(parent + x);
-        if (p >= x) return x;
-        x = p;
-    }
-}
-// union: a + b strictly decreases from try to try
-GG_DEV void cluster_union(uint32_t *parent, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = cluster_find(parent, a);
-        b = cluster_find(parent, b);
-        if (a == b) return;
-        if (a < b) {
-            const uint32_t t = a;
-            a = b;
-            b = t;
-        }
-        const uint32_t old = atomicMin(parent + a, b);
-        if (old == a) return; // a was a root and hangs under b now
-        a = old;              // a had the parent `old` (< a): parent[a] is min(old, b) now, and what is left to unite is old with b
-    }
 }
 
 // The plane as [majors][minors] words, L = major * minors + minor (row-major: major = row; column-major: major = column): 4- and
@@ -114,7 +59,7 @@ __global__ __launch_bounds__(256) void k_cluster_merge(const Arena a, const Clus
     cluster_cell_item(cloud, chunk);
     const int L = chunk * 256 + (int)threadIdx.x;
     if (L >= a.g.C) return;
-    uint32_t *parent = x.planes + (size_t)x.cl.clouds[cloud].io_index * x.plane_stride;
+    uint32_t *parent = x.planes + (size_t)cluster_io(x, cloud) * x.plane_stride;
     if (cluster_load(parent + L) == CLUSTER_EMPTY) return;
     const int minors = x.order == GG_PLANES_ROWMAJOR ? a.g.cols : a.g.rows;
     const int major = L / minors, minor = L - major * minors;
@@ -133,7 +78,7 @@ __global__ __launch_bounds__(256) void k_cluster_flatten(const Arena a, const Cl
     __shared__ uint32_t wave_roots[4];
     int cloud, chunk;
     cluster_cell_item(cloud, chunk);
-    const int io = x.cl.clouds[cloud].io_index;
+    const int io = cluster_io(x, cloud);
     const int L = chunk * 256 + (int)threadIdx.x;
     uint32_t *parent = x.planes + (size_t)io * x.plane_stride;
     bool root = false;
@@ -151,7 +96,7 @@ __global__ __launch_bounds__(256) void k_cluster_flatten(const Arena a, const Cl
 __global__ __launch_bounds__(256) void k_cluster_scan(const Arena a, const ClusterArgs x)
 {
     __shared__ uint32_t sums[256];
-    const int io = x.cl.clouds[blockIdx.x].io_index;
+    const int io = cluster_io(x, (int)blockIdx.x);
     uint32_t *counts = x.chunk_counts + (size_t)io * x.cell_chunks;
     const int t = (int)threadIdx.x;
     const int per = (x.cell_chunks + 255) / 256;
@@ -193,7 +138,7 @@ __global__ __launch_bounds__(256) void k_cluster_rank(const Arena a, const Clust
     __shared__ uint32_t wave_roots[4];
     int cloud, chunk;
     cluster_cell_item(cloud, chunk);
-    const int io = x.cl.clouds[cloud].io_index;
+    const int io = cluster_io(x, cloud);
     const int L = chunk * 256 + (int)threadIdx.x;
     const int wave = threadIdx.x >> 6;
     uint32_t *plane = x.planes + (size_t)io * x.plane_stride;
@@ -212,7 +157,7 @@ __global__ __launch_bounds__(256) void k_cluster_apply(const Arena a, const Clus
 {
     int cloud, chunk;
     cluster_cell_item(cloud, chunk);
-    const int io = x.cl.clouds[cloud].io_index;
+    const int io = cluster_io(x, cloud);
     const int L = chunk * 256 + (int)threadIdx.x;
     const int lane = threadIdx.x & 63;
     uint32_t *plane = x.planes + (size_t)io * x.plane_stride;
@@ -329,15 +274,29 @@ void launch_cluster_occupancy(const Arena &a, const ClusterArgs &x, int n_clouds
     hipLaunchKernelGGL((k_cluster_cells<true>), cells, dim3(256), 0, s, a, x);
 }
 
+// merge, flatten: from x.planes[L] = occupied ? L : 0xFFFFFFFF to the root of every occupied cell, and the roots of every chunk in scratch
+// (merge = false: the caller has united the cells itself)
+void launch_cluster_forest(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s, bool merge)
+{
+    const dim3 cells(x.cell_chunks, n_clouds);
+    if (merge) hipLaunchKernelGGL(k_cluster_merge, cells, dim3(256), 0, s, a, x);
+    hipLaunchKernelGGL(k_cluster_flatten, cells, dim3(256), 0, s, a, x);
+}
+
+// scan, rank: from the roots of every chunk in scratch to x.n_clusters, the records' initial words and x.planes[root] = -(rank + 2)
+void launch_cluster_ranks(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_cluster_scan, dim3(n_clouds), dim3(256), 0, s, a, x);
+    hipLaunchKernelGGL(k_cluster_rank, dim3(x.cell_chunks, n_clouds), dim3(256), 0, s, a, x);
+}
+
 void launch_cluster(const Arena &a, const ClusterArgs &x, int n_clouds, hipStream_t s)
 {
     const dim3 cells(x.cell_chunks, n_clouds);
     const bool band = cluster_band(x);
     launch_cluster_occupancy(a, x, n_clouds, s);
-    hipLaunchKernelGGL(k_cluster_merge, cells, dim3(256), 0, s, a, x);
-    hipLaunchKernelGGL(k_cluster_flatten, cells, dim3(256), 0, s, a, x);
-    hipLaunchKernelGGL(k_cluster_scan, dim3(n_clouds), dim3(256), 0, s, a, x);
-    hipLaunchKernelGGL(k_cluster_rank, cells, dim3(256), 0, s, a, x);
+    launch_cluster_forest(a, x, n_clouds, s, true);
+    launch_cluster_ranks(a, x, n_clouds, s);
     hipLaunchKernelGGL(k_cluster_apply, cells, dim3(256), 0, s, a, x);
     if (x.point_cluster || x.records) launch_cluster_points<true>(a, x, band || x.records != nullptr, n_clouds, s);
     if (x.records) {

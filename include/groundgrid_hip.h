@@ -1652,6 +1652,82 @@ typedef struct gg_rollouts {
 int gg_score_rollouts(gg_context *ctx, const gg_rollouts *x, void *stream);
 #define GG_HAS_SCORE_ROLLOUTS 1
 
+/* The CONNECTED REGIONS OF ANY PLANE of many maps in DEVICE memory: gg_cluster_clouds labels only the occupancy it rasterises itself from
+ * one scan's points, and every later link of the chain works on planes the caller already holds -- the state plane of gg_visibility_clouds,
+ * the fused and frontier planes of gg_fuse_states, the fit plane of gg_footprint_planes, the D plane of gg_route_planes.  gg_cluster_planes
+ * labels the connected components of the cells of such a plane whose word lies in a range, drops the components of fewer than min_cells
+ * cells, and gives the plane of ids, the plane of component sizes, four counts per map and a table of the regions with their centroid sums
+ * and the minimum of a second plane over every region: frontier regions ranked by size and by how far away they are, the persistent
+ * objects of a fused grid for gg_track_clusters, and the despeckling of a costmap.  What a caller otherwise gets from a download,
+ * scipy.ndimage.label + bincount + a relabel per map on the host and an upload.  Map i of the call is row i of every buffer.  Everything
+ * is integer and in (row, col) terms whatever `order` is; L is the linear cell index of `order` (r * cols + c for GG_PLANES_ROWMAJOR,
+ * r + c * rows for GG_PLANES_COLMAJOR), as in gg_cluster_clouds; per map:
+ *   member       a cell of the plane at d_seeds + i * seed_stride whose int32 word w satisfies lo <= w <= hi.  lo = 0, hi = INT32_MAX is the
+ *                ">= 0" rule of gg_clearance_clouds' seeds (a frontier plane, an id plane, "occupied or unknown" of a state plane);
+ *                lo = hi = 1 selects the occupied cells of a state plane and lo = hi = -1 its free space.
+ *   component    a connected component of members under `connectivity` 4 or 8, with the neighbours of gg_cluster_clouds: nothing wraps
+ *                at the border.  Its size is its number of cells.
+ *   kept         a component is kept when its size is at least min_cells (>= 1); the others are dropped.
+ *   numbering    the kept components of a map are numbered 0 .. K-1 in ascending order of their smallest L.
+ *   d_cell_cluster  required, and the call's working memory: map i's plane of rows * cols int32 at d_cell_cluster + i * plane_stride.
+ *                EVERY cell inside rows * cols is written: -1 on a non-member and on a cell of a dropped component, else the id.  The
+ *                plane is a d_cells plane of gg_track_clusters and a seed plane of gg_clearance_clouds as it stands.  The words between
+ *                rows * cols and plane_stride are never written.  While the call runs the planes hold intermediate words.
+ *   d_cell_size  nullable when min_cells == 1, required otherwise: the working memory of the filter.  Every cell inside rows * cols of
+ *                the plane at d_cell_size + i * size_stride is written: 0 on a non-member, else the size of the cell's component -- on
+ *                the cells of a dropped component too, so the caller sees what was removed.
+ *   d_heads[i]   nullable, four int32: {K, dropped components, member cells, kept cells}, true counts also when K > max_regions.
+ *   d_regions[i][k]  nullable: gg_region records of 48 bytes, written for k < min(K, max_regions), every field; records at and beyond
+ *                that never are.  cells, the four bounds and first_cell (the region's smallest L) as in gg_cluster; sum_row and sum_col
+ *                are the int64 sums of (row, col) over its cells: centroid = sum / cells.  8-byte alignment.
+ *   d_values     a nullable int32 plane per map at d_values + i * value_stride; D of gg_route_planes plugs in as it stands.  value_min
+ *                is the minimum of the plane over the region's cells as a signed int32, value_cell the L of the cell that attains it,
+ *                the smallest L among equals.  Without d_values value_min = INT32_MAX and value_cell = -1.  (While the call runs the two
+ *                words hold one 64-bit key, (value ^ 0x80000000) << 32 | L: that is what their order is for.)
+ *   addressing   cell (row, col) where `order` puts it, the same order for every plane of the call.  4-byte alignment of the planes.
+ *   no overlap   no output may share a byte with an input or with another output; the call compares the address ranges as
+ *                gg_fuse_states does and answers GG_ERR_INVALID.  The inputs may overlap each other.
+ *   determinism  integer arithmetic and integer atomics that commute (add, min, max) only: the result is a function of the inputs alone,
+ *                bit-identical from run to run and independent of scheduling.
+ * The contract is that of gg_fuse_states: NO MAP IS READ OR CHANGED -- no layer, position, freshness, configuration, score or liveness flag,
+ * and the lazily kept layers stay pending.  n <= n_slots (GG_ERR_CAPACITY): the call takes an entry of the same ring of parameter entries
+ * and orders itself on `stream` as that call does; it enqueues and returns.  The caller's device buffers must stay valid and unmodified
+ * until `stream` has passed the call.  With min_cells == 1 and no d_cell_size the size and filter launches do not run.
+ * Argument errors write nothing and change nothing: GG_ERR_INVALID for null ctx (before the device is touched), null x, n < 0; and with
+ * n > 0: null d_seeds or d_cell_cluster, lo > hi, a connectivity that is not 4 or 8, an unknown order, seed_stride or plane_stride
+ * < rows * cols, value_stride < rows * cols with d_values, size_stride < rows * cols with d_cell_size, min_cells < 1, min_cells > 1
+ * without d_cell_size, max_regions < 0, d_regions given with max_regions == 0 or not 8-byte aligned, overlapping buffers;
+ * GG_ERR_CAPACITY for n > n_slots.  n == 0 is GG_OK before anything else is looked at.  The first call of a context may allocate
+ * (GG_ERR_NOMEM) and block; later calls only enqueue.  Capture into a caller's graph is not supported. */
+typedef struct gg_region {         /* 48 bytes: record k describes kept component k of the map */
+    int32_t cells;                 /* cells of the region */
+    int32_t row_min, row_max, col_min, col_max;
+    int32_t first_cell;            /* smallest linear cell index of the region, in `order` */
+    int32_t value_cell;            /* L of the cell that attains value_min, the smallest among equals; -1 without d_values */
+    int32_t value_min;             /* the minimum of d_values over the region; INT32_MAX without d_values */
+    int64_t sum_row, sum_col;      /* sums of (row, col) over its cells: centroid = sum / cells */
+} gg_region;
+typedef struct gg_plane_clusters {
+    int n;                         /* maps */
+    const int32_t *d_seeds;        /* [n] planes, seed_stride apart: a member where lo <= word <= hi; required */
+    size_t seed_stride;            /* int32 words, >= rows * cols */
+    int32_t lo, hi;                /* lo <= hi */
+    int connectivity;              /* 4 or 8 */
+    int min_cells;                 /* >= 1: a component of fewer cells is dropped */
+    int order;                     /* GG_PLANES_COLMAJOR / GG_PLANES_ROWMAJOR, of every plane of the call */
+    const int32_t *d_values;       /* [n] planes, value_stride apart; nullable */
+    size_t value_stride;           /* >= rows * cols with d_values */
+    int32_t *d_cell_cluster;       /* [n] planes of rows * cols int32, plane_stride apart; required */
+    size_t plane_stride;           /* >= rows * cols */
+    int32_t *d_cell_size;          /* [n] planes, size_stride apart; nullable when min_cells == 1 */
+    size_t size_stride;            /* >= rows * cols with d_cell_size */
+    int32_t *d_heads;              /* [n][4]: K, dropped components, member cells, kept cells; nullable */
+    gg_region *d_regions;          /* [n][max_regions], 8-byte aligned; nullable */
+    int max_regions;               /* >= 0; must be > 0 when d_regions is given */
+} gg_plane_clusters;
+int gg_cluster_planes(gg_context *ctx, const gg_plane_clusters *x, void *stream);
+#define GG_HAS_CLUSTER_PLANES 1
+
 /* insert_cloud's per-point decision (include/groundgrid/GroundSegmentation.h:55): after a filter call,
  * class (GG_CLASS_*) and cell (row + col*rows, -1 outside) of every input point of `slot`. */
 int gg_get_point_classes(gg_context *ctx, int slot, size_t n, uint8_t *out_class, int32_t *out_cell);
